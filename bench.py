@@ -13,6 +13,11 @@ hipGraph.  The per-kernel split, the roofline figures and the counters come from
 same steps with HIP events around every launch (on the library's stream), which is slower and is NOT what `value` is
 computed from.
 
+A plain run sets up, warms up, times the K steps and prints the line: nothing else.  `--full` adds everything beyond
+the headline figure -- the acceptance check of the posteriors, the profiling pass (roofline), the CPU baseline, the
+same solve with every bandwidth fit, the 10 000-variable north-star graph -- each as before (`--no-*` leave parts out).
+`--dump-outputs DIR` writes the posteriors of the last timed step (what a caller of solveTree receives) as .npy files.
+
 Prints ONE JSON line (see the driver contract).  value = clique messages (one per tree edge and direction,
 CliqueStateMachine.jl:590-593/900-903) per second over all ranks.
 """
@@ -61,6 +66,11 @@ def parse():
     ap.add_argument("--pipeline-min", type=int, default=None,
                     help="rounds with at least this many variable updates run as two halves on two streams, one launch apart "
                          "(NBP_PIPELINE_MIN; same posteriors bit for bit)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: posterior acceptance, profiling pass "
+                         "(roofline), CPU baseline, every-fit solve, 10 000-variable graph (off: set up, warm up, time, print)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the posteriors of the last timed step to DIR/<name>.npy (float64; a fixed sample above 60 MB)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-sample-vars", type=int, default=1000, help="variables of the CPU baseline's chain (default: the whole config-2 graph)")
     ap.add_argument("--no-10k", action="store_true", help="skip the secondary 10 000-variable north-star measurement")
@@ -71,7 +81,10 @@ def parse():
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="testing: process-group backend.  gloo lets several ranks SHARE one GPU (RCCL refuses two ranks on one "
                          "device), separator slots then travel host-staged: every line of the sharded path but the RCCL calls")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return a
 
 
 def kernel_sources_sha():
@@ -138,6 +151,43 @@ def timed_steps(rs, steps, warmup, barrier):
         rs.step(k)
     barrier()
     return time.perf_counter() - t0
+
+
+DUMP_BUDGET_BYTES = 60_000_000
+
+
+def dump_outputs(rs, path, rank, world):
+    """--dump-outputs: what the timed path delivered in its last step -- the posterior of every variable of this rank, as a
+    caller of solveTree receives it (N particles and the bandwidth) -- one group of float64 arrays per manifold:
+    posterior_points_<manifold>.npy (variables x N x P), posterior_bandwidth_<manifold>.npy (variables x D) and
+    posterior_index_<manifold>.npy (each variable's position in the graph's variable list).  Where all of it would exceed
+    DUMP_BUDGET_BYTES (over all ranks), a fixed sample of the variables (seed 0) is written.  Several ranks: rank<r>_ prefix."""
+    from iif_amd import abi
+    names = {abi.EUCLID1: "euclid1", abi.EUCLID2: "euclid2", abi.EUCLID3: "euclid3", abi.CIRCULAR: "circular", abi.SE2: "se2"}
+    fg = rs.fg
+    index = {v: i for i, v in enumerate(fg.ls())}
+    mine = list(rs.mine)
+    mans = [fg.getVariable(v).varType.manifold for v in mine]
+    size = [8 * (rs.N * abi.MANIFOLD_P[m] + abi.MANIFOLD_DIM[m] + 1) for m in mans]
+    keep = range(len(mine))
+    if sum(size) > DUMP_BUDGET_BYTES // world:
+        keep, total = [], 0
+        for i in np.random.default_rng(0).permutation(len(mine)):
+            if total + size[i] > DUMP_BUDGET_BYTES // world:
+                break
+            keep.append(int(i))
+            total += size[i]
+        keep = sorted(keep)
+    os.makedirs(path, exist_ok=True)
+    prefix = f"rank{rank}_" if world > 1 else ""
+    for m in sorted(set(mans)):
+        vs = [mine[i] for i in keep if mans[i] == m]
+        if not vs:
+            continue
+        read = [rs.be.slot_read(rs.main[v], m) for v in vs]
+        np.save(os.path.join(path, f"{prefix}posterior_points_{names[m]}.npy"), np.stack([p for p, _ in read]).astype(np.float64))
+        np.save(os.path.join(path, f"{prefix}posterior_bandwidth_{names[m]}.npy"), np.stack([b for _, b in read]).astype(np.float64))
+        np.save(os.path.join(path, f"{prefix}posterior_index_{names[m]}.npy"), np.array([index[v] for v in vs], dtype=np.float64))
 
 
 def launch_ranks_if_asked():
@@ -239,12 +289,15 @@ def _main(real_stdout):
         t = torch.tensor([dt], device="cuda" if dist.get_backend() == "nccl" else "cpu", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
-    try:
-        rs.check_posteriors()
-    finally:
-        if world > 1 or os.environ.get("NBP_BENCH_SHA"):
-            print(f"[bench rank {rank}] posterior_max_mean_err={rs.posterior_max_mean_err} mode_share={rs.posterior_mode_share} "
-                  f"sha={rs.posterior_sha()} ({len(rs.mine)} variables of this rank)", file=sys.stderr, flush=True)
+    if a.dump_outputs:
+        dump_outputs(rs, a.dump_outputs, rank, world)
+    if a.full:
+        try:
+            rs.check_posteriors()
+        finally:
+            if world > 1 or os.environ.get("NBP_BENCH_SHA"):
+                print(f"[bench rank {rank}] posterior_max_mean_err={rs.posterior_max_mean_err} mode_share={rs.posterior_mode_share} "
+                      f"sha={rs.posterior_sha()} ({len(rs.mine)} variables of this rank)", file=sys.stderr, flush=True)
     msgs_total = rs.global_messages
     value = msgs_total * a.steps / dt
     st = rs.stats
@@ -252,7 +305,7 @@ def _main(real_stdout):
     # ---- profiling pass (not timed): HIP events around every launch, counters ------------------------------------------
     prof = None
     psteps = min(a.steps, 5)
-    if not a.no_profile_pass:
+    if a.full and not a.no_profile_pass:
         rs.be.timing_enable(True)
         rs.be.timing_read()
         rs.be.diag(reset=True)
@@ -262,7 +315,6 @@ def _main(real_stdout):
         rs.be.timing_enable(False)
         prof = (tim, diag, tprof)
 
-    peak, peak_src = hbm_peak_gbps(local)
     out = {
         "metric": "clique-messages/sec", "value": value, "unit": "messages/s", "n_gpus": world, "steps": a.steps,
         "warmup": a.warmup, "ms_per_step": dt / a.steps * 1e3, "higher_is_better": True, "scaling": scaling,
@@ -280,11 +332,14 @@ def _main(real_stdout):
         # (ncclCommCount through nbp_comm_info; null where no RCCL communicator exists: one rank, or the gloo test transport)
         "exchange_transport": getattr(getattr(rs, "impl", None), "transport", "none") if world > 1 else "none",
         "rccl_ranks": getattr(getattr(rs, "impl", None), "rccl_ranks", None),
-        "solve_wall_s": dt / a.steps, "posterior_max_mean_err": rs.posterior_max_mean_err,
-        "posterior_baseline5_band_share": getattr(rs, "posterior_baseline5_band_share", None),
-        "posterior_mode_share_min_median": rs.posterior_mode_share,
-        "posterior_alias_share_min_median": getattr(rs, "posterior_alias_share", None), "host_setup": rs.host_setup,
+        "solve_wall_s": dt / a.steps, "host_setup": rs.host_setup,
     }
+    if a.full:
+        out.update({"posterior_max_mean_err": rs.posterior_max_mean_err,
+                    "posterior_baseline5_band_share": getattr(rs, "posterior_baseline5_band_share", None),
+                    "posterior_mode_share_min_median": rs.posterior_mode_share,
+                    "posterior_alias_share_min_median": getattr(rs, "posterior_alias_share", None)})
+        peak, peak_src = hbm_peak_gbps(local)
     hs = out["host_setup"]
     if hs:
         tb = hs["elimination_order_s"] + hs["tree_build_s"] + hs["schedule_compile_s"]
@@ -366,10 +421,10 @@ def _main(real_stdout):
                                 "lcv_evals_per_step": diag["lcv_evals"] / psteps, "lcv_evals_f32_per_step": diag.get("lcv_evals_f32", 0) / psteps,
                                 "residual_evals_per_step": diag["residual_evals"] / psteps,
                                 "nonconverged_solves": diag["nonconverged"], "nan_results": diag["nan_results"]}
-    else:
+    elif a.full:
         out["roofline"] = {"bound": "hbm", "kernel": None, "achieved": None, "peak": peak, "unit": "GB/s", "frac": None, "traffic": None,
                            "peak_source": peak_src}
-    if rank == 0 and not a.no_cpu_baseline and world == 1 and dist is None:
+    if a.full and rank == 0 and not a.no_cpu_baseline and world == 1 and dist is None:
         # the OpenMP port parallelises over the independent ops of a stage; with hundreds of threads it is oversubscribed
         # (measured on the MI355X host: 16-32 threads is the sweet spot), so the baseline is the best of a few thread counts
         # and `cores` is the count actually used
@@ -400,7 +455,7 @@ def _main(real_stdout):
         if a.config in ("2", "2p"):
             out["vs_cpu_baseline_lazy_fits"] = value / v  # (the device leaves out the fits nothing reads; like for like below)
     out["lazy_bandwidth"] = True  # NBP_OPT_LAZY_BANDWIDTH: fits whose result nothing reads are not made (same posteriors, bit for bit)
-    if world == 1 and dist is None and not a.no_profile_pass:
+    if a.full and world == 1 and dist is None and not a.no_profile_pass:
         # the same solve with every bandwidth fit the reference makes (manikde! on every setBelief!): what the option saves
         rs.close()
         os.environ["NBP_NO_LAZY_BANDWIDTH"] = "1"
@@ -420,7 +475,7 @@ def _main(real_stdout):
             rse.close()
         finally:
             os.environ.pop("NBP_NO_LAZY_BANDWIDTH", None)
-    if world == 1 and dist is None and not a.no_10k and a.config == "2":
+    if a.full and world == 1 and dist is None and not a.no_10k and a.config == "2":
         # BASELINE.md config 2': the same chain with 10 000 variables is the graph the north-star target (>= 20x the CPU
         # baseline) is stated on; measured the same way (same --steps / --warmup), reported beside the headline value
         if not getattr(rs, "_closed", False):

@@ -32,7 +32,7 @@ def _check(line):
 
 
 def test_bench_single_process():
-    out = subprocess.run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--nvars", "200", "--cpu-sample-vars", "40"],
+    out = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "2", "--warmup", "1", "--nvars", "200", "--cpu-sample-vars", "40"],
                          cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, _why(out)
     d = _check(out.stdout.strip().splitlines()[-1])
@@ -42,10 +42,38 @@ def test_bench_single_process():
     assert ns["messages_per_step"] > 19000 and ns["vs_cpu_baseline"] > 20.0
 
 
+def test_bench_plain_run_times_the_steps_and_dumps_the_last_one(tmp_path):
+    """a plain run (no --full) sets up, warms up, times --steps steps and prints the headline line without what --full adds;
+    --dump-outputs writes the posteriors of the last timed step, and two runs with the same arguments write the same arrays"""
+    import numpy as np
+    dumps = []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        out = subprocess.run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--nvars", "200", "--dump-outputs", str(d)],
+                             cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, _why(out)
+        line = json.loads(out.stdout.strip().splitlines()[-1])
+        assert line["metric"] == "clique-messages/sec" and line["unit"] == "messages/s" and line["higher_is_better"] is True
+        assert line["dtype"] == "f64" and line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0
+        assert abs(line["value"] - line["config"]["messages_per_step"] * 1e3 / line["ms_per_step"]) < 1e-9 * line["value"]
+        for key in ("roofline", "cpu_baseline", "north_star_10k", "ms_per_step_every_fit", "posterior_max_mean_err"):
+            assert key not in line, key
+        names = sorted(p.name for p in d.iterdir())
+        assert names == ["posterior_bandwidth_euclid2.npy", "posterior_index_euclid2.npy", "posterior_points_euclid2.npy"], names
+        arrs = {n: np.load(d / n) for n in names}
+        assert all(a.dtype == np.float64 and np.isfinite(a).all() for a in arrs.values())
+        pts, idx = arrs["posterior_points_euclid2.npy"], arrs["posterior_index_euclid2.npy"]
+        assert pts.shape == (200, 200, 2) and np.array_equal(idx, np.arange(200.0))
+        assert np.abs(pts.mean(axis=1) - idx[:, None]).max() < 3.0  # the chain's truth: x_i at (i, i)
+        dumps.append(arrs)
+    for n in dumps[0]:
+        assert np.array_equal(dumps[0][n], dumps[1][n]), n
+
+
 def test_bench_sharded_path_one_rank():
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
-                          "--master-addr", "127.0.0.1", "--master-port", "29533", "bench.py", "--gpus", "1", "--steps", "2",
+                          "--master-addr", "127.0.0.1", "--master-port", "29533", "bench.py", "--full", "--gpus", "1", "--steps", "2",
                           "--warmup", "1", "--nvars", "200", "--force-dist", "--no-cpu-baseline"],
                          cwd=ROOT, capture_output=True, text=True, timeout=600, env=env)
     assert out.returncode == 0, _why(out)
@@ -60,7 +88,7 @@ def test_bench_ranks_sharing_one_gpu(config, size, scaling, world):
     line from rank 0 only."""
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world),
-                          "--master-addr", "127.0.0.1", "--master-port", str(29555 + world), "bench.py", "--gpus", str(world), "--steps", "2",
+                          "--master-addr", "127.0.0.1", "--master-port", str(29555 + world), "bench.py", "--full", "--gpus", str(world), "--steps", "2",
                           "--warmup", "1", "--config", config, "--nvars", size, "--dist-backend", "gloo", "--no-cpu-baseline"],
                          cwd=ROOT, capture_output=True, text=True, timeout=900, env=env)
     assert out.returncode == 0, _why(out)
@@ -79,7 +107,7 @@ def test_bench_launches_its_own_ranks_from_a_bare_environment():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT",
                                                                 "LOCAL_WORLD_SIZE", "GROUP_RANK", "ROLE_RANK", "TORCHELASTIC_RUN_ID")}
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
-    out = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--nvars", "300",
+    out = subprocess.run([sys.executable, "bench.py", "--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--nvars", "300",
                           "--dist-backend", "gloo", "--no-cpu-baseline", "--no-10k"],
                          cwd=ROOT, capture_output=True, text=True, timeout=900, env=env)
     assert out.returncode == 0, _why(out)
@@ -89,7 +117,7 @@ def test_bench_launches_its_own_ranks_from_a_bare_environment():
     assert d["n_gpus"] == 2 and d["scaling"] == "weak"
     assert d["exchange_transport"] == "staged" and d["rccl_ranks"] is None  # gloo ranks sharing one GPU: no RCCL communicator
     # and the one-rank line is what it was: no launcher, n_gpus 1, no exchange
-    out1 = subprocess.run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--nvars", "200", "--no-cpu-baseline", "--no-10k"],
+    out1 = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "2", "--warmup", "1", "--nvars", "200", "--no-cpu-baseline", "--no-10k"],
                           cwd=ROOT, capture_output=True, text=True, timeout=600, env=env)
     assert out1.returncode == 0, _why(out1)
     d1 = _check(out1.stdout.strip().splitlines()[-1])
@@ -110,7 +138,7 @@ def test_ranks_in_lock_step_are_deterministic_and_equal_to_the_sequential_fits()
     def run(port, extra_env):
         env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0", **extra_env)
         out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                              "--master-port", str(port), "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--config", "2", "--nvars", "300",
+                              "--master-port", str(port), "bench.py", "--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--config", "2", "--nvars", "300",
                               "--dist-backend", "gloo", "--no-cpu-baseline", "--no-profile-pass"],
                              cwd=ROOT, capture_output=True, text=True, timeout=900, env=env)
         assert out.returncode == 0, _why(out)
@@ -130,7 +158,7 @@ def test_bench_two_ranks_if_two_gpus():
         pytest.skip("needs two GPUs")
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
-                          "--master-addr", "127.0.0.1", "--master-port", "29544", "bench.py", "--gpus", "2", "--steps", "2",
+                          "--master-addr", "127.0.0.1", "--master-port", "29544", "bench.py", "--full", "--gpus", "2", "--steps", "2",
                           "--warmup", "1", "--nvars", "300"],
                          cwd=ROOT, capture_output=True, text=True, timeout=900, env=env)
     assert out.returncode == 0, _why(out)

@@ -189,7 +189,7 @@ def test_whole_solve_posteriors_do_not_depend_on_the_bracketing(config, nvars):
     shas = []
     for f64 in ("0", "1"):
         env = dict(os.environ, NBP_BENCH_SHA="1", NBP_FIT_F64=f64)
-        cmd = [sys.executable, os.path.join(root, "bench.py"), "--config", config, "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--no-10k",
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--config", config, "--steps", "1", "--warmup", "0", "--full", "--no-cpu-baseline", "--no-10k",
                "--no-profile-pass"] + (["--nvars", str(nvars)] if nvars else [])
         out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env)
         assert out.returncode == 0, out.stderr[-2000:]

@@ -8,8 +8,8 @@ R=${GRAFT_REPO_ROOT:-$PWD}
 O=$R/gpurun_out/$TAG
 rm -rf $O; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-python $R/bench.py > $O/bench_plain.json 2> $O/bench_plain.err
-python $R/bench.py --fused-min 256 --no-cpu-baseline --no-10k > $O/bench_fused.json 2> $O/bench_fused.err
+python $R/bench.py --full > $O/bench_plain.json 2> $O/bench_plain.err
+python $R/bench.py --full --fused-min 256 --no-cpu-baseline --no-10k > $O/bench_fused.json 2> $O/bench_fused.err
 rocprofv3 --kernel-trace --stats -d $O/trace -- python $R/bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-10k --no-profile-pass > $O/bench_under_rocprof.json 2> $O/trace.err
 python $R/tools/summarize_trace.py $O/trace 5 > $O/bench_timed_region_summary.txt
 python $R/tools/kernel_stats.py $O/trace > $O/bench_kernel_stats.csv
@@ -23,7 +23,7 @@ tools/pmc_quick.sh $TAG/pmc_default NBP_X=1 > $O/pmc_traffic.txt 2>&1
 tools/pmc_quick.sh $TAG/pmc_fused NBP_FUSED_MIN=256 > $O/pmc_traffic_fused.txt 2>&1
 cd /tmp
 for c in 3 4 5; do
-  python $R/bench.py --config $c --steps 5 --warmup 2 --no-cpu-baseline > $O/bench_config$c.json 2> $O/bench_config$c.err
+  python $R/bench.py --full --config $c --steps 5 --warmup 2 --no-cpu-baseline > $O/bench_config$c.json 2> $O/bench_config$c.err
   rocprofv3 --kernel-trace --stats -d $O/trace_c$c -- python $R/bench.py --config $c --steps 3 --warmup 1 --no-cpu-baseline --no-profile-pass > /dev/null 2> $O/trace_c$c.err
   python $R/tools/summarize_trace.py $O/trace_c$c 3 > $O/bench_config${c}_timed_region_summary.txt
   python $R/tools/kernel_stats.py $O/trace_c$c > $O/bench_config${c}_kernel_stats.csv

@@ -6,9 +6,9 @@ R=${GRAFT_REPO_ROOT:-$PWD}
 O=$R/gpurun_out/$TAG
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-python $R/bench.py > $O/bench_plain.json 2> $O/bench_plain.err
-python $R/bench.py --fused-min 256 --no-cpu-baseline --no-10k > $O/bench_fused.json 2> $O/bench_fused.err
-for c in 3 4 5; do python $R/bench.py --config $c --steps 5 --warmup 2 --no-cpu-baseline > $O/bench_config$c.json 2> $O/bench_config$c.err; done
+python $R/bench.py --full > $O/bench_plain.json 2> $O/bench_plain.err
+python $R/bench.py --full --fused-min 256 --no-cpu-baseline --no-10k > $O/bench_fused.json 2> $O/bench_fused.err
+for c in 3 4 5; do python $R/bench.py --full --config $c --steps 5 --warmup 2 --no-cpu-baseline > $O/bench_config$c.json 2> $O/bench_config$c.err; done
 python - <<PY
 import json
 for f in ("bench_plain", "bench_fused", "bench_config3", "bench_config4", "bench_config5"):

@@ -2,7 +2,7 @@
 # The same differential check over particle counts (the kernels' geometries -- rows of a fit, waves of a workgroup, helper lanes --
 # follow N): a 400-variable Euclid(2) chain and a 300-pose circular chain at several N under the geometry switches.
 R=${GRAFT_REPO_ROOT:-$PWD}
-sha() { env "$@" NBP_BENCH_SHA=1 python $R/bench.py --config $C --nvars $NV --particles $N --steps 1 --warmup 0 --no-cpu-baseline --no-10k --no-profile-pass 2>&1 >/dev/null | grep -o "sha=[0-9a-f]*\|Error.*\|error.*" | head -1; }
+sha() { env "$@" NBP_BENCH_SHA=1 python $R/bench.py --full --config $C --nvars $NV --particles $N --steps 1 --warmup 0 --no-cpu-baseline --no-10k --no-profile-pass 2>&1 >/dev/null | grep -o "sha=[0-9a-f]*\|Error.*\|error.*" | head -1; }
 for C in 2 3; do
   NV=$([ $C == 2 ] && echo 400 || echo 300)
   for N in 64 100 128 192 256 257 300 320 500; do

@@ -1,7 +1,7 @@
 #!/bin/bash
 # the differential check on SE(2) (config 4's shape, a small lattice) and on the Euclid(3) mixture chain (config 5's shape)
 R=${GRAFT_REPO_ROOT:-$PWD}
-sha() { env "$@" NBP_BENCH_SHA=1 python $R/bench.py --config $C --nvars $NV --particles $N --steps 1 --warmup 0 --no-cpu-baseline --no-10k --no-profile-pass 2>&1 >/dev/null | grep -o "sha=[0-9a-f]*\|Error.*" | head -1; }
+sha() { env "$@" NBP_BENCH_SHA=1 python $R/bench.py --full --config $C --nvars $NV --particles $N --steps 1 --warmup 0 --no-cpu-baseline --no-10k --no-profile-pass 2>&1 >/dev/null | grep -o "sha=[0-9a-f]*\|Error.*" | head -1; }
 for C in 4 5; do
   NV=$([ $C == 4 ] && echo 8 || echo 300)
   for N in 100 200 257 300; do

@@ -2,7 +2,7 @@
 # Whole-solve posterior sha of BASELINE configurations under the library's geometry switches: every alternative kernel path claims
 # the shipped path's particles bit for bit -- here checked on full solves.   Usage (GPU box): tools/exp/whole_solve_sha_switches.sh
 R=${GRAFT_REPO_ROOT:-$PWD}
-sha() { env "$@" NBP_BENCH_SHA=1 python $R/bench.py --config $C --steps 2 --warmup 1 --no-cpu-baseline --no-10k --no-profile-pass 2>&1 >/dev/null | grep -o "sha=[0-9a-f]*"; }
+sha() { env "$@" NBP_BENCH_SHA=1 python $R/bench.py --full --config $C --steps 2 --warmup 1 --no-cpu-baseline --no-10k --no-profile-pass 2>&1 >/dev/null | grep -o "sha=[0-9a-f]*"; }
 for C in ${CONFIGS:-2 3 4 5}; do
   base=$(sha NBP_X=1)
   echo "config $C: shipped $base"

@@ -10,7 +10,7 @@ cd /tmp && export TMPDIR=/tmp
 B="python $R/bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-10k --no-profile-pass"
 for p in FETCH_SIZE WRITE_SIZE; do env "$@" rocprofv3 --pmc $p -d $O/pmc/$p -- $B > $O/bench_$p.json 2> $O/pmc_$p.err; done
 env "$@" rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum -d $O/pmc/TCC -- $B > /dev/null 2> $O/pmc_TCC.err
-ALG=$(env "$@" python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-10k | python -c "import json,sys; print(json.load(sys.stdin)['roofline']['alg_bytes_per_step'])")
+ALG=$(env "$@" python $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-10k | python -c "import json,sys; print(json.load(sys.stdin)['roofline']['alg_bytes_per_step'])")
 python $R/tools/pmc_traffic.py $O/pmc 5 200 $O/pmc_traffic.json $ALG > /dev/null 2> $O/pmc_traffic.err
 rm -rf $O/pmc
 python - <<EOF
