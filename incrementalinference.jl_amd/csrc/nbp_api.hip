@@ -283,7 +283,11 @@ nbp_status nbp_ctx_create(int32_t device, int32_t N, int32_t n_slots, void *aren
                         (const void *)nbp_product_kernel_m4_se, (const void *)nbp_product_kernel_t2_e1_xs, (const void *)nbp_product_kernel_t2_e2_xs,
                         (const void *)nbp_product_kernel_t2_e3_xs, (const void *)nbp_product_kernel_t2_ci_xs, (const void *)nbp_product_kernel_t2_se_xs,
                         (const void *)nbp_product_kernel_m4_e1_xs, (const void *)nbp_product_kernel_m4_e2_xs, (const void *)nbp_product_kernel_m4_e3_xs,
-                        (const void *)nbp_product_kernel_m4_ci_xs, (const void *)nbp_product_kernel_m4_se_xs})
+                        (const void *)nbp_product_kernel_m4_ci_xs, (const void *)nbp_product_kernel_m4_se_xs,
+                        (const void *)nbp_product_kernel_y32_e1, (const void *)nbp_product_kernel_y32_e2, (const void *)nbp_product_kernel_y32_e3,
+                        (const void *)nbp_product_kernel_y32_ci, (const void *)nbp_product_kernel_y32_se, (const void *)nbp_product_kernel_l8_e1,
+                        (const void *)nbp_product_kernel_l8_e2, (const void *)nbp_product_kernel_l8_e3, (const void *)nbp_product_kernel_l8_ci,
+                        (const void *)nbp_product_kernel_l8_se})
     HIPCHK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   HIPCHK(hipFuncSetAttribute((const void *)nbp_bandwidth_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   HIPCHK(hipFuncSetAttribute((const void *)nbp_prep_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
@@ -978,14 +982,18 @@ static nbp_status launch_prep(nbp_ctx *c, const int32_t *bw_slots, const int32_t
 
 // product launch geometry: HL helper lanes per sample (64/HL samples per wave), workgroups of `wpb` <= 8
 // waves, grid.y = G workgroups per product.  Latency mode (the launch cannot fill the chip): HL = 32 (fewer than 16
-// products; NBP_PRODUCT_HL32_MAX) or 8 and several small workgroups per product; throughput mode: HL = 2 so that one
+// products; NBP_PRODUCT_HL32_MAX) or 8 and several small workgroups per product (below NBP_PRODUCT_HL2_MIN products: the HL = 4
+// geometry between them is reached with NBP_PRODUCT_HL4_MIN only); throughput mode: HL = 2 so that one
 // workgroup covers all samples and the node statistics of a product are computed once.
 // `mani`: the manifold of a single-manifold batch (0: mixed; < 0: size for the widest workgroup any kernel takes)
 static void product_geometry(nbp_ctx *c, int n, int *HL, int *wpb, int *G, int mani) {
   if (c->geom_n) n = c->geom_n;  // one half of a two-stream round: the geometry of the whole batch
   static const int hl2_min = getenv("NBP_PRODUCT_HL2_MIN") ? atoi(getenv("NBP_PRODUCT_HL2_MIN")) : 192;
   static const int hl32_max = getenv("NBP_PRODUCT_HL32_MAX") ? atoi(getenv("NBP_PRODUCT_HL32_MAX")) : 15;
-  static const int hl4_min = getenv("NBP_PRODUCT_HL4_MIN") ? atoi(getenv("NBP_PRODUCT_HL4_MIN")) : 80;  // (48 until round 4: 66-product rounds of config 2 run 147 instead of 207 us with eight helpers)
+  // four helper lanes from hl4_min products on: never by default since the single-manifold latency instances (80 until then --
+  // 48 until round 4 -- and 128 / 160 / 192 measured after: config 2 17.18 / 17.12 / 16.94 / 16.98 ms, config 3 49.39 / 49.17 /
+  // 49.04 / 48.73, config 4 325.2 / - / 322.9 / 321.8, config 5 341.1 / - / 341.2 / 341.4; profiles/r07_latency_product_instances.txt)
+  static const int hl4_min = getenv("NBP_PRODUCT_HL4_MIN") ? atoi(getenv("NBP_PRODUCT_HL4_MIN")) : 192;
   *HL = n >= hl2_min ? 2 : (n >= hl4_min ? 4 : (n >= 16 ? 8 : (n > hl32_max ? 16 : 32)));
   // latency geometries: workgroups of FOUR waves (one per SIMD of their CU; six until round 4: config 3's products 25.9 -> 24.4 ms,
   // config 2's 7.93 -> 7.77, config 4's 110.6 -> 107.8; two / three / five waves measured worse than four)
@@ -1034,7 +1042,24 @@ typedef void (*nbp_product_fn)(const nbp_product_desc *, double *, const double 
 // the kernel of a product launch: HL helper lanes per sample; `mani` != 0: every multi-density product of the batch lives
 // on that manifold and has only full inputs (the throughput variants then run the single-instantiation kernels)
 // `w1`: the launch has at most one workgroup (of at most four waves) per CU -- the latency instances that own their SIMDs
-static nbp_product_fn product_kernel_for(int HL, int mani, bool xs = false, bool w1 = false) {
+// `big`: the node statistics live in global memory (product_is_big) -- the generic latency kernels alone have that path
+static nbp_product_fn product_kernel_for(int HL, int mani, bool xs = false, bool w1 = false, bool big = false) {
+  // the single-manifold latency instances (NBP_NO_UNIFORM_LATENCY_PRODUCTS: the generic kernels, for A/B runs and tests)
+  static const bool lat_uni = getenv("NBP_NO_UNIFORM_LATENCY_PRODUCTS") == nullptr;
+  if (lat_uni && !big && mani > 0 && (HL == 32 || HL == 8)) {
+    switch (mani * 64 + HL) {
+    case NBP_EUCLID1 * 64 + 32: return nbp_product_kernel_y32_e1;
+    case NBP_EUCLID2 * 64 + 32: return nbp_product_kernel_y32_e2;
+    case NBP_EUCLID3 * 64 + 32: return nbp_product_kernel_y32_e3;
+    case NBP_CIRCULAR * 64 + 32: return nbp_product_kernel_y32_ci;
+    case NBP_SE2 * 64 + 32: return nbp_product_kernel_y32_se;
+    case NBP_EUCLID1 * 64 + 8: return nbp_product_kernel_l8_e1;
+    case NBP_EUCLID2 * 64 + 8: return nbp_product_kernel_l8_e2;
+    case NBP_EUCLID3 * 64 + 8: return nbp_product_kernel_l8_e3;
+    case NBP_CIRCULAR * 64 + 8: return nbp_product_kernel_l8_ci;
+    case NBP_SE2 * 64 + 8: return nbp_product_kernel_l8_se;
+    }
+  }
   if (HL == 32) return w1 ? nbp_product_kernel_y32_w1 : nbp_product_kernel_y32;
   if (HL == 16) return w1 ? nbp_product_kernel_x16_w1 : nbp_product_kernel_x16;
   if (HL == 8) return w1 ? nbp_product_kernel_l8_w1 : nbp_product_kernel_l8;
@@ -1166,7 +1191,7 @@ static nbp_status launch_products(nbp_ctx *c, const nbp_product_desc *dev, int n
   (void)hipGetLastError();
   static const int w1_max = getenv("NBP_PRODUCT_W1_MAX") ? atoi(getenv("NBP_PRODUCT_W1_MAX")) : 256;  // workgroups (= CUs of the chip)
   const bool w1 = HL >= 8 && TB <= 256 && (long)n * G <= w1_max && !c->geom_n;
-  hipLaunchKernelGGL(product_kernel_for(HL, mani, xs, w1), dim3(n, G), dim3(TB), lds, c->stream, dev, c->arena, c->ws, flagsF, gs, c->N, c->S, c->side, c->T);
+  hipLaunchKernelGGL(product_kernel_for(HL, mani, xs, w1, big), dim3(n, G), dim3(TB), lds, c->stream, dev, c->arena, c->ws, flagsF, gs, c->N, c->S, c->side, c->T);
   HIPCHK(hipGetLastError());
   return toc(c, c->ev[2]);
 }

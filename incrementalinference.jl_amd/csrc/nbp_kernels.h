@@ -21,6 +21,7 @@
 #define NBP_TU_PRODUNI4 128 // product kernels, one manifold per instance, four helper lanes (the two-lane ones: NBP_TU_PRODUNI)
 #define NBP_TU_PREPW5 256   // bandwidth fits + KD builds at five waves per SIMD (rows of 4k + 1 waves: N = 257 .. 320)
 #define NBP_TU_PROPWAVE 512 // proposal kernels, one wave per proposal (chip-filling launches of simple Euclidean batches)
+#define NBP_TU_PRODLATUNI 1024 // product kernels, latency geometries (y32, l8), one manifold per instance
 #ifndef NBP_TU
 #define NBP_TU 0xFFFF
 #endif
@@ -1199,7 +1200,10 @@ struct nbp_fused_io {
 // FUSED: 0 = densities from the KD workspaces; 1 = the fused update kernel (everything in LDS, `fio` made by the caller);
 //        2 = the _xs product kernels (sorted coordinates staged in LDS, `fio->L` laid out by product_lds_layout)
 // nch (throughput geometries, HL <= 4, not the update kernel): chunks per helper range, their sums kept in LDS (`L.ck`)
-template <int MANI, bool PARTIAL, int HL, bool BIG, int FUSED = 0>
+// PRENORM (the single-manifold latency instances, HL >= 8): the normals of samplePoint! for the first 2 x HL passes are made up
+// front, those of pass ps by helper lane (ps - 1) % HL of the sample, and handed to the sample's lanes by a shuffle at the top of
+// the pass -- the same values, off the dependent chain of the passes
+template <int MANI, bool PARTIAL, int HL, bool BIG, int FUSED = 0, bool PRENORM = false>
 __device__ __forceinline__ void product_body(const nbp_product_desc *d, double *arena, const double *ws, int kdF, double *gstats,
                                              int N, int64_t S, int32_t *side, const nbp_levels &T, double *smem,
                                              const nbp_fused_io *fio = nullptr, bool all_levels = false, int nch = 2, bool lay_circ = true) {
@@ -1259,17 +1263,39 @@ __device__ __forceinline__ void product_body(const nbp_product_desc *d, double *
   int npass = 1;
   for (int n2_ = N; n2_ > 1; n2_ >>= 1) npass++;
   if (npass < T.L) npass = T.L;
+  static_assert(!PRENORM || HL >= 8, "PRENORM: the latency geometries");
+  constexpr int NPRE = PRENORM ? (HL >= 16 ? 1 : 2) : 1;  // passes per helper lane (N = 200: ten passes make normals)
+  double pre[NPRE][3];
+#pragma unroll
+  for (int q = 0; q < NPRE; q++) {
+    pre[q][0] = pre[q][1] = pre[q][2] = 0.0;
+    const int pp = q * HL + h + 1;
+    if (PRENORM && live && pp <= npass + 1) {
+      const uint32_t purpose = (pp <= npass) ? PURP_PLEVEL : PURP_PFINAL, k0 = (pp <= npass) ? (uint32_t)(2 * pp) : 0u;
+      const double2 na = normal_pair_call(d->seed, (uint32_t)s, purpose, k0);
+      pre[q][0] = na.x;
+      pre[q][1] = na.y;
+      if (D > 2) pre[q][2] = normal_pair_call(d->seed, (uint32_t)s, purpose, k0 + 1).x;
+    }
+  }
   int Lc = 0;  // the coarse levels 0 .. Lc share one staging (below): as many as one row of the statistics holds
   while (Lc + 1 <= T.L && T.off[Lc + 1] + T.cnt[Lc + 1] <= N) Lc++;
   for (int ps = 0; ps <= npass + 1; ps++) {
     const int l = ps < T.L ? ps : T.L;  // the tree level of this pass
     if (ps > 0 && live) {  // samplePoint!
-      double n0, n1, n2 = 0, n3 = 0;
-      const uint32_t purpose = (ps <= npass) ? PURP_PLEVEL : PURP_PFINAL, k0 = (ps <= npass) ? (uint32_t)(2 * ps) : 0u;
-      const double2 na = normal_pair_call(d->seed, (uint32_t)s, purpose, k0);
-      n0 = na.x;
-      n1 = na.y;
-      if (D > 2) { const double2 nb = normal_pair_call(d->seed, (uint32_t)s, purpose, k0 + 1); n2 = nb.x; n3 = nb.y; }
+      double n0, n1 = 0, n2 = 0, n3 = 0;
+      if (PRENORM && ps - 1 < NPRE * HL) {
+        const int q = (ps - 1) / HL, src = (ps - 1) % HL;  // (q, src: the same for the whole wave)
+        n0 = __shfl(q == 0 ? pre[0][0] : pre[NPRE - 1][0], src, HL);
+        if (D > 1) n1 = __shfl(q == 0 ? pre[0][1] : pre[NPRE - 1][1], src, HL);
+        if (D > 2) n2 = __shfl(q == 0 ? pre[0][2] : pre[NPRE - 1][2], src, HL);
+      } else {
+        const uint32_t purpose = (ps <= npass) ? PURP_PLEVEL : PURP_PFINAL, k0 = (ps <= npass) ? (uint32_t)(2 * ps) : 0u;
+        const double2 na = normal_pair_call(d->seed, (uint32_t)s, purpose, k0);
+        n0 = na.x;
+        n1 = na.y;
+        if (D > 2) { const double2 nb = normal_pair_call(d->seed, (uint32_t)s, purpose, k0 + 1); n2 = nb.x; n3 = nb.y; }
+      }
       (void)n3;
       const double nn[3] = {n0, n1, n2};
 #pragma unroll
@@ -1804,7 +1830,8 @@ __device__ __forceinline__ void product_kernel_body(const nbp_product_desc *desc
 // A batch whose multi-density products all live on ONE manifold and have no partial inputs (every stage of a
 // homogeneous graph) runs a kernel that holds that one instantiation: the register allocation of the throughput
 // variants is then the body's own need instead of the maximum over all manifolds (scratch per lane at 4 waves per
-// SIMD: generic 308-328 B, Euclid(1) 0, Euclid(2) 64 B, Euclid(3) 52 B).
+// SIMD: generic 308-328 B, Euclid(1) 0, Euclid(2) 64 B, Euclid(3) 52 B).  The latency geometries (HL = 8 / 32) run it too
+// when the node statistics fit the LDS (never BIG, never XS).
 // XS: the workgroup stages the sorted, centred coordinates of its F <= NBP_FUSED_MAXF densities in LDS (F x D x N doubles
 // behind the product's own areas) and takes the node sums of every level from there -- the same leaf-order sums kd_build
 // would have left in the workspace -- so that a KD workspace carries 4 KB per density (coordinates, centres, permutation)
@@ -1816,7 +1843,8 @@ __device__ __forceinline__ void product_kernel_uniform(const nbp_product_desc *d
   const nbp_product_desc *d = descs + blockIdx.x;
   const bool all_levels = (kdF & NBP_PROD_ALL_LEVELS) != 0;
   const int nch = NBP_PROD_NCH(kdF);
-  constexpr bool lay_circ = (MANI == NBP_CIRCULAR || MANI == NBP_SE2);  // (the host lays the LDS out the same way: launch_products)
+  // (the host lays the LDS out the same way: product_lays_circ in nbp_api.hip -- the latency geometries always keep the rows)
+  constexpr bool lay_circ = HL >= 8 || MANI == NBP_CIRCULAR || MANI == NBP_SE2;
   kdF &= 0xFFFF;
   if (d->nfactors == 1) { product_passthrough(d, arena, N, S, side); return; }
   product_write_ipc(d, arena, N, S);
@@ -1848,7 +1876,7 @@ __device__ __forceinline__ void product_kernel_uniform(const nbp_product_desc *d
     __syncthreads();
     product_body<MANI, false, HL, false, 2>(d, arena, ws, kdF, gstats, N, S, side, T, smem, &fio, false, nch, lay_circ);
   } else
-    product_body<MANI, false, HL, false>(d, arena, ws, kdF, gstats, N, S, side, T, smem, nullptr, all_levels, nch, lay_circ);  // HL = 4 / 2: never BIG (launch_products)
+    product_body<MANI, false, HL, false, 0, (HL >= 8)>(d, arena, ws, kdF, gstats, N, S, side, T, smem, nullptr, all_levels, nch, lay_circ);  // never BIG (launch_products)
 }
 
 // Entry points: the latency variants (HL = 32 for fewer than 16 products, 16 on request, HL = 8; few workgroups in flight) and the
@@ -1939,6 +1967,32 @@ NBP_PRODUCT_UNIFORM(nbp_product_kernel_m4_e2, NBP_EUCLID2, 4)
 NBP_PRODUCT_UNIFORM(nbp_product_kernel_m4_e3, NBP_EUCLID3, 4)
 NBP_PRODUCT_UNIFORM(nbp_product_kernel_m4_ci, NBP_CIRCULAR, 4)
 NBP_PRODUCT_UNIFORM(nbp_product_kernel_m4_se, NBP_SE2, 4)
+// The latency geometries of a single-manifold batch whose node statistics fit the LDS (every launch at the top of a homogeneous
+// tree): the same product_body the generic y32 / l8 run for it, without the other manifolds, the partial inputs and the
+// global-memory statistics.  The generic latency kernels inline sixteen bodies and hold 248-256 VGPRs and ~2 500 spilled SGPRs
+// in ~650 KB of code each; an instance here holds its own body only (and the normals of PRENORM): 116-177 VGPRs on the Euclidean
+// manifolds and the circle, 219-223 on SE(2), no scratch (profiles/r07_kernel_resources.txt).  No `_w1` form: at launch bound 256
+// the compiler gives an instance the registers it takes at 512 (SE(2): 225 instead of 211 before PRENORM, the same two waves per
+// SIMD) -- the generic kernels have it only to keep their 16 B of scratch per lane away.
+#if NBP_TU & NBP_TU_PRODLATUNI
+#define NBP_PRODUCT_LATENCY_UNIFORM(NAME, MANI, HL_)                                                  \
+  __global__ void __launch_bounds__(512) NAME(NBP_PRODUCT_ARGS) {                                     \
+    extern __shared__ double smem[];                                                                  \
+    product_kernel_uniform<MANI, HL_, false>(descs, arena, ws, kdF, gstats, N, S, side, T, smem);     \
+  }
+#else
+#define NBP_PRODUCT_LATENCY_UNIFORM(NAME, MANI, HL_) __global__ void NAME(NBP_PRODUCT_ARGS);
+#endif
+NBP_PRODUCT_LATENCY_UNIFORM(nbp_product_kernel_y32_e1, NBP_EUCLID1, 32)
+NBP_PRODUCT_LATENCY_UNIFORM(nbp_product_kernel_y32_e2, NBP_EUCLID2, 32)
+NBP_PRODUCT_LATENCY_UNIFORM(nbp_product_kernel_y32_e3, NBP_EUCLID3, 32)
+NBP_PRODUCT_LATENCY_UNIFORM(nbp_product_kernel_y32_ci, NBP_CIRCULAR, 32)
+NBP_PRODUCT_LATENCY_UNIFORM(nbp_product_kernel_y32_se, NBP_SE2, 32)
+NBP_PRODUCT_LATENCY_UNIFORM(nbp_product_kernel_l8_e1, NBP_EUCLID1, 8)
+NBP_PRODUCT_LATENCY_UNIFORM(nbp_product_kernel_l8_e2, NBP_EUCLID2, 8)
+NBP_PRODUCT_LATENCY_UNIFORM(nbp_product_kernel_l8_e3, NBP_EUCLID3, 8)
+NBP_PRODUCT_LATENCY_UNIFORM(nbp_product_kernel_l8_ci, NBP_CIRCULAR, 8)
+NBP_PRODUCT_LATENCY_UNIFORM(nbp_product_kernel_l8_se, NBP_SE2, 8)
 
 static inline size_t nbp_product_lds_bytes(int F, int D, int N, int SPB, bool big, size_t CK = 0, bool circ = true) {
   return product_lds_layout(F, D, N, SPB, big, nullptr, nullptr, 0, CK, circ);
