@@ -128,11 +128,39 @@ struct nbp_ctx {
   hipEvent_t pipe_ev[2] = {nullptr, nullptr};
   int pipe_min = 1 << 30;
   int geom_n = 0, geom_blocks = 0;
+  // product launches (product_plan): NBP_PRODUCT_HL2_MIN = smallest batch in the throughput geometry, NBP_PRODUCT_NCH = chunks
+  // per helper range (0: as many as the LDS takes), NBP_PRODUCT_ALL_LEVELS_HL = fewest helper lanes that stage every level at
+  // once; NBP_NO_XS_PRODUCTS: node sums from the KD workspace only; NBP_NO_UNIFORM_LATENCY_PRODUCTS: the generic latency
+  // kernels (for A/B runs and tests)
+  int prod_hl2_min = 192, prod_nch = 0, prod_all_levels_hl = 8;
+  bool prod_xs = true, prod_lat_uni = true;
   // timing: 0 proposal, 1 prep, 2 product, 3 plain bandwidth, 4 fused update kernel
   bool timing = false;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev[5];
   double ms[5] = {0, 0, 0, 0, 0};
   int64_t nl[5] = {0, 0, 0, 0, 0};
+};
+
+// The product kernels: helper lanes per sample, the manifold of a single-manifold instance (0: any mix), node sums from the
+// sorted coordinates (`xs`), launch bound for at most one workgroup per CU (`w1`).  product_plan picks its kernel here.
+typedef void (*nbp_product_fn)(const nbp_product_desc *, double *, const double *, int, double *, int, int64_t, int32_t *, nbp_levels);
+struct nbp_product_kernel_row { nbp_product_fn fn; int HL, mani; bool xs, w1; };
+static const nbp_product_kernel_row NBP_PRODUCT_KERNELS[] = {
+    {nbp_product_kernel_y32, 32, 0, false, false},           {nbp_product_kernel_y32_w1, 32, 0, false, true},
+    {nbp_product_kernel_l8, 8, 0, false, false},             {nbp_product_kernel_l8_w1, 8, 0, false, true},
+    {nbp_product_kernel_t2, 2, 0, false, false},
+    {nbp_product_kernel_y32_e1, 32, NBP_EUCLID1, false, false}, {nbp_product_kernel_y32_e2, 32, NBP_EUCLID2, false, false},
+    {nbp_product_kernel_y32_e3, 32, NBP_EUCLID3, false, false}, {nbp_product_kernel_y32_ci, 32, NBP_CIRCULAR, false, false},
+    {nbp_product_kernel_y32_se, 32, NBP_SE2, false, false},
+    {nbp_product_kernel_l8_e1, 8, NBP_EUCLID1, false, false},   {nbp_product_kernel_l8_e2, 8, NBP_EUCLID2, false, false},
+    {nbp_product_kernel_l8_e3, 8, NBP_EUCLID3, false, false},   {nbp_product_kernel_l8_ci, 8, NBP_CIRCULAR, false, false},
+    {nbp_product_kernel_l8_se, 8, NBP_SE2, false, false},
+    {nbp_product_kernel_t2_e1, 2, NBP_EUCLID1, false, false},   {nbp_product_kernel_t2_e2, 2, NBP_EUCLID2, false, false},
+    {nbp_product_kernel_t2_e3, 2, NBP_EUCLID3, false, false},   {nbp_product_kernel_t2_ci, 2, NBP_CIRCULAR, false, false},
+    {nbp_product_kernel_t2_se, 2, NBP_SE2, false, false},
+    {nbp_product_kernel_t2_e1_xs, 2, NBP_EUCLID1, true, false}, {nbp_product_kernel_t2_e2_xs, 2, NBP_EUCLID2, true, false},
+    {nbp_product_kernel_t2_e3_xs, 2, NBP_EUCLID3, true, false}, {nbp_product_kernel_t2_ci_xs, 2, NBP_CIRCULAR, true, false},
+    {nbp_product_kernel_t2_se_xs, 2, NBP_SE2, true, false},
 };
 
 static int manifold_dim_h(int m) { return m == NBP_SE2 ? 3 : (m == NBP_CIRCULAR ? 1 : m); }
@@ -266,29 +294,16 @@ nbp_status nbp_ctx_create(int32_t device, int32_t N, int32_t n_slots, void *aren
   HIPCHK(hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking));
   for (int i = 0; i < 2; i++) HIPCHK(hipEventCreateWithFlags(&c->pipe_ev[i], hipEventDisableTiming));
   if (getenv("NBP_FUSED_P1_MIN")) c->fused_p1_min = atoi(getenv("NBP_FUSED_P1_MIN"));
+  if (getenv("NBP_PRODUCT_HL2_MIN")) c->prod_hl2_min = atoi(getenv("NBP_PRODUCT_HL2_MIN"));
+  if (getenv("NBP_PRODUCT_NCH")) c->prod_nch = atoi(getenv("NBP_PRODUCT_NCH"));
+  if (getenv("NBP_PRODUCT_ALL_LEVELS_HL")) c->prod_all_levels_hl = atoi(getenv("NBP_PRODUCT_ALL_LEVELS_HL"));
+  c->prod_xs = getenv("NBP_NO_XS_PRODUCTS") == nullptr;
+  c->prod_lat_uni = getenv("NBP_NO_UNIFORM_LATENCY_PRODUCTS") == nullptr;
   nbp_status rc = build_levels(c);
   if (rc != NBP_OK) return rc;
-  // allow the full 160 KiB LDS for the product kernel
-  HIPCHK(hipFuncSetAttribute((const void *)nbp_product_kernel_x16, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIPCHK(hipFuncSetAttribute((const void *)nbp_product_kernel_y32, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIPCHK(hipFuncSetAttribute((const void *)nbp_product_kernel_l8, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIPCHK(hipFuncSetAttribute((const void *)nbp_product_kernel_x16_w1, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIPCHK(hipFuncSetAttribute((const void *)nbp_product_kernel_y32_w1, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIPCHK(hipFuncSetAttribute((const void *)nbp_product_kernel_l8_w1, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIPCHK(hipFuncSetAttribute((const void *)nbp_product_kernel_m4, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIPCHK(hipFuncSetAttribute((const void *)nbp_product_kernel_t2, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  for (const void *k : {(const void *)nbp_product_kernel_t2_e1, (const void *)nbp_product_kernel_t2_e2, (const void *)nbp_product_kernel_t2_e3,
-                        (const void *)nbp_product_kernel_t2_ci, (const void *)nbp_product_kernel_t2_se, (const void *)nbp_product_kernel_m4_e1,
-                        (const void *)nbp_product_kernel_m4_e2, (const void *)nbp_product_kernel_m4_e3, (const void *)nbp_product_kernel_m4_ci,
-                        (const void *)nbp_product_kernel_m4_se, (const void *)nbp_product_kernel_t2_e1_xs, (const void *)nbp_product_kernel_t2_e2_xs,
-                        (const void *)nbp_product_kernel_t2_e3_xs, (const void *)nbp_product_kernel_t2_ci_xs, (const void *)nbp_product_kernel_t2_se_xs,
-                        (const void *)nbp_product_kernel_m4_e1_xs, (const void *)nbp_product_kernel_m4_e2_xs, (const void *)nbp_product_kernel_m4_e3_xs,
-                        (const void *)nbp_product_kernel_m4_ci_xs, (const void *)nbp_product_kernel_m4_se_xs,
-                        (const void *)nbp_product_kernel_y32_e1, (const void *)nbp_product_kernel_y32_e2, (const void *)nbp_product_kernel_y32_e3,
-                        (const void *)nbp_product_kernel_y32_ci, (const void *)nbp_product_kernel_y32_se, (const void *)nbp_product_kernel_l8_e1,
-                        (const void *)nbp_product_kernel_l8_e2, (const void *)nbp_product_kernel_l8_e3, (const void *)nbp_product_kernel_l8_ci,
-                        (const void *)nbp_product_kernel_l8_se})
-    HIPCHK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  // allow the full 160 KiB LDS for the product kernels
+  for (const nbp_product_kernel_row &k : NBP_PRODUCT_KERNELS)
+    HIPCHK(hipFuncSetAttribute((const void *)k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   HIPCHK(hipFuncSetAttribute((const void *)nbp_bandwidth_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   HIPCHK(hipFuncSetAttribute((const void *)nbp_prep_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   HIPCHK(hipFuncSetAttribute((const void *)nbp_bandwidth_kernel_spec<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
@@ -911,29 +926,147 @@ static int lcv_helpers(nbp_ctx *c, int nblocks) {
   return P;
 }
 
-// nbp_prep_kernel: pending bandwidth fits + KD builds of this product batch, one launch
 static int coords_of(const int32_t *manis, size_t n) {
   int cds = 0;
   for (size_t i = 0; i < n; i++) cds += manifold_dim_h(manis[i]);
   return cds;
 }
-static void product_geometry(nbp_ctx *c, int n, int *HL, int *wpb, int *G, int mani = 0);
+// ---- product launches ----
+// Geometry: HL helper lanes per sample (64/HL samples per wave), workgroups of `wpb` waves, grid.y = G workgroups per product.
+// Latency mode (the launch cannot fill the chip): HL = 32 for fewer than 16 products, else HL = 8, with several small
+// workgroups per product (below NBP_PRODUCT_HL2_MIN products); throughput mode: HL = 2 so that one workgroup covers all samples
+// and the node statistics of a product are computed once.
+// Latency geometries: workgroups of FOUR waves (one per SIMD of their CU; six until round 4: config 3's products 25.9 -> 24.4 ms,
+// config 2's 7.93 -> 7.77, config 4's 110.6 -> 107.8; two / three / five waves measured worse than four)
+static const int NBP_PRODUCT_LAT_WAVES = 4;
+// Throughput geometries: workgroups of EIGHT waves when the even split is not a multiple of four (N = 300 at two helper
+// lanes: 10 waves of samples -> two workgroups of 8 instead of two of 5; N = 200: 7 -> 8).  A workgroup whose waves do not
+// divide over the four SIMDs leaves one of them a wave short and makes its own waves wait for each other at the level
+// barriers; the idle waves of the rounder workgroup have no samples and cost a few barriers.  Config 5: products 174.9 ->
+// 164.2 ms per solve; config 2: unchanged (7.91 / 7.92 ms).  Workgroups of four (more of them per product, every one staging
+// the node statistics again) measured worse: 215.7 ms.
+static const int NBP_PRODUCT_THR_WAVES = 8;
+// The circle: workgroups of FOUR waves in the throughput geometries too.  Its instances hold 162 VGPRs = three waves per SIMD =
+// twelve wave slots per CU, of which one workgroup of eight leaves four empty and three workgroups of four none; the second
+// staging per product is cheap in one dimension.  Config 3: products 24.4 -> 22.8 ms, 52.8 -> 51.3 ms per solve.  (SE(2), two
+// waves per SIMD and a costly staging: 107 -> 126 ms -- it keeps eight.)
+static const int NBP_PRODUCT_CIRC_WAVES = 4;
+// A product whose samples need more than eight waves: ONE workgroup of up to sixteen (a multiple of four) where the kernel takes
+// it -- the Euclidean instances, NBP_PROD_WIDE in nbp_kernels.h -- instead of a full workgroup and a nearly empty one, each
+// staging the node statistics (N = 300 at two helper lanes: ten waves of samples; config 5's products 162 -> 122 ms per solve).
+// (two helper lanes only, i.e. launches that fill the chip: a launch of 80-191 products at four helper lanes leaves CUs idle, and
+//  there two workgroups per product on two CUs beat one on one -- config 2: 18.34 against 18.58 ms)
+static const int NBP_PRODUCT_WIDE_WAVES = 16;
+// LDS budget of a product workgroup: beyond it the node statistics live in global memory ("big")
+static const size_t NBP_PRODUCT_LDS_CAP = 150 * 1024;
+// chunks per helper range of a throughput launch: as many as the LDS takes while two workgroups still share a CU (80 KB each)
+static const size_t NBP_PRODUCT_NCH_LDS = 80 * 1024;
+// resident levels: where two workgroups of the launch still fit a CU's 160 KB
+static const size_t NBP_PRODUCT_ALL_LEVELS_LDS = 76 * 1024;
+// the `_w1` instances: launches of at most this many workgroups (= CUs of the chip)
+static const long NBP_PRODUCT_W1_BLOCKS = 256;
+
+// `mani`: the manifold of a single-manifold batch (0: mixed; < 0: size for the widest workgroup any kernel takes)
+static void product_geometry(const nbp_ctx *c, int n, int *HL, int *wpb, int *G, int mani) {
+  if (c->geom_n) n = c->geom_n;  // one half of a two-stream round: the geometry of the whole batch
+  *HL = n >= c->prod_hl2_min ? 2 : (n >= 16 ? 8 : 32);
+  const int SW = 64 / *HL, waves = (c->N + SW - 1) / SW, cap = (*HL >= 8) ? NBP_PRODUCT_LAT_WAVES : 8;
+  int g = (waves + cap - 1) / cap;
+  *wpb = (waves + g - 1) / g;
+  *G = (waves + *wpb - 1) / *wpb;
+  if (*HL <= 4 && (*wpb & 3)) {
+    *wpb = NBP_PRODUCT_THR_WAVES;
+    *G = (waves + *wpb - 1) / *wpb;
+  }
+  if (mani == NBP_CIRCULAR && *HL <= 4) {
+    *wpb = NBP_PRODUCT_CIRC_WAVES;
+    *G = (waves + *wpb - 1) / *wpb;
+  }
+  const bool wide = mani < 0 || NBP_PROD_WIDE(mani);
+  if (wide && *HL == 2 && waves > 8) {
+    const int g2 = (waves + NBP_PRODUCT_WIDE_WAVES - 1) / NBP_PRODUCT_WIDE_WAVES;
+    *wpb = (((waves + g2 - 1) / g2) + 3) & ~3;
+    *G = (waves + *wpb - 1) / *wpb;
+  }
+}
 // the sin / cos rows of the node statistics are part of a product launch's LDS unless it runs a single-manifold throughput
 // kernel of a manifold without a circular coordinate (product_kernel_uniform lays its LDS out by the same rule)
 static inline bool product_lays_circ(int HL, int mani) { return HL >= 8 || !(mani == NBP_EUCLID1 || mani == NBP_EUCLID2 || mani == NBP_EUCLID3); }
-// The product launch of a batch takes the node sums from the sorted coordinates itself (the _xs kernels: 4 KB instead of
-// 33 KB of KD workspace per density through HBM) when the batch runs a single-manifold throughput kernel and every
-// product has at most NBP_FUSED_MAXF densities; the prep launch in front then leaves the node sums out.
-static bool products_use_xs(nbp_ctx *c, int n, int maxFD, int mani) {
-  static const bool off = getenv("NBP_NO_XS_PRODUCTS") != nullptr;
-  if (off || mani == 0 || n <= 0) return false;
-  int HL, wpb, G;
-  product_geometry(c, n, &HL, &wpb, &G, mani);
+
+// Everything a product launch of n products needs to know, decided in ONE place: the launch itself, the prep launch in front
+// of it (whether the node sums are left out), the presizing of its scratch area and the two-stream guard of
+// nbp_program_finalize all read this plan.  (Through round 5 the guard and the presizing decided "big" on their own and left
+// the chunk sums out: a round of Euclid(3) products at N = 300 with five densities passed the guard, was pipelined, and its
+// halves -- laid out by the geometry of the whole batch, whose kernels have no scratch path -- ran past the LDS the launch
+// had allocated.)
+struct nbp_product_plan {
+  int HL = 0, wpb = 0, G = 0;   // product_geometry
+  bool big = false;             // the node statistics live in global memory (`gstats` doubles of it)
+  bool xs = false;              // node sums from the sorted coordinates (the _xs kernels): the prep launch leaves them out
+  bool circ = false;            // the LDS holds the sin / cos rows (product_lays_circ)
+  int nch = 0;                  // chunks per helper range whose sums live in LDS (throughput geometry; 0: none)
+  bool all_levels = false;      // the statistics of every level staged at once (NBP_PROD_ALL_LEVELS)
+  bool w1 = false;              // a `_w1` kernel
+  size_t lds = 0, gstats = 0;   // dynamic LDS bytes per workgroup; doubles of the global statistics area (big only)
+  nbp_product_fn fn = nullptr;  // from NBP_PRODUCT_KERNELS (nullptr: the table has none for this plan)
+};
+// `maxFD` encodes the largest (F, D) of the batch as F*4 + D; `mani` as for product_geometry
+static nbp_product_plan product_plan(const nbp_ctx *c, int n, int maxFD, int mani) {
+  nbp_product_plan p;
   const int F = maxFD / 4, D = maxFD % 4;
-  if (HL > 4 || F > NBP_FUSED_MAXF) return false;
-  return nbp_product_lds_bytes(F, D, c->N, wpb * 64 / HL, false, (size_t)2 * 2 * wpb * 64, product_lays_circ(HL, mani)) + 8 +
-             nbp_product_xs_doubles(F, D, c->N) * 8 <= 150 * 1024;
+  product_geometry(c, n, &p.HL, &p.wpb, &p.G, mani);
+  // big: the statistics do not fit with the chunk sums the throughput geometries keep in LDS (two chunks per lane at least)
+  p.big = nbp_product_lds_bytes(F, D, c->N, p.wpb * 64 / p.HL, false, p.HL <= 4 ? (size_t)2 * 2 * p.wpb * 64 : 0,
+                                product_lays_circ(p.HL, mani)) > NBP_PRODUCT_LDS_CAP;
+  if (p.big && p.HL != 8) product_geometry(c, 16, &p.HL, &p.wpb, &p.G, 0);  // many densities: small sample groups keep the label table in LDS
+  const int TB = p.wpb * 64, SPB = TB / p.HL;
+  p.circ = product_lays_circ(p.HL, mani);
+  // The launch takes the node sums from the sorted coordinates itself (4 KB instead of 33 KB of KD workspace per density
+  // through HBM) when the batch runs a single-manifold throughput kernel and every product has at most NBP_FUSED_MAXF densities
+  p.xs = c->prod_xs && mani > 0 && n > 0 && !p.big && p.HL <= 4 && F <= NBP_FUSED_MAXF &&
+         nbp_product_lds_bytes(F, D, c->N, SPB, false, (size_t)2 * 2 * TB, p.circ) + 8 + nbp_product_xs_doubles(F, D, c->N) * 8 <=
+             NBP_PRODUCT_LDS_CAP;
+  const size_t xsb = p.xs ? 8 + nbp_product_xs_doubles(F, D, c->N) * 8 : 0;
+  // chunks per helper range of a throughput launch (pass 2 of a draw rescans ONE chunk): as many as the LDS takes while two
+  // workgroups still share a CU, else as many as one workgroup's budget takes
+  if (p.HL <= 4 && !p.big) {
+    auto lds_for = [&](int k) { return nbp_product_lds_bytes(F, D, c->N, SPB, false, (size_t)k * 2 * TB, p.circ) + xsb; };
+    // (8 and 4 cost the same, 2 is ~5 % slower, 1 -- a range is its own chunk, pass 2 rescans all of it -- slower again; but ONE
+    //  workgroup per CU costs a launch of 257 .. 512 workgroups a second generation: a mixed launch of two- and three-density
+    //  products, sized by the three, took 736 us where two resident workgroups take ~600: profiles/r05_product_chunks_by_launch_size.txt)
+    const int cand[4] = {8, 4, 2, 1};
+    for (int k : cand)
+      if (lds_for(k) <= NBP_PRODUCT_NCH_LDS) { p.nch = k; break; }
+    if (!p.nch) {
+      p.nch = 2;
+      for (int k : cand)
+        if (lds_for(k) <= NBP_PRODUCT_LDS_CAP) { p.nch = k; break; }
+    }
+    if (c->prod_nch >= 1 && c->prod_nch <= 15 && lds_for(c->prod_nch) <= 160 * 1024) p.nch = c->prod_nch;
+  }
+  p.lds = nbp_product_lds_bytes(F, D, c->N, SPB, p.big, (size_t)p.nch * 2 * TB, p.circ) + xsb;
+  // resident levels (NBP_PROD_ALL_LEVELS): the statistics of every tree level staged once, no barrier between the levels
+  // of the Gibbs walk
+  // (the latency geometries only: a lone product saves nine round trips to the KD workspace and eighteen barriers, 126 -> 116 us;
+  //  a chip-filling launch gains nothing -- NBP_PRODUCT_ALL_LEVELS_HL = 2 switches it on there too)
+  if (!p.big && p.HL >= c->prod_all_levels_hl) {
+    const int TOT = c->T.off[c->T.L] + c->T.cnt[c->T.L];
+    // (with the chunk sums of the throughput geometries, which the kernel lays out behind the statistics: without them the
+    //  experiment NBP_PRODUCT_ALL_LEVELS_HL <= 4 ran config 3's products past their LDS -- non-finite posteriors)
+    const size_t lds_all = product_lds_layout(F, D, c->N, SPB, false, nullptr, nullptr, TOT, p.HL <= 4 ? (size_t)p.nch * 2 * TB : 0, p.circ) + xsb;
+    if (lds_all <= NBP_PRODUCT_ALL_LEVELS_LDS) { p.lds = lds_all; p.all_levels = true; }
+  }
+  if (p.big) p.gstats = (size_t)n * p.G * nbp_product_gstats_doubles(F, 3, c->N);  // (the kernel's stride: largest F of the launch, D = 3)
+  // the kernel: the batch's single-manifold instance where the geometry has one -- in the latency geometries only where the
+  // node statistics fit the LDS (and unless NBP_NO_UNIFORM_LATENCY_PRODUCTS) -- else a generic one; `_w1` where the launch
+  // has at most one workgroup (of at most four waves) per CU
+  const int km = (mani > 0 && (p.HL <= 4 || (c->prod_lat_uni && !p.big))) ? mani : 0;
+  p.w1 = km == 0 && p.HL >= 8 && TB <= 256 && (long)n * p.G <= NBP_PRODUCT_W1_BLOCKS && !c->geom_n;
+  for (const nbp_product_kernel_row &k : NBP_PRODUCT_KERNELS)
+    if (k.HL == p.HL && k.mani == km && k.xs == p.xs && k.w1 == p.w1) p.fn = k.fn;
+  return p;
 }
+
 // the rendezvous areas of the next launch of speculative fits, blanked on the library's stream (nbp_spec_blank_kernel)
 static void blank_spec_areas(nbp_ctx *c, int jobs) {
 #ifdef NBP_SPEC_BLANK_MEMSET  // experiment (tools/exp/concurrency_probe3.sh): the hipMemsetAsync this kernel replaced
@@ -944,6 +1077,7 @@ static void blank_spec_areas(nbp_ctx *c, int jobs) {
 #endif
 }
 
+// nbp_prep_kernel: pending bandwidth fits + KD builds of this product batch, one launch
 static nbp_status launch_prep(nbp_ctx *c, const int32_t *bw_slots, const int32_t *bw_manis, int nbw,
                               const nbp_product_desc *dev, int n, int maxFD, int coords = -1, int mani = 0) {
   if (coords < 0) coords = 3 * nbw;
@@ -955,7 +1089,7 @@ static nbp_status launch_prep(nbp_ctx *c, const int32_t *bw_slots, const int32_t
   size_t lds = nbp_kd_lds_bytes(3, c->N, c->Npad, P);
   if (nbw > 0 && nbp_bandwidth_lds_bytes(c->N, c->Npad, P) > lds) lds = nbp_bandwidth_lds_bytes(c->N, c->Npad, P);
   (void)hipGetLastError();
-  const int kdF = (maxFD / 4) | (products_use_xs(c, n, maxFD, mani) ? NBP_KD_NOSTATS : 0);
+  const int kdF = (maxFD / 4) | (product_plan(c, n, maxFD, mani).xs ? NBP_KD_NOSTATS : 0);
   const int nkd = n * (maxFD / 4);  // KD-build workgroups
   // latency mode: a handful of fits, the rest of the chip idle -> NBP_SPEC_K workgroups per fit
   // 3 workgroups per fit (two iterations per rendezvous) when the whole launch is resident at once (7 / three on request)
@@ -980,122 +1114,6 @@ static nbp_status launch_prep(nbp_ctx *c, const int32_t *bw_slots, const int32_t
   return toc(c, c->ev[1]);
 }
 
-// product launch geometry: HL helper lanes per sample (64/HL samples per wave), workgroups of `wpb` <= 8
-// waves, grid.y = G workgroups per product.  Latency mode (the launch cannot fill the chip): HL = 32 (fewer than 16
-// products; NBP_PRODUCT_HL32_MAX) or 8 and several small workgroups per product (below NBP_PRODUCT_HL2_MIN products: the HL = 4
-// geometry between them is reached with NBP_PRODUCT_HL4_MIN only); throughput mode: HL = 2 so that one
-// workgroup covers all samples and the node statistics of a product are computed once.
-// `mani`: the manifold of a single-manifold batch (0: mixed; < 0: size for the widest workgroup any kernel takes)
-static void product_geometry(nbp_ctx *c, int n, int *HL, int *wpb, int *G, int mani) {
-  if (c->geom_n) n = c->geom_n;  // one half of a two-stream round: the geometry of the whole batch
-  static const int hl2_min = getenv("NBP_PRODUCT_HL2_MIN") ? atoi(getenv("NBP_PRODUCT_HL2_MIN")) : 192;
-  static const int hl32_max = getenv("NBP_PRODUCT_HL32_MAX") ? atoi(getenv("NBP_PRODUCT_HL32_MAX")) : 15;
-  // four helper lanes from hl4_min products on: never by default since the single-manifold latency instances (80 until then --
-  // 48 until round 4 -- and 128 / 160 / 192 measured after: config 2 17.18 / 17.12 / 16.94 / 16.98 ms, config 3 49.39 / 49.17 /
-  // 49.04 / 48.73, config 4 325.2 / - / 322.9 / 321.8, config 5 341.1 / - / 341.2 / 341.4; profiles/r07_latency_product_instances.txt)
-  static const int hl4_min = getenv("NBP_PRODUCT_HL4_MIN") ? atoi(getenv("NBP_PRODUCT_HL4_MIN")) : 192;
-  *HL = n >= hl2_min ? 2 : (n >= hl4_min ? 4 : (n >= 16 ? 8 : (n > hl32_max ? 16 : 32)));
-  // latency geometries: workgroups of FOUR waves (one per SIMD of their CU; six until round 4: config 3's products 25.9 -> 24.4 ms,
-  // config 2's 7.93 -> 7.77, config 4's 110.6 -> 107.8; two / three / five waves measured worse than four)
-  static const int lat_cap = getenv("NBP_PRODUCT_LAT_CAP") ? atoi(getenv("NBP_PRODUCT_LAT_CAP")) : 4;
-  const int SW = 64 / *HL, waves = (c->N + SW - 1) / SW, cap = (*HL >= 8) ? lat_cap : 8;
-  int g = (waves + cap - 1) / cap;
-  *wpb = (waves + g - 1) / g;
-  *G = (waves + *wpb - 1) / *wpb;
-  // Throughput geometries: workgroups of EIGHT waves when the even split is not a multiple of four (N = 300 at two helper
-  // lanes: 10 waves of samples -> two workgroups of 8 instead of two of 5; N = 200: 7 -> 8).  A workgroup whose waves do not
-  // divide over the four SIMDs leaves one of them a wave short and makes its own waves wait for each other at the level
-  // barriers; the idle waves of the rounder workgroup have no samples and cost a few barriers.  Config 5: products 174.9 ->
-  // 164.2 ms per solve; config 2: unchanged (7.91 / 7.92 ms).  Workgroups of four (more of them per product, every one staging
-  // the node statistics again) measured worse: 215.7 ms.  NBP_PRODUCT_WPB8=0: the even split.
-  static const bool wpb8 = !(getenv("NBP_PRODUCT_WPB8") && atoi(getenv("NBP_PRODUCT_WPB8")) == 0);
-  if (wpb8 && *HL <= 4 && (*wpb & 3)) {
-    *wpb = 8;
-    *G = (waves + 7) / 8;
-  }
-  // The circle: workgroups of FOUR waves in the throughput geometries too.  Its instances hold 162 VGPRs = three waves per SIMD =
-  // twelve wave slots per CU, of which one workgroup of eight leaves four empty and three workgroups of four none; the second
-  // staging per product is cheap in one dimension.  Config 3: products 24.4 -> 22.8 ms, 52.8 -> 51.3 ms per solve.  (SE(2), two
-  // waves per SIMD and a costly staging: 107 -> 126 ms -- it keeps eight.)  NBP_PRODUCT_THR_WPB overrides for every manifold.
-  static const int thr_wpb = getenv("NBP_PRODUCT_THR_WPB") ? atoi(getenv("NBP_PRODUCT_THR_WPB")) : 0;
-  const int tw = thr_wpb > 0 ? thr_wpb : (mani == NBP_CIRCULAR ? 4 : 0);
-  if (tw > 0 && *HL <= 4) {
-    *wpb = tw;
-    *G = (waves + tw - 1) / tw;
-  }
-  // a product whose samples need more than eight waves: ONE workgroup of up to sixteen (a multiple of four) where the kernel takes
-  // it -- the Euclidean instances, NBP_PROD_WIDE in nbp_kernels.h -- instead of a full workgroup and a nearly empty one, each
-  // staging the node statistics (N = 300 at two helper lanes: ten waves of samples; config 5's products 162 -> 122 ms per solve)
-  static const int wpb_max = getenv("NBP_PRODUCT_WPB_MAX") ? atoi(getenv("NBP_PRODUCT_WPB_MAX")) : 16;
-  const bool wide = mani < 0 || NBP_PROD_WIDE(mani);
-  // (two helper lanes only, i.e. launches that fill the chip: a launch of 80-191 products at four helper lanes leaves CUs idle, and
-  //  there two workgroups per product on two CUs beat one on one -- config 2: 18.34 against 18.58 ms)
-  if (wide && wpb_max > 8 && *HL == 2 && waves > 8) {
-    const int g2 = (waves + wpb_max - 1) / wpb_max;
-    *wpb = (((waves + g2 - 1) / g2) + 3) & ~3;
-    *G = (waves + *wpb - 1) / *wpb;
-  }
-}
-// LDS budget of a product workgroup: beyond it the node statistics live in global memory ("big")
-static const size_t NBP_PRODUCT_LDS_CAP = 150 * 1024;
-typedef void (*nbp_product_fn)(const nbp_product_desc *, double *, const double *, int, double *, int, int64_t, int32_t *, nbp_levels);
-// the kernel of a product launch: HL helper lanes per sample; `mani` != 0: every multi-density product of the batch lives
-// on that manifold and has only full inputs (the throughput variants then run the single-instantiation kernels)
-// `w1`: the launch has at most one workgroup (of at most four waves) per CU -- the latency instances that own their SIMDs
-// `big`: the node statistics live in global memory (product_is_big) -- the generic latency kernels alone have that path
-static nbp_product_fn product_kernel_for(int HL, int mani, bool xs = false, bool w1 = false, bool big = false) {
-  // the single-manifold latency instances (NBP_NO_UNIFORM_LATENCY_PRODUCTS: the generic kernels, for A/B runs and tests)
-  static const bool lat_uni = getenv("NBP_NO_UNIFORM_LATENCY_PRODUCTS") == nullptr;
-  if (lat_uni && !big && mani > 0 && (HL == 32 || HL == 8)) {
-    switch (mani * 64 + HL) {
-    case NBP_EUCLID1 * 64 + 32: return nbp_product_kernel_y32_e1;
-    case NBP_EUCLID2 * 64 + 32: return nbp_product_kernel_y32_e2;
-    case NBP_EUCLID3 * 64 + 32: return nbp_product_kernel_y32_e3;
-    case NBP_CIRCULAR * 64 + 32: return nbp_product_kernel_y32_ci;
-    case NBP_SE2 * 64 + 32: return nbp_product_kernel_y32_se;
-    case NBP_EUCLID1 * 64 + 8: return nbp_product_kernel_l8_e1;
-    case NBP_EUCLID2 * 64 + 8: return nbp_product_kernel_l8_e2;
-    case NBP_EUCLID3 * 64 + 8: return nbp_product_kernel_l8_e3;
-    case NBP_CIRCULAR * 64 + 8: return nbp_product_kernel_l8_ci;
-    case NBP_SE2 * 64 + 8: return nbp_product_kernel_l8_se;
-    }
-  }
-  if (HL == 32) return w1 ? nbp_product_kernel_y32_w1 : nbp_product_kernel_y32;
-  if (HL == 16) return w1 ? nbp_product_kernel_x16_w1 : nbp_product_kernel_x16;
-  if (HL == 8) return w1 ? nbp_product_kernel_l8_w1 : nbp_product_kernel_l8;
-  if (xs) {
-    switch (mani * 8 + HL) {
-    case NBP_EUCLID1 * 8 + 4: return nbp_product_kernel_m4_e1_xs;
-    case NBP_EUCLID2 * 8 + 4: return nbp_product_kernel_m4_e2_xs;
-    case NBP_EUCLID3 * 8 + 4: return nbp_product_kernel_m4_e3_xs;
-    case NBP_CIRCULAR * 8 + 4: return nbp_product_kernel_m4_ci_xs;
-    case NBP_SE2 * 8 + 4: return nbp_product_kernel_m4_se_xs;
-    case NBP_EUCLID1 * 8 + 2: return nbp_product_kernel_t2_e1_xs;
-    case NBP_EUCLID2 * 8 + 2: return nbp_product_kernel_t2_e2_xs;
-    case NBP_EUCLID3 * 8 + 2: return nbp_product_kernel_t2_e3_xs;
-    case NBP_CIRCULAR * 8 + 2: return nbp_product_kernel_t2_ci_xs;
-    default: return nbp_product_kernel_t2_se_xs;
-    }
-  }
-  if (HL == 4) {
-    switch (mani) {
-    case NBP_EUCLID1: return nbp_product_kernel_m4_e1;
-    case NBP_EUCLID2: return nbp_product_kernel_m4_e2;
-    case NBP_EUCLID3: return nbp_product_kernel_m4_e3;
-    case NBP_CIRCULAR: return nbp_product_kernel_m4_ci;
-    case NBP_SE2: return nbp_product_kernel_m4_se;
-    default: return nbp_product_kernel_m4;
-    }
-  }
-  switch (mani) {
-  case NBP_EUCLID1: return nbp_product_kernel_t2_e1;
-  case NBP_EUCLID2: return nbp_product_kernel_t2_e2;
-  case NBP_EUCLID3: return nbp_product_kernel_t2_e3;
-  case NBP_CIRCULAR: return nbp_product_kernel_t2_ci;
-  case NBP_SE2: return nbp_product_kernel_t2_se;
-  default: return nbp_product_kernel_t2;
-  }
-}
 // 0 unless all products with more than one density share a manifold and none has a partial input
 static int products_uniform_manifold(const nbp_product_desc *d, int n) {
   int mani = -1;
@@ -1113,85 +1131,25 @@ static int products_uniform_manifold(const nbp_product_desc *d, int n) {
   }
   return mani > 0 ? mani : 0;
 }
-// ONE answer to "do the node statistics of this product launch fit the LDS" -- asked by the launch itself, by the presizing of
-// its scratch area and by the two-stream guard of nbp_program_finalize, with the same terms: the launch's geometry, the chunk
-// sums the throughput geometries keep in LDS (two chunks per lane at least) and the sin / cos rows of a circular coordinate.
-// (Through round 5 the guard and the presizing left the chunk sums out: a round of Euclid(3) products at N = 300 with five
-//  densities passed the guard, was pipelined, and its halves -- laid out by the geometry of the whole batch, whose kernels
-//  have no scratch path -- ran past the LDS the launch had allocated.)
-static bool product_is_big(nbp_ctx *c, int n, int maxFD, int mani) {
-  int HL, wpb, G;
-  product_geometry(c, n, &HL, &wpb, &G, mani);
-  const int F = maxFD / 4, D = maxFD % 4;  // maxFD encodes the largest (F, D) of the batch as F*4 + D
-  return nbp_product_lds_bytes(F, D, c->N, wpb * 64 / HL, false, HL <= 4 ? (size_t)2 * 2 * wpb * 64 : 0, product_lays_circ(HL, mani)) > NBP_PRODUCT_LDS_CAP;
-}
 static nbp_status launch_products(nbp_ctx *c, const nbp_product_desc *dev, int n, int maxFD, int mani = 0) {
   if (n <= 0) return NBP_OK;
-  int HL, wpb, G;
-  product_geometry(c, n, &HL, &wpb, &G, mani);
-  const int F = maxFD / 4, D = maxFD % 4;
-  bool big = product_is_big(c, n, maxFD, mani);
+  const nbp_product_plan p = product_plan(c, n, maxFD, mani);
   // (the halves of a two-stream round take the geometry of the whole batch, whose throughput kernels have no scratch path, and
   //  share one scratch area: nbp_program_finalize pipelines no round whose products are big -- refused here should it ever)
-  if (big && c->geom_n) return fail(NBP_ERR_RANGE, "product: node statistics beyond the LDS inside a two-stream round");
-  if (big && HL != 8) {  // many densities: small sample groups keep the label table in LDS
-    product_geometry(c, 16, &HL, &wpb, &G);
-  }
-  const int TB = wpb * 64, SPB = TB / HL;
-  const bool circ = product_lays_circ(HL, mani);
-  const bool xs = !big && products_use_xs(c, n, maxFD, mani);
-  const size_t xsb = xs ? 8 + nbp_product_xs_doubles(F, D, c->N) * 8 : 0;
-  // chunks per helper range of a throughput launch (pass 2 of a draw rescans ONE chunk): as many as the LDS takes while two
-  // workgroups still share a CU (80 KB each), else as many as one workgroup's budget takes
-  int nch = 0;
-  if (HL <= 4 && !big) {
-    static const int nch_env = getenv("NBP_PRODUCT_NCH") ? atoi(getenv("NBP_PRODUCT_NCH")) : 0;
-    static const size_t half = getenv("NBP_PRODUCT_NCH_KB") ? (size_t)atoi(getenv("NBP_PRODUCT_NCH_KB")) * 1024 : 80 * 1024;
-    auto lds_for = [&](int k) { return nbp_product_lds_bytes(F, D, c->N, SPB, false, (size_t)k * 2 * TB, circ) + xsb; };
-    // (8 and 4 cost the same, 2 is ~5 % slower, 1 -- a range is its own chunk, pass 2 rescans all of it -- slower again; but ONE
-    //  workgroup per CU costs a launch of 257 .. 512 workgroups a second generation: a mixed launch of two- and three-density
-    //  products, sized by the three, took 736 us where two resident workgroups take ~600: profiles/r05_product_chunks_by_launch_size.txt)
-    nch = 0;
-    const int cand[4] = {8, 4, 2, 1};
-    for (int k : cand)
-      if (lds_for(k) <= half) { nch = k; break; }
-    if (!nch) {
-      nch = 2;
-      for (int k : cand)
-        if (lds_for(k) <= NBP_PRODUCT_LDS_CAP) { nch = k; break; }
-    }
-    if (nch_env >= 1 && nch_env <= 15 && lds_for(nch_env) <= 160 * 1024) nch = nch_env;
-  }
-  size_t lds = nbp_product_lds_bytes(F, D, c->N, SPB, big, (size_t)nch * 2 * TB, circ) + xsb;
-  if (lds > 160 * 1024) return fail(NBP_ERR_RANGE, "product: too many densities for the LDS label table");
-  // resident levels (NBP_PROD_ALL_LEVELS): the statistics of every tree level staged once, no barrier between the levels
-  // of the Gibbs walk -- where two workgroups of the launch still fit a CU's 160 KB
-  static const size_t all_cap = getenv("NBP_PRODUCT_ALL_LEVELS_KB") ? (size_t)atoi(getenv("NBP_PRODUCT_ALL_LEVELS_KB")) * 1024 : 76 * 1024;
-  int flagsF = F | (nch << NBP_PROD_NCH_SHIFT);
-  // (the latency geometries only: a lone product saves nine round trips to the KD workspace and eighteen barriers, 126 -> 116 us;
-  //  a chip-filling launch gains nothing -- NBP_PRODUCT_ALL_LEVELS_HL = 2 switches it on there too)
-  static const int all_hl = getenv("NBP_PRODUCT_ALL_LEVELS_HL") ? atoi(getenv("NBP_PRODUCT_ALL_LEVELS_HL")) : 8;
-  if (!big && HL >= all_hl) {
-    const int TOT = c->T.off[c->T.L] + c->T.cnt[c->T.L];
-    // (with the chunk sums of the throughput geometries, which the kernel lays out behind the statistics: without them the
-    //  experiment NBP_PRODUCT_ALL_LEVELS_HL <= 4 ran config 3's products past their LDS -- non-finite posteriors)
-    const size_t lds_all = product_lds_layout(F, D, c->N, SPB, false, nullptr, nullptr, TOT, HL <= 4 ? (size_t)nch * 2 * TB : 0, circ) +
-                           (xs ? 8 + nbp_product_xs_doubles(F, D, c->N) * 8 : 0);
-    if (lds_all <= all_cap) { lds = lds_all; flagsF |= NBP_PROD_ALL_LEVELS; }
-  }
+  if (p.big && c->geom_n) return fail(NBP_ERR_RANGE, "product: node statistics beyond the LDS inside a two-stream round");
+  if (p.lds > 160 * 1024) return fail(NBP_ERR_RANGE, "product: too many densities for the LDS label table");
+  if (!p.fn) return fail(NBP_ERR_RANGE, "product: no kernel for the launch's geometry");
   nbp_status rc = NBP_OK;
-  double *gs = nullptr;
-  if (big) {
-    rc = ensure_gstats(c, (size_t)n * G * nbp_product_gstats_doubles(F, 3, c->N));  // (the kernel's stride: largest F of the launch, D = 3)
+  if (p.big) {
+    rc = ensure_gstats(c, p.gstats);
     if (rc) return rc;
-    gs = c->gstats;
   }
   rc = tic(c, c->ev[2]);
   if (rc) return rc;
   (void)hipGetLastError();
-  static const int w1_max = getenv("NBP_PRODUCT_W1_MAX") ? atoi(getenv("NBP_PRODUCT_W1_MAX")) : 256;  // workgroups (= CUs of the chip)
-  const bool w1 = HL >= 8 && TB <= 256 && (long)n * G <= w1_max && !c->geom_n;
-  hipLaunchKernelGGL(product_kernel_for(HL, mani, xs, w1, big), dim3(n, G), dim3(TB), lds, c->stream, dev, c->arena, c->ws, flagsF, gs, c->N, c->S, c->side, c->T);
+  const int flagsF = (maxFD / 4) | (p.nch << NBP_PROD_NCH_SHIFT) | (p.all_levels ? NBP_PROD_ALL_LEVELS : 0);
+  hipLaunchKernelGGL(p.fn, dim3(n, p.G), dim3(p.wpb * 64), p.lds, c->stream, dev, c->arena, c->ws, flagsF, p.big ? c->gstats : nullptr, c->N, c->S,
+                     c->side, c->T);
   HIPCHK(hipGetLastError());
   return toc(c, c->ev[2]);
 }
@@ -1200,15 +1158,10 @@ static nbp_status launch_products(nbp_ctx *c, const nbp_product_desc *dev, int n
 static nbp_status presize_products(nbp_ctx *c, int n, int maxFD, int mani = 0) {
   nbp_status rc = ensure_ws(c, n, maxFD / 4);
   if (rc) return rc;
-  // the launch's own decision (product_is_big), or the widest workgroup any kernel may take (mani = -1: its larger label table
-  // decides about the scratch) -- whichever asks for the scratch area gets it allocated here, outside the replayed region
-  if (product_is_big(c, n, maxFD, mani) || product_is_big(c, n, maxFD, -1)) {
-    int HL, wpb, G;
-    product_geometry(c, n, &HL, &wpb, &G, mani);
-    if (HL != 8) product_geometry(c, 16, &HL, &wpb, &G);
-    const int F = maxFD / 4;
-    rc = ensure_gstats(c, (size_t)n * G * nbp_product_gstats_doubles(F, 3, c->N));
-  }
+  // the launch's own plan, or the widest workgroup any kernel may take (mani = -1: its larger label table decides about the
+  // scratch) -- whichever asks for the scratch area gets it allocated here, outside the replayed region
+  const size_t gs = std::max(product_plan(c, n, maxFD, mani).gstats, product_plan(c, n, maxFD, -1).gstats);
+  if (gs) rc = ensure_gstats(c, gs);
   return rc;
 }
 
@@ -2079,7 +2032,7 @@ nbp_status nbp_program_finalize(nbp_program *p) {
     if (ps.kind != NBP_STAGE_PROPOSALS || qs.kind != NBP_STAGE_PRODUCTS || ps.pipe_split < 0 || qs.pipe_split < 0) continue;
     if (ps.fused || !qs.need_prep || qs.flush_before) continue;
     // products too large for the LDS share one node-statistics workspace: single stream (the launch's own decision)
-    if (product_is_big(p->ctx, qs.n, qs.maxfd, qs.mani)) continue;
+    if (product_plan(p->ctx, qs.n, qs.maxfd, qs.mani).big) continue;
     const nbp_product_desc *qd = (const nbp_product_desc *)(p->blob.data() + qs.offset);
     std::unordered_map<int32_t, int> second;  // slots the second half's products read
     for (int i = qs.pipe_split; i < qs.n; i++)

@@ -1,3 +1,3 @@
-// product kernels, latency geometries (x16, l8)
+// product kernels, latency geometries, any mix of manifolds (y32, l8)
 #define NBP_TU 8
 #include "nbp_kernels.h"

@@ -1,3 +1,3 @@
-// product kernels, throughput geometries, any mix of manifolds (m4, t2)
+// product kernels, throughput geometry, any mix of manifolds (t2)
 #define NBP_TU 16
 #include "nbp_kernels.h"

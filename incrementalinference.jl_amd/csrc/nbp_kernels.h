@@ -14,11 +14,10 @@
 #define NBP_TU_PROPOSAL 1   // proposal / deconv kernels + the small copy / reseed / resample kernels
 #define NBP_TU_PREP 2       // bandwidth fits + KD builds, sequential search
 #define NBP_TU_PREPSPEC 4   // the same with the speculative search
-#define NBP_TU_PRODLAT 8    // product kernels, latency geometries (y32, x16, l8)
-#define NBP_TU_PRODTHR 16   // product kernels, throughput geometries, generic (m4, t2)
-#define NBP_TU_PRODUNI 32   // product kernels, throughput geometries, one manifold per instance
+#define NBP_TU_PRODLAT 8    // product kernels, latency geometries, any mix of manifolds (y32, l8)
+#define NBP_TU_PRODTHR 16   // product kernels, throughput geometry, any mix of manifolds (t2)
+#define NBP_TU_PRODUNI 32   // product kernels, throughput geometry, one manifold per instance (t2)
 #define NBP_TU_FUSED 64     // the fused variable-update kernels
-#define NBP_TU_PRODUNI4 128 // product kernels, one manifold per instance, four helper lanes (the two-lane ones: NBP_TU_PRODUNI)
 #define NBP_TU_PREPW5 256   // bandwidth fits + KD builds at five waves per SIMD (rows of 4k + 1 waves: N = 257 .. 320)
 #define NBP_TU_PROPWAVE 512 // proposal kernels, one wave per proposal (chip-filling launches of simple Euclidean batches)
 #define NBP_TU_PRODLATUNI 1024 // product kernels, latency geometries (y32, l8), one manifold per instance
@@ -867,8 +866,8 @@ __global__ void nbp_spec_blank_kernel(unsigned long long *p, int n);
 //                   leave the sorted, centred coordinates in an HBM workspace.  The tree build does
 //                   not need bandwidths, so it runs beside the LCV fits of the same update instead
 //                   of behind them.
-// nbp_product_kernel_{l8,m4,t2}: grid (nprod, G): workgroup (p, g) draws the output samples
-//                   [g*SPB, (g+1)*SPB) of product p with HL = 8/4/2 helper lanes per sample (adjacent
+// nbp_product_kernel_{y32,l8,t2}: grid (nprod, G): workgroup (p, g) draws the output samples
+//                   [g*SPB, (g+1)*SPB) of product p with HL = 32/8/2 helper lanes per sample (adjacent
 //                   lanes of one wave); results do not depend on the geometry beyond rounding (the
 //                   RNG is keyed by the sample index).
 // ================================================================================================
@@ -1181,7 +1180,7 @@ __host__ __device__ inline size_t product_lds_layout(int F, int D, int N, int SP
 // no density informs keeps the old point (GraphProductOperations.jl:39-45).  Separate instantiation so
 // that the all-full path carries no masks.
 // BIG: the node statistics live in this workgroup's scratch in global memory (products with many densities; only the
-// latency geometries HL = 16 / 8 run them).  A compile-time switch: with a run-time one every access to the statistics
+// latency geometry HL = 8 runs them).  A compile-time switch: with a run-time one every access to the statistics
 // goes through a generic 64-bit pointer -- flat loads in the Gibbs loop and register pairs for what is an LDS offset.
 // FUSED (the fused update kernel, nbp_fused.h): the densities are the proposals this workgroup has just made -- sorted,
 // centred coordinates, centres, permutations and bandwidths in LDS (`fio`), node sums taken from the sorted coordinates
@@ -1314,10 +1313,7 @@ __device__ __forceinline__ void product_body(const nbp_product_desc *d, double *
     // staged one by one.  A level's staging is two loops, three barriers and a dependent chain of table reads whatever its node
     // count -- six of nine of them per product were spent on levels whose draws take a few hundred cycles.  Same statistics,
     // same draws: only where a level's nodes sit in the row changes (`lb`).
-#ifndef NBP_X_COARSE_BLOCK
-#define NBP_X_COARSE_BLOCK 1
-#endif
-    const bool inblock = !all && NBP_X_COARSE_BLOCK && l <= Lc;
+    const bool inblock = !all && l <= Lc;
     const int lb = (all || inblock) ? off : 0;  // where this level's nodes start in a row of the statistics
     if ((all ? ps == 0 : (ps == 0 || !inblock)) && ps <= T.L) {  // (a repeated leaf pass finds its statistics in place)
     __syncthreads();
@@ -1387,13 +1383,7 @@ __device__ __forceinline__ void product_body(const nbp_product_desc *d, double *
     // the first sweep's sampleIndex.  The helper lanes of a sample take turns at the densities (lane h makes the blocks of
     // j = h, h + HL, ...: with two densities and two helpers one block's worth of instructions per pass instead of four) and
     // hand them over through LDS; the lanes of a sample are lanes of one wave, whose LDS operations stay in order.
-    // (the latency geometries -- 8 to 32 helpers per sample, a CU to themselves, five manifolds' instances in one kernel at
-    //  252 registers -- make the block where it is used, once for each of its two uniforms: the hand-over cost them scratch)
-#ifndef NBP_X_UUL_LAT
-#define NBP_X_UUL_LAT 1
-#endif
-    constexpr bool UUL = HL <= 4 || NBP_X_UUL_LAT;
-    if (UUL && ps > 0 && live)
+    if (ps > 0 && live)
       for (int j0 = 0; j0 < F; j0 += HL) {
         const int j = j0 + h;
         if (j < F) {
@@ -1441,10 +1431,10 @@ __device__ __forceinline__ void product_body(const nbp_product_desc *d, double *
         // Pass 2 (the helper whose share holds u * total): locate the chunk, re-evaluate just that chunk.
         auto draw = [&](auto xp_c) {
         constexpr bool XP = decltype(xp_c)::value;  // sampleIndices!: the label given the POINT x (nothing added to a node's variance)
-#ifndef NBP_X_NCH
-#define NBP_X_NCH 2  // (four chunks cost sixteen more registers: 51 spilled at four waves per SIMD, 142 MB of scratch traffic per chip-filling launch; with the helpers rescanning a chunk together the longer chunk costs nothing)
-#endif
-        constexpr int NCH = NBP_X_NCH;  // chunks per helper range where their sums stay in registers
+        // chunks per helper range where their sums stay in registers (four chunks cost sixteen more registers: 51 spilled at four
+        // waves per SIMD, 142 MB of scratch traffic per chip-filling launch; with the helpers rescanning a chunk together the
+        // longer chunk costs nothing)
+        constexpr int NCH = 2;
         const int nchk = CKL ? nch : NCH;
         double mn[D], vn[D], ua = 0, ub = 0, m = -INFINITY, tot = 0;
         double cs[CKL ? 1 : NCH], ms[CKL ? 1 : NCH];
@@ -1491,14 +1481,12 @@ __device__ __forceinline__ void product_body(const nbp_product_desc *d, double *
         };
         // chunk size of this helper's range: a multiple of 4, the pass-1 loop takes the nodes four at a time
         const int zr = z1 - z0, csz = (((zr + nchk - 1) / nchk) + 3) & ~3;
-        // a level with at most SR nodes per helper -- every level of a 200-particle tree at 32 helpers, the three or four
-        // coarsest levels at 2 or 4 -- keeps the weights in registers: no chunks, no rescan, one exponential per node
-#ifndef NBP_X_SR_THR
-#define NBP_X_SR_THR 0  // register slots of the short-range draw in the throughput geometries (0 = chunks on every level; 4: measured 1 % on config 2 for 8 spilled registers and an occupancy step on Euclid(3): off)
-#endif
-        constexpr int SR = (HL >= 8) ? 8 : (NBP_X_SR_THR > 0 ? NBP_X_SR_THR : 1);
+        // a level with at most SR nodes per helper -- every level of a 200-particle tree at 32 helpers -- keeps the weights in
+        // registers: no chunks, no rescan, one exponential per node (the latency geometries only: in the throughput geometries four register slots measured 1 % on config 2 for 8 spilled
+        //  registers and an occupancy step on Euclid(3) -- there the chunks serve every level)
+        constexpr int SR = (HL >= 8) ? 8 : 1;
         const int nzmax = (cnt + HL - 1) / HL;
-        const bool shortr = (HL >= 8 || NBP_X_SR_THR > 0) && nzmax <= SR;
+        const bool shortr = HL >= 8 && nzmax <= SR;
         double wr[SR], gr[SR];
         NBP_CTICK(40);
         if (live) {
@@ -1534,11 +1522,9 @@ __device__ __forceinline__ void product_body(const nbp_product_desc *d, double *
 #pragma unroll
             for (int k = 0; k < D; k++) linv[k] = (PARTIAL && !use[k]) ? 0.0 : 1.0 / (h2[j * 3 + k] + vn[k]);
           }
-          if (UUL && it <= 0) ua = L.uu[(j * SPB + sl) * 2 + (it < 0 ? 0 : 1)];
-          else {  // further sweeps: a block each
-            uniform_pair(d->seed, s, it <= 0 ? PURP_PINDEX : PURP_PGIBBS, (uint32_t)(it <= 0 ? ps * NBP_MAXF + j : (ps * 8 + it) * NBP_MAXF + j), ua, ub);
-            if (it == 0) ua = ub;
-          }
+          if (it <= 0) ua = L.uu[(j * SPB + sl) * 2 + (it < 0 ? 0 : 1)];
+          else  // further sweeps: a block each
+            uniform_pair(d->seed, s, PURP_PGIBBS, (uint32_t)((ps * 8 + it) * NBP_MAXF + j), ua, ub);
           NBP_CTICK(44);  // conditional mean / variance of the other densities
           if (shortr) {  // at most SR nodes per helper: their weights stay in registers, nothing is evaluated twice
             // (nzmax = the longest range of the level, wave-uniform: the coarse levels of a 32-helper geometry have one node
@@ -1737,10 +1723,7 @@ __device__ __forceinline__ void product_body(const nbp_product_desc *d, double *
         // (the throughput geometries instantiate the draw on the point separately: g_z and the precisions from the staging,
         //  no rsqrt per node; in the latency kernels -- five manifolds x partial x big in one kernel -- the second copy costs
         //  300 spilled registers and goes through the general form)
-#ifndef NBP_X_XP_HL
-#define NBP_X_XP_HL 4
-#endif
-        if (HL <= NBP_X_XP_HL && it < 0) draw(std::true_type{});
+        if (HL <= 4 && it < 0) draw(std::true_type{});
         else draw(std::false_type{});
       }
     }
@@ -1879,11 +1862,12 @@ __device__ __forceinline__ void product_kernel_uniform(const nbp_product_desc *d
     product_body<MANI, false, HL, false, 0, (HL >= 8)>(d, arena, ws, kdF, gstats, N, S, side, T, smem, nullptr, all_levels, nch, lay_circ);  // never BIG (launch_products)
 }
 
-// Entry points: the latency variants (HL = 32 for fewer than 16 products, 16 on request, HL = 8; few workgroups in flight) and the
-// throughput variants (one workgroup per product, per-manifold instances); none of them uses scratch
-// (profiles/r03_kernel_resources.txt).
+// Entry points: the latency variants (HL = 32 for fewer than 16 products, HL = 8 below NBP_PRODUCT_HL2_MIN; few workgroups in
+// flight) and the throughput variants (HL = 2, one workgroup per product), each generic and per manifold; the host picks one
+// from its table (NBP_PRODUCT_KERNELS in nbp_api.hip).  None of them uses scratch (profiles/r03_kernel_resources.txt).
+// One definition macro per family; outside the family's translation unit it declares the kernels only.
 #define NBP_PRODUCT_ARGS const nbp_product_desc *descs, double *arena, const double *ws, int kdF, double *gstats, int N, int64_t S, int32_t *side, nbp_levels T
-// Latency geometries (8 / 16 / 32 helper lanes per sample, workgroups of at most four waves).  Each in two instances: the
+// Latency geometries (8 / 32 helper lanes per sample, workgroups of at most four waves).  Each in two instances: the
 // plain one (launch bound 512: two waves per SIMD, 256 registers, 16 B of scratch per lane since the uniforms of a pass are made
 // once per sample and handed over through LDS) and `_w1` for launches with at most one workgroup per CU (launch bound 256: one
 // wave per SIMD may hold 512 registers, the compiler parks four values in accumulation registers: no scratch).  A lone product of
@@ -1898,25 +1882,18 @@ __device__ __forceinline__ void product_kernel_uniform(const nbp_product_desc *d
 #else
 #define NBP_PRODUCT_LATENCY(NAME, HL_, BOUNDS) __global__ void NAME(NBP_PRODUCT_ARGS);
 #endif
-NBP_PRODUCT_LATENCY(nbp_product_kernel_x16, 16, 512)
 NBP_PRODUCT_LATENCY(nbp_product_kernel_l8, 8, 512)
 // fewer than 16 products alone on the chip: 32 helper lanes per sample halve the node range of every lane once more
 // (a lone F = 2 product: 87 -> 77 us; 64 lanes per sample gain nothing more and cost twelve F = 3 products 209 instead of 109 us)
 NBP_PRODUCT_LATENCY(nbp_product_kernel_y32, 32, 512)
-NBP_PRODUCT_LATENCY(nbp_product_kernel_x16_w1, 16, 256)
 NBP_PRODUCT_LATENCY(nbp_product_kernel_l8_w1, 8, 256)
 NBP_PRODUCT_LATENCY(nbp_product_kernel_y32_w1, 32, 256)
 #if NBP_TU & NBP_TU_PRODTHR
-__global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2))) nbp_product_kernel_m4(NBP_PRODUCT_ARGS) {
-  extern __shared__ double smem[];
-  product_kernel_body<4>(descs, arena, ws, kdF, gstats, N, S, side, T, smem);
-}
 __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2))) nbp_product_kernel_t2(NBP_PRODUCT_ARGS) {
   extern __shared__ double smem[];
   product_kernel_body<2>(descs, arena, ws, kdF, gstats, N, S, side, T, smem);
 }
 #else
-__global__ void nbp_product_kernel_m4(NBP_PRODUCT_ARGS);
 __global__ void nbp_product_kernel_t2(NBP_PRODUCT_ARGS);
 #endif
 // waves per SIMD of the single-manifold kernels, measured (profiles/r02_product_waves.txt): Euclid(1/2) are faster at 4
@@ -1931,42 +1908,27 @@ __global__ void nbp_product_kernel_t2(NBP_PRODUCT_ARGS);
 #ifndef NBP_W_CI
 #define NBP_W_CI 2  // (two waves: no spill -- three spilled 12 B per lane -- and 2 % faster on config 3)
 #endif
-#define NBP_PRODUCT_UNIFORM(NAME, MANI, HL) NBP_PRODUCT_UNIFORM_W(NAME, MANI, HL, ((MANI) == NBP_EUCLID1 ? 4 : (MANI) == NBP_EUCLID2 ? NBP_W_E2 : (MANI) == NBP_SE2 ? NBP_W_SE : (MANI) == NBP_CIRCULAR ? NBP_W_CI : 3))
-#define NBP_PRODUCT_UNIFORM_DECL(NAME) __global__ void NAME(NBP_PRODUCT_ARGS); __global__ void NAME##_xs(NBP_PRODUCT_ARGS);
-#if NBP_TU & (NBP_TU_PRODUNI | NBP_TU_PRODUNI4)
-#define NBP_PRODUCT_UNIFORM_W(NAME, MANI, HL, NBP_UNIFORM_WAVES) NBP_PRODUCT_UNIFORM_W##HL(NAME, MANI, HL, NBP_UNIFORM_WAVES)
-#define NBP_PRODUCT_UNIFORM_DEF(NAME, MANI, HL, NBP_UNIFORM_WAVES)                                                                        \
-  __global__ void __launch_bounds__(NBP_PROD_LB(MANI)) __attribute__((amdgpu_waves_per_eu(NBP_UNIFORM_WAVES))) NAME(NBP_PRODUCT_ARGS) { \
-    extern __shared__ double smem[];                                                                               \
-    product_kernel_uniform<MANI, HL, false>(descs, arena, ws, kdF, gstats, N, S, side, T, smem);                    \
-  }                                                                                                                \
-  __global__ void __launch_bounds__(NBP_PROD_LB(MANI)) __attribute__((amdgpu_waves_per_eu(NBP_UNIFORM_WAVES))) NAME##_xs(NBP_PRODUCT_ARGS) { \
-    extern __shared__ double smem[];                                                                               \
-    product_kernel_uniform<MANI, HL, true>(descs, arena, ws, kdF, gstats, N, S, side, T, smem);                     \
-  }
+#define NBP_UNIFORM_WAVES(MANI) ((MANI) == NBP_EUCLID1 ? 4 : (MANI) == NBP_EUCLID2 ? NBP_W_E2 : (MANI) == NBP_SE2 ? NBP_W_SE : (MANI) == NBP_CIRCULAR ? NBP_W_CI : 3)
+// the throughput geometry of a single-manifold batch, in two instances: node sums from the KD workspace, and `_xs` (from the
+// sorted coordinates, product_kernel_uniform)
 #if NBP_TU & NBP_TU_PRODUNI
-#define NBP_PRODUCT_UNIFORM_W2(NAME, MANI, HL, W) NBP_PRODUCT_UNIFORM_DEF(NAME, MANI, HL, W)
+#define NBP_PRODUCT_UNIFORM(NAME, MANI)                                                                                              \
+  __global__ void __launch_bounds__(NBP_PROD_LB(MANI)) __attribute__((amdgpu_waves_per_eu(NBP_UNIFORM_WAVES(MANI)))) NAME(NBP_PRODUCT_ARGS) { \
+    extern __shared__ double smem[];                                                                                                  \
+    product_kernel_uniform<MANI, 2, false>(descs, arena, ws, kdF, gstats, N, S, side, T, smem);                                       \
+  }                                                                                                                                   \
+  __global__ void __launch_bounds__(NBP_PROD_LB(MANI)) __attribute__((amdgpu_waves_per_eu(NBP_UNIFORM_WAVES(MANI)))) NAME##_xs(NBP_PRODUCT_ARGS) { \
+    extern __shared__ double smem[];                                                                                                  \
+    product_kernel_uniform<MANI, 2, true>(descs, arena, ws, kdF, gstats, N, S, side, T, smem);                                        \
+  }
 #else
-#define NBP_PRODUCT_UNIFORM_W2(NAME, MANI, HL, W) NBP_PRODUCT_UNIFORM_DECL(NAME)
+#define NBP_PRODUCT_UNIFORM(NAME, MANI) __global__ void NAME(NBP_PRODUCT_ARGS); __global__ void NAME##_xs(NBP_PRODUCT_ARGS);
 #endif
-#if NBP_TU & NBP_TU_PRODUNI4
-#define NBP_PRODUCT_UNIFORM_W4(NAME, MANI, HL, W) NBP_PRODUCT_UNIFORM_DEF(NAME, MANI, HL, W)
-#else
-#define NBP_PRODUCT_UNIFORM_W4(NAME, MANI, HL, W) NBP_PRODUCT_UNIFORM_DECL(NAME)
-#endif
-#else
-#define NBP_PRODUCT_UNIFORM_W(NAME, MANI, HL, NBP_UNIFORM_WAVES) NBP_PRODUCT_UNIFORM_DECL(NAME)
-#endif
-NBP_PRODUCT_UNIFORM(nbp_product_kernel_t2_e1, NBP_EUCLID1, 2)
-NBP_PRODUCT_UNIFORM(nbp_product_kernel_t2_e2, NBP_EUCLID2, 2)
-NBP_PRODUCT_UNIFORM(nbp_product_kernel_t2_e3, NBP_EUCLID3, 2)
-NBP_PRODUCT_UNIFORM(nbp_product_kernel_t2_ci, NBP_CIRCULAR, 2)
-NBP_PRODUCT_UNIFORM(nbp_product_kernel_t2_se, NBP_SE2, 2)
-NBP_PRODUCT_UNIFORM(nbp_product_kernel_m4_e1, NBP_EUCLID1, 4)
-NBP_PRODUCT_UNIFORM(nbp_product_kernel_m4_e2, NBP_EUCLID2, 4)
-NBP_PRODUCT_UNIFORM(nbp_product_kernel_m4_e3, NBP_EUCLID3, 4)
-NBP_PRODUCT_UNIFORM(nbp_product_kernel_m4_ci, NBP_CIRCULAR, 4)
-NBP_PRODUCT_UNIFORM(nbp_product_kernel_m4_se, NBP_SE2, 4)
+NBP_PRODUCT_UNIFORM(nbp_product_kernel_t2_e1, NBP_EUCLID1)
+NBP_PRODUCT_UNIFORM(nbp_product_kernel_t2_e2, NBP_EUCLID2)
+NBP_PRODUCT_UNIFORM(nbp_product_kernel_t2_e3, NBP_EUCLID3)
+NBP_PRODUCT_UNIFORM(nbp_product_kernel_t2_ci, NBP_CIRCULAR)
+NBP_PRODUCT_UNIFORM(nbp_product_kernel_t2_se, NBP_SE2)
 // The latency geometries of a single-manifold batch whose node statistics fit the LDS (every launch at the top of a homogeneous
 // tree): the same product_body the generic y32 / l8 run for it, without the other manifolds, the partial inputs and the
 // global-memory statistics.  The generic latency kernels inline sixteen bodies and hold 248-256 VGPRs and ~2 500 spilled SGPRs

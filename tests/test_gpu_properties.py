@@ -100,7 +100,7 @@ def test_baseline_config2_full_size_properties(hip_backend):
 @pytest.mark.parametrize("manifold,F,N", [(abi.SE2, 3, 200), (abi.EUCLID3, 2, 300), (abi.CIRCULAR, 4, 100), (abi.EUCLID2, 8, 64), (abi.EUCLID2, 2, 200)])
 @pytest.mark.parametrize("batch", [1, 64, 256])
 def test_product_geometries_match_oracle(oracle_backend, hip_backend, manifold, F, N, batch):
-    """The three product-kernel geometries (latency l8, m4, throughput t2 -- picked from the batch size)
+    """The three product-kernel geometries (latency y32, l8, throughput t2 -- picked from the batch size)
     against the oracle: identical labels, points and bandwidths to 1e-9, for the first and the last
     product of the batch.  Sweeps per level: 1, 2 (the second sweep draws from a block of its own) and, on the Euclid(2)
     pair, the maximum of 8."""

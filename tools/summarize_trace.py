@@ -25,7 +25,7 @@ def main(path, steps, lps=60):
     for r in rows:
         name = short_name(r["Kernel_Name"])
         if name.startswith("nbp_product_kernel"):
-            name = "nbp_product_kernel(x16|l8|m4|t2)"  # one launch per stage, three geometries
+            name = "nbp_product_kernel(y32|l8|t2)"  # one launch per stage, three geometries
         if name.startswith("nbp_proposal_kernel"):
             name = "nbp_proposal_kernel(generic|lin2|lin3)"  # one launch per stage
         if name.startswith("nbp_"):
