@@ -122,12 +122,16 @@ struct nbp_ctx {
   int prop_wave_min = -1;
   int fused_p1_min = 2048;  // rounds with at least this many updates run one lane per particle (NBP_FUSED_P1_MIN); smaller
                             // ones two helper rows per update, so that they fill the chip with twice the lanes each
-  // two-stream rounds (NBP_PIPELINE_MIN = smallest product batch; see plan_pipeline): the second stream, the fork / join
-  // events, and the geometry of the WHOLE batch that both halves launch with (so that no result depends on the split)
+  // two-stream rounds (NBP_PIPELINE_MIN = smallest product batch; see plan_pipeline): the second stream and the fork / join
+  // events (what a half launches with is its nbp_launch_env)
   hipStream_t stream2 = nullptr;
   hipEvent_t pipe_ev[2] = {nullptr, nullptr};
   int pipe_min = 1 << 30;
-  int geom_n = 0, geom_blocks = 0;
+  // fit launches (fit_plan): NBP_LCV_P2_MIN / NBP_LCV_P1_MIN = workgroups of a launch above which a fit runs on two / one helper
+  // rows; NBP_NO_W5_FITS: never the five-wave instances; NBP_DEBUG_OCCUPANCY: print what the runtime says a CU holds of a
+  // plain bandwidth launch
+  int lcv_p2_min = 256, lcv_p1_min = 4 * 256;
+  bool fit_w5 = true, debug_occupancy = false;
   // product launches (product_plan): NBP_PRODUCT_HL2_MIN = smallest batch in the throughput geometry, NBP_PRODUCT_NCH = chunks
   // per helper range (0: as many as the LDS takes), NBP_PRODUCT_ALL_LEVELS_HL = fewest helper lanes that stage every level at
   // once; NBP_NO_XS_PRODUCTS: node sums from the KD workspace only; NBP_NO_UNIFORM_LATENCY_PRODUCTS: the generic latency
@@ -299,17 +303,18 @@ nbp_status nbp_ctx_create(int32_t device, int32_t N, int32_t n_slots, void *aren
   if (getenv("NBP_PRODUCT_ALL_LEVELS_HL")) c->prod_all_levels_hl = atoi(getenv("NBP_PRODUCT_ALL_LEVELS_HL"));
   c->prod_xs = getenv("NBP_NO_XS_PRODUCTS") == nullptr;
   c->prod_lat_uni = getenv("NBP_NO_UNIFORM_LATENCY_PRODUCTS") == nullptr;
+  if (getenv("NBP_LCV_P2_MIN")) c->lcv_p2_min = atoi(getenv("NBP_LCV_P2_MIN"));
+  if (getenv("NBP_LCV_P1_MIN")) c->lcv_p1_min = atoi(getenv("NBP_LCV_P1_MIN"));
+  c->fit_w5 = getenv("NBP_NO_W5_FITS") == nullptr;
+  c->debug_occupancy = getenv("NBP_DEBUG_OCCUPANCY") != nullptr;
   nbp_status rc = build_levels(c);
   if (rc != NBP_OK) return rc;
   // allow the full 160 KiB LDS for the product kernels
   for (const nbp_product_kernel_row &k : NBP_PRODUCT_KERNELS)
     HIPCHK(hipFuncSetAttribute((const void *)k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIPCHK(hipFuncSetAttribute((const void *)nbp_bandwidth_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIPCHK(hipFuncSetAttribute((const void *)nbp_prep_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIPCHK(hipFuncSetAttribute((const void *)nbp_bandwidth_kernel_spec<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIPCHK(hipFuncSetAttribute((const void *)nbp_bandwidth_kernel_spec<3>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIPCHK(hipFuncSetAttribute((const void *)nbp_prep_kernel_spec<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIPCHK(hipFuncSetAttribute((const void *)nbp_prep_kernel_spec<3>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  for (const void *k : {(const void *)nbp_bandwidth_kernel, (const void *)nbp_prep_kernel, (const void *)nbp_bandwidth_kernel_spec<2>,
+                        (const void *)nbp_bandwidth_kernel_spec<3>, (const void *)nbp_prep_kernel_spec<2>, (const void *)nbp_prep_kernel_spec<3>})
+    HIPCHK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   // (the kernel has 608 B of static LDS, the hypothesis recipe: static + dynamic must stay within the 160 KiB)
   HIPCHK(hipFuncSetAttribute((const void *)nbp_update_kernel_lin2_p1, hipFuncAttributeMaxDynamicSharedMemorySize, 158 * 1024));
   HIPCHK(hipFuncSetAttribute((const void *)nbp_update_kernel_lin2_p2, hipFuncAttributeMaxDynamicSharedMemorySize, 158 * 1024));
@@ -830,15 +835,27 @@ static nbp_status toc(nbp_ctx *c, std::vector<std::pair<hipEvent_t, hipEvent_t>>
   return NBP_OK;
 }
 
+// What a launch runs with: the stream, the KD workspace it may use and, inside a two-stream round, the size of the WHOLE
+// batch (products, and workgroups of its prep launch), by which both halves pick their geometry so that no result depends
+// on the split.  geom_n = geom_blocks = 0 outside a round.  By value: nothing a launch does depends on context state that
+// a round would have to set and put back.
+struct nbp_launch_env {
+  hipStream_t stream = nullptr;
+  double *ws = nullptr;
+  size_t ws_doubles = 0;
+  int geom_n = 0, geom_blocks = 0;
+};
+static nbp_launch_env ctx_env(const nbp_ctx *c) { return {c->stream, c->ws, c->ws_doubles, 0, 0}; }
+
 // 0, or the class of a batch whose relative factors are all full (non-partial) factors of one kind on one manifold, with
-// everything else in it (priors, message priors, pass-through densities) on that manifold as well:
-// 1 LinearRelative / Euclid(2), 3 LinearRelative / Euclid(3)
+// everything else in it (priors, message priors, pass-through densities) on that manifold as well: LinearRelative on
+// Euclid(2) / Euclid(3), CircularCircular on the circle, ManifoldFactor on SE(2)
+enum { NBP_CLS_LIN2 = 1, NBP_CLS_LIN3 = 3, NBP_CLS_CIRC = 4, NBP_CLS_SE2 = 5 };
 #define NBP_CLS_SIMPLE 256
 static int proposals_uniform_class(const nbp_proposal_desc *d, int n) {
   if (n <= 0) return 0;
   const int M = d[0].manifold;
-  // class = the manifold code: LinearRelative on Euclid(2) / Euclid(3), CircularCircular on the circle, ManifoldFactor on SE(2)
-  const int cls = M == NBP_EUCLID2 ? 1 : (M == NBP_EUCLID3 ? 3 : (M == NBP_CIRCULAR ? 4 : (M == NBP_SE2 ? 5 : 0)));
+  const int cls = M == NBP_EUCLID2 ? NBP_CLS_LIN2 : (M == NBP_EUCLID3 ? NBP_CLS_LIN3 : (M == NBP_CIRCULAR ? NBP_CLS_CIRC : (M == NBP_SE2 ? NBP_CLS_SE2 : 0)));
   const int want = M == NBP_CIRCULAR ? NBP_F_CIRCULAR : (M == NBP_SE2 ? NBP_F_SE2 : NBP_F_LINREL);
   if (!cls) return 0;
   // "simple" (bit 8, NBP_CLS_SIMPLE): every particle of every proposal on the factor's one hypothesis -- no multihypo, no
@@ -856,7 +873,7 @@ static int proposals_uniform_class(const nbp_proposal_desc *d, int n) {
   // (a batch of priors / message priors alone runs its manifold's instance as well)
   return cls | (simple ? NBP_CLS_SIMPLE : 0);
 }
-static nbp_status launch_proposals(nbp_ctx *c, const nbp_proposal_desc *dev, int n, int cls = 0) {
+static nbp_status launch_proposals(nbp_ctx *c, const nbp_launch_env &env, const nbp_proposal_desc *dev, int n, int cls = 0) {
   if (n <= 0) return NBP_OK;
   nbp_status rc = tic(c, c->ev[0]);
   if (rc) return rc;
@@ -865,33 +882,39 @@ static nbp_status launch_proposals(nbp_ctx *c, const nbp_proposal_desc *dev, int
   cls &= NBP_CLS_SIMPLE - 1;
   // chip-filling launches of simple Euclidean batches: one wave per proposal, no workgroup barrier (nbp_kernels.h,
   // proposal_wave_body); rows of up to five waves (N <= 320)
-  const int wave_min = c->prop_wave_min >= 0 ? c->prop_wave_min : (cls == 1 ? 900 : (c->N > 256 ? 1500 : (1 << 30)));
-  if (simple && n >= wave_min && (cls == 1 || cls == 3) && c->N <= (cls == 1 ? 256 : 320)) {
-    auto *wk = cls == 1 ? nbp_proposal_wave_kernel_lin2 : (c->N <= 256 ? nbp_proposal_wave_kernel_lin3 : nbp_proposal_wave_kernel_lin3n5);
-    hipLaunchKernelGGL(wk, dim3((n + NBP_PW_WAVES - 1) / NBP_PW_WAVES), dim3(64 * NBP_PW_WAVES), nbp_proposal_wave_lds_bytes(c->N, cls == 1 ? 2 : 3),
-                       c->stream, dev, n, c->arena, c->N, c->S, c->side, c->counters);
+  const int wave_min = c->prop_wave_min >= 0 ? c->prop_wave_min : (cls == NBP_CLS_LIN2 ? 900 : (c->N > 256 ? 1500 : (1 << 30)));
+  if (simple && n >= wave_min && (cls == NBP_CLS_LIN2 || cls == NBP_CLS_LIN3) && c->N <= (cls == NBP_CLS_LIN2 ? 256 : 320)) {
+    auto *wk = cls == NBP_CLS_LIN2 ? nbp_proposal_wave_kernel_lin2 : (c->N <= 256 ? nbp_proposal_wave_kernel_lin3 : nbp_proposal_wave_kernel_lin3n5);
+    hipLaunchKernelGGL(wk, dim3((n + NBP_PW_WAVES - 1) / NBP_PW_WAVES), dim3(64 * NBP_PW_WAVES), nbp_proposal_wave_lds_bytes(c->N, cls == NBP_CLS_LIN2 ? 2 : 3),
+                       env.stream, dev, n, c->arena, c->N, c->S, c->side, c->counters);
     HIPCHK(hipGetLastError());
     return toc(c, c->ev[0]);
   }
-  auto *kern = cls == 1 ? nbp_proposal_kernel_lin2 : (cls == 3 ? nbp_proposal_kernel_lin3 : (cls == 4 ? nbp_proposal_kernel_circ :
-               (cls == 5 ? nbp_proposal_kernel_se2 : nbp_proposal_kernel)));
-  hipLaunchKernelGGL(kern, dim3(n), dim3(c->Npad), nbp_proposal_lds_bytes(c->N), c->stream, dev, c->arena, c->N, c->Npad, c->S, c->side,
+  auto *kern = cls == NBP_CLS_LIN2 ? nbp_proposal_kernel_lin2 : (cls == NBP_CLS_LIN3 ? nbp_proposal_kernel_lin3 : (cls == NBP_CLS_CIRC ? nbp_proposal_kernel_circ :
+               (cls == NBP_CLS_SE2 ? nbp_proposal_kernel_se2 : nbp_proposal_kernel)));
+  hipLaunchKernelGGL(kern, dim3(n), dim3(c->Npad), nbp_proposal_lds_bytes(c->N), env.stream, dev, c->arena, c->N, c->Npad, c->S, c->side,
                      c->counters);
   HIPCHK(hipGetLastError());
   return toc(c, c->ev[0]);
 }
-static nbp_status ensure_ws(nbp_ctx *c, int nprod, int kdF) {
+// room for the KD builds of nprod products in the environment's workspace; outside a round the context's workspace grows
+// (and `env` follows it)
+static nbp_status ensure_ws(nbp_ctx *c, nbp_launch_env &env, int nprod, int kdF) {
   const size_t need = (size_t)nprod * (size_t)kdF * nbp_kd_ws_doubles(c->N);
-  if (need <= c->ws_doubles) return NBP_OK;
-  // inside a two-stream round c->ws is an INTERIOR pointer of the workspace (the second half's share): it must never be
-  // freed or re-allocated here -- the round is sized at finalize, a shortfall now is a planning error, not a reason to grow
-  if (c->geom_n) return fail(NBP_ERR_RANGE, "KD workspace too small inside a two-stream round (sized at nbp_program_finalize)");
+  if (need <= env.ws_doubles) return NBP_OK;
+  // a half of a two-stream round may hold an INTERIOR pointer of the workspace (the second half's share): never freed or
+  // re-allocated here -- the round is sized at finalize, a shortfall now is a planning error, not a reason to grow
+  if (env.geom_n) return fail(NBP_ERR_RANGE, "KD workspace too small inside a two-stream round (sized at nbp_program_finalize)");
   HIPCHK(hipStreamSynchronize(c->stream));
   if (c->ws) HIPCHK(hipFree(c->ws));
   c->ws = nullptr;
+  c->ws_doubles = 0;
   c->ws_gen++;  // captured graphs hold the old pointer as a kernel argument: they are re-captured before their next replay
-  c->ws_doubles = need + need / 4 + 16 * nbp_kd_ws_doubles(c->N);
-  HIPCHK(hipMalloc(&c->ws, c->ws_doubles * 8));
+  const size_t grown = need + need / 4 + 16 * nbp_kd_ws_doubles(c->N);
+  HIPCHK(hipMalloc(&c->ws, grown * 8));
+  c->ws_doubles = grown;
+  env.ws = c->ws;
+  env.ws_doubles = c->ws_doubles;
   return NBP_OK;
 }
 static nbp_status ensure_gstats(nbp_ctx *c, size_t need) {
@@ -905,32 +928,83 @@ static nbp_status ensure_gstats(nbp_ctx *c, size_t need) {
   return NBP_OK;
 }
 
-// sample groups per product: spread a product over G workgroups when the launch cannot fill the chip
+// A list of bandwidth fits (manikde!): one (slot, manifold) per fit, in launch order.  The kernels read a list as
+// [slots | manifolds] (append_fits lays it out; `off` = where, in the program blob).
+struct nbp_fits {
+  struct fit { int32_t slot, mani; };
+  std::vector<fit> v;
+  size_t off = 0;
+  void push(int32_t slot, int32_t mani) { v.push_back({slot, mani}); }
+  void clear() { v.clear(); }
+  bool empty() const { return v.empty(); }
+  int size() const { return (int)v.size(); }
+  bool has(int32_t slot) const { return std::any_of(v.begin(), v.end(), [&](const fit &f) { return f.slot == slot; }); }
+  void drop(int32_t slot) { v.erase(std::remove_if(v.begin(), v.end(), [&](const fit &f) { return f.slot == slot; }), v.end()); }
+  void rename(int32_t a, int32_t b) { for (fit &f : v) if (f.slot == a) f.slot = b; }
+  void dedup() {  // one fit per slot: the first
+    for (size_t q = 0; q < v.size(); q++)
+      v.erase(std::remove_if(v.begin() + q + 1, v.end(), [&](const fit &f) { return f.slot == v[q].slot; }), v.end());
+  }
+  // fitted coordinates (sum of the manifold dimensions) of fits [from, from + n)
+  int coords(int from = 0, int n = -1) const {
+    int cds = 0;
+    for (int i = from; i < (n < 0 ? size() : from + n); i++) cds += manifold_dim_h(v[i].mani);
+    return cds;
+  }
+};
+// fits [from, from + n) of a list as a launch takes them: device pointers into the uploaded copy at `base`
+struct nbp_fits_dev { const int32_t *slots = nullptr, *manis = nullptr; int n = 0, coords = 0; };
+static nbp_fits_dev fits_dev(const nbp_fits &f, const void *base, int from = 0, int n = -1) {
+  if (n < 0) n = f.size() - from;
+  const int32_t *s = (const int32_t *)((const char *)base + f.off);
+  return {s + from, s + f.size() + from, n, f.coords(from, n)};
+}
+// the list behind `blob`, 64-byte aligned: slots, manifolds, `tail` spare bytes
+static void append_fits(std::vector<char> &blob, nbp_fits &f, size_t tail = 0) {
+  f.off = (blob.size() + 63) & ~(size_t)63;
+  blob.resize(f.off + (size_t)f.size() * 8 + tail);
+  int32_t *w = (int32_t *)(blob.data() + f.off);
+  for (int i = 0; i < f.size(); i++) { w[i] = f.v[i].slot; w[f.size() + i] = f.v[i].mani; }
+}
 
-// Helper lanes per particle for the LCV / KD launches: P = 4 (1024-lane workgroups) minimises the
+// ---- fit launches ----
+// Helper rows per particle for the LCV / KD launches: P = 4 (1024-lane workgroups) minimises the
 // latency of a single fit when the launch cannot fill the chip; P = 2 (512 lanes) lets four
 // workgroups share a CU so that the barrier/combine phases of one overlap the pair loop of the
 // others when there are many fits (throughput mode).
 // throughput-mode fits whose workgroup is 4k + 1 waves (N = 257 .. 320: config 5's N = 300) run the five-waves-per-SIMD
 // instances of the fit kernels: four such workgroups per CU, five waves on every SIMD, instead of three (nbp_kernels.h)
-static bool rows_of_4k_plus_1_waves(const nbp_ctx *c, int P) {
-  static const bool off = getenv("NBP_NO_W5_FITS") != nullptr;
-  return !off && P == 1 && ((c->Npad >> 6) & 3) == 1 && c->Npad > 64;
-}
-static int lcv_helpers(nbp_ctx *c, int nblocks) {
-  static const int p2_min = getenv("NBP_LCV_P2_MIN") ? atoi(getenv("NBP_LCV_P2_MIN")) : 256;
-  static const int p1_min = getenv("NBP_LCV_P1_MIN") ? atoi(getenv("NBP_LCV_P1_MIN")) : 4 * 256;
-  int P = c->P;
-  if (nblocks > p2_min && P > 2) P = 2;
-  if (nblocks > p1_min) P = 1;
-  return P;
+// Speculation: latency mode, a handful of fits and the rest of the chip idle -> 3 workgroups per fitted coordinate (two
+// iterations per rendezvous), 7 (three) where the whole launch is still resident at once (NBP_SPEC_MAXBLOCKS above).
+// One plan for the fits of a prep launch (beside the KD builds of nprod products of up to kdF densities) and of a plain
+// bandwidth launch (nprod = 0); each keeps its own grid shape, which its kernel indexes by.
+struct nbp_fit_plan {
+  int P = 1;          // helper rows per particle
+  int depth = 0;      // speculation: 0 (none), 2 or 3 iterations per rendezvous = KS workgroups per fitted coordinate
+  int KS = 1;
+  bool w5 = false;    // the five-wave instance (plain launches only)
+  int threads = 0;    // workgroup size
+  size_t lds = 0;     // dynamic LDS bytes
+};
+static nbp_fit_plan fit_plan(const nbp_ctx *c, const nbp_launch_env &env, int nbw, int coords, int nprod = 0, int kdF = 0) {
+  nbp_fit_plan f;
+  const int nkd = nprod * kdF;  // KD-build workgroups
+  const int nblocks = env.geom_blocks ? env.geom_blocks : 2 * nbw + 2 * nprod;
+  f.P = c->P;
+  if (nblocks > c->lcv_p2_min && f.P > 2) f.P = 2;
+  if (nblocks > c->lcv_p1_min) f.P = 1;
+  if (c->spec_on && nbw > 0 && nbw <= NBP_SPEC_MAXJOBS && !env.geom_n) {
+    if (c->spec_depth3 && coords * 7 + nkd <= NBP_SPEC_MAXBLOCKS) f.depth = 3;
+    else if (coords * 3 + nkd <= NBP_SPEC_MAXBLOCKS) f.depth = 2;
+  }
+  f.KS = f.depth ? (1 << f.depth) - 1 : 1;
+  f.w5 = !f.depth && c->fit_w5 && f.P == 1 && ((c->Npad >> 6) & 3) == 1 && c->Npad > 64;
+  f.threads = f.P * c->Npad;
+  if (nbw > 0) f.lds = nbp_bandwidth_lds_bytes(c->N, c->Npad, f.P);
+  if (nkd > 0) f.lds = std::max(f.lds, nbp_kd_lds_bytes(3, c->N, c->Npad, f.P));
+  return f;
 }
 
-static int coords_of(const int32_t *manis, size_t n) {
-  int cds = 0;
-  for (size_t i = 0; i < n; i++) cds += manifold_dim_h(manis[i]);
-  return cds;
-}
 // ---- product launches ----
 // Geometry: HL helper lanes per sample (64/HL samples per wave), workgroups of `wpb` waves, grid.y = G workgroups per product.
 // Latency mode (the launch cannot fill the chip): HL = 32 for fewer than 16 products, else HL = 8, with several small
@@ -967,8 +1041,8 @@ static const size_t NBP_PRODUCT_ALL_LEVELS_LDS = 76 * 1024;
 static const long NBP_PRODUCT_W1_BLOCKS = 256;
 
 // `mani`: the manifold of a single-manifold batch (0: mixed; < 0: size for the widest workgroup any kernel takes)
-static void product_geometry(const nbp_ctx *c, int n, int *HL, int *wpb, int *G, int mani) {
-  if (c->geom_n) n = c->geom_n;  // one half of a two-stream round: the geometry of the whole batch
+static void product_geometry(const nbp_ctx *c, const nbp_launch_env &env, int n, int *HL, int *wpb, int *G, int mani) {
+  if (env.geom_n) n = env.geom_n;  // one half of a two-stream round: the geometry of the whole batch
   *HL = n >= c->prod_hl2_min ? 2 : (n >= 16 ? 8 : 32);
   const int SW = 64 / *HL, waves = (c->N + SW - 1) / SW, cap = (*HL >= 8) ? NBP_PRODUCT_LAT_WAVES : 8;
   int g = (waves + cap - 1) / cap;
@@ -1011,14 +1085,14 @@ struct nbp_product_plan {
   nbp_product_fn fn = nullptr;  // from NBP_PRODUCT_KERNELS (nullptr: the table has none for this plan)
 };
 // `maxFD` encodes the largest (F, D) of the batch as F*4 + D; `mani` as for product_geometry
-static nbp_product_plan product_plan(const nbp_ctx *c, int n, int maxFD, int mani) {
+static nbp_product_plan product_plan(const nbp_ctx *c, const nbp_launch_env &env, int n, int maxFD, int mani) {
   nbp_product_plan p;
   const int F = maxFD / 4, D = maxFD % 4;
-  product_geometry(c, n, &p.HL, &p.wpb, &p.G, mani);
+  product_geometry(c, env, n, &p.HL, &p.wpb, &p.G, mani);
   // big: the statistics do not fit with the chunk sums the throughput geometries keep in LDS (two chunks per lane at least)
   p.big = nbp_product_lds_bytes(F, D, c->N, p.wpb * 64 / p.HL, false, p.HL <= 4 ? (size_t)2 * 2 * p.wpb * 64 : 0,
                                 product_lays_circ(p.HL, mani)) > NBP_PRODUCT_LDS_CAP;
-  if (p.big && p.HL != 8) product_geometry(c, 16, &p.HL, &p.wpb, &p.G, 0);  // many densities: small sample groups keep the label table in LDS
+  if (p.big && p.HL != 8) product_geometry(c, env, 16, &p.HL, &p.wpb, &p.G, 0);  // many densities: small sample groups keep the label table in LDS
   const int TB = p.wpb * 64, SPB = TB / p.HL;
   p.circ = product_lays_circ(p.HL, mani);
   // The launch takes the node sums from the sorted coordinates itself (4 KB instead of 33 KB of KD workspace per density
@@ -1061,55 +1135,37 @@ static nbp_product_plan product_plan(const nbp_ctx *c, int n, int maxFD, int man
   // node statistics fit the LDS (and unless NBP_NO_UNIFORM_LATENCY_PRODUCTS) -- else a generic one; `_w1` where the launch
   // has at most one workgroup (of at most four waves) per CU
   const int km = (mani > 0 && (p.HL <= 4 || (c->prod_lat_uni && !p.big))) ? mani : 0;
-  p.w1 = km == 0 && p.HL >= 8 && TB <= 256 && (long)n * p.G <= NBP_PRODUCT_W1_BLOCKS && !c->geom_n;
+  p.w1 = km == 0 && p.HL >= 8 && TB <= 256 && (long)n * p.G <= NBP_PRODUCT_W1_BLOCKS && !env.geom_n;
   for (const nbp_product_kernel_row &k : NBP_PRODUCT_KERNELS)
     if (k.HL == p.HL && k.mani == km && k.xs == p.xs && k.w1 == p.w1) p.fn = k.fn;
   return p;
 }
 
-// the rendezvous areas of the next launch of speculative fits, blanked on the library's stream (nbp_spec_blank_kernel)
-static void blank_spec_areas(nbp_ctx *c, int jobs) {
-#ifdef NBP_SPEC_BLANK_MEMSET  // experiment (tools/exp/concurrency_probe3.sh): the hipMemsetAsync this kernel replaced
-  (void)hipMemsetAsync(c->spec, 0xFF, sizeof(nbp_spec_area) * 3 * (size_t)jobs, c->stream);
-#else
+// the rendezvous areas of the next launch of speculative fits, blanked on the launch's stream
+static void blank_spec_areas(nbp_ctx *c, const nbp_launch_env &env, int jobs) {
   const int words = (int)(sizeof(nbp_spec_area) / 8) * 3 * jobs;
-  hipLaunchKernelGGL(nbp_spec_blank_kernel, dim3((words + 255) / 256), dim3(256), 0, c->stream, (unsigned long long *)c->spec, words);
-#endif
+  hipLaunchKernelGGL(nbp_spec_blank_kernel, dim3((words + 255) / 256), dim3(256), 0, env.stream, (unsigned long long *)c->spec, words);
 }
 
-// nbp_prep_kernel: pending bandwidth fits + KD builds of this product batch, one launch
-static nbp_status launch_prep(nbp_ctx *c, const int32_t *bw_slots, const int32_t *bw_manis, int nbw,
-                              const nbp_product_desc *dev, int n, int maxFD, int coords = -1, int mani = 0) {
-  if (coords < 0) coords = 3 * nbw;
-  nbp_status rc = ensure_ws(c, n, maxFD / 4);
+// nbp_prep_kernel: pending bandwidth fits + KD builds of this product batch, one launch (grid: 3 * KS workgroups per fit,
+// then one per product and density)
+static nbp_status launch_prep(nbp_ctx *c, nbp_launch_env &env, const nbp_fits_dev &bw, const nbp_product_desc *dev, int n, int maxFD, int mani = 0) {
+  const int F = maxFD / 4;
+  nbp_status rc = ensure_ws(c, env, n, F);
   if (rc) return rc;
   rc = tic(c, c->ev[1]);
   if (rc) return rc;
-  const int P = lcv_helpers(c, c->geom_blocks ? c->geom_blocks : 2 * nbw + 2 * n);
-  size_t lds = nbp_kd_lds_bytes(3, c->N, c->Npad, P);
-  if (nbw > 0 && nbp_bandwidth_lds_bytes(c->N, c->Npad, P) > lds) lds = nbp_bandwidth_lds_bytes(c->N, c->Npad, P);
+  const nbp_fit_plan f = fit_plan(c, env, bw.n, bw.coords, n, F);
   (void)hipGetLastError();
-  const int kdF = (maxFD / 4) | (product_plan(c, n, maxFD, mani).xs ? NBP_KD_NOSTATS : 0);
-  const int nkd = n * (maxFD / 4);  // KD-build workgroups
-  // latency mode: a handful of fits, the rest of the chip idle -> NBP_SPEC_K workgroups per fit
-  // 3 workgroups per fit (two iterations per rendezvous) when the whole launch is resident at once (7 / three on request)
-  int depth = 0;
-  if (c->spec_on && nbw > 0 && nbw <= NBP_SPEC_MAXJOBS && !c->geom_n) {
-    if (c->spec_depth3 && coords * 7 + nkd <= NBP_SPEC_MAXBLOCKS) depth = 3;
-    else if (coords * 3 + nkd <= NBP_SPEC_MAXBLOCKS) depth = 2;
-  }
-  const bool spec = depth > 0;
-  const int KS = spec ? (1 << depth) - 1 : 1;
-  if (spec) blank_spec_areas(c, nbw);
-  if (depth == 3)
-    hipLaunchKernelGGL(nbp_prep_kernel_spec<3>, dim3(3 * nbw * KS + nkd), dim3(P * c->Npad), lds, c->stream, bw_slots, bw_manis, nbw,
-                       dev, n, kdF, c->arena, c->ws, c->N, c->Npad, c->S, c->T, c->counters, c->spec);
-  else if (depth == 2)
-    hipLaunchKernelGGL(nbp_prep_kernel_spec<2>, dim3(3 * nbw * KS + nkd), dim3(P * c->Npad), lds, c->stream, bw_slots, bw_manis, nbw,
-                       dev, n, kdF, c->arena, c->ws, c->N, c->Npad, c->S, c->T, c->counters, c->spec);
-  else
-    hipLaunchKernelGGL(rows_of_4k_plus_1_waves(c, P) ? nbp_prep_kernel_w5 : nbp_prep_kernel, dim3(3 * nbw + nkd), dim3(P * c->Npad), lds, c->stream,
-                       bw_slots, bw_manis, nbw, dev, n, kdF, c->arena, c->ws, c->N, c->Npad, c->S, c->T, c->counters);
+  const int kdF = F | (product_plan(c, env, n, maxFD, mani).xs ? NBP_KD_NOSTATS : 0);
+  const dim3 grid(3 * bw.n * f.KS + n * F);
+  if (f.depth) {
+    blank_spec_areas(c, env, bw.n);
+    hipLaunchKernelGGL(f.depth == 3 ? nbp_prep_kernel_spec<3> : nbp_prep_kernel_spec<2>, grid, dim3(f.threads), f.lds, env.stream, bw.slots, bw.manis,
+                       bw.n, dev, n, kdF, c->arena, env.ws, c->N, c->Npad, c->S, c->T, c->counters, c->spec);
+  } else
+    hipLaunchKernelGGL(f.w5 ? nbp_prep_kernel_w5 : nbp_prep_kernel, grid, dim3(f.threads), f.lds, env.stream, bw.slots, bw.manis, bw.n, dev, n, kdF,
+                       c->arena, env.ws, c->N, c->Npad, c->S, c->T, c->counters);
   HIPCHK(hipGetLastError());
   return toc(c, c->ev[1]);
 }
@@ -1131,12 +1187,12 @@ static int products_uniform_manifold(const nbp_product_desc *d, int n) {
   }
   return mani > 0 ? mani : 0;
 }
-static nbp_status launch_products(nbp_ctx *c, const nbp_product_desc *dev, int n, int maxFD, int mani = 0) {
+static nbp_status launch_products(nbp_ctx *c, const nbp_launch_env &env, const nbp_product_desc *dev, int n, int maxFD, int mani = 0) {
   if (n <= 0) return NBP_OK;
-  const nbp_product_plan p = product_plan(c, n, maxFD, mani);
+  const nbp_product_plan p = product_plan(c, env, n, maxFD, mani);
   // (the halves of a two-stream round take the geometry of the whole batch, whose throughput kernels have no scratch path, and
   //  share one scratch area: nbp_program_finalize pipelines no round whose products are big -- refused here should it ever)
-  if (p.big && c->geom_n) return fail(NBP_ERR_RANGE, "product: node statistics beyond the LDS inside a two-stream round");
+  if (p.big && env.geom_n) return fail(NBP_ERR_RANGE, "product: node statistics beyond the LDS inside a two-stream round");
   if (p.lds > 160 * 1024) return fail(NBP_ERR_RANGE, "product: too many densities for the LDS label table");
   if (!p.fn) return fail(NBP_ERR_RANGE, "product: no kernel for the launch's geometry");
   nbp_status rc = NBP_OK;
@@ -1148,64 +1204,59 @@ static nbp_status launch_products(nbp_ctx *c, const nbp_product_desc *dev, int n
   if (rc) return rc;
   (void)hipGetLastError();
   const int flagsF = (maxFD / 4) | (p.nch << NBP_PROD_NCH_SHIFT) | (p.all_levels ? NBP_PROD_ALL_LEVELS : 0);
-  hipLaunchKernelGGL(p.fn, dim3(n, p.G), dim3(p.wpb * 64), p.lds, c->stream, dev, c->arena, c->ws, flagsF, p.big ? c->gstats : nullptr, c->N, c->S,
+  hipLaunchKernelGGL(p.fn, dim3(n, p.G), dim3(p.wpb * 64), p.lds, env.stream, dev, c->arena, env.ws, flagsF, p.big ? c->gstats : nullptr, c->N, c->S,
                      c->side, c->T);
   HIPCHK(hipGetLastError());
   return toc(c, c->ev[2]);
 }
 
-// the allocations launch_prep / launch_products would make on demand for a batch of n products
+// the allocations launch_prep / launch_products would make on demand for a batch of n products (outside a round: a round
+// shares the workspace of its whole batch)
 static nbp_status presize_products(nbp_ctx *c, int n, int maxFD, int mani = 0) {
-  nbp_status rc = ensure_ws(c, n, maxFD / 4);
+  nbp_launch_env env = ctx_env(c);
+  nbp_status rc = ensure_ws(c, env, n, maxFD / 4);
   if (rc) return rc;
   // the launch's own plan, or the widest workgroup any kernel may take (mani = -1: its larger label table decides about the
   // scratch) -- whichever asks for the scratch area gets it allocated here, outside the replayed region
-  const size_t gs = std::max(product_plan(c, n, maxFD, mani).gstats, product_plan(c, n, maxFD, -1).gstats);
+  const size_t gs = std::max(product_plan(c, env, n, maxFD, mani).gstats, product_plan(c, env, n, maxFD, -1).gstats);
   if (gs) rc = ensure_gstats(c, gs);
   return rc;
 }
 
-static nbp_status launch_bandwidth(nbp_ctx *c, const int32_t *dev_slots, const int32_t *dev_manis, int n, int coords = -1) {
-  if (n <= 0) return NBP_OK;
-  if (coords < 0) coords = 3 * n;
+// nbp_bandwidth_kernel: fits alone (grid: fit x coordinate x KS)
+static nbp_status launch_bandwidth(nbp_ctx *c, const nbp_launch_env &env, const nbp_fits_dev &bw) {
+  if (bw.n <= 0) return NBP_OK;
   nbp_status rc = tic(c, c->ev[3]);
   if (rc) return rc;
   (void)hipGetLastError();
-  const int P = lcv_helpers(c, 2 * n);
-  int depth = 0;
-  if (c->spec_on && n <= NBP_SPEC_MAXJOBS) depth = (c->spec_depth3 && coords * 7 <= NBP_SPEC_MAXBLOCKS) ? 3 : ((coords * 3 <= NBP_SPEC_MAXBLOCKS) ? 2 : 0);
-  const bool spec = depth > 0;
-  if (spec) blank_spec_areas(c, n);
-  if (depth == 3)
-    hipLaunchKernelGGL(nbp_bandwidth_kernel_spec<3>, dim3(n, 3, 7), dim3(P * c->Npad), nbp_bandwidth_lds_bytes(c->N, c->Npad, P), c->stream,
-                       dev_slots, dev_manis, c->arena, c->N, c->Npad, c->S, c->counters, c->spec);
-  else if (depth == 2)
-    hipLaunchKernelGGL(nbp_bandwidth_kernel_spec<2>, dim3(n, 3, 3), dim3(P * c->Npad), nbp_bandwidth_lds_bytes(c->N, c->Npad, P), c->stream,
-                       dev_slots, dev_manis, c->arena, c->N, c->Npad, c->S, c->counters, c->spec);
-  else
-  {
-    auto *kern = rows_of_4k_plus_1_waves(c, P) ? nbp_bandwidth_kernel_w5 : nbp_bandwidth_kernel;
-    if (getenv("NBP_DEBUG_OCCUPANCY")) {  // what the runtime says a CU can hold of this launch
+  const nbp_fit_plan f = fit_plan(c, env, bw.n, bw.coords);
+  if (f.depth) {
+    blank_spec_areas(c, env, bw.n);
+    hipLaunchKernelGGL(f.depth == 3 ? nbp_bandwidth_kernel_spec<3> : nbp_bandwidth_kernel_spec<2>, dim3(bw.n, 3, f.KS), dim3(f.threads), f.lds, env.stream,
+                       bw.slots, bw.manis, c->arena, c->N, c->Npad, c->S, c->counters, c->spec);
+  } else {
+    auto *kern = f.w5 ? nbp_bandwidth_kernel_w5 : nbp_bandwidth_kernel;
+    if (c->debug_occupancy) {  // what the runtime says a CU can hold of this launch
       int nb = 0;
-      (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, P * c->Npad, nbp_bandwidth_lds_bytes(c->N, c->Npad, P));
-      fprintf(stderr, "[nbp] nbp_bandwidth_kernel%s: %d lanes, %zu B of LDS per workgroup: %d workgroups = %d waves per CU\n",
-              kern == nbp_bandwidth_kernel_w5 ? "_w5" : "", P * c->Npad, nbp_bandwidth_lds_bytes(c->N, c->Npad, P), nb, nb * (P * c->Npad / 64));
+      (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, f.threads, f.lds);
+      fprintf(stderr, "[nbp] nbp_bandwidth_kernel%s: %d lanes, %zu B of LDS per workgroup: %d workgroups = %d waves per CU\n", f.w5 ? "_w5" : "",
+              f.threads, f.lds, nb, nb * (f.threads / 64));
     }
-    hipLaunchKernelGGL(kern, dim3(n, 3), dim3(P * c->Npad), nbp_bandwidth_lds_bytes(c->N, c->Npad, P), c->stream,
-                       dev_slots, dev_manis, c->arena, c->N, c->Npad, c->S, c->counters);
+    hipLaunchKernelGGL(kern, dim3(bw.n, 3), dim3(f.threads), f.lds, env.stream, bw.slots, bw.manis, c->arena, c->N, c->Npad, c->S, c->counters);
   }
   HIPCHK(hipGetLastError());
   return toc(c, c->ev[3]);
 }
 
-// bandwidth jobs of a batch of proposals / products (host side)
-static void jobs_of_proposals(const nbp_proposal_desc *d, int n, std::vector<int32_t> &slots, std::vector<int32_t> &manis) {
+// The fits a batch of proposals / products queues (host side): every proposal but a pass-through and one that asks for
+// none; every real product (a pass-through keeps the bandwidth of its input).  `dead`: per descriptor, fits that
+// product_liveness found unread (null: none).
+static bool wants_fit(const nbp_proposal_desc &d) { return !d.skip_bandwidth && d.factor_kind != NBP_F_PASSTHROUGH; }
+static bool wants_fit(const nbp_product_desc &d) { return d.nfactors > 1; }
+extern "C++" template <class D>
+static void queue_fits(nbp_fits &q, const D *d, int n, const char *dead = nullptr) {
   for (int i = 0; i < n; i++)
-    if (!d[i].skip_bandwidth && d[i].factor_kind != NBP_F_PASSTHROUGH) { slots.push_back(d[i].out_slot); manis.push_back(d[i].manifold); }
-}
-static void jobs_of_products(const nbp_product_desc *d, int n, std::vector<int32_t> &slots, std::vector<int32_t> &manis) {
-  for (int i = 0; i < n; i++)
-    if (d[i].nfactors > 1) { slots.push_back(d[i].out_slot); manis.push_back(d[i].manifold); }  // pass-through keeps its bw
+    if (wants_fit(d[i]) && !(dead && dead[i])) q.push(d[i].out_slot, d[i].manifold);
 }
 
 // largest (F, D) of a product batch, encoded F*4 + D (sizes the LDS of the launch)
@@ -1218,18 +1269,12 @@ static int products_maxfd(const nbp_product_desc *d, int n) {
     }
   return F * 4 + D;
 }
-static nbp_status launch_copies(nbp_ctx *c, const nbp_copy_desc *dev, int n) {
+// whole slots, or (points_only: NBP_STAGE_COPY_POINTS) the points and the count, the destination's bandwidth left alone
+static nbp_status launch_copies(nbp_ctx *c, const nbp_copy_desc *dev, int n, bool points_only = false) {
   if (n <= 0) return NBP_OK;
   (void)hipGetLastError();
-  hipLaunchKernelGGL(nbp_copy_kernel, dim3(n), dim3(256), 0, c->stream, dev, c->arena, c->S);
-  HIPCHK(hipGetLastError());
-  return NBP_OK;
-}
-
-static nbp_status launch_copy_points(nbp_ctx *c, const nbp_copy_desc *dev, int n) {
-  if (n <= 0) return NBP_OK;
-  (void)hipGetLastError();
-  hipLaunchKernelGGL(nbp_copy_points_kernel, dim3(n), dim3(256), 0, c->stream, dev, c->arena, c->S, c->N);
+  if (points_only) hipLaunchKernelGGL(nbp_copy_points_kernel, dim3(n), dim3(256), 0, c->stream, dev, c->arena, c->S, c->N);
+  else hipLaunchKernelGGL(nbp_copy_kernel, dim3(n), dim3(256), 0, c->stream, dev, c->arena, c->S);
   HIPCHK(hipGetLastError());
   return NBP_OK;
 }
@@ -1246,21 +1291,11 @@ static nbp_status stage_upload(nbp_ctx *c, const void *src, size_t bytes) {
   return NBP_OK;
 }
 
-// upload [descriptors | job slots | job manifolds] in one staging copy and return the device views
-static nbp_status stage_with_jobs(nbp_ctx *c, const void *descs, size_t desc_bytes, const std::vector<int32_t> &slots,
-                                  const std::vector<int32_t> &manis, const int32_t **dslots, const int32_t **dmanis) {
-  size_t off = (desc_bytes + 63) & ~(size_t)63;
-  std::vector<char> buf(off + (slots.size() + manis.size()) * 4 + 8);
-  memcpy(buf.data(), descs, desc_bytes);
-  if (!slots.empty()) {
-    memcpy(buf.data() + off, slots.data(), slots.size() * 4);
-    memcpy(buf.data() + off + slots.size() * 4, manis.data(), manis.size() * 4);
-  }
-  nbp_status rc = stage_upload(c, buf.data(), buf.size());
-  if (rc) return rc;
-  *dslots = (const int32_t *)((char *)c->stage + off);
-  *dmanis = *dslots + slots.size();
-  return NBP_OK;
+// upload [descriptors | fits] in one staging copy (fits.off = where the list lies in c->stage)
+static nbp_status stage_with_fits(nbp_ctx *c, const void *descs, size_t desc_bytes, nbp_fits &fits) {
+  std::vector<char> buf((const char *)descs, (const char *)descs + desc_bytes);
+  append_fits(buf, fits, 8);
+  return stage_upload(c, buf.data(), buf.size());
 }
 
 nbp_status nbp_run_proposals(nbp_ctx *c, const nbp_proposal_desc *descs, int32_t n) {
@@ -1269,14 +1304,13 @@ nbp_status nbp_run_proposals(nbp_ctx *c, const nbp_proposal_desc *descs, int32_t
   HIPCHK(hipSetDevice(c->device));
   nbp_status rc = check_proposals(c, descs, n);
   if (rc) return rc;
-  std::vector<int32_t> js, jm;
-  jobs_of_proposals(descs, n, js, jm);
-  const int32_t *ds, *dm;
-  rc = stage_with_jobs(c, descs, sizeof(nbp_proposal_desc) * (size_t)n, js, jm, &ds, &dm);
+  nbp_fits fits;
+  queue_fits(fits, descs, n);
+  rc = stage_with_fits(c, descs, sizeof(nbp_proposal_desc) * (size_t)n, fits);
   if (rc) return rc;
-  rc = launch_proposals(c, (const nbp_proposal_desc *)c->stage, n, proposals_uniform_class(descs, n));
+  rc = launch_proposals(c, ctx_env(c), (const nbp_proposal_desc *)c->stage, n, proposals_uniform_class(descs, n));
   if (rc) return rc;
-  rc = launch_bandwidth(c, ds, dm, (int)js.size(), coords_of(jm.data(), jm.size()));  // manikde!(M, pts), ApproxConv.jl:36-42
+  rc = launch_bandwidth(c, ctx_env(c), fits_dev(fits, c->stage));  // manikde!(M, pts), ApproxConv.jl:36-42
   if (rc) return rc;
   HIPCHK(hipStreamSynchronize(c->stream));
   return NBP_OK;
@@ -1288,16 +1322,17 @@ nbp_status nbp_run_products(nbp_ctx *c, const nbp_product_desc *descs, int32_t n
   HIPCHK(hipSetDevice(c->device));
   nbp_status rc = check_products(c, descs, n);
   if (rc) return rc;
-  std::vector<int32_t> js, jm;
-  jobs_of_products(descs, n, js, jm);
-  const int32_t *ds, *dm;
-  rc = stage_with_jobs(c, descs, sizeof(nbp_product_desc) * (size_t)n, js, jm, &ds, &dm);
+  nbp_fits fits;
+  queue_fits(fits, descs, n);
+  rc = stage_with_fits(c, descs, sizeof(nbp_product_desc) * (size_t)n, fits);
   if (rc) return rc;
-  rc = launch_prep(c, nullptr, nullptr, 0, (const nbp_product_desc *)c->stage, n, products_maxfd(descs, n), -1, products_uniform_manifold(descs, n));  // KD trees
+  const int maxfd = products_maxfd(descs, n), mani = products_uniform_manifold(descs, n);
+  nbp_launch_env env = ctx_env(c);
+  rc = launch_prep(c, env, nbp_fits_dev{}, (const nbp_product_desc *)c->stage, n, maxfd, mani);  // KD trees
   if (rc) return rc;
-  rc = launch_products(c, (const nbp_product_desc *)c->stage, n, products_maxfd(descs, n), products_uniform_manifold(descs, n));
+  rc = launch_products(c, env, (const nbp_product_desc *)c->stage, n, maxfd, mani);
   if (rc) return rc;
-  rc = launch_bandwidth(c, ds, dm, (int)js.size(), coords_of(jm.data(), jm.size()));  // rebandwidth of the product
+  rc = launch_bandwidth(c, env, fits_dev(fits, c->stage));  // rebandwidth of the product
   if (rc) return rc;
   HIPCHK(hipStreamSynchronize(c->stream));
   return NBP_OK;
@@ -1329,16 +1364,17 @@ nbp_status nbp_run_deconv(nbp_ctx *c, const nbp_proposal_desc *descs, const int3
   HIPCHK(hipSetDevice(c->device));
   nbp_status rc = check_deconv(c, descs, n);
   if (rc) return rc;
-  std::vector<int32_t> ms((size_t)n, -1), none;
+  // [descriptors | slot of each measurement, or -1] in one staging copy
+  const size_t off = (sizeof(nbp_proposal_desc) * (size_t)n + 63) & ~(size_t)63;
+  std::vector<char> buf(off + (size_t)n * 4);
+  memcpy(buf.data(), descs, sizeof(nbp_proposal_desc) * (size_t)n);
   for (int i = 0; i < n; i++) {
-    if (meas_slots) {
-      if (meas_slots[i] >= c->n_slots) return fail(NBP_ERR_RANGE, "deconv: meas_slot");
-      ms[i] = meas_slots[i];
-    }
+    if (meas_slots && meas_slots[i] >= c->n_slots) return fail(NBP_ERR_RANGE, "deconv: meas_slot");
+    ((int32_t *)(buf.data() + off))[i] = meas_slots ? meas_slots[i] : -1;
   }
-  const int32_t *ds, *dm;
-  rc = stage_with_jobs(c, descs, sizeof(nbp_proposal_desc) * (size_t)n, ms, none, &ds, &dm);
+  rc = stage_upload(c, buf.data(), buf.size());
   if (rc) return rc;
+  const int32_t *ds = (const int32_t *)((char *)c->stage + off);
   rc = tic(c, c->ev[0]);
   if (rc) return rc;
   rc = launch_deconv(c, (const nbp_proposal_desc *)c->stage, ds, n);
@@ -1456,7 +1492,7 @@ nbp_status nbp_run_copies_async(nbp_ctx *c, const nbp_copy_desc *descs, int32_t 
   nbp_ctx::pin_buf *b = pin_acquire(c, sizeof(nbp_copy_desc) * (size_t)n);
   if (!b) return fail(NBP_ERR_HIP, "pinned staging buffer");
   memcpy(b->p, descs, sizeof(nbp_copy_desc) * (size_t)n);
-  rc = points_only ? launch_copy_points(c, (const nbp_copy_desc *)b->p, n) : launch_copies(c, (const nbp_copy_desc *)b->p, n);
+  rc = launch_copies(c, (const nbp_copy_desc *)b->p, n, points_only != 0);
   pin_release_behind_stream(c, b);
   return rc;
 }
@@ -1469,12 +1505,11 @@ nbp_status nbp_run_bandwidth(nbp_ctx *c, const int32_t *slots, const int32_t *ma
     if (slots[i] < 0 || slots[i] >= c->n_slots) return fail(NBP_ERR_RANGE, "bandwidth: slot out of range");
     if (!manifold_ok(manifolds[i])) return fail(NBP_ERR_ARG, "bandwidth: unknown manifold");
   }
-  std::vector<int32_t> both(slots, slots + n);
-  both.insert(both.end(), manifolds, manifolds + n);
-  nbp_status rc = stage_upload(c, both.data(), both.size() * 4);
+  nbp_fits fits;
+  for (int i = 0; i < n; i++) fits.push(slots[i], manifolds[i]);
+  nbp_status rc = stage_with_fits(c, nullptr, 0, fits);
   if (rc) return rc;
-  const int32_t *ds = (const int32_t *)c->stage;
-  rc = launch_bandwidth(c, ds, ds + n, n, coords_of(manifolds, (size_t)n));
+  rc = launch_bandwidth(c, ctx_env(c), fits_dev(fits, c->stage));
   if (rc) return rc;
   HIPCHK(hipStreamSynchronize(c->stream));
   return NBP_OK;
@@ -1508,24 +1543,26 @@ nbp_status nbp_run_resample(nbp_ctx *c, const int32_t *slots, const int32_t *man
 // nbp_bandwidth_kernel launch) when a later stage reads the bandwidth of that slot: a MsgPrior
 // proposal sampling from it, or a copy stage moving whole slots.  Per update the critical path is
 // proposal -> prep (LCV || KD) -> product.
+// nbp_program_finalize compiles the stages in named steps: plan_pipeline (reorders the descriptors of a round into its two
+// halves), product_liveness, schedule_fits (the walk over the pending fits; schedule_fused_pair where a round runs as one
+// launch), split_piped_entry_fits, layout_blob, presize, acquire_device_blob, upload_blob.  What a stage of any kind reads
+// and writes they all learn from one walk, stage_reads / stage_writes.
 struct nbp_stage {
   int kind = 0, n = 0, maxfd = 0, mani = 0;  // mani: products_uniform_manifold / proposals_uniform_class
   size_t offset = 0;            // byte offset of the descriptors in the program blob
-  std::vector<int32_t> ent_s, ent_m;  // fits pending at ENTRY of the stage
-  size_t ent_off = 0;
+  nbp_fits ent;                 // fits pending at ENTRY of the stage
   bool flush_before = false;    // run the pending fits in a plain bandwidth launch before the stage
   bool need_prep = true;        // products: some product multiplies > 1 densities (KD builds; the entry fits run beside them)
   // fused variable updates: this PROPOSALS stage and the PRODUCTS stage behind it run as ONE nbp_update_kernel launch
   // (fused_second marks that PRODUCTS stage); upd = one nbp_update_desc per product
   bool fused = false, fused_second = false;
-  int upd_F = 0, upd_cls = 0;
+  int upd_F = 0;
   std::vector<nbp_update_desc> upd;
   size_t upd_off = 0;
   // a range of nbp_program_run that ends or starts BETWEEN the two stages of a fused pair runs them in the three-launch
   // form (run_range): the fused_second stage keeps, as its entry fits, the proposals of the pair that carry a bandwidth
-  // (ent_s / ent_m) and, here, the outputs the fused launch fits itself
-  std::vector<int32_t> split_in_s, split_in_m, split_out_s, split_out_m;
-  size_t split_out_off = 0;
+  // and, here, the outputs the fused launch fits itself
+  nbp_fits split_out;
   // two-stream round (plan_pipeline): descriptors [0, pipe_split) are the first half; on the PRODUCTS stage pipe_ent splits
   // the entry fits the same way.  `pipe` on the PROPOSALS stage = the pair runs that way.
   bool pipe = false;
@@ -1623,6 +1660,48 @@ nbp_status nbp_program_set_option(nbp_program *p, int32_t option, int32_t value)
   return fail(NBP_ERR_ARG, "unknown program option");
 }
 
+// What the descriptors of a stage read and write, slot by slot: stage_reads / stage_writes, the one place that knows their
+// anatomy (product_liveness, fused_plan, plan_pipeline and schedule_fits ask it).  What a read takes from its slot:
+enum nbp_access {
+  NBP_RD_POINTS,  // the points only: the variables of a factor, a product's old_slot, COPY_POINTS, a deconvolution's variables
+  NBP_RD_KDE,     // points and bandwidth: the density a MsgPrior / pass-through proposal takes (var_slot[1]), a measurement
+                  // KDE, an input of a real product, the source of a whole-slot copy
+  NBP_RD_CARRY    // the single input of a pass-through product: the points, and whatever bandwidth the slot has (fitted or
+                  // still pending) moves to the output with them
+};
+extern "C++" {  // (templates)
+template <class F>  // f(slot, access)
+static void proposal_reads(const nbp_proposal_desc &d, F &&f) {
+  for (int k = 0; k < d.nvars; k++) f(d.var_slot[k], NBP_RD_POINTS);
+  if (d.factor_kind == NBP_F_MSGPRIOR || d.factor_kind == NBP_F_PASSTHROUGH) f(d.var_slot[1], NBP_RD_KDE);  // (unary: nvars = 1)
+  if (d.meas_kde > 0) f(d.meas_kde - 1, NBP_RD_KDE);
+}
+// f(descriptor, slot, access).  idle_old: also the old_slot of a pass-through product, which no kernel reads (fused_plan
+// has always counted it: DESIGN.md 3)
+template <class F>
+static void stage_reads(const nbp_program *p, const nbp_stage &st, F &&f, bool idle_old = false) {
+  const char *d = p->blob.data() + st.offset;
+  for (int i = 0; i < st.n; i++)
+    if (st.kind == NBP_STAGE_PROPOSALS || st.kind == NBP_STAGE_DECONV) {
+      proposal_reads(((const nbp_proposal_desc *)d)[i], [&](int32_t slot, nbp_access a) { f(i, slot, a); });
+    } else if (st.kind == NBP_STAGE_PRODUCTS) {
+      const nbp_product_desc &q = ((const nbp_product_desc *)d)[i];
+      for (int j = 0; j < q.nfactors; j++) f(i, q.in_slot[j], q.nfactors > 1 ? NBP_RD_KDE : NBP_RD_CARRY);
+      if (q.old_slot >= 0 && (q.nfactors > 1 || idle_old)) f(i, q.old_slot, NBP_RD_POINTS);
+    } else if (st.kind == NBP_STAGE_COPIES || st.kind == NBP_STAGE_COPY_POINTS) {
+      f(i, ((const nbp_copy_desc *)d)[i].src_slot, st.kind == NBP_STAGE_COPIES ? NBP_RD_KDE : NBP_RD_POINTS);
+    }
+}
+template <class F>  // f(descriptor, slot)
+static void stage_writes(const nbp_program *p, const nbp_stage &st, F &&f) {
+  const char *d = p->blob.data() + st.offset;
+  for (int i = 0; i < st.n; i++)
+    if (st.kind == NBP_STAGE_PROPOSALS || st.kind == NBP_STAGE_DECONV) f(i, ((const nbp_proposal_desc *)d)[i].out_slot);
+    else if (st.kind == NBP_STAGE_PRODUCTS) f(i, ((const nbp_product_desc *)d)[i].out_slot);
+    else if (st.kind == NBP_STAGE_COPIES || st.kind == NBP_STAGE_COPY_POINTS) f(i, ((const nbp_copy_desc *)d)[i].dst_slot);
+}
+}  // extern "C++"
+
 // Liveness of product rebandwidths (NBP_OPT_LAZY_BANDWIDTH): the bandwidth of a product's output is read
 // only by a MsgPrior proposal sampling that slot, by a product taking it as input, and by slot copies
 // (which carry it along).  dead[s][i] = the output of product i of stage s is overwritten by a later
@@ -1657,52 +1736,35 @@ static nbp_liveness product_liveness(const nbp_program *p) {
   };
   for (int s = 0; s < p->n_user_stages; s++) {
     const nbp_stage &st = p->stages[s];
-    const char *d = p->blob.data() + st.offset;
-    if (st.kind == NBP_STAGE_PROPOSALS) {
-      const nbp_proposal_desc *pd = (const nbp_proposal_desc *)d;
-      L.dead_proposal[s].assign(st.n, 0);
-      for (int i = 0; i < st.n; i++) {
-        if (pd[i].factor_kind == NBP_F_MSGPRIOR || pd[i].factor_kind == NBP_F_PASSTHROUGH) read_kde(pd[i].var_slot[1]);  // read: live
-        if (pd[i].meas_kde > 0) read_kde(pd[i].meas_kde - 1);
-      }
-      for (int i = 0; i < st.n; i++) {
-        kill(pd[i].out_slot);  // overwritten
-        last_prop[pd[i].out_slot] = {s, i};
-      }
-    } else if (st.kind == NBP_STAGE_DECONV) {  // reads points only; its outputs are always fitted
-      const nbp_proposal_desc *pd = (const nbp_proposal_desc *)d;
-      for (int i = 0; i < st.n; i++) { kill(pd[i].out_slot); last_prop.erase(pd[i].out_slot); }
-    } else if (st.kind == NBP_STAGE_COPY_POINTS) {  // not a reader of the source's bandwidth; the destination is overwritten
-      const nbp_copy_desc *cd = (const nbp_copy_desc *)d;
-      for (int i = 0; i < st.n; i++) { kill(cd[i].dst_slot); last_prop.erase(cd[i].dst_slot); }
-    } else if (st.kind == NBP_STAGE_COPIES) {
-      const nbp_copy_desc *cd = (const nbp_copy_desc *)d;
-      if (st.n == 0) {  // barrier: all live
-        open.clear();
-        for (auto &lp : last_prop) needed.push_back(lp.second);
-      }
-      for (int i = 0; i < st.n; i++) read_kde(cd[i].src_slot);
-      for (int i = 0; i < st.n; i++) { kill(cd[i].dst_slot); last_prop.erase(cd[i].dst_slot); }
-    } else if (st.kind == NBP_STAGE_PRODUCTS) {
-      const nbp_product_desc *qd = (const nbp_product_desc *)d;
-      L.dead_product[s].assign(st.n, 0);
-      for (int i = 0; i < st.n; i++)
-        for (int j = 0; j < qd[i].nfactors; j++) {  // input KDE: bandwidth read
-          if (qd[i].nfactors > 1) read_kde(qd[i].in_slot[j]);
-          else open.erase(qd[i].in_slot[j]);  // pass-through: the proposal's fit travels with the output (below)
-        }
-      for (int i = 0; i < st.n; i++) {
-        kill(qd[i].out_slot);
-        if (qd[i].nfactors > 1) {
-          open[qd[i].out_slot] = {s, i, -1, -1};
-        } else {  // pass-through: the output carries the bandwidth fitted for the proposal
-          auto lp = last_prop.find(qd[i].in_slot[0]);
-          if (lp != last_prop.end() && !((const nbp_proposal_desc *)(p->blob.data() + p->stages[lp->second.first].offset))[lp->second.second].skip_bandwidth)
-            open[qd[i].out_slot] = {s, i, lp->second.first, lp->second.second};
-        }
-        last_prop.erase(qd[i].out_slot);
-      }
+    if (st.kind == NBP_STAGE_PROPOSALS) L.dead_proposal[s].assign(st.n, 0);
+    if (st.kind == NBP_STAGE_PRODUCTS) L.dead_product[s].assign(st.n, 0);
+    if (!p->lazy_bw) continue;  // every fit is made: nothing is dead
+    if (st.kind == NBP_STAGE_COPIES && st.n == 0) {  // barrier: all live
+      open.clear();
+      for (auto &lp : last_prop) needed.push_back(lp.second);
     }
+    // (a deconvolution counts as reading points only -- its outputs are always fitted; the measurement KDE it may name is
+    //  not seen here: DESIGN.md 3)
+    if (st.kind != NBP_STAGE_DECONV)
+      stage_reads(p, st, [&](int, int32_t slot, nbp_access a) {
+        if (a == NBP_RD_KDE) read_kde(slot);  // read: live
+        else if (a == NBP_RD_CARRY) open.erase(slot);  // pass-through: the proposal's fit travels with the output (below)
+      });
+    stage_writes(p, st, [&](int i, int32_t slot) {
+      kill(slot);  // overwritten
+      if (st.kind == NBP_STAGE_PROPOSALS) { last_prop[slot] = {s, i}; return; }
+      if (st.kind == NBP_STAGE_PRODUCTS) {
+        const nbp_product_desc &q = ((const nbp_product_desc *)(p->blob.data() + st.offset))[i];
+        if (q.nfactors > 1) {
+          open[slot] = {s, i, -1, -1};
+        } else {  // pass-through: the output carries the bandwidth fitted for the proposal
+          auto lp = last_prop.find(q.in_slot[0]);
+          if (lp != last_prop.end() && !((const nbp_proposal_desc *)(p->blob.data() + p->stages[lp->second.first].offset))[lp->second.second].skip_bandwidth)
+            open[slot] = {s, i, lp->second.first, lp->second.second};
+        }
+      }
+      last_prop.erase(slot);
+    });
   }
   for (auto &nd : needed) L.dead_proposal[nd.first][nd.second] = 0;
   return L;  // whatever is still open is flushed at the end of the program: live
@@ -1717,12 +1779,12 @@ static nbp_liveness product_liveness(const nbp_program *p) {
 //   * no proposal reads a slot another update of the round writes (the three-launch form runs all proposals before any
 //     product; fused, the updates of a round run in any order) -- rounds of commuting Gibbs steps satisfy this by construction;
 //   * class: LinearRelative / priors / message priors on Euclid(2), full (non-partial) densities, no label output.
-static bool fused_plan(const nbp_program *p, int s, std::vector<nbp_update_desc> &upd, int &Fmax, int &cls) {
+static bool fused_plan(const nbp_program *p, int s, std::vector<nbp_update_desc> &upd, int &Fmax) {
   const nbp_ctx *c = p->ctx;
   if (!c->fused_on || !p->use_fused || s + 1 >= p->n_user_stages || c->Npad > 256) return false;
   const nbp_stage &A = p->stages[s], &B = p->stages[s + 1];
   if (A.kind != NBP_STAGE_PROPOSALS || B.kind != NBP_STAGE_PRODUCTS || B.n < c->fused_min || A.n < B.n) return false;
-  if ((A.mani & (NBP_CLS_SIMPLE - 1)) != 1) return false;  // proposals_uniform_class: 1 = LinearRelative on Euclid(2)
+  if ((A.mani & (NBP_CLS_SIMPLE - 1)) != NBP_CLS_LIN2) return false;
   const int M = NBP_EUCLID2;
   const nbp_proposal_desc *pd = (const nbp_proposal_desc *)(p->blob.data() + A.offset);
   const nbp_product_desc *qd = (const nbp_product_desc *)(p->blob.data() + B.offset);
@@ -1754,14 +1816,12 @@ static bool fused_plan(const nbp_program *p, int s, std::vector<nbp_update_desc>
       nused++;
       u.prop[j] = it->second;
       // what the proposal reads: never a slot that another update of this launch writes, nor another proposal's slot
-      const int nv = (q.factor_kind == NBP_F_MSGPRIOR || q.factor_kind == NBP_F_PASSTHROUGH) ? 2 : q.nvars;
-      for (int k = 0; k <= nv; k++) {
-        const int32_t r = k < nv ? q.var_slot[k] : (q.meas_kde > 0 ? q.meas_kde - 1 : -1);
-        if (r < 0) continue;
+      bool clash = false;
+      proposal_reads(q, [&](int32_t r, nbp_access) {
         auto w = prod_of.find(r);
-        if (w != prod_of.end() && w->second != i) return false;
-        if (prop_of.count(r)) return false;
-      }
+        clash |= (w != prod_of.end() && w->second != i) || prop_of.count(r);
+      });
+      if (clash) return false;
     }
   }
   if (nused != A.n) return false;
@@ -1770,40 +1830,20 @@ static bool fused_plan(const nbp_program *p, int s, std::vector<nbp_update_desc>
   std::unordered_map<int32_t, std::pair<int, int>> watch;  // slot -> (update, input)
   for (int i = 0; i < B.n; i++)
     for (int j = 0; j < qd[i].nfactors; j++) watch[qd[i].in_slot[j]] = {i, j};
-  auto rd = [&](int32_t slot) {
-    auto it = watch.find(slot);
-    if (it == watch.end()) return;
-    upd[it->second.first].flags |= 2 << it->second.second;
-    watch.erase(it);
-  };
   for (int i = 0; i < B.n; i++) watch.erase(qd[i].out_slot);  // (a product writing a proposal slot: overwritten at once)
   for (int t = s + 2; t < p->n_user_stages && !watch.empty(); t++) {
     const nbp_stage &st = p->stages[t];
-    const char *d = p->blob.data() + st.offset;
-    if (st.kind == NBP_STAGE_PROPOSALS || st.kind == NBP_STAGE_DECONV) {
-      const nbp_proposal_desc *x = (const nbp_proposal_desc *)d;
-      for (int i = 0; i < st.n; i++) {
-        const int nv = (x[i].factor_kind == NBP_F_MSGPRIOR || x[i].factor_kind == NBP_F_PASSTHROUGH) ? 2 : x[i].nvars;
-        for (int k = 0; k < nv; k++) rd(x[i].var_slot[k]);
-        if (x[i].meas_kde > 0) rd(x[i].meas_kde - 1);
-      }
-      for (int i = 0; i < st.n; i++) watch.erase(x[i].out_slot);
-    } else if (st.kind == NBP_STAGE_PRODUCTS) {
-      const nbp_product_desc *x = (const nbp_product_desc *)d;
-      for (int i = 0; i < st.n; i++) {
-        for (int j = 0; j < x[i].nfactors; j++) rd(x[i].in_slot[j]);
-        if (x[i].old_slot >= 0) rd(x[i].old_slot);
-      }
-      for (int i = 0; i < st.n; i++) watch.erase(x[i].out_slot);
-    } else {
-      const nbp_copy_desc *x = (const nbp_copy_desc *)d;
-      if (st.n == 0) break;  // barrier: slots leave the device -- whatever is still watched is written (below)
-      for (int i = 0; i < st.n; i++) rd(x[i].src_slot);
-      for (int i = 0; i < st.n; i++) watch.erase(x[i].dst_slot);
-    }
+    // barrier: slots leave the device -- whatever is still watched is written (below)
+    if ((st.kind == NBP_STAGE_COPIES || st.kind == NBP_STAGE_COPY_POINTS) && st.n == 0) break;
+    stage_reads(p, st, [&](int, int32_t slot, nbp_access) {
+      auto it = watch.find(slot);
+      if (it == watch.end()) return;
+      upd[it->second.first].flags |= 2 << it->second.second;
+      watch.erase(it);
+    }, true);
+    stage_writes(p, st, [&](int, int32_t slot) { watch.erase(slot); });
   }
   for (auto &w : watch) upd[w.second.first].flags |= 2 << w.second.second;
-  cls = A.mani & (NBP_CLS_SIMPLE - 1);
   return true;
 }
 
@@ -1819,7 +1859,6 @@ static nbp_status launch_update(nbp_ctx *c, const nbp_stage &st, const nbp_updat
   HIPCHK(hipGetLastError());
   return toc(c, c->ev[4]);
 }
-
 
 // ---- two-stream rounds --------------------------------------------------------------------------------------------------
 // A round of many variable updates is three chip-filling launches with different bottlenecks: the proposal launch waits
@@ -1856,13 +1895,11 @@ static void plan_pipeline(nbp_program *p, int s) {
       if (it != prop_of.end() && owner[it->second] < 0) owner[it->second] = i;
     }
   }
-  for (int k = 0; k < ps.n; k++) {
-    if (owner[k] < 0) continue;  // feeds no product of this round: first half, done before any product starts
-    auto reads = [&](int32_t slot) { auto it = prod_of.find(slot); if (it != prod_of.end()) unite(owner[k], it->second); };
-    for (int v = 0; v < pd[k].nvars && v < NBP_MAXV; v++) reads(pd[k].var_slot[v]);
-    if (pd[k].factor_kind == NBP_F_MSGPRIOR || pd[k].factor_kind == NBP_F_PASSTHROUGH) reads(pd[k].var_slot[1]);
-    if (pd[k].meas_kde > 0) reads(pd[k].meas_kde - 1);
-  }
+  stage_reads(p, ps, [&](int k, int32_t slot, nbp_access) {
+    if (owner[k] < 0) return;  // feeds no product of this round: first half, done before any product starts
+    auto it = prod_of.find(slot);
+    if (it != prod_of.end()) unite(owner[k], it->second);
+  });
   // components, largest first, each to the lighter half (weight: densities, the unit of the fit and KD work)
   std::unordered_map<int, std::pair<int, std::vector<int>>> comp;
   for (int i = 0; i < qs.n; i++) { auto &c = comp[find(i)]; c.first += qd[i].nfactors; c.second.push_back(i); }
@@ -1893,330 +1930,281 @@ static void plan_pipeline(nbp_program *p, int s) {
   qs.pipe_split = cnt[0];
 }
 
+// The round at stages s, s + 1 runs as one launch of the fused update kernel (fused_plan agreed): every fit of the round
+// happens inside the launch -- what is pending runs first, nothing is queued behind it.  The PRODUCTS stage keeps the lists
+// of a range that splits the pair (never read when the pair runs as one launch).
+static void schedule_fused_pair(nbp_program *p, int s, std::vector<nbp_update_desc> &upd, int Fmax, const nbp_liveness &live, nbp_fits &pend) {
+  nbp_stage &st = p->stages[s], &nx = p->stages[s + 1];
+  const nbp_proposal_desc *pd = (const nbp_proposal_desc *)(p->blob.data() + st.offset);
+  const nbp_product_desc *qd = (const nbp_product_desc *)(p->blob.data() + nx.offset);
+  nx.split_out.clear();
+  for (int i = 0; i < nx.n; i++) {
+    // the output's fit: a real product's own, or the one a pass-through hands on from its proposal
+    const int k = upd[i].prop[0];
+    if (wants_fit(qd[i]) ? live.dead_product[s + 1][i] : (!wants_fit(pd[k]) || live.dead_proposal[s][k])) continue;
+    upd[i].flags |= NBP_UPD_FIT_OUT;
+    nx.split_out.push(qd[i].out_slot, qd[i].manifold);
+  }
+  nx.ent.clear();
+  queue_fits(nx.ent, pd, st.n);  // (of every proposal, dead or not, as the three-launch form of a split range has always made them)
+  nx.fused_second = true;
+  nx.need_prep = false;
+  st.fused = true;
+  st.upd = std::move(upd);
+  st.upd_F = Fmax;
+  st.flush_before = !pend.empty();
+  pend.clear();
+}
+
+// The walk over the pending fits: what each stage finds queued at its entry (`ent`), whether that must run before it
+// (`flush_before`), and what it queues in turn.
+static void schedule_fits(nbp_program *p, const nbp_liveness &live) {
+  nbp_fits pend;
+  for (int s = 0; s < (int)p->stages.size(); s++) {
+    nbp_stage &st = p->stages[s];
+    if (st.fused_second) continue;  // ran inside the launch of the stage in front (schedule_fused_pair)
+    const char *d = p->blob.data() + st.offset;
+    st.ent = pend;
+    auto flush_if_read = [&](nbp_access what) {  // a fit still pending for a slot the stage reads that way runs first
+      stage_reads(p, st, [&](int, int32_t slot, nbp_access a) { st.flush_before |= a == what && pend.has(slot); });
+      if (st.flush_before) pend.clear();
+    };
+    if (st.kind == NBP_STAGE_PROPOSALS) {
+      std::vector<nbp_update_desc> upd;
+      int Fm = 0;
+      if (s + 1 < p->n_user_stages && fused_plan(p, s, upd, Fm) && nbp_update_lds_bytes(Fm, 2, p->ctx->N, p->ctx->Npad, 2, false) <= 158 * 1024) {
+        schedule_fused_pair(p, s, upd, Fm, live, pend);
+        continue;
+      }
+      flush_if_read(NBP_RD_KDE);  // a MsgPrior samples from the KDE in var_slot[1], a measurement KDE: points AND bandwidth
+      queue_fits(pend, (const nbp_proposal_desc *)d, st.n, live.dead_proposal[s].data());
+    } else if (st.kind == NBP_STAGE_PRODUCTS) {
+      const nbp_product_desc *qd = (const nbp_product_desc *)d;
+      st.need_prep = false;
+      for (int i = 0; i < st.n; i++) st.need_prep |= qd[i].nfactors > 1;
+      // the prep launch tops up the oldPoints of a partial product in place (topup_slot: reads the slot's bandwidth and
+      // count, writes points and count) beside the fits of the same launch: a fit still pending for that very slot would
+      // race with it, so such fits run first, in a launch of their own  (old_slot is the one points-only read of a product)
+      flush_if_read(NBP_RD_POINTS);
+      if (st.need_prep) {
+        pend.clear();  // the entry fits run inside this stage's prep launch
+      } else {
+        // Only pass-through products (AMP returns the single density): nothing here reads a bandwidth, so nothing is
+        // launched for the fits.  A pending fit of a density that is handed on moves with it -- same points, same
+        // bandwidth, fitted in the output slot when the next launch with fits comes along (graph initialisation of a
+        // chain: one proposal + one copy per variable on the critical path, all the fits in one launch at the end).
+        for (int i = 0; i < st.n; i++) pend.rename(qd[i].in_slot[0], qd[i].out_slot);
+        // (an output slot whose OLD points still had a fit queued: that fit would now see the new points -- which is what
+        //  the reference's setBelief! does anyway: manikde! of the points it stores)
+        pend.dedup();
+      }
+      queue_fits(pend, qd, st.n, live.dead_product[s].data());
+    } else if (st.kind == NBP_STAGE_DECONV || st.kind == NBP_STAGE_COPY_POINTS) {
+      // nothing is flushed (points only are read); a fit still queued for a slot that is overwritten would see the new
+      // points: void.  A deconvolution queues the fits of its outputs.
+      stage_writes(p, st, [&](int, int32_t slot) { pend.drop(slot); });
+      st.ent = pend;
+      if (st.kind == NBP_STAGE_DECONV)
+        for (int i = 0; i < st.n; i++) pend.push(((const nbp_proposal_desc *)d)[i].out_slot, ((const nbp_proposal_desc *)d)[i].manifold);
+    } else {  // copies (move bandwidths too) and the trailing pseudo stage
+      st.flush_before = true;
+      pend.clear();
+    }
+  }
+}
+
+// A round that plan_pipeline cut in two runs on two streams unless it is fused, has no prep launch, flushes first, or has
+// products too large for the LDS (they share one node-statistics workspace: the launch's own decision).  Its entry fits
+// are reordered like its descriptors: those of densities only the first half's products read, then the rest.
+static void split_piped_entry_fits(nbp_program *p) {
+  for (int s = 0; s + 1 < p->n_user_stages; s++) {
+    nbp_stage &ps = p->stages[s], &qs = p->stages[s + 1];
+    if (ps.kind != NBP_STAGE_PROPOSALS || qs.kind != NBP_STAGE_PRODUCTS || ps.pipe_split < 0 || qs.pipe_split < 0) continue;
+    if (ps.fused || !qs.need_prep || qs.flush_before) continue;
+    nbp_launch_env round = ctx_env(p->ctx);
+    round.geom_n = qs.n;
+    if (product_plan(p->ctx, round, qs.n, qs.maxfd, qs.mani).big) continue;
+    const nbp_product_desc *qd = (const nbp_product_desc *)(p->blob.data() + qs.offset);
+    std::unordered_map<int32_t, int> second;  // slots the second half's products read
+    for (int i = qs.pipe_split; i < qs.n; i++)
+      for (int j = 0; j < qd[i].nfactors; j++) second[qd[i].in_slot[j]] = 1;
+    nbp_fits ent;
+    for (int h = 0; h < 2; h++)
+      for (const nbp_fits::fit &f : qs.ent.v)
+        if ((int)second.count(f.slot) == h) { ent.push(f.slot, f.mani); if (!h) qs.pipe_ent++; }
+    qs.ent = ent;
+    ps.pipe = true;
+  }
+}
+
+// Behind the descriptors, each region 64-byte aligned: the entry fits of every stage, the split-out fits of the fused
+// pairs, their update descriptors, the seed table.  (This order and these sizes are what captured graphs and the plan
+// cache of nbp_host.cpp hold offsets into.)
+static void layout_blob(nbp_program *p) {
+  for (nbp_stage &st : p->stages) append_fits(p->blob, st.ent);
+  for (nbp_stage &st : p->stages)
+    if (st.fused_second) append_fits(p->blob, st.split_out, 4);
+  for (nbp_stage &st : p->stages)
+    if (st.fused) {
+      st.upd_off = (p->blob.size() + 63) & ~(size_t)63;
+      p->blob.resize(st.upd_off + st.upd.size() * sizeof(nbp_update_desc));
+      memcpy(p->blob.data() + st.upd_off, st.upd.data(), st.upd.size() * sizeof(nbp_update_desc));
+    }
+  std::vector<int64_t> so;  // blob offsets of every descriptor's seed field
+  for (int s = 0; s < p->n_user_stages; s++) {
+    const nbp_stage &st = p->stages[s];
+    if (st.kind == NBP_STAGE_PROPOSALS || st.kind == NBP_STAGE_DECONV)
+      for (int i = 0; i < st.n; i++) {
+        const size_t o = st.offset + (size_t)i * sizeof(nbp_proposal_desc);
+        so.push_back((int64_t)(o + offsetof(nbp_proposal_desc, seed)));
+        // a reused measurement names another op's seed: re-keyed the same way, it keeps naming that op
+        if (((const nbp_proposal_desc *)(p->blob.data() + o))->meas_seed) so.push_back((int64_t)(o + offsetof(nbp_proposal_desc, meas_seed)));
+      }
+    else if (st.kind == NBP_STAGE_PRODUCTS)
+      for (int i = 0; i < st.n; i++) so.push_back((int64_t)(st.offset + (size_t)i * sizeof(nbp_product_desc) + offsetof(nbp_product_desc, seed)));
+  }
+  p->seed_off = (p->blob.size() + 63) & ~(size_t)63;
+  p->n_seeds = (int)so.size();
+  p->seed_val_off = p->seed_off + so.size() * 8;
+  p->blob.resize(p->seed_val_off + so.size() * 8);
+  if (!so.empty()) memcpy(p->blob.data() + p->seed_off, so.data(), so.size() * 8);
+}
+
+// size the workspaces now: nothing may allocate once a launch sequence is being captured
+static nbp_status presize(nbp_program *p) {
+  for (const nbp_stage &st : p->stages)
+    if (st.kind == NBP_STAGE_PRODUCTS && st.n > 0 && !st.fused_second) {
+      nbp_status rc = presize_products(p->ctx, st.n, st.maxfd, st.mani);
+      if (rc) return rc;
+    }
+  return NBP_OK;
+}
+
+// device memory for the blob: one a destroyed program left behind, if one is large enough (the smallest such), or new
+static nbp_status acquire_device_blob(nbp_program *p) {
+  const size_t bytes = p->blob.size() ? p->blob.size() : 64;
+  auto &bc = p->ctx->blob_cache;
+  int best = -1;
+  for (size_t i = 0; i < bc.size(); i++)
+    if (bc[i].second >= bytes && (best < 0 || bc[i].second < bc[(size_t)best].second)) best = (int)i;
+  if (best >= 0) {
+    p->dev = bc[(size_t)best].first;
+    p->dev_bytes = bc[(size_t)best].second;
+    bc.erase(bc.begin() + best);
+    return NBP_OK;
+  }
+  p->dev_bytes = bytes < 65536 ? 65536 : bytes;
+  HIPCHK(hipMalloc(&p->dev, p->dev_bytes));
+  return NBP_OK;
+}
+
+static nbp_status upload_blob(nbp_program *p) {
+  if (p->blob.empty()) return NBP_OK;
+  if (p->async_upload) {
+    // stream-ordered: behind whatever still reads a blob taken over from a retired program, in front of this program's launches
+    nbp_ctx::pin_buf *b = pin_acquire(p->ctx, p->blob.size());
+    if (!b) return fail(NBP_ERR_HIP, "pinned staging buffer");
+    memcpy(b->p, p->blob.data(), p->blob.size());
+    const hipError_t e = hipMemcpyAsync(p->dev, b->p, p->blob.size(), hipMemcpyHostToDevice, p->ctx->stream);
+    pin_release_behind_stream(p->ctx, b);
+    if (e != hipSuccess) return fail(NBP_ERR_HIP, std::string("hipMemcpyAsync (descriptors): ") + hipGetErrorString(e));
+    return NBP_OK;
+  }
+  // (a blob from the cache may come from a RETIRED program whose launches are still queued: the library stream does not
+  //  wait for the legacy stream this copy runs on)
+  if (!p->ctx->retired.empty()) HIPCHK(hipStreamSynchronize(p->ctx->stream));
+  HIPCHK(hipMemcpy(p->dev, p->blob.data(), p->blob.size(), hipMemcpyHostToDevice));
+  return NBP_OK;
+}
+
 nbp_status nbp_program_finalize(nbp_program *p) {
   if (!p) return fail(NBP_ERR_ARG, "null argument");
   PROG_ALIVE(p);
   if (p->finalized) return NBP_OK;
   HIPCHK(hipSetDevice(p->ctx->device));
   p->n_user_stages = (int)p->stages.size();
-  p->stages.emplace_back();  // trailing pseudo stage: fits pending at exit
-  p->stages.back().kind = 0;
-  std::vector<int32_t> pend_s, pend_m;
-  int maxprod = 0;
-  for (int s0 = 0; s0 + 1 < p->n_user_stages; s0++) plan_pipeline(p, s0);  // reorders descriptors: before anything indexes them
-  nbp_liveness live;
-  if (p->lazy_bw) live = product_liveness(p);
-  int sidx = -1;
-  for (nbp_stage &st : p->stages) {
-    sidx++;
-    const char *d = p->blob.data() + st.offset;
-    st.ent_s = pend_s;
-    st.ent_m = pend_m;
-    if (st.kind == NBP_STAGE_PROPOSALS && sidx + 1 < p->n_user_stages && !st.fused) {
-      std::vector<nbp_update_desc> upd;
-      int Fm = 0, cls = 0;
-      if (fused_plan(p, sidx, upd, Fm, cls) && nbp_update_lds_bytes(Fm, 2, p->ctx->N, p->ctx->Npad, 2, false) <= 158 * 1024) {
-        // every fit of the round happens inside the launch: what is pending runs first, nothing is queued behind it
-        nbp_stage &nx = p->stages[sidx + 1];
-        const nbp_proposal_desc *pd = (const nbp_proposal_desc *)d;
-        const nbp_product_desc *qd = (const nbp_product_desc *)(p->blob.data() + nx.offset);
-        for (int i = 0; i < nx.n; i++) {
-          bool fit;
-          if (qd[i].nfactors > 1) fit = !p->lazy_bw || !live.dead_product[sidx + 1][i];
-          else {
-            const nbp_proposal_desc &q = pd[upd[i].prop[0]];
-            fit = !q.skip_bandwidth && q.factor_kind != NBP_F_PASSTHROUGH && (!p->lazy_bw || !live.dead_proposal[sidx][upd[i].prop[0]]);
-          }
-          if (fit) upd[i].flags |= NBP_UPD_FIT_OUT;
-        }
-        nx.split_out_s.clear(); nx.split_out_m.clear();
-        std::vector<int32_t> in_s, in_m;
-        for (int i = 0; i < st.n; i++)
-          if (!pd[i].skip_bandwidth && pd[i].factor_kind != NBP_F_PASSTHROUGH) { in_s.push_back(pd[i].out_slot); in_m.push_back(pd[i].manifold); }
-        for (int i = 0; i < nx.n; i++)
-          if (upd[i].flags & NBP_UPD_FIT_OUT) { nx.split_out_s.push_back(qd[i].out_slot); nx.split_out_m.push_back(qd[i].manifold); }
-        nx.split_in_s = in_s;
-        nx.split_in_m = in_m;
-        st.fused = true;
-        st.upd = std::move(upd);
-        st.upd_F = Fm;
-        st.upd_cls = cls;
-        nx.fused_second = true;
-        st.flush_before = !pend_s.empty();
-        pend_s.clear(); pend_m.clear();
-        continue;
-      }
-    }
-    if (st.kind == NBP_STAGE_PRODUCTS && st.fused_second) {  // ran inside the launch of the stage in front
-      // (its entry list: the fits of a range that splits the pair -- never read when the pair runs as one launch)
-      st.ent_s = st.split_in_s;
-      st.ent_m = st.split_in_m;
-      st.need_prep = false;
-      // an output slot whose old points still had a fit queued cannot be: the launch in front flushed everything
-      continue;
-    }
-    if (st.kind == NBP_STAGE_PROPOSALS) {
-      // a MsgPrior samples from the KDE in var_slot[1] (points AND bandwidth)
-      for (int i = 0; i < st.n && !st.flush_before; i++) {
-        const nbp_proposal_desc &pd = ((const nbp_proposal_desc *)d)[i];
-        if (pd.factor_kind == NBP_F_MSGPRIOR || pd.factor_kind == NBP_F_PASSTHROUGH)
-          for (int32_t ps : pend_s) st.flush_before |= (ps == pd.var_slot[1]);
-        if (pd.meas_kde > 0)  // a measurement KDE: points and bandwidth
-          for (int32_t ps : pend_s) st.flush_before |= (ps == pd.meas_kde - 1);
-      }
-      if (st.flush_before) { pend_s.clear(); pend_m.clear(); }
-      if (p->lazy_bw) {
-        const nbp_proposal_desc *pd = (const nbp_proposal_desc *)d;
-        for (int i = 0; i < st.n; i++)
-          if (!pd[i].skip_bandwidth && pd[i].factor_kind != NBP_F_PASSTHROUGH && !live.dead_proposal[sidx][i]) { pend_s.push_back(pd[i].out_slot); pend_m.push_back(pd[i].manifold); }
-      } else
-        jobs_of_proposals((const nbp_proposal_desc *)d, st.n, pend_s, pend_m);
-    } else if (st.kind == NBP_STAGE_PRODUCTS) {
-      const nbp_product_desc *qd0 = (const nbp_product_desc *)d;
-      st.need_prep = false;
-      for (int i = 0; i < st.n; i++) st.need_prep |= qd0[i].nfactors > 1;
-      // the prep launch tops up the oldPoints of a partial product in place (topup_slot: reads the slot's bandwidth and
-      // count, writes points and count) beside the fits of the same launch: a fit still pending for that very slot would
-      // race with it, so such fits run first, in a launch of their own
-      for (int i = 0; i < st.n && !st.flush_before; i++)
-        if (qd0[i].nfactors > 1 && qd0[i].old_slot >= 0)
-          for (int32_t ps : pend_s) st.flush_before |= (ps == qd0[i].old_slot);
-      if (st.flush_before) { pend_s.clear(); pend_m.clear(); }
-      if (st.need_prep) {
-        pend_s.clear(); pend_m.clear();  // the entry fits run inside this stage's prep launch
-      } else {
-        // Only pass-through products (AMP returns the single density): nothing here reads a bandwidth, so nothing is
-        // launched for the fits.  A pending fit of a density that is handed on moves with it -- same points, same
-        // bandwidth, fitted in the output slot when the next launch with fits comes along (graph initialisation of a
-        // chain: one proposal + one copy per variable on the critical path, all the fits in one launch at the end).
-        for (int i = 0; i < st.n; i++)
-          for (size_t q = 0; q < pend_s.size(); q++)
-            if (pend_s[q] == qd0[i].in_slot[0]) pend_s[q] = qd0[i].out_slot;
-        // (an output slot whose OLD points still had a fit queued: that fit would now see the new points -- which is what
-        //  the reference's setBelief! does anyway: manikde! of the points it stores)
-        for (size_t q = 0; q < pend_s.size(); q++)  // one fit per slot
-          for (size_t r = q + 1; r < pend_s.size(); r++)
-            if (pend_s[r] == pend_s[q]) { pend_s.erase(pend_s.begin() + r); pend_m.erase(pend_m.begin() + r); r--; }
-      }
-      if (p->lazy_bw) {
-        const nbp_product_desc *qd = (const nbp_product_desc *)d;
-        for (int i = 0; i < st.n; i++)
-          if (qd[i].nfactors > 1 && !live.dead_product[sidx][i]) { pend_s.push_back(qd[i].out_slot); pend_m.push_back(qd[i].manifold); }
-      } else
-        jobs_of_products((const nbp_product_desc *)d, st.n, pend_s, pend_m);
-      if (st.n > maxprod) maxprod = st.n;
-    } else if (st.kind == NBP_STAGE_DECONV) {  // reads points only; queues the fits of its outputs
-      const nbp_proposal_desc *pd = (const nbp_proposal_desc *)d;
-      for (int i = 0; i < st.n; i++) {
-        // an output slot that still has an older fit pending: that fit would see the new points, drop it
-        for (size_t q = 0; q < pend_s.size(); q++)
-          if (pend_s[q] == pd[i].out_slot) { pend_s.erase(pend_s.begin() + q); pend_m.erase(pend_m.begin() + q); q--; }
-      }
-      st.ent_s = pend_s;
-      st.ent_m = pend_m;
-      for (int i = 0; i < st.n; i++) { pend_s.push_back(pd[i].out_slot); pend_m.push_back(pd[i].manifold); }
-    } else if (st.kind == NBP_STAGE_COPY_POINTS) {  // nothing is flushed; a fit still queued for a destination is void
-      const nbp_copy_desc *cd = (const nbp_copy_desc *)d;
-      for (int i = 0; i < st.n; i++)
-        for (size_t q = 0; q < pend_s.size(); q++)
-          if (pend_s[q] == cd[i].dst_slot) { pend_s.erase(pend_s.begin() + q); pend_m.erase(pend_m.begin() + q); q--; }
-      st.ent_s = pend_s;
-      st.ent_m = pend_m;
-    } else {  // copies (move bandwidths too) and the trailing pseudo stage
-      st.flush_before = true;
-      pend_s.clear(); pend_m.clear();
-    }
-  }
-  for (int s0 = 0; s0 + 1 < p->n_user_stages; s0++) {
-    nbp_stage &ps = p->stages[s0], &qs = p->stages[s0 + 1];
-    if (ps.kind != NBP_STAGE_PROPOSALS || qs.kind != NBP_STAGE_PRODUCTS || ps.pipe_split < 0 || qs.pipe_split < 0) continue;
-    if (ps.fused || !qs.need_prep || qs.flush_before) continue;
-    // products too large for the LDS share one node-statistics workspace: single stream (the launch's own decision)
-    if (product_plan(p->ctx, qs.n, qs.maxfd, qs.mani).big) continue;
-    const nbp_product_desc *qd = (const nbp_product_desc *)(p->blob.data() + qs.offset);
-    std::unordered_map<int32_t, int> second;  // slots the second half's products read
-    for (int i = qs.pipe_split; i < qs.n; i++)
-      for (int j = 0; j < qd[i].nfactors; j++) second[qd[i].in_slot[j]] = 1;
-    std::vector<int32_t> es, em;
-    for (int h = 0; h < 2; h++)
-      for (size_t q = 0; q < qs.ent_s.size(); q++)
-        if ((int)second.count(qs.ent_s[q]) == h) { es.push_back(qs.ent_s[q]); em.push_back(qs.ent_m[q]); if (!h) qs.pipe_ent++; }
-    qs.ent_s = es;
-    qs.ent_m = em;
-    ps.pipe = true;
-  }
-  for (nbp_stage &st : p->stages) {
-    size_t off = (p->blob.size() + 63) & ~(size_t)63;
-    p->blob.resize(off + (st.ent_s.size() + st.ent_m.size()) * 4);
-    if (!st.ent_s.empty()) {
-      memcpy(p->blob.data() + off, st.ent_s.data(), st.ent_s.size() * 4);
-      memcpy(p->blob.data() + off + st.ent_s.size() * 4, st.ent_m.data(), st.ent_m.size() * 4);
-    }
-    st.ent_off = off;
-  }
-  for (nbp_stage &st : p->stages)
-    if (st.fused_second) {
-      size_t off = (p->blob.size() + 63) & ~(size_t)63;
-      p->blob.resize(off + (st.split_out_s.size() + st.split_out_m.size()) * 4 + 4);
-      if (!st.split_out_s.empty()) {
-        memcpy(p->blob.data() + off, st.split_out_s.data(), st.split_out_s.size() * 4);
-        memcpy(p->blob.data() + off + st.split_out_s.size() * 4, st.split_out_m.data(), st.split_out_m.size() * 4);
-      }
-      st.split_out_off = off;
-    }
-  for (nbp_stage &st : p->stages)
-    if (st.fused) {
-      size_t off = (p->blob.size() + 63) & ~(size_t)63;
-      p->blob.resize(off + st.upd.size() * sizeof(nbp_update_desc));
-      memcpy(p->blob.data() + off, st.upd.data(), st.upd.size() * sizeof(nbp_update_desc));
-      st.upd_off = off;
-    }
-  {
-    std::vector<int64_t> so;
-    for (int s = 0; s < p->n_user_stages; s++) {
-      const nbp_stage &st = p->stages[s];
-      if (st.kind == NBP_STAGE_PROPOSALS || st.kind == NBP_STAGE_DECONV)
-        for (int i = 0; i < st.n; i++) {
-          const size_t o = st.offset + (size_t)i * sizeof(nbp_proposal_desc);
-          so.push_back((int64_t)(o + offsetof(nbp_proposal_desc, seed)));
-          // a reused measurement names another op's seed: re-keyed the same way, it keeps naming that op
-          if (((const nbp_proposal_desc *)(p->blob.data() + o))->meas_seed) so.push_back((int64_t)(o + offsetof(nbp_proposal_desc, meas_seed)));
-        }
-      else if (st.kind == NBP_STAGE_PRODUCTS)
-        for (int i = 0; i < st.n; i++) so.push_back((int64_t)(st.offset + (size_t)i * sizeof(nbp_product_desc) + offsetof(nbp_product_desc, seed)));
-    }
-    p->seed_off = (p->blob.size() + 63) & ~(size_t)63;
-    p->n_seeds = (int)so.size();
-    p->seed_val_off = p->seed_off + so.size() * 8;
-    p->blob.resize(p->seed_val_off + so.size() * 8);
-    if (!so.empty()) memcpy(p->blob.data() + p->seed_off, so.data(), so.size() * 8);
-  }
-  // size the workspaces now: nothing may allocate once a launch sequence is being captured
-  nbp_status rc = NBP_OK;
-  for (const nbp_stage &st : p->stages)
-    if (st.kind == NBP_STAGE_PRODUCTS && st.n > 0 && !st.fused_second) {
-      rc = presize_products(p->ctx, st.n, st.maxfd, st.mani);
-      if (rc) return rc;
-    }
-  size_t bytes = p->blob.size() ? p->blob.size() : 64;
-  {  // a blob a destroyed program left behind, if one is large enough (the smallest such)
-    auto &bc = p->ctx->blob_cache;
-    int best = -1;
-    for (size_t i = 0; i < bc.size(); i++)
-      if (bc[i].second >= bytes && (best < 0 || bc[i].second < bc[(size_t)best].second)) best = (int)i;
-    if (best >= 0) {
-      p->dev = bc[(size_t)best].first;
-      p->dev_bytes = bc[(size_t)best].second;
-      bc.erase(bc.begin() + best);
-    }
-  }
-  if (!p->dev) {
-    p->dev_bytes = bytes < 65536 ? 65536 : bytes;
-    HIPCHK(hipMalloc(&p->dev, p->dev_bytes));
-  }
-  if (p->blob.size()) {
-    if (p->async_upload) {
-      // stream-ordered: behind whatever still reads a blob taken over from a retired program, in front of this program's launches
-      nbp_ctx::pin_buf *b = pin_acquire(p->ctx, p->blob.size());
-      if (!b) return fail(NBP_ERR_HIP, "pinned staging buffer");
-      memcpy(b->p, p->blob.data(), p->blob.size());
-      const hipError_t e = hipMemcpyAsync(p->dev, b->p, p->blob.size(), hipMemcpyHostToDevice, p->ctx->stream);
-      pin_release_behind_stream(p->ctx, b);
-      if (e != hipSuccess) return fail(NBP_ERR_HIP, std::string("hipMemcpyAsync (descriptors): ") + hipGetErrorString(e));
-    } else {
-      // (a blob from the cache may come from a RETIRED program whose launches are still queued: the library stream does not
-      //  wait for the legacy stream this copy runs on)
-      if (!p->ctx->retired.empty()) HIPCHK(hipStreamSynchronize(p->ctx->stream));
-      HIPCHK(hipMemcpy(p->dev, p->blob.data(), p->blob.size(), hipMemcpyHostToDevice));
-    }
-  }
+  p->stages.emplace_back();  // trailing pseudo stage (kind 0): the fits pending at exit
+  for (int s = 0; s + 1 < p->n_user_stages; s++) plan_pipeline(p, s);  // reorders descriptors: before anything indexes them
+  schedule_fits(p, product_liveness(p));
+  split_piped_entry_fits(p);
+  layout_blob(p);
+  nbp_status rc = presize(p);
+  if (!rc) rc = acquire_device_blob(p);
+  if (!rc) rc = upload_blob(p);
+  if (rc) return rc;
   p->finalized = true;
   return NBP_OK;
 }
 
 static nbp_status run_range(nbp_program *p, int first, int last) {
   nbp_ctx *c = p->ctx;
-  auto ent_s = [&](const nbp_stage &st) { return (const int32_t *)(p->dev + st.ent_off); };
+  nbp_launch_env env = ctx_env(c);
   for (int s = first; s < last; s++) {
     const nbp_stage &st = p->stages[s];
-    const int nent = (int)st.ent_s.size();
     nbp_status rc = NBP_OK;
-    if (st.flush_before) rc = launch_bandwidth(c, ent_s(st), ent_s(st) + nent, nent, coords_of(st.ent_m.data(), st.ent_m.size()));
+    if (st.flush_before) rc = launch_bandwidth(c, env, fits_dev(st.ent, p->dev));
     if (rc) return rc;
     if (st.kind == NBP_STAGE_PROPOSALS && st.fused && s + 1 >= last) {
       // the range ends between the two stages of a fused pair: the proposals alone, to their arena slots; their fits are the
       // entry list of the stage behind, which the end of the range runs (below)
-      rc = launch_proposals(c, (const nbp_proposal_desc *)(p->dev + st.offset), st.n, st.mani);
+      rc = launch_proposals(c, env, (const nbp_proposal_desc *)(p->dev + st.offset), st.n, st.mani);
     } else if (st.kind == NBP_STAGE_PROPOSALS && st.fused) {
       const nbp_stage &nx = p->stages[s + 1];
       rc = launch_update(c, st, (const nbp_update_desc *)(p->dev + st.upd_off), (const nbp_proposal_desc *)(p->dev + st.offset),
                          (const nbp_product_desc *)(p->dev + nx.offset), nx.n);
       s++;  // the products ran inside
     } else if (st.kind == NBP_STAGE_PROPOSALS && st.pipe && !c->timing && s + 1 < last) {
-      // two-stream round (plan_pipeline): the second half runs one launch behind the first
+      // two-stream round (plan_pipeline): the second half runs one launch behind the first.  Both launch with the geometry
+      // of the whole batch; the second on stream2, its KD builds in the workspace behind the first half's.
       const nbp_stage &nx = p->stages[s + 1];
       const nbp_proposal_desc *pd = (const nbp_proposal_desc *)(p->dev + st.offset);
       const nbp_product_desc *dd = (const nbp_product_desc *)(p->dev + nx.offset);
-      const int ne = (int)nx.ent_s.size(), ea = nx.pipe_ent, qa = nx.pipe_split, pa = st.pipe_split;
-      const int32_t *es = ent_s(nx), *em = ent_s(nx) + ne;
-      c->geom_n = nx.n;
-      c->geom_blocks = 2 * ne + 2 * nx.n;
-      hipStream_t s1 = c->stream;
-      double *ws1 = c->ws;
-      const size_t wsd1 = c->ws_doubles, wsa = (size_t)qa * (size_t)(nx.maxfd / 4) * nbp_kd_ws_doubles(c->N);
-      auto half = [&](int h) -> nbp_status {
-        const nbp_product_desc *dh = dd + (h ? qa : 0);
-        const int nq = h ? nx.n - qa : qa, nf = h ? ne - ea : ea;
-        nbp_status r = launch_prep(c, es + (h ? ea : 0), em + (h ? ea : 0), nf, dh, nq, nx.maxfd, coords_of(nx.ent_m.data() + (h ? ea : 0), nf), nx.mani);
-        if (!r) r = launch_products(c, dh, nq, nx.maxfd, nx.mani);
+      const int ne = nx.ent.size(), ea = nx.pipe_ent, qa = nx.pipe_split, pa = st.pipe_split;
+      const size_t wsa = (size_t)qa * (size_t)(nx.maxfd / 4) * nbp_kd_ws_doubles(c->N);
+      nbp_launch_env h[2] = {env, env};
+      h[0].geom_n = h[1].geom_n = nx.n;
+      h[0].geom_blocks = h[1].geom_blocks = 2 * ne + 2 * nx.n;
+      h[1].stream = c->stream2;
+      h[1].ws = env.ws + wsa;
+      h[1].ws_doubles = env.ws_doubles - wsa;
+      auto half = [&](int k) -> nbp_status {
+        const nbp_product_desc *dh = dd + (k ? qa : 0);
+        const int nq = k ? nx.n - qa : qa;
+        nbp_status r = launch_prep(c, h[k], fits_dev(nx.ent, p->dev, k ? ea : 0, k ? ne - ea : ea), dh, nq, nx.maxfd, nx.mani);
+        if (!r) r = launch_products(c, h[k], dh, nq, nx.maxfd, nx.mani);
         return r;
       };
-      rc = launch_proposals(c, pd, pa, st.mani);
+      rc = launch_proposals(c, h[0], pd, pa, st.mani);
       hipError_t he = hipSuccess;
-      if (!rc) he = hipEventRecord(c->pipe_ev[0], s1);
+      if (!rc) he = hipEventRecord(c->pipe_ev[0], env.stream);
       if (!rc && he == hipSuccess) he = hipStreamWaitEvent(c->stream2, c->pipe_ev[0], 0);
       if (!rc && he == hipSuccess) {
-        c->stream = c->stream2;
-        c->ws = ws1 + wsa;
-        c->ws_doubles = wsd1 - wsa;
-        rc = launch_proposals(c, pd + pa, st.n - pa, st.mani);
+        rc = launch_proposals(c, h[1], pd + pa, st.n - pa, st.mani);
         if (!rc) rc = half(1);
-        c->stream = s1;
-        c->ws = ws1;
-        c->ws_doubles = wsd1;
         if (!rc) he = hipEventRecord(c->pipe_ev[1], c->stream2);
       }
       if (!rc && he == hipSuccess) rc = half(0);
-      if (!rc && he == hipSuccess) he = hipStreamWaitEvent(s1, c->pipe_ev[1], 0);
-      c->geom_n = c->geom_blocks = 0;
+      if (!rc && he == hipSuccess) he = hipStreamWaitEvent(env.stream, c->pipe_ev[1], 0);
       if (he != hipSuccess) return fail(NBP_ERR_HIP, std::string("two-stream round: ") + hipGetErrorString(he));
       s++;  // the products ran here
     } else if (st.kind == NBP_STAGE_PROPOSALS) {
-      rc = launch_proposals(c, (const nbp_proposal_desc *)(p->dev + st.offset), st.n, st.mani);
+      rc = launch_proposals(c, env, (const nbp_proposal_desc *)(p->dev + st.offset), st.n, st.mani);
     } else if (st.kind == NBP_STAGE_PRODUCTS) {
       const nbp_product_desc *dd = (const nbp_product_desc *)(p->dev + st.offset);
       // (fused_second: only a range that starts between the two stages of a fused pair gets here -- three-launch form, the
       //  proposals' fits beside the KD builds, the outputs the fused launch would have fitted behind the products)
-      if (st.need_prep || st.fused_second)
-        rc = launch_prep(c, ent_s(st), ent_s(st) + nent, nent, dd, st.n, st.maxfd, coords_of(st.ent_m.data(), st.ent_m.size()), st.mani);
-      if (!rc) rc = launch_products(c, dd, st.n, st.maxfd, st.mani);
-      if (!rc && st.fused_second && !st.split_out_s.empty()) {
-        const int32_t *os = (const int32_t *)(p->dev + st.split_out_off);
-        const int no = (int)st.split_out_s.size();
-        rc = launch_bandwidth(c, os, os + no, no, coords_of(st.split_out_m.data(), st.split_out_m.size()));
-      }
+      if (st.need_prep || st.fused_second) rc = launch_prep(c, env, fits_dev(st.ent, p->dev), dd, st.n, st.maxfd, st.mani);
+      if (!rc) rc = launch_products(c, env, dd, st.n, st.maxfd, st.mani);
+      if (!rc && st.fused_second) rc = launch_bandwidth(c, env, fits_dev(st.split_out, p->dev));
     } else if (st.kind == NBP_STAGE_DECONV) {
       rc = launch_deconv(c, (const nbp_proposal_desc *)(p->dev + st.offset), nullptr, st.n);
-    } else if (st.kind == NBP_STAGE_COPY_POINTS) {
-      rc = launch_copy_points(c, (const nbp_copy_desc *)(p->dev + st.offset), st.n);
     } else {
-      rc = launch_copies(c, (const nbp_copy_desc *)(p->dev + st.offset), st.n);
+      rc = launch_copies(c, (const nbp_copy_desc *)(p->dev + st.offset), st.n, st.kind == NBP_STAGE_COPY_POINTS);
     }
     if (rc) return rc;
   }
   // leave every slot consistent: run whatever is still pending at the end of the range
-  const nbp_stage &nx = p->stages[last];
-  return launch_bandwidth(c, ent_s(nx), ent_s(nx) + nx.ent_s.size(), (int)nx.ent_s.size(), coords_of(nx.ent_m.data(), nx.ent_m.size()));
+  return launch_bandwidth(c, env, fits_dev(p->stages[last].ent, p->dev));
 }
 
 nbp_status nbp_program_run(nbp_program *p, int32_t first, int32_t last) {
