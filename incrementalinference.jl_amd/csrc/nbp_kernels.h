@@ -1380,9 +1380,10 @@ __device__ __forceinline__ void product_body(const nbp_product_desc *d, double *
     NBP_CTICK(41);  // node statistics
     }
     // The uniforms of this pass: ONE Philox block per (sample, density) -- its first uniform for sampleIndices!, its second for
-    // the first sweep's sampleIndex.  The helper lanes of a sample take turns at the densities (lane h makes the blocks of
-    // j = h, h + HL, ...: with two densities and two helpers one block's worth of instructions per pass instead of four) and
-    // hand them over through LDS; the lanes of a sample are lanes of one wave, whose LDS operations stay in order.
+    // the first sweep's sampleIndex.  (Density 0's first uniform is made and not used: its draw on the point is the dead one
+    // left out below; the block is needed for its second uniform all the same.)
+    // The helper lanes of a sample take turns at the densities (lane h makes the blocks of j = h, h + HL, ...: with two
+    // densities and two helpers one block's worth of instructions per pass instead of four) and hand them over through LDS; the lanes of a sample are lanes of one wave, whose LDS operations stay in order.
     if (ps > 0 && live)
       for (int j0 = 0; j0 < F; j0 += HL) {
         const int j = j0 + h;
@@ -1419,8 +1420,14 @@ __device__ __forceinline__ void product_body(const nbp_product_desc *d, double *
     // wave-uniform branch in front of every node weight (two taken branches per node in the pass-1 loop)
     auto sweep = [&](auto leaf_c) {
     constexpr bool leaf = decltype(leaf_c)::value;
-    for (int it = -1; ps > 0 && it < d->niter; it++) {  // it = -1: sampleIndices! (every label given the point x of the level above)
-      for (int j = 0; j < F; j++) {  // sampleIndex(j): sequential Gibbs sweep
+    // it = -1: sampleIndices! (a label given the point x of the level above) -- of the densities j >= 1 only.  The label of
+    // density 0 drawn on the point has no reader: a draw on the point reads no label (mn = x, vn = 0), the first draw of
+    // the first sweep (it = 0, j = 0; niter >= 1 always) reads the labels q != 0 and then writes ind[0] itself, and
+    // point_moments runs behind the sweeps.  The labels of j >= 1 are read by the sweep's draws of 0 .. j - 1 and stay.  The
+    // streams are keyed by (sample, pass, density, purpose), so the draw left out moves no other draw's uniform: the same
+    // labels and points as with it, for F x niter + F - 1 draws per pass instead of F x (niter + 1).
+    for (int it = -1; ps > 0 && it < d->niter; it++) {
+      for (int j = it < 0 ? 1 : 0; j < F; j++) {  // sampleIndex(j): sequential Gibbs sweep
         // Draw l_j ~ p(l_j | others) by inverse CDF over the nodes of this level.
         //   weight_z = w_z * N(mean_z; mn, var_z + vn)  =  exp(a_z) * g_z,
         //   a_z = -0.5 * sum_k t_k^2 / v_k  (<= 0),   g_z = w_z / sqrt(prod_k v_k)
