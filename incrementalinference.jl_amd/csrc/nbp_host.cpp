@@ -84,6 +84,7 @@ struct Clique {
 };
 
 struct Stage { int kind; std::vector<char> bytes; int n; };
+using MeasKey = std::array<int, 5>;  // names the stored measurement of one density (needFreshMeasurements)
 
 }  // namespace
 
@@ -121,7 +122,8 @@ struct nbp_tree {
   // rounds = the steps of a schedule grouped into sets of commuting steps (solver.TreeProgram._rounds)
   std::vector<std::vector<int>> usched, uiter, dsched;
   std::vector<std::vector<std::vector<int>>> urounds, drounds;
-  std::map<std::array<int, 5>, uint64_t> meas_seed;  // (clique, tag, a, b, variable of a message) -> seed of the last fresh draw
+  std::map<MeasKey, uint64_t> meas_seed;  // (clique, tag, a, b, variable of a message) -> seed of the last fresh draw
+  std::vector<char> isinit;               // the graph's initialised flags as the last compile found them (multihypo)
   // multi-rank compile (solver.TreeProgram(owner=, rank=)): owner[c] = rank of clique c (index c - 1); this rank compiles
   // only its own cliques; tree edges that cross a rank boundary become exchange segments between the stage segments
   std::vector<int> owner;
@@ -421,49 +423,67 @@ nbp_status clique_potentials_and_ids(nbp_tree *t) {
   return NBP_OK;
 }
 
+// upGibbsCliqueDensity: the four fmcmc! passes (SolveTree.jl:193-235) as one list of steps and, for each, the iteration
+// (1-based) of its pass; a pass over one label runs once (:106-108)
+void up_gibbs_schedule(const std::vector<int> &directFrtlMsg, const std::vector<int> &msgskip, const std::vector<int> &itervar,
+                       const std::vector<int> &directPriorMsg, int gibbs_iters, std::vector<int> &sched, std::vector<int> &iter) {
+  auto fmcmc = [&](const std::vector<int> &l, int it) {
+    if (l.size() == 1) it = 1;
+    for (int k = 0; k < it; k++) {
+      sched.insert(sched.end(), l.begin(), l.end());
+      iter.insert(iter.end(), l.size(), k + 1);
+    }
+  };
+  fmcmc(directFrtlMsg, 1);
+  fmcmc(msgskip, 1);
+  fmcmc(itervar, gibbs_iters);
+  std::vector<int> l;
+  for (int v : directPriorMsg)
+    if (!contains(msgskip, v)) l.push_back(v);
+  fmcmc(l, 1);
+}
+
+// doFMCIteration passes over marginalized variables and variables without a density (SolveTree.jl:61): `skip(v)` says which
+template <class Skip>
+void drop_skipped_steps(std::vector<int> &sched, std::vector<int> &iter, Skip skip) {
+  size_t n = 0;
+  for (size_t k = 0; k < sched.size(); k++)
+    if (!skip(sched[k])) { sched[n] = sched[k]; iter[n++] = iter[k]; }
+  sched.resize(n);
+  iter.resize(n);
+}
+
+// determineCliqVariableDownSequence + solveCliqDownFrontalProducts! (CliqStateMachineUtils.jl:424-571): the frontals that share
+// one of `facs` iterate behind the others, which are solved once; limitfixeddown drops the marginalized ones
+struct VarList { const int32_t *v; int n; };
+template <class IsMargin>
+std::vector<int> down_sequence(const std::vector<int> &frontals, const std::vector<VarList> &facs, bool limitfixeddown, IsMargin ismargin) {
+  std::vector<int> iterv, hit;
+  for (const VarList &f : facs) {
+    hit.clear();
+    for (int k = 0; k < f.n; k++)
+      if (contains(frontals, (int)f.v[k])) hit.push_back(f.v[k]);
+    if (hit.size() > 1)
+      for (int v : hit)
+        if (!contains(iterv, v)) iterv.push_back(v);
+  }
+  std::vector<int> seq, itf;
+  for (int v : frontals)
+    if (!(limitfixeddown && ismargin(v))) (contains(iterv, v) ? itf : seq).push_back(v);
+  // MCIters = 3 is solveCliqDownFrontalProducts!'s own keyword default (CliqStateMachineUtils.jl:485); its only
+  // caller (CliqueStateMachine.jl:838) does not pass gibbsIters
+  for (int k = 0; k < NBP_DOWN_MCITERS; k++) seq.insert(seq.end(), itf.begin(), itf.end());
+  return seq;
+}
+
 void schedules(nbp_tree *t) {
   const nbp_graph *g = t->g;
-  const int iters = g->sp.gibbs_iters;
   for (Clique &c : t->cl) {
-    auto fmcmc = [&](const std::vector<int> &l, int it) {
-      if (l.size() == 1) it = 1;
-      for (int k = 0; k < it; k++) {
-        c.upsched.insert(c.upsched.end(), l.begin(), l.end());
-        c.upiter.insert(c.upiter.end(), l.size(), k + 1);
-      }
-    };
-    fmcmc(c.directFrtlMsg, 1);
-    if (!c.msgskip.empty()) fmcmc(c.msgskip, 1);
-    if (!c.itervar.empty()) fmcmc(c.itervar, iters);
-    if (!c.directPriorMsg.empty()) {
-      std::vector<int> l;
-      for (int v : c.directPriorMsg)
-        if (!contains(c.msgskip, v)) l.push_back(v);
-      fmcmc(l, 1);
-    }
-    // down: determineCliqVariableDownSequence + solveCliqDownFrontalProducts!
-    std::set<int> frs(c.frontals.begin(), c.frontals.end());
-    std::vector<int> iterv;
-    for (int f : c.dwnPotentials) {
-      std::vector<int> hit;
-      for (int k = 0; k < g->facs[f].s.nvars; k++)
-        if (frs.count(g->facs[f].s.vars[k])) hit.push_back(g->facs[f].s.vars[k]);
-      if (hit.size() > 1)
-        for (int v : hit)
-          if (!contains(iterv, v)) iterv.push_back(v);
-    }
-    std::vector<int> itf, directs;
-    for (int v : c.frontals) (contains(iterv, v) ? itf : directs).push_back(v);
-    if (g->sp.limitfixeddown) {
-      auto drop = [&](std::vector<int> &l) { l.erase(std::remove_if(l.begin(), l.end(), [&](int v) { return g->vars[v].ismargin; }), l.end()); };
-      drop(itf);
-      drop(directs);
-    }
-    c.dnsched = directs;
-    // MCIters = 3 is solveCliqDownFrontalProducts!'s own keyword default (CliqStateMachineUtils.jl:485); its only
-    // caller (CliqueStateMachine.jl:838) does not pass gibbsIters
-    for (int k = 0; k < NBP_DOWN_MCITERS; k++) c.dnsched.insert(c.dnsched.end(), itf.begin(), itf.end());
-    if (c.parent == 0) c.dnsched.clear();
+    up_gibbs_schedule(c.directFrtlMsg, c.msgskip, c.itervar, c.directPriorMsg, g->sp.gibbs_iters, c.upsched, c.upiter);
+    if (c.parent == 0) continue;  // a root receives nothing from above
+    std::vector<VarList> facs;
+    for (int f : c.dwnPotentials) facs.push_back({g->facs[f].s.vars, g->facs[f].s.nvars});
+    c.dnsched = down_sequence(c.frontals, facs, g->sp.limitfixeddown != 0, [&](int v) { return g->vars[v].ismargin; });
   }
 }
 
@@ -525,23 +545,25 @@ bool shortest_path_factors(const std::vector<int> &vars, const std::vector<Cliqu
   return false;
 }
 
+// height of every clique above the leaves below it (index = clique id)
+std::vector<int> clique_heights(const nbp_tree *t) {
+  std::vector<int> height(t->cl.size() + 1, 0);
+  for (int cid : postorder(t))
+    for (int chd : t->cl[cid - 1].children) height[cid] = std::max(height[cid], height[chd] + 1);
+  return height;
+}
+// the clique ids by ascending key (height or depth), ties by id
+std::vector<int> cliques_by(const std::vector<int> &key) {
+  std::vector<int> ids;
+  for (size_t k = 1; k < key.size(); k++) ids.push_back((int)k);
+  std::stable_sort(ids.begin(), ids.end(), [&](int a, int b) { return key[a] < key[b]; });
+  return ids;
+}
+
 // plan_joint_messages (jointmsg.py): children before parents
 void plan_joint(nbp_tree *t) {
   const nbp_graph *g = t->g;
-  std::vector<int> height(t->cl.size() + 1, 0);
-  for (int cid : postorder(t)) {
-    int h = 0;
-    const Clique &c = t->cl[cid - 1];
-    if (!c.children.empty()) {
-      for (int chd : c.children) h = std::max(h, height[chd]);
-      h += 1;
-    }
-    height[cid] = h;
-  }
-  std::vector<int> ids;
-  for (const Clique &c : t->cl) ids.push_back(c.id);
-  std::stable_sort(ids.begin(), ids.end(), [&](int a, int b) { return height[a] != height[b] ? height[a] < height[b] : a < b; });
-  for (int cid : ids) {
+  for (int cid : cliques_by(clique_heights(t))) {
     Clique &c = t->cl[cid - 1];
     c.jf.clear(); c.rel.clear(); c.jpriors.clear();
     for (int f : c.potentials) {
@@ -636,72 +658,197 @@ std::vector<Entry> joint_entries(const Clique &c, int v, bool down) {
   return e;
 }
 
-void fill_proposal(const nbp_graph *g, nbp_proposal_desc &d, const HFac *fac, int msg_slot, int target, const std::map<int, int> *Bc,
-                   const std::vector<int> *main_slot, const std::set<int> *inclq, int out_slot, uint64_t seed, double nullSurplus,
-                   const std::vector<char> *isinit = nullptr, int keep_count = 0) {
+// measurement dimension of a relative factor kind between variables of `manifold`
+int rel_zdim(int kind, int manifold) { return kind == NBP_F_LINREL ? mani_dim(manifold) : (kind == NBP_F_SE2 ? 3 : 1); }
+// LinearRelative & co. between variables a and b as a default-constructed factor: zero mean, an identity square-root
+// covariance in its first `ndiag` diagonal entries
+HFac differential_factor(int kind, int a, int b, int ndiag) {
+  HFac f;
+  memset(&f.s, 0, sizeof(f.s));
+  f.is_prior = false;
+  f.s.factor_kind = kind;
+  f.s.nvars = 2;
+  f.s.vars[0] = a;
+  f.s.vars[1] = b;
+  f.s.ncomp = 1;
+  f.s.comp[0][0] = 1.0;
+  for (int q = 0; q < ndiag; q++) f.s.comp[0][4 + 4 * q] = 1.0;
+  return f;
+}
+
+// ---- one variable update, for every compiler (whole tree, graph initialisation, clique seam) -------------------------------
+// variable -> belief slot: the clique's own copy where it has one, else the slot in `other`; neither given: the variable's index
+struct Slots {
+  const std::map<int, int> *own = nullptr;
+  const std::vector<int> *other = nullptr;
+  int operator()(int v) const {
+    if (own) {
+      auto it = own->find(v);
+      if (it != own->end()) return it->second;
+    }
+    return other ? (*other)[v] : v;
+  }
+};
+// one density of an update, in the order the caller multiplies them
+struct Density {
+  const HFac *fac;  // null: the message prior of a child
+  int side_slot;    // the message's belief, a pass-through density or a sampler table; -1: none
+  int meas_kde;     // 1 + the slot of the KDE that is the factor's measurement (LinearRelative(::MKD) & co.), 0: none
+  MeasKey key;      // its stored measurement
+};
+// where an update lives.  Derived from it: the belief written (slot(v), also old_slot when a density is partial), the scratch
+// slot of density i (scratch + i), the seeds (pass, id, step, i + 1 | PRODUCT_ID), the null-hypothesis surplus
+struct Update {
+  int v = 0, manifold = 0;
+  Slots slot;
+  int scratch = 0;                  // first slot of its scratch row
+  int pass = 0, id = 0, step = 0;   // seed key
+  bool fresh = true;                // draw the measurements anew, else take the stored ones (`meas`)
+  int keep_count = 0;               // what a pass-through density that is the update's only one gets: 1 = the belief keeps its point count, 2 = graph init
+  const std::vector<char> *initialized = nullptr;  // per variable, for multihypo; null: every variable is
+  std::map<MeasKey, uint64_t> *meas = nullptr;     // seeds of the last fresh draws; null: nothing is stored
+};
+
+void fill_proposal(const nbp_solver_params &sp, nbp_proposal_desc &d, const Update &u, const Density &e, int out_slot, uint64_t seed,
+                   double nullSurplus, int keep_count) {
   memset(&d, 0, sizeof(d));
-  const nbp_solver_params &sp = g->sp;
-  auto slot_of = [&](int v) { return Bc == nullptr ? v : ((inclq == nullptr || inclq->count(v)) ? Bc->at(v) : (*main_slot)[v]); };
-  d.manifold = g->vars[target].manifold;
+  d.manifold = u.manifold;
   d.out_slot = out_slot;
   d.inflate_cycles = sp.inflate_cycles;
   d.mhidx_in = d.mhidx_out = -1;
   d.spread_nh = sp.spread_nh;
   d.seed = seed;
-  if (!fac) {  // MsgPrior (generateMsgPrior, TreeMessageUtils.jl:86-89)
-    d.factor_kind = NBP_F_MSGPRIOR;
-    d.inflation = sp.inflation;
-    d.nullhypo = std::max(0.0, nullSurplus);
+  d.meas_kde = e.meas_kde;
+  const bool passthrough = e.fac && e.fac->s.factor_kind == NBP_F_PASSTHROUGH;
+  if (!e.fac || passthrough) {  // side_slot holds the proposal: a MsgPrior (generateMsgPrior, TreeMessageUtils.jl:86-89) or a
+    d.factor_kind = passthrough ? NBP_F_PASSTHROUGH : NBP_F_MSGPRIOR;  // pass-through density (ApproxConv.jl:196-227)
+    d.inflation = passthrough && e.fac->s.inflation > 0 ? e.fac->s.inflation : sp.inflation;
     d.nvars = 1;
     d.sfidx = 0;
-    d.var_slot[0] = slot_of(target);
-    d.var_slot[1] = msg_slot;
+    d.var_slot[0] = u.slot(u.v);
+    d.var_slot[1] = e.side_slot;
     d.ncomp = 1;
     d.comp[0][0] = 1.0;
+    if (passthrough) {
+      d.partial_mask = e.fac->s.partial_mask;
+      d.skip_bandwidth = 1;
+      d.keep_count = keep_count;
+    } else
+      d.nullhypo = std::max(0.0, nullSurplus);
     return;
   }
-  const nbp_factor_spec &s = fac->s;
-  if (s.factor_kind == NBP_F_PASSTHROUGH) {  // the density is the proposal (ApproxConv.jl:196-227); msg_slot = its slot
-    d.factor_kind = NBP_F_PASSTHROUGH;
-    d.partial_mask = s.partial_mask;
-    d.inflation = s.inflation > 0 ? s.inflation : sp.inflation;
-    d.nvars = 1;
-    d.sfidx = 0;
-    d.var_slot[0] = slot_of(target);
-    d.var_slot[1] = msg_slot;
-    d.ncomp = 1;
-    d.comp[0][0] = 1.0;
-    d.skip_bandwidth = 1;
-    d.keep_count = keep_count;  // the only factor of its update: 1 = the belief keeps the density's point count, 2 = graph init
-    return;
-  }
+  const nbp_factor_spec &s = e.fac->s;
   d.factor_kind = s.factor_kind;
   d.partial_mask = s.partial_mask;
   d.inflation = s.inflation > 0 ? s.inflation : sp.inflation;
   d.nullhypo = std::max(s.nullhypo, nullSurplus);
   d.nvars = s.nvars;
   for (int i = 0; i < s.nvars; i++) {
-    if (s.vars[i] == target) d.sfidx = i;
-    d.var_slot[i] = slot_of(s.vars[i]);
+    if (s.vars[i] == u.v) d.sfidx = i;
+    d.var_slot[i] = u.slot(s.vars[i]);
   }
-  if (spec_has_table(s)) d.var_slot[NBP_MAXV - 1] = msg_slot;  // the slot of the sampler's table (callers pass it like a density slot)
+  if (spec_has_table(s)) d.var_slot[NBP_MAXV - 1] = e.side_slot;
   d.ncomp = s.ncomp;
   memcpy(d.comp, s.comp, sizeof(d.comp));
   if (s.has_multihypo) {
     int flags = 1 | 0x80;
     for (int i = 0; i < s.nvars; i++)
-      if (isinit ? (*isinit)[s.vars[i]] != 0 : g->vars[s.vars[i]].initialized) flags |= 1 << (8 + i);
+      if (!u.initialized || (*u.initialized)[s.vars[i]] != 0) flags |= 1 << (8 + i);
     d.has_multihypo = flags;
     for (int i = 0; i < s.nvars; i++) d.multihypo[i] = s.multihypo[i];
   }
 }
 
-void add_stage(nbp_tree *t, int kind, const void *descs, size_t esz, int n) {
+// "update u.v from its densities": one proposal per density into the scratch row, one product over the row
+nbp_status emit_update(const nbp_solver_params &sp, uint64_t seed, const Update &u, const std::vector<Density> &dens,
+                       std::vector<nbp_proposal_desc> &props, std::vector<nbp_product_desc> &prods) {
+  const int F = (int)dens.size();
+  if (F > NBP_MAXF) return hfail(NBP_ERR_RANGE, "a product exceeds NBP_MAXF densities");
+  bool anymh = false, anypartial = false;
+  for (const Density &e : dens) anymh |= e.fac && e.fac->s.has_multihypo;
+  nbp_product_desc q;
+  memset(&q, 0, sizeof(q));
+  for (int i = 0; i < F; i++) {
+    const Density &e = dens[i];
+    // proposalbeliefs! (ApproxConv.jl:255-265), _null_surplus: relative non-multihypo siblings of a multihypo factor
+    const double ns = (anymh && e.fac && !e.fac->is_prior && !e.fac->s.has_multihypo) ? sp.null_surplus_add : 0.0;
+    const uint64_t sd = op_seed(seed, u.pass, u.id, u.step, i + 1);
+    nbp_proposal_desc d;
+    fill_proposal(sp, d, u, e, u.scratch + i, sd, ns, F == 1 ? u.keep_count : 0);
+    if (u.meas) {  // needFreshMeasurements (SolveTree.jl:119): one stored measurement per factor object
+      if (u.fresh) (*u.meas)[e.key] = sd;
+      else {
+        auto it = u.meas->find(e.key);
+        d.meas_seed = it == u.meas->end() ? 0 : it->second;
+      }
+    }
+    props.push_back(d);
+    q.in_slot[i] = u.scratch + i;
+    const int pm = e.fac ? e.fac->s.partial_mask : 0;
+    q.in_partial[i] = (uint8_t)pm;
+    anypartial |= pm != 0;
+  }
+  q.manifold = u.manifold;
+  q.nfactors = F;
+  q.niter = sp.product_niter;
+  q.out_slot = u.slot(u.v);
+  q.labels_out = -1;
+  q.old_slot = anypartial ? u.slot(u.v) : -1;
+  if (!anypartial) memset(q.in_partial, 0, sizeof(q.in_partial));
+  q.seed = op_seed(seed, u.pass, u.id, u.step, PRODUCT_ID);
+  prods.push_back(q);
+  return NBP_OK;
+}
+
+// prepCliqueMsgUp -> addLikelihoodsDifferentialCHILD! (TreeMessageUtils.jl:279-335) for differential pair i = (a, b) of a clique
+// that has finished its up solve: approxDeconv between the solved beliefs of the pair (searched from samples of the
+// default-constructed factor), manikde! of the result into out_slot
+nbp_proposal_desc deconv_op(const nbp_solver_params &sp, uint64_t seed, int clique_id, int i, int kind, int a, int b, int manifold_a,
+                            int manifold_b, const Slots &slot, int out_slot) {
+  const HFac dflt = differential_factor(kind, a, b, rel_zdim(kind, manifold_a));
+  Update u;
+  u.v = b;
+  u.manifold = manifold_b;
+  u.slot = slot;
+  nbp_proposal_desc d;
+  fill_proposal(sp, d, u, Density{&dflt, -1, 0, {}}, out_slot, op_seed(seed, PASS_UP, clique_id, 0x4000 + i, 0), 0.0, 0);
+  return d;
+}
+
+void add_stage(std::vector<Stage> &stages, int kind, const void *descs, size_t esz, int n) {
   Stage st;
   st.kind = kind;
   st.n = n;
   st.bytes.assign((const char *)descs, (const char *)descs + esz * (size_t)n);
-  t->stages.push_back(std::move(st));
+  stages.push_back(std::move(st));
+}
+
+void add_update_stages(std::vector<Stage> &stages, const std::vector<nbp_proposal_desc> &props, const std::vector<nbp_product_desc> &prods) {
+  add_stage(stages, NBP_STAGE_PROPOSALS, props.data(), sizeof(nbp_proposal_desc), (int)props.size());
+  add_stage(stages, NBP_STAGE_PRODUCTS, prods.data(), sizeof(nbp_product_desc), (int)prods.size());
+}
+// a stage as the getters hand it out
+nbp_status stage_out(const Stage &st, int32_t *kind, int32_t *n, void *out, int64_t cap) {
+  if (kind) *kind = st.kind;
+  if (n) *n = st.n;
+  if (out && cap > 0) memcpy(out, st.bytes.data(), std::min<size_t>((size_t)cap, st.bytes.size()));
+  return NBP_OK;
+}
+
+// stages -> a finalized program of `ctx`: the options (option, value) first, then the stages; nothing is left behind on an error
+nbp_status assemble_program(nbp_ctx *ctx, const std::vector<Stage> &stages, const std::vector<std::array<int32_t, 2>> &options,
+                            nbp_program **out) {
+  nbp_program *p = nullptr;
+  nbp_status rc = nbp_program_create(ctx, &p);
+  if (rc) return rc;
+  for (const auto &o : options)
+    if (!rc) rc = nbp_program_set_option(p, o[0], o[1]);
+  for (const Stage &s : stages)
+    if (!rc) rc = nbp_program_add_stage(p, s.kind, s.bytes.empty() ? nullptr : s.bytes.data(), s.n);
+  if (!rc) rc = nbp_program_finalize(p);
+  if (rc) { nbp_program_destroy(p); return rc; }
+  *out = p;
+  return NBP_OK;
 }
 
 // solver.TreeProgram._exchange: `edges` = (src rank, src slot or -1, dst rank, dst slot or -1) in a globally agreed order;
@@ -717,7 +864,7 @@ void rank_exchange(nbp_tree *t, const std::vector<Edge> &edges) {
     if (e.dst_rank == t->rank && e.src_rank != t->rank) x.recvs.push_back({e.src_rank, e.dst_slot});
   }
   if (x.sends.empty() && x.recvs.empty()) return;
-  add_stage(t, NBP_STAGE_COPIES, nullptr, sizeof(nbp_copy_desc), 0);
+  add_stage(t->stages, NBP_STAGE_COPIES, nullptr, sizeof(nbp_copy_desc), 0);
   t->segments.push_back({0, t->seg_start, (int)t->stages.size(), {}, {}});
   t->segments.push_back(x);
   t->seg_start = (int)t->stages.size();
@@ -761,21 +908,14 @@ std::vector<Entry> down_entries(const nbp_tree *t, const Clique &c, int v) {
 }
 
 // solver.TreeProgram._rounds: steps whose variables differ and share no factor commute (disjoint beliefs, random
-// streams keyed by the step index); round[j] = 1 + the latest round among the earlier steps j conflicts with
-template <typename EntriesOf>
-std::vector<std::vector<int>> schedule_rounds(const nbp_tree *t, const std::vector<int> &sched, EntriesOf entries_of) {
+// streams keyed by the step index); round[j] = 1 + the latest round among the earlier steps j conflicts with.
+// reads_of(v): the variables whose beliefs an update of v reads
+template <typename ReadsOf>
+std::vector<std::vector<int>> schedule_rounds(const std::vector<int> &sched, ReadsOf reads_of) {
   std::map<int, std::set<int>> reads;
   for (int v : sched) {
     if (reads.count(v)) continue;
-    std::set<int> &r = reads[v];
-    for (const Entry &e : entries_of(v)) {
-      if (e.tag == 'f')
-        for (int q = 0; q < t->g->facs[e.a].s.nvars; q++) r.insert(t->g->facs[e.a].s.vars[q]);
-      else if (e.tag == 'd') {
-        r.insert(t->cl[e.a - 1].rel[e.b][0]);
-        r.insert(t->cl[e.a - 1].rel[e.b][1]);
-      }
-    }
+    std::set<int> &r = reads[v] = reads_of(v);
     r.erase(v);
   }
   std::vector<int> rnd(sched.size(), 0);
@@ -793,6 +933,19 @@ std::vector<std::vector<int>> schedule_rounds(const nbp_tree *t, const std::vect
   return groups;
 }
 
+std::set<int> entry_reads(const nbp_tree *t, const std::vector<Entry> &entries) {
+  std::set<int> r;
+  for (const Entry &e : entries) {
+    if (e.tag == 'f')
+      for (int q = 0; q < t->g->facs[e.a].s.nvars; q++) r.insert(t->g->facs[e.a].s.vars[q]);
+    else if (e.tag == 'd') {
+      r.insert(t->cl[e.a - 1].rel[e.b][0]);
+      r.insert(t->cl[e.a - 1].rel[e.b][1]);
+    }
+  }
+  return r;
+}
+
 void plan_rounds(nbp_tree *t) {
   const nbp_graph *g = t->g;
   const size_t nc = t->cl.size();
@@ -803,87 +956,56 @@ void plan_rounds(nbp_tree *t) {
   t->drounds.assign(nc, {});
   for (const Clique &c : t->cl) {
     const size_t k0 = c.id - 1;
-    for (size_t k = 0; k < c.upsched.size(); k++) {  // doFMCIteration passes over marginalized variables and variables without a density
-      const int v = c.upsched[k];
-      if (!up_entries(t, c, v).empty() && !g->vars[v].ismargin) { t->usched[k0].push_back(v); t->uiter[k0].push_back(c.upiter[k]); }
-    }
-    t->dsched[k0] = t->joint ? t->jdnsched[k0] : c.dnsched;
-    t->urounds[k0] = schedule_rounds(t, t->usched[k0], [&](int v) { return up_entries(t, c, v); });
-    t->drounds[k0] = schedule_rounds(t, t->dsched[k0], [&](int v) { return down_entries(t, c, v); });
+    t->usched[k0] = c.upsched;
+    t->uiter[k0] = c.upiter;
+    drop_skipped_steps(t->usched[k0], t->uiter[k0], [&](int v) { return up_entries(t, c, v).empty() || g->vars[v].ismargin; });
+    t->dsched[k0] = t->joint ? t->jdnsched[k0] : c.dnsched;  // (down steps are not filtered)
+    t->urounds[k0] = schedule_rounds(t->usched[k0], [&](int v) { return entry_reads(t, up_entries(t, c, v)); });
+    t->drounds[k0] = schedule_rounds(t->dsched[k0], [&](int v) { return entry_reads(t, down_entries(t, c, v)); });
   }
 }
 
-nbp_status update_ops(nbp_tree *t, int cid, int v, const std::vector<Entry> &entries, const std::set<int> *inclq, int out_slot, int passid,
-                      int step, uint64_t seed, std::vector<nbp_proposal_desc> &props, std::vector<nbp_product_desc> &prods,
-                      bool fresh = true, int lane = 0) {
+// one update of the whole-tree compile: step `step` of clique c's up or down schedule, in scratch row `lane` of its round
+nbp_status tree_update(nbp_tree *t, const Clique &c, int v, const std::vector<Entry> &entries, int passid, int step, uint64_t seed,
+                       std::vector<nbp_proposal_desc> &props, std::vector<nbp_product_desc> &prods, bool fresh, int lane) {
   const nbp_graph *g = t->g;
-  const int base = t->scratch[cid - 1] + lane * t->maxf[cid - 1];  // `lane`: position of this step within its round
-  const std::map<int, int> &Bc = t->B[cid - 1];
-  const int F = (int)entries.size();
-  if (F > NBP_MAXF) return hfail(NBP_ERR_RANGE, "a product exceeds NBP_MAXF densities");
-  bool anymh = false;
-  for (const Entry &e : entries)
-    if (e.tag == 'f' && g->facs[e.a].s.has_multihypo) anymh = true;
-  bool anypartial = false;
-  nbp_product_desc q;
-  memset(&q, 0, sizeof(q));
-  int F_in = 0;
-  for (int i = 0; i < F; i++) {
-    const Entry &e = entries[i];
-    HFac diff;  // 'd': LinearRelative(::MKD) & co. between the two separators, measurement = the child's KDE slot
-    const HFac *fac = e.tag == 'f' ? &g->facs[e.a] : nullptr;
-    if (e.tag == 'd') {
+  std::vector<HFac> diffs;
+  diffs.reserve(entries.size());
+  std::vector<Density> dens;
+  long F_in = 0;
+  for (const Entry &e : entries) {
+    Density d{nullptr, -1, 0, {c.id, (int)e.tag, e.a, e.b, e.tag == 'm' ? v : -1}};
+    if (e.tag == 'm') d.side_slot = t->msg_slot(e.a, v);
+    else if (e.tag == 'f') {
+      d.fac = &g->facs[e.a];
+      if (d.fac->dens >= 0) d.side_slot = t->dens0 + d.fac->dens;  // the slot of its density / sampler table
+    } else {  // 'd': LinearRelative(::MKD) & co. between the two separators, measurement = the child's KDE slot
       const auto &r = t->cl[e.a - 1].rel[e.b];
-      memset(&diff, 0, sizeof(diff));
-      diff.is_prior = false;
-      diff.s.factor_kind = r[3];
-      diff.s.nvars = 2;
-      diff.s.vars[0] = r[0];
-      diff.s.vars[1] = r[1];
-      diff.s.ncomp = 1;
-      diff.s.comp[0][0] = 1.0;
-      diff.s.comp[0][4] = diff.s.comp[0][8] = diff.s.comp[0][12] = 1.0;
-      fac = &diff;
+      diffs.push_back(differential_factor(r[3], r[0], r[1], 3));  // (three diagonal entries whatever the measurement dimension)
+      d.fac = &diffs.back();
+      d.meas_kde = t->cl[e.a - 1].Dslot[e.b] + 1;
     }
-    double ns = 0.0;  // _null_surplus: relative non-multihypo siblings of a multihypo factor
-    if (anymh && fac && !fac->is_prior && !fac->s.has_multihypo) ns = g->sp.null_surplus_add;
-    int msg_slot = e.tag == 'm' ? t->msg_slot(e.a, v) : -1;
-    if (fac && fac->dens >= 0 && e.tag != 'm') msg_slot = t->dens0 + fac->dens;  // the slot of its density / sampler table
-    nbp_proposal_desc d;
-    const uint64_t sd = op_seed(seed, passid, cid, step, i + 1);
-    fill_proposal(g, d, fac, msg_slot, v, &Bc, &t->main_slot, inclq, base + i, sd, ns, nullptr, F == 1 ? 1 : 0);
-    if (e.tag == 'd') d.meas_kde = t->cl[e.a - 1].Dslot[e.b] + 1;
-    {  // needFreshMeasurements (SolveTree.jl:119): one stored measurement per factor object
-      const std::array<int, 5> key{cid, (int)e.tag, e.a, e.b, e.tag == 'm' ? v : -1};
-      if (fresh) t->meas_seed[key] = sd;
-      else {
-        auto it = t->meas_seed.find(key);
-        d.meas_seed = it == t->meas_seed.end() ? 0 : it->second;
-      }
-    }
-    props.push_back(d);
-    q.in_slot[i] = base + i;
-    const int pm = fac ? fac->s.partial_mask : 0;
-    q.in_partial[i] = (uint8_t)pm;
-    anypartial |= pm != 0;
-    F_in += (fac && fac->is_prior) ? 0 : 1;
+    F_in += (d.fac && d.fac->is_prior) ? 0 : 1;
+    dens.push_back(d);
   }
-  const int man = g->vars[v].manifold;
-  q.manifold = man;
-  q.nfactors = F;
-  q.niter = g->sp.product_niter;
-  q.out_slot = out_slot;
-  q.labels_out = -1;
-  q.old_slot = -1;
-  if (anypartial) q.old_slot = (inclq == nullptr || inclq->count(v)) ? Bc.at(v) : t->main_slot[v];
-  else memset(q.in_partial, 0, sizeof(q.in_partial));
-  q.seed = op_seed(seed, passid, cid, step, PRODUCT_ID);
-  prods.push_back(q);
-  const long N = g->sp.N, P = mani_P(man), D = mani_dim(man);
+  Update u;
+  u.v = v;
+  u.manifold = g->vars[v].manifold;
+  u.slot = {&t->B[c.id - 1], &t->main_slot};  // (down: factors of a frontal reach variables outside the clique)
+  u.scratch = t->scratch[c.id - 1] + lane * t->maxf[c.id - 1];
+  u.pass = passid; u.id = c.id; u.step = step;
+  u.fresh = fresh;
+  u.keep_count = 1;
+  u.initialized = &t->isinit;
+  u.meas = &t->meas_seed;
+  nbp_status rc = emit_update(g->sp, seed, u, dens, props, prods);
+  if (rc) return rc;
+  const long N = g->sp.N, P = mani_P(u.manifold), D = mani_dim(u.manifold);
   t->st.alg_bytes += (F_in + 2) * N * P * 8 + (F_in + 1) * D * 8;
   t->st.alg_bytes_proposal += (F_in + 1) * N * P * 8;
   t->st.alg_bytes_prep += (F_in + 1) * D * 8;
   t->st.alg_bytes_product += N * P * 8;
+  (passid == PASS_UP ? t->st.updates_up : t->st.updates_down)++;
   return NBP_OK;
 }
 
@@ -972,22 +1094,11 @@ nbp_status nbp_tree_build(const nbp_graph *g, const int32_t *order, int32_t n, n
     t->jdnsched.assign(t->cl.size(), {});
     for (Clique &c : t->cl) {
       if (c.parent == 0) continue;
-      std::set<int> frs(c.frontals.begin(), c.frontals.end()), itv;
-      for (const auto &f : c.jf) {
-        if (f.tag == 'p') continue;
-        int nfr = 0;
-        for (int u : f.vars) nfr += frs.count(u) ? 1 : 0;
-        if (nfr > 1)
-          for (int u : f.vars)
-            if (frs.count(u)) itv.insert(u);
-      }
-      auto skip = [&](int v) { return g->sp.limitfixeddown && g->vars[v].ismargin; };
-      std::vector<int> &d = t->jdnsched[c.id - 1];
-      for (int v : c.frontals)
-        if (!itv.count(v) && !skip(v) && !joint_entries(c, v, true).empty()) d.push_back(v);
-      for (int k = 0; k < NBP_DOWN_MCITERS; k++)
-        for (int v : c.frontals)
-          if (itv.count(v) && !skip(v)) d.push_back(v);
+      std::vector<VarList> facs;
+      for (const auto &f : c.jf)
+        if (f.tag != 'p') facs.push_back({f.vars.data(), (int)f.vars.size()});
+      for (int v : down_sequence(c.frontals, facs, g->sp.limitfixeddown != 0, [&](int u) { return g->vars[u].ismargin; }))
+        if (!joint_entries(c, v, true).empty()) t->jdnsched[c.id - 1].push_back(v);  // (a lone frontal nothing speaks of)
     }
   }
   plan_rounds(t);
@@ -1072,30 +1183,15 @@ int32_t nbp_tree_plan_slots(nbp_tree *t, int32_t snapshot) {
         for (size_t i = 0; i < cc.rel.size(); i++) cc.Dslot.push_back(nxt++);
       }
     }
-    // widest product of this clique: up = potentials touching v + child messages on v; down = all factors of v
-    size_t maxf = 1;
     if (t->joint) {
       c.Dslot.clear();
       for (size_t i = 0; i < c.rel.size(); i++) c.Dslot.push_back(nxt++);
-      for (int v : c.upsched)
-        if (!g->vars[v].ismargin) maxf = std::max(maxf, joint_entries(c, v, false).size());
-      for (int v : t->jdnsched[c.id - 1]) maxf = std::max(maxf, joint_entries(c, v, true).size());
-      t->scratch[c.id - 1] = nxt;
-      t->maxf[c.id - 1] = (int)maxf;
-      nxt += (int)maxf * conc(c);
-      continue;
     }
-    for (int v : c.upsched) {
-      if (g->vars[v].ismargin) continue;  // never updated in the up solve (SolveTree.jl:61)
-      size_t k = 0;
-      for (int f : c.potentials)
-        for (int q = 0; q < g->facs[f].s.nvars; q++)
-          if (g->facs[f].s.vars[q] == v) { k++; break; }
-      for (int chd : c.children)
-        if (contains(t->cl[chd - 1].seps, v)) k++;
-      maxf = std::max(maxf, k);
-    }
-    for (int v : c.dnsched) maxf = std::max(maxf, g->vfacs[v].size());
+    // widest product of this clique; marginalized variables are never updated in the up solve (SolveTree.jl:61)
+    size_t maxf = 1;
+    for (int v : c.upsched)
+      if (!g->vars[v].ismargin) maxf = std::max(maxf, up_entries(t, c, v).size());
+    for (int v : t->dsched[c.id - 1]) maxf = std::max(maxf, down_entries(t, c, v).size());
     t->scratch[c.id - 1] = nxt;
     t->maxf[c.id - 1] = (int)maxf;
     nxt += (int)maxf * conc(c);
@@ -1120,29 +1216,23 @@ nbp_status nbp_tree_schedule(nbp_tree *t, uint64_t seed) {
   t->segments.clear();
   t->seg_start = 0;
   t->meas_seed.clear();
+  t->isinit.resize(n);
+  for (int v = 0; v < n; v++) t->isinit[v] = g->vars[v].initialized;
   t->st = nbp_tree_stats{};
   std::vector<nbp_copy_desc> cps;
   if (t->snapshot) {
     for (int v = 0; v < n; v++) cps.push_back({t->snap_slot[v], t->main_slot[v]});
-    add_stage(t, NBP_STAGE_COPIES, cps.data(), sizeof(nbp_copy_desc), (int)cps.size());
+    add_stage(t->stages, NBP_STAGE_COPIES, cps.data(), sizeof(nbp_copy_desc), (int)cps.size());
   }
   cps.clear();
   for (const Clique &c : t->cl)  // deep copy of the clique sub graphs (SubGraphFunctions.jl:48)
     if (t->mine(c.id))
       for (int v : c.all()) cps.push_back({t->main_slot[v], t->B[c.id - 1].at(v)});
-  add_stage(t, NBP_STAGE_COPIES, cps.data(), sizeof(nbp_copy_desc), (int)cps.size());
+  add_stage(t->stages, NBP_STAGE_COPIES, cps.data(), sizeof(nbp_copy_desc), (int)cps.size());
   // heights / depths
-  std::vector<int> height(t->cl.size() + 1, 0), depth(t->cl.size() + 1, 0);
-  for (int cid : postorder(t)) {
-    int h = 0;
-    const Clique &c = t->cl[cid - 1];
-    if (!c.children.empty()) {
-      for (int chd : c.children) h = std::max(h, height[chd]);
-      h += 1;
-    }
-    height[cid] = h;
-  }
-  int maxh = 0, maxd = 0;
+  const std::vector<int> height = clique_heights(t);
+  std::vector<int> depth(t->cl.size() + 1, 0);
+  int maxd = 0;
   {
     std::vector<std::pair<int, int>> st;
     for (int r : t->roots) st.push_back({r, 0});
@@ -1153,18 +1243,33 @@ nbp_status nbp_tree_schedule(nbp_tree *t, uint64_t seed) {
       maxd = std::max(maxd, d);
       for (int chd : t->cl[cid - 1].children) st.push_back({chd, d + 1});
     }
-    for (size_t k = 1; k <= t->cl.size(); k++) maxh = std::max(maxh, height[k]);
   }
   std::vector<nbp_proposal_desc> props;
   std::vector<nbp_product_desc> prods;
-  nbp_status rc = NBP_OK;
+  // stage pair tt of a pass: round tt - start[c] of every clique of this rank that is running then
+  auto batch = [&](bool down, int tt, const std::vector<int> &start, const std::vector<int> &finish) {
+    props.clear();
+    prods.clear();
+    for (const Clique &c : t->cl) {
+      if (!(start[c.id] <= tt && tt < finish[c.id]) || !t->mine(c.id)) continue;
+      const std::vector<int> &round = (down ? t->drounds : t->urounds)[c.id - 1][tt - start[c.id]];
+      for (size_t lane = 0; lane < round.size(); lane++) {
+        const int k = round[lane], v = (down ? t->dsched : t->usched)[c.id - 1][k];
+        const bool fresh = down || !t->stored || t->uiter[c.id - 1][k] == 1;
+        if (nbp_status rc = tree_update(t, c, v, down ? down_entries(t, c, v) : up_entries(t, c, v), down ? PASS_DOWN : PASS_UP, k, seed, props,
+                                        prods, fresh, (int)lane))
+          return rc;
+      }
+    }
+    if (!prods.empty()) add_update_stages(t->stages, props, prods);
+    return (nbp_status)NBP_OK;
+  };
   // ---- up pass: a clique starts its schedule in the stage after its last child finished (the rendezvous of the
   // CliqueStateMachine, :221-234); stage t batches step t - start[c] of every running clique (solver.TreeProgram)
   if (g->sp.upsolve) {
     const size_t nc = t->cl.size();
-    std::vector<int> ids, start(nc + 1, 0), finish(nc + 1, 0);
-    for (const Clique &c : t->cl) ids.push_back(c.id);
-    std::stable_sort(ids.begin(), ids.end(), [&](int a, int b) { return height[a] != height[b] ? height[a] < height[b] : a < b; });
+    const std::vector<int> ids = cliques_by(height);
+    std::vector<int> start(nc + 1, 0), finish(nc + 1, 0);
     int T = 0;
     for (int cid : ids) {
       int st = 0;
@@ -1175,30 +1280,14 @@ nbp_status nbp_tree_schedule(nbp_tree *t, uint64_t seed) {
     }
     for (int tt = 0; tt < T; tt++) {
       if (t->joint) {
-        // prepCliqueMsgUp -> addLikelihoodsDifferentialCHILD! of the cliques that have just finished: approxDeconv
-        // between the solved separator beliefs of every differential pair (searched from samples of the
-        // default-constructed factor), manikde! of the result
-        props.clear();
+        props.clear();  // the differential factors of the cliques that have just finished
         for (const Clique &c : t->cl) {
           if (finish[c.id] != tt || c.parent == 0 || !t->mine(c.id)) continue;
-          for (size_t i = 0; i < c.rel.size(); i++) {
-            HFac dflt;
-            memset(&dflt, 0, sizeof(dflt));
-            dflt.s.factor_kind = c.rel[i][3];
-            dflt.s.nvars = 2;
-            dflt.s.vars[0] = c.rel[i][0];
-            dflt.s.vars[1] = c.rel[i][1];
-            dflt.s.ncomp = 1;
-            dflt.s.comp[0][0] = 1.0;
-            const int zd = dflt.s.factor_kind == NBP_F_LINREL ? mani_dim(g->vars[c.rel[i][0]].manifold) : (dflt.s.factor_kind == NBP_F_SE2 ? 3 : 1);
-            for (int q = 0; q < zd; q++) dflt.s.comp[0][4 + 4 * q] = 1.0;  // identity square-root covariance
-            nbp_proposal_desc d;
-            fill_proposal(g, d, &dflt, -1, c.rel[i][1], &t->B[c.id - 1], &t->main_slot, nullptr, c.Dslot[i],
-                          op_seed(seed, PASS_UP, c.id, 0x4000 + (int)i, 0), 0.0);
-            props.push_back(d);
-          }
+          for (size_t i = 0; i < c.rel.size(); i++)
+            props.push_back(deconv_op(g->sp, seed, c.id, (int)i, c.rel[i][3], c.rel[i][0], c.rel[i][1], g->vars[c.rel[i][0]].manifold,
+                                      g->vars[c.rel[i][1]].manifold, {&t->B[c.id - 1], &t->main_slot}, c.Dslot[i]));
         }
-        if (!props.empty()) add_stage(t, NBP_STAGE_DECONV, props.data(), sizeof(nbp_proposal_desc), (int)props.size());
+        if (!props.empty()) add_stage(t->stages, NBP_STAGE_DECONV, props.data(), sizeof(nbp_proposal_desc), (int)props.size());
       }
       {  // up messages of the cliques that finished at tt and whose parent lives on another rank
         std::vector<int> crossing;
@@ -1208,49 +1297,30 @@ nbp_status nbp_tree_schedule(nbp_tree *t, uint64_t seed) {
         up_edges(t, crossing, edges);
         rank_exchange(t, edges);
       }
-      props.clear();
-      prods.clear();
-      for (const Clique &c : t->cl) {
-        if (!(start[c.id] <= tt && tt < finish[c.id]) || !t->mine(c.id)) continue;
-        const std::vector<int> &round = t->urounds[c.id - 1][tt - start[c.id]];
-        for (size_t lane = 0; lane < round.size(); lane++) {
-          const int k = round[lane], v = t->usched[c.id - 1][k];
-          const bool fresh = t->uiter[c.id - 1][k] == 1 || !t->stored;
-          rc = update_ops(t, c.id, v, up_entries(t, c, v), nullptr, t->B[c.id - 1].at(v), PASS_UP, k, seed, props, prods, fresh, (int)lane);
-          if (rc) return rc;
-          t->st.updates_up++;
-        }
-      }
-      if (!prods.empty()) {
-        add_stage(t, NBP_STAGE_PROPOSALS, props.data(), sizeof(nbp_proposal_desc), (int)props.size());
-        add_stage(t, NBP_STAGE_PRODUCTS, prods.data(), sizeof(nbp_product_desc), (int)prods.size());
-      }
+      if (nbp_status rc = batch(false, tt, start, finish)) return rc;
     }
   }
+  auto frontals_out = [&](const Clique &c, std::vector<nbp_copy_desc> &to) {  // this rank's solved frontals -> their main slots
+    if (t->mine(c.id))
+      for (int v : c.frontals) to.push_back({t->B[c.id - 1].at(v), t->main_slot[v]});
+  };
+  cps.clear();
   if (!g->sp.downsolve) {
-    cps.clear();
-    for (const Clique &c : t->cl)
-      if (t->mine(c.id))
-        for (int v : c.frontals) cps.push_back({t->B[c.id - 1].at(v), t->main_slot[v]});
-    add_stage(t, NBP_STAGE_COPIES, cps.data(), sizeof(nbp_copy_desc), (int)cps.size());
+    for (const Clique &c : t->cl) frontals_out(c, cps);
+    add_stage(t->stages, NBP_STAGE_COPIES, cps.data(), sizeof(nbp_copy_desc), (int)cps.size());
   } else {
-    cps.clear();
-    for (int r : t->roots)
-      if (t->mine(r))
-        for (int v : t->cl[r - 1].frontals) cps.push_back({t->B[r - 1].at(v), t->main_slot[v]});
-    add_stage(t, NBP_STAGE_COPIES, cps.data(), sizeof(nbp_copy_desc), (int)cps.size());
+    for (int r : t->roots) frontals_out(t->cl[r - 1], cps);
+    add_stage(t->stages, NBP_STAGE_COPIES, cps.data(), sizeof(nbp_copy_desc), (int)cps.size());
     std::vector<nbp_copy_desc> final_cps;
     for (int dpt = 1; dpt <= maxd; dpt++)
       for (const Clique &c : t->cl)
-        if (depth[c.id] == dpt && t->mine(c.id))
-          for (int v : c.frontals) final_cps.push_back({t->B[c.id - 1].at(v), t->main_slot[v]});
+        if (depth[c.id] == dpt) frontals_out(c, final_cps);
     // batched by dependency like the up pass: a clique receives its parent's separator values (points-only copy)
     // and starts in the stage after the parent's last update (solver.TreeProgram._compile_down_asap)
     {
       const size_t nc = t->cl.size();
-      std::vector<int> ids, start(nc + 1, 0), finish(nc + 1, 0);
-      for (const Clique &c : t->cl) ids.push_back(c.id);
-      std::stable_sort(ids.begin(), ids.end(), [&](int a, int b) { return depth[a] != depth[b] ? depth[a] < depth[b] : a < b; });
+      const std::vector<int> ids = cliques_by(depth);
+      std::vector<int> start(nc + 1, 0), finish(nc + 1, 0);
       int T = 0;
       for (int cid : ids) {
         const Clique &c = t->cl[cid - 1];
@@ -1286,30 +1356,13 @@ nbp_status nbp_tree_schedule(nbp_tree *t, uint64_t seed) {
             if (it == rnd.end() || it->second != r || !t->mine(c.id) || !t->mine(c.parent)) continue;
             for (int s : c.seps) cps.push_back({t->B[c.parent - 1].at(s), t->B[c.id - 1].at(s)});
           }
-          if (!cps.empty()) add_stage(t, NBP_STAGE_COPY_POINTS, cps.data(), sizeof(nbp_copy_desc), (int)cps.size());  // read as points only
+          if (!cps.empty()) add_stage(t->stages, NBP_STAGE_COPY_POINTS, cps.data(), sizeof(nbp_copy_desc), (int)cps.size());  // read as points only
         }
-        props.clear();
-        prods.clear();
-        for (const Clique &c : t->cl) {
-          if (!(start[c.id] <= tt && tt < finish[c.id]) || !t->mine(c.id)) continue;
-          const std::vector<int> allv = c.all();
-          std::set<int> inclq(allv.begin(), allv.end());
-          const std::vector<int> &round = t->drounds[c.id - 1][tt - start[c.id]];
-          for (size_t lane = 0; lane < round.size(); lane++) {
-            const int k = round[lane], v = t->dsched[c.id - 1][k];
-            rc = update_ops(t, c.id, v, down_entries(t, c, v), &inclq, t->B[c.id - 1].at(v), PASS_DOWN, k, seed, props, prods, true, (int)lane);
-            if (rc) return rc;
-            t->st.updates_down++;
-          }
-        }
-        if (!prods.empty()) {
-          add_stage(t, NBP_STAGE_PROPOSALS, props.data(), sizeof(nbp_proposal_desc), (int)props.size());
-          add_stage(t, NBP_STAGE_PRODUCTS, prods.data(), sizeof(nbp_product_desc), (int)prods.size());
-        }
+        if (nbp_status rc = batch(true, tt, start, finish)) return rc;
       }
     }
     // transferUpdateSubGraph!, once for the whole pass (see solver.TreeProgram)
-    add_stage(t, NBP_STAGE_COPIES, final_cps.data(), sizeof(nbp_copy_desc), (int)final_cps.size());
+    add_stage(t->stages, NBP_STAGE_COPIES, final_cps.data(), sizeof(nbp_copy_desc), (int)final_cps.size());
   }
   t->segments.push_back({0, t->seg_start, (int)t->stages.size(), {}, {}});
   // statistics
@@ -1329,21 +1382,8 @@ nbp_status nbp_tree_compile(nbp_tree *t, nbp_ctx *ctx, uint64_t seed, nbp_progra
   if (!t || !ctx || !out) return hfail(NBP_ERR_ARG, "null argument");
   nbp_status rc = nbp_tree_schedule(t, seed);
   if (rc) return rc;
-  // hand the stages to libnbp
-  nbp_program *p = nullptr;
-  rc = nbp_program_create(ctx, &p);
-  if (rc) return rc;
   // a whole solve: the bandwidth of a belief that the same program overwrites before reading is dead
-  rc = nbp_program_set_option(p, NBP_OPT_LAZY_BANDWIDTH, 1);
-  if (rc) { nbp_program_destroy(p); return rc; }
-  for (const Stage &s : t->stages) {
-    rc = nbp_program_add_stage(p, s.kind, s.bytes.empty() ? nullptr : s.bytes.data(), s.n);
-    if (rc) { nbp_program_destroy(p); return rc; }
-  }
-  rc = nbp_program_finalize(p);
-  if (rc) { nbp_program_destroy(p); return rc; }
-  *out = p;
-  return NBP_OK;
+  return assemble_program(ctx, t->stages, {{NBP_OPT_LAZY_BANDWIDTH, 1}}, out);
 }
 
 // ---- multi-rank compile ---------------------------------------------------------------------------------------------
@@ -1554,43 +1594,25 @@ int32_t nbp_graph_init_plan(nbp_graph *g, uint64_t seed) {
   size_t width = 0;
   for (auto &gr : groups) width = std::max(width, gr.size());
   g->init_dens0 = V + (int)(width * maxF);  // V beliefs | proposal scratch | the pass-through densities
-  nbp_tree tmp;  // only for add_stage's container
-  tmp.g = g;
+  std::vector<Density> dens;
   for (auto &gr : groups) {
     std::vector<nbp_proposal_desc> props;
     std::vector<nbp_product_desc> prods;
     for (size_t ci = 0; ci < gr.size(); ci++) {
       const PlanItem &p = *gr[ci];
-      bool anymh = false, anypartial = false;
-      for (int fl : p.use) anymh |= g->facs[fl].s.has_multihypo != 0;
-      const int base = V + (int)(ci * maxF);
-      nbp_product_desc q;
-      memset(&q, 0, sizeof(q));
-      for (size_t i = 0; i < p.use.size(); i++) {
-        const HFac &fac = g->facs[p.use[i]];
-        const double ns = (anymh && !fac.is_prior && !fac.s.has_multihypo) ? g->sp.null_surplus_add : 0.0;
-        nbp_proposal_desc d;
-        fill_proposal(g, d, &fac, fac.dens >= 0 ? g->init_dens0 + fac.dens : -1, p.sym, nullptr, nullptr, nullptr, base + (int)i,
-                      op_seed(seed, PASS_INIT, p.sym, 0, i + 1), ns, &p.state, p.use.size() == 1 ? 2 : 0);
-        props.push_back(d);
-        q.in_slot[i] = base + (int)i;
-        q.in_partial[i] = (uint8_t)fac.s.partial_mask;
-        anypartial |= fac.s.partial_mask != 0;
-      }
-      q.manifold = g->vars[p.sym].manifold;
-      q.nfactors = (int)p.use.size();
-      q.niter = g->sp.product_niter;
-      q.out_slot = p.sym;
-      q.labels_out = -1;
-      q.old_slot = anypartial ? p.sym : -1;
-      if (!anypartial) memset(q.in_partial, 0, sizeof(q.in_partial));
-      q.seed = op_seed(seed, PASS_INIT, p.sym, 0, PRODUCT_ID);
-      prods.push_back(q);
+      dens.clear();
+      for (int fl : p.use) dens.push_back({&g->facs[fl], g->facs[fl].dens >= 0 ? g->init_dens0 + g->facs[fl].dens : -1, 0, {}});
+      Update u;  // beliefs in their variables' own slots, every measurement drawn fresh
+      u.v = u.id = p.sym;
+      u.manifold = g->vars[p.sym].manifold;
+      u.scratch = V + (int)(ci * maxF);
+      u.pass = PASS_INIT;
+      u.keep_count = 2;
+      u.initialized = &p.state;  // as they were when this variable's turn came
+      if (nbp_status rc = emit_update(g->sp, seed, u, dens, props, prods)) return rc;
     }
-    add_stage(&tmp, NBP_STAGE_PROPOSALS, props.data(), sizeof(nbp_proposal_desc), (int)props.size());
-    add_stage(&tmp, NBP_STAGE_PRODUCTS, prods.data(), sizeof(nbp_product_desc), (int)prods.size());
+    add_update_stages(g->init_stages, props, prods);
   }
-  g->init_stages = std::move(tmp.stages);
   for (auto &p : plan) g->init_vars.push_back(p.sym);
   g->init_slots = V + (int)(width * maxF) + (int)g->dens_facs.size();
   return g->init_slots;
@@ -1615,25 +1637,13 @@ nbp_status nbp_graph_init_variables(const nbp_graph *g, int32_t *out) {
 int32_t nbp_graph_init_num_stages(const nbp_graph *g) { return g ? (int32_t)g->init_stages.size() : 0; }
 nbp_status nbp_graph_init_stage(const nbp_graph *g, int32_t s, int32_t *kind, int32_t *n, void *out, int64_t cap) {
   if (!g || s < 0 || s >= (int)g->init_stages.size()) return hfail(NBP_ERR_RANGE, "stage index");
-  const Stage &st = g->init_stages[s];
-  if (kind) *kind = st.kind;
-  if (n) *n = st.n;
-  if (out && cap > 0) memcpy(out, st.bytes.data(), std::min<size_t>((size_t)cap, st.bytes.size()));
-  return NBP_OK;
+  return stage_out(g->init_stages[s], kind, n, out, cap);
 }
 nbp_status nbp_graph_init_compile(nbp_graph *g, nbp_ctx *ctx, nbp_program **out) {
   if (!g || !ctx || !out) return hfail(NBP_ERR_ARG, "null argument");
-  nbp_program *p = nullptr;
-  nbp_status rc = nbp_program_create(ctx, &p);
+  nbp_status rc = assemble_program(ctx, g->init_stages, {}, out);
   if (rc) return rc;
-  for (const Stage &s : g->init_stages) {
-    rc = nbp_program_add_stage(p, s.kind, s.bytes.empty() ? nullptr : s.bytes.data(), s.n);
-    if (rc) { nbp_program_destroy(p); return rc; }
-  }
-  rc = nbp_program_finalize(p);
-  if (rc) { nbp_program_destroy(p); return rc; }
   for (int v : g->init_vars) g->vars[v].initialized = true;  // what the program does when it is run
-  *out = p;
   return NBP_OK;
 }
 
@@ -1701,22 +1711,7 @@ static void clique_entries(const nbp_clique_desc *q, int v, bool with_msgs, std:
       if (q->msg_var[i] == v) msgs.push_back(i);
 }
 
-int32_t nbp_clique_slots(const nbp_clique_desc *q) {
-  if (!q) return hfail(NBP_ERR_ARG, "null argument");
-  size_t maxf = 1;
-  std::vector<int> fa, ms;
-  for (int v = 0; v < q->nvars; v++) {
-    clique_entries(q, v, true, fa, ms);
-    maxf = std::max(maxf, fa.size() + ms.size());
-  }
-  int ndens = 0, nkde = 0;
-  for (int f = 0; f < q->nfactors; f++) {
-    ndens += q->factors && (q->factors[f].factor_kind == NBP_F_PASSTHROUGH || spec_has_table(q->factors[f]));
-    nkde += q->factor_meas_kde && q->factor_meas_kde[f].pts != nullptr;
-  }
-  // steps that commute run side by side, one scratch row of maxf proposals each: at most one per variable
-  return q->nvars + q->nmsgs + ndens + nkde + (q->n_diff > 0 ? q->n_diff : 0) + (int32_t)maxf * q->nvars;
-}
+// largest density count of a variable of the clique: the width of a scratch row
 static size_t clique_maxf(const nbp_clique_desc *q) {
   size_t maxf = 1;
   std::vector<int> fa, ms;
@@ -1726,9 +1721,16 @@ static size_t clique_maxf(const nbp_clique_desc *q) {
   }
   return maxf;
 }
-
-// measurement dimension of a relative factor kind on a variable's manifold
-static int clique_zdim(int kind, int manifold) { return kind == NBP_F_LINREL ? mani_dim(manifold) : (kind == NBP_F_SE2 ? 3 : 1); }
+int32_t nbp_clique_slots(const nbp_clique_desc *q) {
+  if (!q) return hfail(NBP_ERR_ARG, "null argument");
+  int ndens = 0, nkde = 0;
+  for (int f = 0; f < q->nfactors; f++) {
+    ndens += q->factors && (q->factors[f].factor_kind == NBP_F_PASSTHROUGH || spec_has_table(q->factors[f]));
+    nkde += q->factor_meas_kde && q->factor_meas_kde[f].pts != nullptr;
+  }
+  // steps that commute run side by side, one scratch row of maxf proposals each: at most one per variable
+  return q->nvars + q->nmsgs + ndens + nkde + (q->n_diff > 0 ? q->n_diff : 0) + (int32_t)clique_maxf(q) * q->nvars;
+}
 
 // One clique call, planned: the beliefs to move in, the rounds of (proposals, products), the differential stage, the
 // beliefs to move out -- with every slot number shifted by `off`, so that several cliques can share one context, one
@@ -1769,215 +1771,142 @@ static void relocate(nbp_product_desc &d, const slot_map &m) {
   d.out_slot = m(d.out_slot);
   if (d.old_slot >= 0) d.old_slot = m(d.old_slot);
 }
+// The local slots of a clique call: the clique's variables | the message beliefs | the pass-through densities and sampler
+// tables | the measurement KDEs of differential factors received from children | the differential KDEs this clique sends up
+// | proposal scratch (from `base` on)
+struct clique_layout {
+  std::vector<HFac> facs;
+  std::vector<int> kde_of;  // factor -> index among the measurement KDEs, -1: it has none
+  int msg0 = 0, dens0 = 0, kde0 = 0, diff0 = 0, ndiff = 0, base = 0;
+};
+static nbp_status clique_slot_plan(const nbp_clique_desc *q, bool down, clique_layout &L) {
+  L.facs.resize(q->nfactors);
+  L.kde_of.assign(q->nfactors, -1);
+  int ndens = 0, nkde = 0;
+  for (int f = 0; f < q->nfactors; f++) {
+    const nbp_factor_spec &s = q->factors[f];
+    L.facs[f].s = s;
+    L.facs[f].is_prior = s.factor_kind == NBP_F_PRIOR || s.factor_kind == NBP_F_PASSTHROUGH;
+    if (s.factor_kind == NBP_F_PASSTHROUGH || spec_has_table(s)) L.facs[f].dens = ndens++;
+  }
+  for (int f = 0; f < q->nfactors; f++)
+    if (q->factor_meas_kde && q->factor_meas_kde[f].pts) {
+      const int k = q->factors[f].factor_kind;
+      if ((k != NBP_F_LINREL && k != NBP_F_CIRCULAR && k != NBP_F_SE2) || q->factors[f].nvars != 2 || !q->factor_meas_kde[f].bw)
+        return hfail(NBP_ERR_ARG, "clique: a measurement KDE (points + bandwidth) belongs to a binary LinearRelative / CircularCircular / SE(2) factor");
+      L.kde_of[f] = nkde++;
+    }
+  L.ndiff = down ? 0 : std::max(0, (int)q->n_diff);
+  L.msg0 = q->nvars, L.dens0 = L.msg0 + q->nmsgs, L.kde0 = L.dens0 + ndens, L.diff0 = L.kde0 + nkde, L.base = L.diff0 + L.ndiff;
+  return NBP_OK;
+}
+// the up schedule from the caller's four Gibbs id lists, or the down sequence of the frontals (variables [0, nfrontals))
+static void clique_schedule(const nbp_solver_params *sp, const nbp_clique_desc *q, bool down, std::vector<int> &sched, std::vector<int> &iter) {
+  auto margin = [&](int v) { return q->ismargin && q->ismargin[v] != 0; };
+  if (down) {
+    std::vector<int> frontals;
+    for (int v = 0; v < q->nfrontals; v++) frontals.push_back(v);
+    std::vector<VarList> facs;  // every factor of the request counts
+    for (int f = 0; f < q->nfactors; f++) facs.push_back({q->factors[f].vars, q->factors[f].nvars});
+    sched = down_sequence(frontals, facs, sp->limitfixeddown != 0, margin);
+    return;
+  }
+  auto vec = [](const int32_t *l, int n) { return std::vector<int>(l, l + n); };
+  up_gibbs_schedule(vec(q->direct_frtl_msg, q->n_direct_frtl_msg), vec(q->msgskip, q->n_msgskip), vec(q->itervar, q->n_itervar),
+                    vec(q->direct_prior_msg, q->n_direct_prior_msg), sp->gibbs_iters, sched, iter);
+  std::vector<int> fa, ms;
+  drop_skipped_steps(sched, iter, [&](int v) {
+    clique_entries(q, v, true, fa, ms);
+    return (fa.empty() && ms.empty()) || margin(v);
+  });
+}
+static nbp_status clique_beliefs_in(const nbp_clique_desc *q, const nbp_tree_belief *bel, bool down, const clique_layout &L, clique_plan &P) {
+  auto put = [&](int slot, int mani, const nbp_tree_belief &m, bool with_ipc) { P.in.push_back({slot, mani, &m, nullptr, with_ipc}); };
+  for (int v = 0; v < q->nvars; v++) {
+    if (!bel[v].pts && bel[v].handle <= 0) return hfail(NBP_ERR_ARG, "clique: null belief");
+    put(v, q->manifold[v], bel[v], true);
+  }
+  for (int i = 0; i < (down ? 0 : q->nmsgs); i++) {
+    const nbp_tree_belief &m = q->msg_belief[i];
+    if ((!m.pts || !m.bw) && m.handle <= 0) return hfail(NBP_ERR_ARG, "clique: a message needs points and bandwidth");
+    put(L.msg0 + i, q->manifold[q->msg_var[i]], m, true);
+  }
+  for (int f = 0; f < q->nfactors; f++)
+    if (L.facs[f].dens >= 0)  // a density in the variable's layout, or a sampler table (two rows: domain, cumulative weights)
+      put(L.dens0 + L.facs[f].dens, L.facs[f].s.factor_kind == NBP_F_PASSTHROUGH ? q->manifold[L.facs[f].s.vars[0]] : (int32_t)NBP_EUCLID2,
+          q->factor_density[f], true);
+  for (int f = 0; f < q->nfactors; f++)  // LinearRelative(::MKD) & co.: the measurement is the child's KDE, in measurement coordinates
+    if (L.kde_of[f] >= 0)
+      put(L.kde0 + L.kde_of[f], rel_zdim(q->factors[f].factor_kind, q->manifold[q->factors[f].vars[0]]) /* Euclid(zd) */, q->factor_meas_kde[f], false);
+  return NBP_OK;
+}
+// the rounds of (proposals, products): the same ops, with the same seeds, as the whole-tree compile emits for this clique
+static nbp_status clique_rounds(const nbp_solver_params *sp, const nbp_clique_desc *q, uint64_t seed, bool down, const clique_layout &L,
+                                const std::vector<int> &sched, const std::vector<int> &iter, std::vector<char> &updated, clique_plan &P) {
+  const bool stored = (sp->flags & NBP_SOLVER_STORED_MEASUREMENTS) != 0;
+  std::map<MeasKey, uint64_t> meas_seed;  // (0 = factor | 1 = message, index) -> seed of its last fresh draw
+  std::vector<int> fa, ms;
+  const std::vector<std::vector<int>> rounds = schedule_rounds(sched, [&](int v) {
+    std::set<int> r;
+    clique_entries(q, v, false, fa, ms);
+    for (int f : fa) r.insert(q->factors[f].vars, q->factors[f].vars + q->factors[f].nvars);
+    return r;
+  });
+  const int maxf = (int)clique_maxf(q);
+  int lanes = 1;
+  std::vector<Density> dens;
+  for (const std::vector<int> &round : rounds) {
+    lanes = std::max(lanes, (int)round.size());
+    std::vector<nbp_proposal_desc> props;
+    std::vector<nbp_product_desc> prods;
+    for (size_t lane = 0; lane < round.size(); lane++) {
+      const int k = round[lane], v = sched[(size_t)k];
+      clique_entries(q, v, !down, fa, ms);  // the caller's factor order, then the messages
+      dens.clear();
+      for (int f : fa)
+        dens.push_back({&L.facs[f], L.facs[f].dens >= 0 ? L.dens0 + L.facs[f].dens : -1, L.kde_of[f] >= 0 ? L.kde0 + L.kde_of[f] + 1 : 0, {0, f}});
+      for (int i : ms) dens.push_back({nullptr, L.msg0 + i, 0, {1, i}});
+      if (dens.empty()) continue;  // nothing speaks of v here
+      Update u;  // beliefs in their variables' own (local) slots, every variable initialised
+      u.v = v;
+      u.manifold = q->manifold[v];
+      u.scratch = L.base + (int)lane * maxf;
+      u.pass = down ? PASS_DOWN : PASS_UP; u.id = q->clique_id; u.step = k;
+      u.fresh = down || !stored || iter[(size_t)k] == 1;
+      u.keep_count = 1;
+      u.meas = &meas_seed;
+      if (nbp_status rc = emit_update(*sp, seed, u, dens, props, prods)) return rc;
+      updated[v] = 1;
+    }
+    if (!prods.empty()) P.rounds.emplace_back(std::move(props), std::move(prods));
+  }
+  P.base = L.base;
+  P.nslots = L.base + lanes * maxf;
+  return NBP_OK;
+}
 static nbp_status clique_plan_build(const nbp_solver_params *sp, const nbp_clique_desc *q, uint64_t seed, nbp_tree_belief *bel, bool down,
                                     nbp_tree_belief *diff_out, clique_plan &P) {
   nbp_status rc = clique_check(sp, q);
   if (rc) return rc;
   if (!bel) return hfail(NBP_ERR_ARG, "null argument");
   if (!down && q->n_diff > 0 && !diff_out) return hfail(NBP_ERR_ARG, "clique: differential factors are asked for, diff_out is null (nbp_clique_upsolve_joint)");
-  // a throw-away graph object carries the solver parameters and the variables for fill_proposal
-  nbp_graph g;
-  g.sp = *sp;
-  for (int v = 0; v < q->nvars; v++) g.vars.push_back({q->manifold[v], true, q->ismargin ? q->ismargin[v] != 0 : false});
-  std::vector<HFac> facs(q->nfactors);
-  int ndens = 0;
-  for (int f = 0; f < q->nfactors; f++) {
-    facs[f].s = q->factors[f];
-    facs[f].is_prior = q->factors[f].factor_kind == NBP_F_PRIOR || q->factors[f].factor_kind == NBP_F_PASSTHROUGH;
-    if (q->factors[f].factor_kind == NBP_F_PASSTHROUGH || spec_has_table(q->factors[f])) facs[f].dens = ndens++;
-  }
-  // slot plan: the clique's variables | the message beliefs | the pass-through densities | the measurement KDEs of
-  // differential factors received from children | the differential KDEs this clique sends up | proposal scratch
-  std::vector<int> kde_of(q->nfactors, -1);
-  int nkde = 0;
-  for (int f = 0; f < q->nfactors; f++)
-    if (q->factor_meas_kde && q->factor_meas_kde[f].pts) {
-      const int k = q->factors[f].factor_kind;
-      if ((k != NBP_F_LINREL && k != NBP_F_CIRCULAR && k != NBP_F_SE2) || q->factors[f].nvars != 2 || !q->factor_meas_kde[f].bw)
-        return hfail(NBP_ERR_ARG, "clique: a measurement KDE (points + bandwidth) belongs to a binary LinearRelative / CircularCircular / SE(2) factor");
-      kde_of[f] = nkde++;
-    }
-  const int ndiff = down ? 0 : std::max(0, (int)q->n_diff);
-  const int msg0 = q->nvars, dens0 = q->nvars + q->nmsgs, kde0 = dens0 + ndens, diff0 = kde0 + nkde, base = diff0 + ndiff;
-  // ---- schedule ------------------------------------------------------------------------------------------
+  clique_layout L;
+  if ((rc = clique_slot_plan(q, down, L))) return rc;
   std::vector<int> sched, iter;
-  std::vector<int> fa, ms;
-  if (!down) {  // upGibbsCliqueDensity: four fmcmc! passes (SolveTree.jl:193-235); one label -> one iteration (:106-108)
-    auto fmcmc = [&](const std::vector<int> &l, int it) {
-      if (l.size() == 1) it = 1;
-      for (int k = 0; k < it; k++)
-        for (int v : l) { sched.push_back(v); iter.push_back(k + 1); }
-    };
-    auto vec = [](const int32_t *l, int n) { return std::vector<int>(l, l + n); };
-    const std::vector<int> skip = vec(q->msgskip, q->n_msgskip);
-    fmcmc(vec(q->direct_frtl_msg, q->n_direct_frtl_msg), 1);
-    if (!skip.empty()) fmcmc(skip, 1);
-    if (q->n_itervar > 0) fmcmc(vec(q->itervar, q->n_itervar), sp->gibbs_iters);
-    if (q->n_direct_prior_msg > 0) {
-      std::vector<int> l;
-      for (int i = 0; i < q->n_direct_prior_msg; i++)
-        if (!contains(skip, (int)q->direct_prior_msg[i])) l.push_back(q->direct_prior_msg[i]);
-      fmcmc(l, 1);
-    }
-    // doFMCIteration: marginalized variables and variables without any density are passed over (:61)
-    std::vector<int> s2, i2;
-    for (size_t k = 0; k < sched.size(); k++) {
-      clique_entries(q, sched[k], true, fa, ms);
-      if ((fa.empty() && ms.empty()) || g.vars[sched[k]].ismargin) continue;
-      s2.push_back(sched[k]);
-      i2.push_back(iter[k]);
-    }
-    sched.swap(s2);
-    iter.swap(i2);
-  } else {  // determineCliqVariableDownSequence + solveCliqDownFrontalProducts! (CliqStateMachineUtils.jl:424-571)
-    std::vector<int> iterv;
-    for (int f = 0; f < q->nfactors; f++) {
-      std::vector<int> hit;
-      for (int i = 0; i < q->factors[f].nvars; i++)
-        if (q->factors[f].vars[i] < q->nfrontals) hit.push_back(q->factors[f].vars[i]);
-      if (hit.size() > 1)
-        for (int v : hit)
-          if (!contains(iterv, v)) iterv.push_back(v);
-    }
-    std::vector<int> itf, directs;
-    for (int v = 0; v < q->nfrontals; v++) {
-      if (sp->limitfixeddown && g.vars[v].ismargin) continue;
-      (contains(iterv, v) ? itf : directs).push_back(v);
-    }
-    for (int v : directs) { sched.push_back(v); iter.push_back(1); }
-    for (int k = 0; k < NBP_DOWN_MCITERS; k++)
-      for (int v : itf) { sched.push_back(v); iter.push_back(k + 1); }
-  }
-  // ---- beliefs in --------------------------------------------------------------------------------------------------
-  {
-    auto put = [&](int slot, int mani, const nbp_tree_belief &m, bool with_ipc) { P.in.push_back({slot, mani, &m, nullptr, with_ipc}); };
-    for (int v = 0; v < q->nvars; v++) {
-      if (!bel[v].pts && bel[v].handle <= 0) return hfail(NBP_ERR_ARG, "clique: null belief");
-      put(v, q->manifold[v], bel[v], true);
-    }
-    for (int i = 0; i < (down ? 0 : q->nmsgs); i++) {
-      const nbp_tree_belief &m = q->msg_belief[i];
-      if ((!m.pts || !m.bw) && m.handle <= 0) return hfail(NBP_ERR_ARG, "clique: a message needs points and bandwidth");
-      put(msg0 + i, q->manifold[q->msg_var[i]], m, true);
-    }
-    for (int f = 0; f < q->nfactors; f++)
-      if (facs[f].dens >= 0)  // a density in the variable's layout, or a sampler table (two rows: domain, cumulative weights)
-        put(dens0 + facs[f].dens, facs[f].s.factor_kind == NBP_F_PASSTHROUGH ? q->manifold[facs[f].s.vars[0]] : (int32_t)NBP_EUCLID2,
-            q->factor_density[f], true);
-    for (int f = 0; f < q->nfactors; f++)  // LinearRelative(::MKD) & co.: the measurement is the child's KDE, in measurement coordinates
-      if (kde_of[f] >= 0) put(kde0 + kde_of[f], clique_zdim(q->factors[f].factor_kind, q->manifold[q->factors[f].vars[0]]) /* Euclid(zd) */, q->factor_meas_kde[f], false);
-  }
-  // ---- the schedule -------------------------------------------------------------------------------------------------
-  const bool stored = (sp->flags & NBP_SOLVER_STORED_MEASUREMENTS) != 0;
-  std::map<std::pair<int, int>, uint64_t> meas_seed;  // (0 = factor | 1 = message, index) -> seed of its last fresh draw
-  const int passid = down ? PASS_DOWN : PASS_UP;
+  clique_schedule(sp, q, down, sched, iter);
+  if ((rc = clique_beliefs_in(q, bel, down, L, P))) return rc;
   std::vector<char> updated(q->nvars, 0);
-  // rounds of commuting steps (solver.TreeProgram._rounds): steps whose variables differ and share no factor read and
-  // write disjoint beliefs, and the random streams are keyed by the step index -- one stage pair per round
-  std::vector<std::vector<int>> rounds;
-  {
-    std::vector<std::set<int>> reads(q->nvars);
-    for (int v = 0; v < q->nvars; v++) {
-      clique_entries(q, v, false, fa, ms);
-      for (int f : fa)
-        for (int i = 0; i < q->factors[f].nvars; i++)
-          if (q->factors[f].vars[i] != v) reads[v].insert(q->factors[f].vars[i]);
-    }
-    std::vector<int> rnd(sched.size(), 0);
-    for (size_t j = 0; j < sched.size(); j++) {
-      for (size_t i = 0; i < j; i++)
-        if (sched[i] == sched[j] || reads[sched[j]].count(sched[i]) || reads[sched[i]].count(sched[j])) rnd[j] = std::max(rnd[j], rnd[i] + 1);
-      if ((int)rounds.size() <= rnd[j]) rounds.resize(rnd[j] + 1);
-      rounds[rnd[j]].push_back((int)j);
-    }
-  }
-  const int maxf = (int)clique_maxf(q);
-  for (const std::vector<int> &round : rounds) {
-    std::vector<nbp_proposal_desc> props;
-    std::vector<nbp_product_desc> prods;
-    for (size_t lane = 0; lane < round.size(); lane++) {
-      const size_t k = (size_t)round[lane];
-      const int v = sched[k];
-      clique_entries(q, v, !down, fa, ms);
-      const int F = (int)(fa.size() + ms.size());
-      if (F == 0) continue;
-      if (F > NBP_MAXF) return hfail(NBP_ERR_RANGE, "a product exceeds NBP_MAXF densities");
-      bool anymh = false;
-      for (int f : fa) anymh |= facs[f].s.has_multihypo != 0;
-      nbp_product_desc pq;
-      memset(&pq, 0, sizeof(pq));
-      bool anypartial = false;
-      const bool fresh = iter[k] == 1 || !stored || down;
-      const int row = base + (int)lane * maxf;
-      for (int i = 0; i < F; i++) {
-        const bool ismsg = i >= (int)fa.size();
-        const HFac *fac = ismsg ? nullptr : &facs[fa[i]];
-        const int mi = ismsg ? ms[i - fa.size()] : -1;
-        double ns = 0.0;  // proposalbeliefs!: relative non-multihypo siblings of a multihypo factor (ApproxConv.jl:255-265)
-        if (anymh && fac && !fac->is_prior && !fac->s.has_multihypo) ns = sp->null_surplus_add;
-        nbp_proposal_desc d;
-        const uint64_t sd = op_seed(seed, passid, q->clique_id, (uint64_t)k, (uint64_t)(i + 1));
-        fill_proposal(&g, d, fac, ismsg ? msg0 + mi : (fac->dens >= 0 ? dens0 + fac->dens : -1), v, nullptr, nullptr, nullptr, row + i, sd, ns,
-                      nullptr, F == 1 ? 1 : 0);
-        if (!ismsg && kde_of[fa[i]] >= 0) d.meas_kde = kde0 + kde_of[fa[i]] + 1;
-        const std::pair<int, int> key{ismsg ? 1 : 0, ismsg ? mi : fa[i]};
-        if (fresh) meas_seed[key] = sd;
-        else {
-          auto it = meas_seed.find(key);
-          d.meas_seed = it == meas_seed.end() ? 0 : it->second;
-        }
-        props.push_back(d);
-        pq.in_slot[i] = row + i;
-        pq.in_partial[i] = (uint8_t)(fac ? fac->s.partial_mask : 0);
-        anypartial |= pq.in_partial[i] != 0;
-      }
-      pq.manifold = q->manifold[v];
-      pq.nfactors = F;
-      pq.niter = sp->product_niter;
-      pq.out_slot = v;
-      pq.labels_out = -1;
-      pq.old_slot = anypartial ? v : -1;
-      if (!anypartial) memset(pq.in_partial, 0, sizeof(pq.in_partial));
-      pq.seed = op_seed(seed, passid, q->clique_id, (uint64_t)k, PRODUCT_ID);
-      prods.push_back(pq);
-      updated[v] = 1;
-    }
-    if (prods.empty()) continue;
-    P.rounds.emplace_back(std::move(props), std::move(prods));
-  }
-  int lanes = 1;
-  for (const std::vector<int> &round : rounds) lanes = std::max(lanes, (int)round.size());
-  P.base = base;
-  P.nslots = base + lanes * maxf;
-  if (ndiff > 0) {
-    // prepCliqueMsgUp -> addLikelihoodsDifferentialCHILD! (TreeMessageUtils.jl:279-335): approxDeconv between the solved
-    // beliefs of every pair, searched from samples of the default-constructed factor, manikde! of the result -- the same
-    // ops, with the same seeds, as the whole-tree compile emits when the clique finishes
-    std::vector<nbp_proposal_desc> props;
-    for (int i = 0; i < ndiff; i++) {
-      HFac dflt;
-      memset(&dflt, 0, sizeof(dflt));
-      dflt.s.factor_kind = q->diff_kind[i];
-      dflt.s.nvars = 2;
-      dflt.s.vars[0] = q->diff_a[i];
-      dflt.s.vars[1] = q->diff_b[i];
-      dflt.s.ncomp = 1;
-      dflt.s.comp[0][0] = 1.0;
-      const int zd = clique_zdim(q->diff_kind[i], q->manifold[q->diff_a[i]]);
-      for (int k = 0; k < zd; k++) dflt.s.comp[0][4 + 4 * k] = 1.0;  // identity square-root covariance
-      nbp_proposal_desc d;
-      fill_proposal(&g, d, &dflt, -1, q->diff_b[i], nullptr, nullptr, nullptr, diff0 + i, op_seed(seed, PASS_UP, q->clique_id, 0x4000 + i, 0), 0.0);
-      props.push_back(d);
-    }
-    P.deconv = std::move(props);
-  }
-  // ---- beliefs out: setValKDE!(vnd, mkd, setinit, ipc) (FactorGraph.jl:250-263) for everything the schedule touched, then
-  // the differential KDEs (points in measurement coordinates + fitted bandwidth)
+  if ((rc = clique_rounds(sp, q, seed, down, L, sched, iter, updated, P))) return rc;
+  for (int i = 0; i < L.ndiff; i++)  // the differential factors this clique sends up
+    P.deconv.push_back(deconv_op(*sp, seed, q->clique_id, i, q->diff_kind[i], q->diff_a[i], q->diff_b[i], q->manifold[q->diff_a[i]],
+                                 q->manifold[q->diff_b[i]], Slots{}, L.diff0 + i));
+  // beliefs out: setValKDE!(vnd, mkd, setinit, ipc) (FactorGraph.jl:250-263) for everything the schedule touched, then the
+  // differential KDEs (points in measurement coordinates + fitted bandwidth)
   for (int v = 0; v < q->nvars; v++)
     if (updated[v]) P.out.push_back({v, q->manifold[v], nullptr, &bel[v], true});
-  for (int i = 0; i < ndiff; i++) {
+  for (int i = 0; i < L.ndiff; i++) {
     if (!diff_out[i].pts || !diff_out[i].bw) return hfail(NBP_ERR_ARG, "clique: diff_out entries need pts and bw");
-    P.out.push_back({diff0 + i, clique_zdim(q->diff_kind[i], q->manifold[q->diff_a[i]]), nullptr, &diff_out[i], false});
+    P.out.push_back({L.diff0 + i, rel_zdim(q->diff_kind[i], q->manifold[q->diff_a[i]]), nullptr, &diff_out[i], false});
   }
   return NBP_OK;
 }
@@ -2144,12 +2073,8 @@ static nbp_status clique_plans_submit(nbp_ctx *ctx, std::vector<clique_plan> &pl
   if (rc) return rc;
   const double t1 = seam_now();
   // ---- the stages of the batch's program, in order: [copies in] (proposals, products) x rounds [deconv] [copies out] ----------
-  struct stage_buf { int32_t kind; int32_t n; std::vector<char> bytes; };
-  std::vector<stage_buf> stg;
-  auto add = [&](int32_t kind, const void *d, size_t n, size_t esz) {
-    stg.push_back({kind, (int32_t)n, std::vector<char>((const char *)d, (const char *)d + n * esz)});
-  };
-  if (!cin.empty()) add(NBP_STAGE_COPIES, cin.data(), cin.size(), sizeof(nbp_copy_desc));
+  std::vector<Stage> stg;
+  if (!cin.empty()) add_stage(stg, NBP_STAGE_COPIES, cin.data(), sizeof(nbp_copy_desc), (int)cin.size());
   size_t nr = 0;
   for (const clique_plan &P : plans) nr = std::max(nr, P.rounds.size());
   std::vector<nbp_proposal_desc> props;
@@ -2161,12 +2086,11 @@ static nbp_status clique_plans_submit(nbp_ctx *ctx, std::vector<clique_plan> &pl
         props.insert(props.end(), P.rounds[r].first.begin(), P.rounds[r].first.end());
         prods.insert(prods.end(), P.rounds[r].second.begin(), P.rounds[r].second.end());
       }
-    add(NBP_STAGE_PROPOSALS, props.data(), props.size(), sizeof(nbp_proposal_desc));
-    add(NBP_STAGE_PRODUCTS, prods.data(), prods.size(), sizeof(nbp_product_desc));
+    add_update_stages(stg, props, prods);
   }
   props.clear();
   for (const clique_plan &P : plans) props.insert(props.end(), P.deconv.begin(), P.deconv.end());
-  if (!props.empty()) add(NBP_STAGE_DECONV, props.data(), props.size(), sizeof(nbp_proposal_desc));
+  if (!props.empty()) add_stage(stg, NBP_STAGE_DECONV, props.data(), sizeof(nbp_proposal_desc), (int)props.size());
   // beliefs out: to their resident slots (a copy stage: it carries the fitted bandwidth along), to the host (below)
   std::vector<int32_t> os;
   for (const clique_plan &P : plans)
@@ -2181,7 +2105,7 @@ static nbp_status clique_plans_submit(nbp_ctx *ctx, std::vector<clique_plan> &pl
         T->dst.push_back(e.dst);
       }
     }
-  if (!cout.empty()) add(NBP_STAGE_COPIES, cout.data(), cout.size(), sizeof(nbp_copy_desc));
+  if (!cout.empty()) add_stage(stg, NBP_STAGE_COPIES, cout.data(), sizeof(nbp_copy_desc), (int)cout.size());
   // ---- PLAN CACHE (round 6): a batch whose program is, descriptor for descriptor, one this context has built before -- the
   // requests of a tree level that has not changed since the last walk -- runs that program again with the new seeds
   // (nbp_program_set_seeds) instead of assembling, finalizing and enqueueing ~60 launches: from its third run on the program
@@ -2193,9 +2117,9 @@ static nbp_status clique_plans_submit(nbp_ctx *ctx, std::vector<clique_plan> &pl
   plan_cache *PC = plan_cache_of(ctx);
   if (PC) {
     size_t tot = 0;
-    for (const stage_buf &b : stg) tot += 8 + b.bytes.size();
+    for (const Stage &b : stg) tot += 8 + b.bytes.size();
     sig.reserve(tot);
-    for (stage_buf &b : stg) {
+    for (const Stage &b : stg) {
       const int32_t hdr[2] = {b.kind, b.n};
       sig.insert(sig.end(), (const char *)hdr, (const char *)hdr + 8);
       const size_t at = sig.size();
@@ -2228,23 +2152,19 @@ static nbp_status clique_plans_submit(nbp_ctx *ctx, std::vector<clique_plan> &pl
     if (!rc && t_merged_calls) rc = nbp_program_set_option(p, NBP_OPT_GRAPH_REPLAY, 0);
     if (rc) return rc;
   } else {
-    rc = nbp_program_create(ctx, &p);
-    if (rc) return rc;
-    guard.p = p;
-    guard.owned = true;
-    rc = nbp_program_set_option(p, NBP_OPT_LAZY_BANDWIDTH, 1);
-    if (!rc && async) rc = nbp_program_set_option(p, NBP_OPT_ASYNC_UPLOAD, 1);
+    std::vector<std::array<int32_t, 2>> opts{{NBP_OPT_LAZY_BANDWIDTH, 1}};
+    if (async) opts.push_back({NBP_OPT_ASYNC_UPLOAD, 1});
     // (the program of a single clique or of a handful is a few launches: replayed as it is, no hipGraph -- a capture per
     //  clique program costs more than it saves, and sixteen callers' contexts would be capturing side by side)
     static const size_t graph_min = getenv("NBP_PLAN_CACHE_GRAPH_MIN") ? (size_t)atoi(getenv("NBP_PLAN_CACHE_GRAPH_MIN")) : 8;
     // (nor the batches merged from concurrent callers: their composition changes from round to round, and a capture on one lane
     //  while another lane's leader synchronises its stream is refused by the runtime -- "operation not permitted when stream is
     //  capturing", one walk in a few, whatever the capture mode)
-    if (!rc && (plans.size() < graph_min || t_merged_calls)) rc = nbp_program_set_option(p, NBP_OPT_GRAPH_REPLAY, 0);
-    for (const stage_buf &b : stg)
-      if (!rc) rc = nbp_program_add_stage(p, b.kind, b.bytes.data(), b.n);
-    if (!rc) rc = nbp_program_finalize(p);
+    if (plans.size() < graph_min || t_merged_calls) opts.push_back({NBP_OPT_GRAPH_REPLAY, 0});
+    rc = assemble_program(ctx, stg, opts, &p);
     if (rc) return rc;
+    guard.p = p;
+    guard.owned = true;
     if (PC && PC->insert(std::move(sig), p)) guard.owned = false;  // the cache keeps it
   }
   const double t2 = seam_now();
@@ -2609,11 +2529,7 @@ nbp_status nbp_clique_seam_times(double *out, int32_t mode) {
 int32_t nbp_tree_num_stages(const nbp_tree *t) { return t ? (int32_t)t->stages.size() : 0; }
 nbp_status nbp_tree_stage(const nbp_tree *t, int32_t s, int32_t *kind, int32_t *n, void *out, int64_t cap) {
   if (!t || s < 0 || s >= (int)t->stages.size()) return hfail(NBP_ERR_RANGE, "stage index");
-  const Stage &st = t->stages[s];
-  if (kind) *kind = st.kind;
-  if (n) *n = st.n;
-  if (out && cap > 0) memcpy(out, st.bytes.data(), std::min<size_t>((size_t)cap, st.bytes.size()));
-  return NBP_OK;
+  return stage_out(t->stages[s], kind, n, out, cap);
 }
 
 }  // extern "C"
