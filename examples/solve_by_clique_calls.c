@@ -494,6 +494,14 @@ int main(int argc, char **argv) {
       if (H.depth[c] == d) failed |= down_clique(&H, &W[omp_get_thread_num()], c);
   }
   t_walk[pass] = now_s() - tb;
+  /* NBP_WALK_DUMP=file: the posteriors of every walk, in walk order (points and bandwidth of every variable, raw doubles) -- what a
+   * test compares between two runs of this program, e.g. with and without the library's plan cache */
+  if (getenv("NBP_WALK_DUMP") && !failed && pass < nwalks) {
+    FILE *df = fopen(getenv("NBP_WALK_DUMP"), pass ? "ab" : "wb");
+    if (!df) return 5;
+    for (int v = 0; v < nvars; v++) { fwrite(post[v].pts, sizeof(double), (size_t)N * D, df); fwrite(post[v].bw, sizeof(double), D, df); }
+    fclose(df);
+  }
   if (!pass) t_first = now_s() - tb; else if (pass < nwalks) { t_calls = now_s() - tb; t_queued_calls = t_queued; } else { t_timed = now_s() - tb; nbp_clique_seam_times(ph, 1); }
   }
   if (failed) return 4;

@@ -364,9 +364,15 @@ nbp_status nbp_program_reseed(nbp_program *prog, uint64_t salt); /* xor-mix all 
 /* New seeds for every op of a finalized program, in stage order: per proposal / deconvolution descriptor its seed and, where the
  * descriptor named a stored measurement when the program was finalized (meas_seed != 0), that one behind it; per product
  * descriptor its seed.  n = nbp_program_num_seeds.  Stream-ordered.  (The native host's plan cache: a batch of clique requests
- * whose structure has not changed is the same program with other seeds -- include/nbp_host.h.) */
+ * whose structure has not changed is the same program with other seeds -- include/nbp_host.h.)
+ * The order is the CALLER's: the stages and descriptors as nbp_program_add_stage took them.  nbp_program_finalize may move the
+ * descriptors of a two-stream round inside their stage (NBP_PIPELINE_MIN); the library keeps track of where each one went, so
+ * seeds[i] reaches the descriptor the caller gave i-th, and a stored measurement keeps naming the op that drew it.
+ * nbp_program_seed_order tells where they went: order[i] = the place of seeds[i]'s field in a walk over the descriptors as
+ * they lie in the finalized program (0, 1, 2 ... where nothing was moved). */
 nbp_status nbp_program_num_seeds(nbp_program *prog, int32_t *out);
 nbp_status nbp_program_set_seeds(nbp_program *prog, const uint64_t *seeds, int32_t n);
+nbp_status nbp_program_seed_order(nbp_program *prog, int32_t *order, int32_t n);
 nbp_status nbp_program_num_stages(nbp_program *prog, int32_t *out);
 /* rounds of a finalized program that run as one launch of the fused update kernel (NBP_OPT_FUSED_UPDATES) */
 nbp_status nbp_program_num_fused(nbp_program *prog, int32_t *out);

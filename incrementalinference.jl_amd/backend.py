@@ -325,9 +325,18 @@ class HipProgram:
 
     def set_seeds(self, seeds):
         """new seeds for every op, in stage order: per proposal / deconv descriptor its seed and (where the descriptor named a
-        stored measurement at finalize) its meas_seed behind it; per product descriptor its seed (nbp_program_set_seeds)"""
+        stored measurement at finalize) its meas_seed behind it; per product descriptor its seed (nbp_program_set_seeds).
+        The order of the stages as they were handed to the program, also where a two-stream round moved descriptors."""
         arr = (C.c_uint64 * len(seeds))(*[int(x) for x in seeds])
         self.backend._check(self.backend.lib.nbp_program_set_seeds(self._p, arr, len(seeds)))
+
+    def seed_order(self):
+        """where the seeds of set_seeds() go: entry i = the place of seeds[i]'s field in a walk over the descriptors as they lie
+        in the finalized program; range(num_seeds()) unless a two-stream round moved descriptors (nbp_program_seed_order)"""
+        n = self.num_seeds()
+        arr = (C.c_int32 * max(n, 1))()
+        self.backend._check(self.backend.lib.nbp_program_seed_order(self._p, arr, n))
+        return list(arr[:n])
 
     @staticmethod
     def seeds_of(stages):

@@ -1567,6 +1567,9 @@ struct nbp_stage {
   // the entry fits the same way.  `pipe` on the PROPOSALS stage = the pair runs that way.
   bool pipe = false;
   int pipe_split = -1, pipe_ent = 0;
+  // where plan_pipeline put the descriptor the caller gave as the i-th of the stage (empty: where it was).  The seed table is
+  // laid out through it (layout_blob): nbp_program_set_seeds takes its seeds in the CALLER's order
+  std::vector<int> moved_to;
 };
 struct nbp_program {
   nbp_ctx *ctx = nullptr;
@@ -1587,6 +1590,7 @@ struct nbp_program {
   size_t seed_off = 0;  // table of the blob offsets of every descriptor's seed field (one reseed launch)
   size_t seed_val_off = 0;  // n_seeds values behind the table: where nbp_program_set_seeds puts the new seeds before it scatters them
   int n_seeds = 0;
+  std::vector<int32_t> seed_rank;  // nbp_program_seed_order
 };
 
 nbp_status nbp_program_create(nbp_ctx *c, nbp_program **out) {
@@ -1915,14 +1919,16 @@ static void plan_pipeline(nbp_program *p, int s) {
   }
   if (cnt[0] < qs.n / 3 || cnt[1] < qs.n / 3) return;  // one big component: nothing to run side by side
   std::vector<nbp_product_desc> q2;
+  qs.moved_to.assign((size_t)qs.n, 0);
   for (int h = 0; h < 2; h++)
-    for (int i = 0; i < qs.n; i++) if (half[i] == h) q2.push_back(qd[i]);
+    for (int i = 0; i < qs.n; i++) if (half[i] == h) { qs.moved_to[(size_t)i] = (int)q2.size(); q2.push_back(qd[i]); }
   std::vector<nbp_proposal_desc> p2;
+  ps.moved_to.assign((size_t)ps.n, 0);
   int np0 = 0;
   for (int h = 0; h < 2; h++)
     for (int k = 0; k < ps.n; k++) {
       const int hk = owner[k] < 0 ? 0 : half[owner[k]];
-      if (hk == h) { p2.push_back(pd[k]); np0 += h == 0; }
+      if (hk == h) { ps.moved_to[(size_t)k] = (int)p2.size(); p2.push_back(pd[k]); np0 += h == 0; }
     }
   memcpy(qd, q2.data(), q2.size() * sizeof(nbp_product_desc));
   memcpy(pd, p2.data(), p2.size() * sizeof(nbp_proposal_desc));
@@ -2040,6 +2046,9 @@ static void split_piped_entry_fits(nbp_program *p) {
 // Behind the descriptors, each region 64-byte aligned: the entry fits of every stage, the split-out fits of the fused
 // pairs, their update descriptors, the seed table.  (This order and these sizes are what captured graphs and the plan
 // cache of nbp_host.cpp hold offsets into.)
+// The seed table is in the CALLER's order -- the stages as nbp_program_add_stage took them -- whatever plan_pipeline did to
+// the descriptors of a two-stream round since (nbp_stage::moved_to): entry i is the field seeds[i] of nbp_program_set_seeds
+// belongs to.  Whether a proposal has a meas_seed entry is read off the descriptor at its new place.
 static void layout_blob(nbp_program *p) {
   for (nbp_stage &st : p->stages) append_fits(p->blob, st.ent);
   for (nbp_stage &st : p->stages)
@@ -2055,14 +2064,20 @@ static void layout_blob(nbp_program *p) {
     const nbp_stage &st = p->stages[s];
     if (st.kind == NBP_STAGE_PROPOSALS || st.kind == NBP_STAGE_DECONV)
       for (int i = 0; i < st.n; i++) {
-        const size_t o = st.offset + (size_t)i * sizeof(nbp_proposal_desc);
+        const size_t o = st.offset + (size_t)(st.moved_to.empty() ? i : st.moved_to[(size_t)i]) * sizeof(nbp_proposal_desc);
         so.push_back((int64_t)(o + offsetof(nbp_proposal_desc, seed)));
         // a reused measurement names another op's seed: re-keyed the same way, it keeps naming that op
         if (((const nbp_proposal_desc *)(p->blob.data() + o))->meas_seed) so.push_back((int64_t)(o + offsetof(nbp_proposal_desc, meas_seed)));
       }
     else if (st.kind == NBP_STAGE_PRODUCTS)
-      for (int i = 0; i < st.n; i++) so.push_back((int64_t)(st.offset + (size_t)i * sizeof(nbp_product_desc) + offsetof(nbp_product_desc, seed)));
+      for (int i = 0; i < st.n; i++)
+        so.push_back((int64_t)(st.offset + (size_t)(st.moved_to.empty() ? i : st.moved_to[(size_t)i]) * sizeof(nbp_product_desc) + offsetof(nbp_product_desc, seed)));
   }
+  // (nbp_program_seed_order: the rank of every entry's offset = its place in a walk over the descriptors as they lie now)
+  std::vector<int64_t> sorted(so);
+  std::sort(sorted.begin(), sorted.end());
+  p->seed_rank.resize(so.size());
+  for (size_t i = 0; i < so.size(); i++) p->seed_rank[i] = (int32_t)(std::lower_bound(sorted.begin(), sorted.end(), so[i]) - sorted.begin());
   p->seed_off = (p->blob.size() + 63) & ~(size_t)63;
   p->n_seeds = (int)so.size();
   p->seed_val_off = p->seed_off + so.size() * 8;
@@ -2278,8 +2293,9 @@ nbp_status nbp_program_reseed(nbp_program *p, uint64_t salt) {
 // New seeds for every op of a finalized program (the native host's plan cache: a batch of clique requests whose structure has not
 // changed is the same program with other seeds).  `seeds` in stage order: per proposal / deconvolution descriptor its seed and,
 // where the descriptor names a stored measurement (meas_seed != 0 when the program was finalized), that one behind it; per
-// product descriptor its seed -- the order of the program's own seed table.  Stream-ordered: behind what the program has
-// queued so far, in front of its next run.
+// product descriptor its seed -- the order in which the caller added the stages and their descriptors, which is the order of the
+// program's seed table (layout_blob), also where a two-stream round has reordered its descriptors.  Stream-ordered: behind what
+// the program has queued so far, in front of its next run.
 __global__ void nbp_setseed_kernel(char *blob, const int64_t *seed_off, const uint64_t *vals, int n) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) *(uint64_t *)(blob + seed_off[i]) = vals[i];
@@ -2308,6 +2324,15 @@ nbp_status nbp_program_set_seeds(nbp_program *p, const uint64_t *seeds, int32_t 
   hipLaunchKernelGGL(nbp_setseed_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, p->dev, (const int64_t *)(p->dev + p->seed_off),
                      (const uint64_t *)(p->dev + p->seed_val_off), n);
   HIPCHK(hipGetLastError());
+  return NBP_OK;
+}
+
+// order[i] = where, in a walk over the program's descriptors as they lie in its blob, the seed field seeds[i] goes to: 0, 1, 2 ...
+// unless a two-stream round moved descriptors (what tests ask to know that a round they made really is reordered)
+nbp_status nbp_program_seed_order(nbp_program *p, int32_t *order, int32_t n) {
+  if (!p || !p->finalized) return fail(NBP_ERR_ARG, "program not finalized");
+  if (n != p->n_seeds || (n > 0 && !order)) return fail(NBP_ERR_ARG, "seed_order: the count is not the program's (nbp_program_num_seeds)");
+  if (n > 0) memcpy(order, p->seed_rank.data(), (size_t)n * sizeof(int32_t));
   return NBP_OK;
 }
 

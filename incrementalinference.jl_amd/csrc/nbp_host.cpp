@@ -1933,6 +1933,7 @@ struct plan_cache {
   std::vector<entry> e;
   size_t cap = 64;
   uint64_t tick = 0, hits = 0, misses = 0;
+  uint64_t two_stream = 0;  // two-stream rounds (NBP_PIPELINE_MIN) in the programs the cache has taken: re-seeded in the caller's order
   std::mutex mu;  // (clique calls on one context may come from several host threads)
   static uint64_t hash_of(const std::vector<char> &v) {
     uint64_t h = 1469598103934665603ull;  // FNV-1a over 8-byte words (the tail byte-wise)
@@ -1965,10 +1966,12 @@ struct plan_cache {
     }
     const uint64_t h = hash_of(sig);
     e.push_back({h, std::move(sig), p, ++tick});
+    int32_t n2 = 0;
+    if (nbp_program_num_two_stream(p, &n2) == NBP_OK) two_stream += (uint64_t)n2;
     return true;
   }
   ~plan_cache() {
-    if (getenv("NBP_PLAN_CACHE_STATS")) fprintf(stderr, "[libnbp] plan cache: %llu hits, %llu misses, %zu programs kept\n", (unsigned long long)hits, (unsigned long long)misses, e.size());
+    if (getenv("NBP_PLAN_CACHE_STATS")) fprintf(stderr, "[libnbp] plan cache: %llu hits, %llu misses, %zu programs kept, %llu two-stream rounds in cached programs\n", (unsigned long long)hits, (unsigned long long)misses, e.size(), (unsigned long long)two_stream);
     for (entry &x : e) nbp_program_destroy(x.prog);
   }
 };
@@ -2112,7 +2115,7 @@ static nbp_status clique_plans_submit(nbp_ctx *ctx, std::vector<clique_plan> &pl
   // is one hipGraph launch.  The key is the PROGRAM, not the request: the fresh plan is built either way (2-3 ms of a walk,
   // on the planning pool) and compared byte for byte with its seed fields blanked, so nothing the planner looks at can be
   // missed by the key.  NBP_PLAN_CACHE=0 switches it off, NBP_PLAN_CACHE_ENTRIES (default 64) sizes it (least recently used out).
-  std::vector<uint64_t> seeds;     // the seeds of the fresh plan in the order of the program's seed table
+  std::vector<uint64_t> seeds;     // the seeds of the fresh plan in the order of its stages: the order nbp_program_set_seeds takes them in
   std::vector<char> sig;           // the stages with their seed fields blanked
   plan_cache *PC = plan_cache_of(ctx);
   if (PC) {

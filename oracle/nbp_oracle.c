@@ -251,7 +251,7 @@ void orc_slot_read(const double *arena, int32_t N, int32_t slot, int32_t manifol
 /* last bit -- so ONE order is fixed for both sides, the one the device's reductions have: the 64 values of a chunk by the  */
 /* butterfly of a wave (pairs 32 apart, then 16, ... 1), chunks added one after the other (block_sum / wave_chunks_sum in   */
 /* csrc/nbp_device.h); prefix sums in the order of the wave scan (wave_inclusive_scan).  The reference's own definition,     */
-/* the running geodesic mean, stays below as orc_mean_geodesic_walk and tests/test_spread_statistics.py holds the two to     */
+/* the running geodesic mean, stays below as orc_mean_geodesic_walk and tests/test_nbp_math.py holds the two to     */
 /* 1e-13 of each other.                                                                                                       */
 /* ------------------------------------------------------------------------------------------ */
 static double chunked_tree_sum(const double *v, int n) {
@@ -413,7 +413,7 @@ double orc_std_basic_spread(int manifold, const double *x, int N) {
   free(acc);
   return (1e-10 < sg) ? sg : 1.0;
 }
-/* exposed for tests/test_spread_statistics.py */
+/* exposed for tests/test_nbp_math.py */
 double orc_mean_geodesic_device_order(const double *x, int32_t cnt, int32_t circ) {
   return circ ? mean_geodesic_circ(x, cnt) : chunked_tree_sum(x, cnt) / (double)cnt;
 }

@@ -35,7 +35,9 @@ def use_native_build(out):
 def lib():
     global _lib
     if _lib is None:
-        if _SO.startswith(_DIR) and (not os.path.exists(_SO) or os.path.getmtime(_SO) < os.path.getmtime(os.path.join(_DIR, "nbp_oracle.c"))):
+        # (what the Makefile names as prerequisites: the checker's source and the headers it shares with the library)
+        srcs = [os.path.join(_DIR, "nbp_oracle.c")] + [os.path.join(os.path.dirname(_DIR), "include", h) for h in ("nbp.h", "nbp_math.h")]
+        if _SO.startswith(_DIR) and (not os.path.exists(_SO) or os.path.getmtime(_SO) < max(os.path.getmtime(s) for s in srcs)):
             build()
         L = C.CDLL(_SO)
         dp, ip, i32 = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.c_int32
