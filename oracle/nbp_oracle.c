@@ -252,7 +252,8 @@ void orc_slot_read(const double *arena, int32_t N, int32_t slot, int32_t manifol
 /* butterfly of a wave (pairs 32 apart, then 16, ... 1), chunks added one after the other (block_sum / wave_chunks_sum in   */
 /* csrc/nbp_device.h); prefix sums in the order of the wave scan (wave_inclusive_scan).  The reference's own definition,     */
 /* the running geodesic mean, stays below as orc_mean_geodesic_walk and tests/test_nbp_math.py holds the two to     */
-/* 1e-13 of each other.                                                                                                       */
+/* 1e-13 of each other; tests/sampling_cases.py (case_entropy_of_null_particles) restates the spread statistic in numpy     */
+/* from the reference's definition and holds this file AND the kernels to it through the entropy of null particles.         */
 /* ------------------------------------------------------------------------------------------ */
 static double chunked_tree_sum(const double *v, int n) {
   double tot = 0.0;
