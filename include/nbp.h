@@ -277,6 +277,18 @@ nbp_status nbp_side_read(nbp_ctx *ctx, int32_t offset, int32_t *dst, int32_t n);
 nbp_status nbp_run_proposals(nbp_ctx *ctx, const nbp_proposal_desc *descs, int32_t n);
 /* ---- AMP.manikde!(M, pts) bandwidth selection for slots already resident ------------------ */
 nbp_status nbp_run_bandwidth(nbp_ctx *ctx, const int32_t *slots, const int32_t *manifolds, int32_t n);
+/* calcPPE (FGOSUtils.jl:237-275) for beliefs resident in slots: manifold mean and the KDE's maximum among the belief's
+ * own points.  Queued on the library stream behind whatever runs there; one copy back; synchronises.
+ * mean = mean(M, pts, GeodesicInterpolation()) per coordinate over the points the belief holds; max = the point i (max_index, the
+ * lowest among equals) with the greatest p_i = sum_j exp(-1/2 sum_d (delta_d(i, j) / bw_d)^2), delta wrapped on circular
+ * coordinates (not KernelDensityEstimate.jl's getKDEMax: DESIGN.md 8).  Tangent coordinates (SE(2): x, y, theta),
+ * entries beyond the manifold's dimension zero.  A bandwidth entry that is not positive and finite: max = NaN, max_index = -1. */
+nbp_status nbp_run_ppe(nbp_ctx *ctx, const int32_t *slots, const int32_t *manifolds, int32_t n,
+                       double *mean_out /* n x NBP_MAXD */, double *max_out /* n x NBP_MAXD */,
+                       int32_t *max_index_out /* n, nullable */);
+/* host-buffer form, like nbp_kde_bandwidth: stages through slot 0 */
+nbp_status nbp_kde_ppe(nbp_ctx *ctx, int32_t manifold, const double *pts_NxP, int32_t n_pts, const double *bw_D,
+                       double *mean_out_D, double *max_out_D, int32_t *max_index_out /* nullable */);
 /* ---- variable seam: AMP.manifoldProduct + rebandwidth (GraphProductOperations.jl:53-60) --- */
 nbp_status nbp_run_products(nbp_ctx *ctx, const nbp_product_desc *descs, int32_t n);
 /* ---- host-buffer entry points: one call per reference function ----------------------------------

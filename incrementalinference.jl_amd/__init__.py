@@ -4,7 +4,7 @@ clique Gibbs schedule).  Compute lives in csrc/libnbp.so (hand-written HIP, gfx9
 C ABI of include/nbp.h; this package is the host-side mirror of the reference's API for that
 path.  There is no CPU fallback: the compute entry points raise when libnbp.so or a GPU is
 missing."""
-from . import abi, bayestree, canonical, seeds  # noqa: F401
+from . import abi, bayestree, canonical, ppe, seeds  # noqa: F401
 from .backend import HipBackend, NbpError  # noqa: F401
 from .bayestree import (buildTreeFromOrdering, buildTreeReset, getEliminationOrder,  # noqa: F401
                         nestedDissectionOrder)
@@ -14,6 +14,8 @@ from .factorgraph import (AliasingScalarSampler, Circular, CircularCircular, Con
                           EuclidDistance, LinearRelative, ManifoldFactor, ManifoldPrior, Mixture,
                           MsgPrior, MvNormal, Normal, PartialLinearRelative, PartialManifoldFactor, PartialPrior, PartialPriorPassThrough, Prior, Rayleigh, Uniform, PriorCircular, SolverParams,
                           SpecialEuclidean2, addFactor, addVariable, deleteFactor, getSolverParams, initfg, isPartial)
+from .ppe import (MeanMaxPPE, calcPPE, getPPE, getPPEMax, getPPEMean, getPPESuggested, getPPESuggestedAll,  # noqa: F401
+                  setPPE)
 from .solver import (TreeProgram, approxConv, approxConvBelief, approxConvBeliefPath, approxDeconv, findShortestPath,  # noqa: F401
                      product_desc, proposal_desc,
                      initAll, initVariable, localProduct, localProductAndUpdate, manikde, propagateBelief,

@@ -154,6 +154,18 @@ class HipBackend:
         ip = C.POINTER(C.c_int32)
         self._check(self.lib.nbp_run_bandwidth(self._ctx, s.ctypes.data_as(ip), m.ctypes.data_as(ip), s.size))
 
+    def run_ppe(self, slots, manifolds):
+        """calcPPE of resident beliefs (nbp_run_ppe) -> (mean[n, 3], max[n, 3], max_index[n]): the manifold mean and the point
+        of the belief at which its own KDE is greatest, in tangent coordinates (entries beyond the manifold's dimension zero)"""
+        s = np.ascontiguousarray(slots, dtype=np.int32)
+        m = np.ascontiguousarray(manifolds, dtype=np.int32)
+        n = s.size
+        mean, mx, idx = np.zeros((n, abi.MAXD)), np.zeros((n, abi.MAXD)), np.zeros(n, dtype=np.int32)
+        ip, dp = C.POINTER(C.c_int32), C.POINTER(C.c_double)
+        self._check(self.lib.nbp_run_ppe(self._ctx, s.ctypes.data_as(ip), m.ctypes.data_as(ip), n, mean.ctypes.data_as(dp),
+                                         mx.ctypes.data_as(dp), idx.ctypes.data_as(ip)))
+        return mean, mx, idx
+
     def run_resample(self, slots, manifolds, seed=0):
         """sample(oldBel, N - Npts): top beliefs with fewer than N points up to N, in place"""
         s = np.ascontiguousarray(slots, dtype=np.int32)
@@ -168,6 +180,17 @@ class HipBackend:
         dp = C.POINTER(C.c_double)
         self._check(self.lib.nbp_kde_bandwidth(self._ctx, manifold, pts.ctypes.data_as(dp), bw.ctypes.data_as(dp)))
         return bw
+
+    def kde_ppe(self, manifold, pts, bw):
+        """calcPPE of a belief held on the host (nbp_kde_ppe; clobbers slot 0) -> (mean[D], max[D], max_index)"""
+        dp = C.POINTER(C.c_double)
+        pts = np.ascontiguousarray(pts, dtype=np.float64).reshape(-1, abi.MANIFOLD_P[manifold])
+        bw = np.ascontiguousarray(bw, dtype=np.float64)
+        D = abi.MANIFOLD_DIM[manifold]
+        mean, mx, idx = np.zeros(D), np.zeros(D), C.c_int32(0)
+        self._check(self.lib.nbp_kde_ppe(self._ctx, manifold, pts.ctypes.data_as(dp), pts.shape[0], bw.ctypes.data_as(dp),
+                                         mean.ctypes.data_as(dp), mx.ctypes.data_as(dp), C.byref(idx)))
+        return mean, mx, idx.value
 
     def conv(self, desc, var_pts, var_bw=None, mhidx_in=None, want_mhidx=False, want_bw=True):
         dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)

@@ -20,6 +20,7 @@
 #endif
 #include "nbp_kernels.h"
 #include "nbp_fused.h"
+#include "nbp_ppe.h"
 
 static thread_local std::string g_err;
 static nbp_status fail(nbp_status code, const std::string &msg) {
@@ -95,6 +96,9 @@ struct nbp_ctx {
   // staging for immediate-mode calls
   void *stage = nullptr;
   size_t stage_bytes = 0;
+  // point estimates (nbp_run_ppe): one record per belief of the batch, grown on demand
+  nbp_ppe_rec *ppe = nullptr;
+  size_t ppe_cap = 0;
   // pinned host staging of the batched belief transfers (nbp_belief_write_batch / _read_batch): one copy per run of
   // consecutive slots, asynchronous on the library stream
   double *pin = nullptr;
@@ -355,6 +359,7 @@ nbp_status nbp_ctx_destroy(nbp_ctx *c) {
   if (c->lv_ints) hipFree(c->lv_ints);
   if (c->lv_dbls) hipFree(c->lv_dbls);
   if (c->stage) hipFree(c->stage);
+  if (c->ppe) hipFree(c->ppe);
   if (c->pin) hipHostFree(c->pin);
   for (auto &b : c->blob_cache) hipFree(b.first);
   c->blob_cache.clear();
@@ -1512,6 +1517,63 @@ nbp_status nbp_run_bandwidth(nbp_ctx *c, const int32_t *slots, const int32_t *ma
   rc = launch_bandwidth(c, ctx_env(c), fits_dev(fits, c->stage));
   if (rc) return rc;
   HIPCHK(hipStreamSynchronize(c->stream));
+  return NBP_OK;
+}
+
+// calcPPE (FGOSUtils.jl:237-275) of resident beliefs: one workgroup per belief (nbp_ppe.h), one copy back
+nbp_status nbp_run_ppe(nbp_ctx *c, const int32_t *slots, const int32_t *manifolds, int32_t n, double *mean_out, double *max_out,
+                       int32_t *max_index_out) {
+  if (!c || ((!slots || !manifolds || !mean_out || !max_out) && n > 0)) return fail(NBP_ERR_ARG, "null argument");
+  if (n <= 0) return NBP_OK;
+  HIPCHK(hipSetDevice(c->device));
+  for (int i = 0; i < n; i++) {
+    if (slots[i] < 0 || slots[i] >= c->n_slots) return fail(NBP_ERR_RANGE, "ppe: slot out of range");
+    if (!manifold_ok(manifolds[i])) return fail(NBP_ERR_ARG, "ppe: unknown manifold");
+  }
+  std::vector<int32_t> both(slots, slots + n);
+  both.insert(both.end(), manifolds, manifolds + n);
+  nbp_status rc = stage_upload(c, both.data(), both.size() * 4);  // (waits for the stream: the record buffer is free as well)
+  if (rc) return rc;
+  if ((size_t)n > c->ppe_cap) {
+    if (c->ppe) HIPCHK(hipFree(c->ppe));
+    c->ppe = nullptr;
+    c->ppe_cap = 0;
+    HIPCHK(hipMalloc(&c->ppe, sizeof(nbp_ppe_rec) * (size_t)n * 2));
+    c->ppe_cap = (size_t)n * 2;
+  }
+  const int32_t *ds = (const int32_t *)c->stage;
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(nbp_ppe_kernel, dim3(n), dim3(c->Npad), nbp_ppe_lds_bytes(c->N), c->stream, ds, ds + n, c->arena, c->N, c->S, c->ppe);
+  HIPCHK(hipGetLastError());
+  std::vector<nbp_ppe_rec> rec((size_t)n);
+  HIPCHK(hipMemcpyAsync(rec.data(), c->ppe, sizeof(nbp_ppe_rec) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  for (int i = 0; i < n; i++) {
+    for (int k = 0; k < NBP_MAXD; k++) {
+      mean_out[(size_t)i * NBP_MAXD + k] = rec[i].mean[k];
+      max_out[(size_t)i * NBP_MAXD + k] = rec[i].max[k];
+    }
+    if (max_index_out) max_index_out[i] = rec[i].max_index;
+  }
+  return NBP_OK;
+}
+
+// host-buffer form: stages through slot 0 (which it clobbers), like nbp_kde_bandwidth
+nbp_status nbp_kde_ppe(nbp_ctx *c, int32_t manifold, const double *pts, int32_t n_pts, const double *bw, double *mean_out,
+                       double *max_out, int32_t *max_index_out) {
+  if (!c || !pts || !bw || !mean_out || !max_out) return fail(NBP_ERR_ARG, "null argument");
+  if (!manifold_ok(manifold)) return fail(NBP_ERR_ARG, "ppe: unknown manifold");
+  if (n_pts < 1) return fail(NBP_ERR_ARG, "ppe: a belief holds at least one point");
+  nbp_status rc = nbp_belief_write(c, 0, manifold, pts, n_pts, bw, nullptr);
+  if (rc) return rc;
+  const int32_t slot = 0;
+  double mean3[NBP_MAXD], max3[NBP_MAXD];
+  rc = nbp_run_ppe(c, &slot, &manifold, 1, mean3, max3, max_index_out);
+  if (rc) return rc;
+  for (int k = 0; k < manifold_dim_h(manifold); k++) {
+    mean_out[k] = mean3[k];
+    max_out[k] = max3[k];
+  }
   return NBP_OK;
 }
 

@@ -394,6 +394,7 @@ class DFGVariable:
     bw: np.ndarray = None
     solvedCount: int = 0
     ismargin: bool = False
+    ppe: object = None  # MeanMaxPPE of (val, bw); None = stale: setValKDE drops it, getPPE computes it on demand (ppe.py)
 
 
 @dataclass

@@ -22,6 +22,7 @@ import numpy as np
 from . import abi, bayestree, jointmsg
 from .backend import HipBackend
 from .factorgraph import DFGFactor, DifferentialRelative, MsgPrior, PartialPriorPassThrough
+from .ppe import MeanMaxPPE
 from .seeds import op_seed
 
 PASS_INIT, PASS_UP, PASS_DOWN, PASS_UNIT = 0, 1, 2, 3
@@ -400,6 +401,7 @@ def setValKDE(fg, sym, pts, bw, setinit=True):
     """setValKDE!(vari, mkd, setinit, ipc)   FactorGraph.jl:250-263"""
     v = fg.getVariable(sym)
     v.val, v.bw = np.array(pts, dtype=float), np.array(bw, dtype=float)
+    v.ppe = None  # the reference ends with setPPE!; here the estimate is computed when it is asked for (getPPE)
     if setinit:
         v.initialized = True
 
@@ -1098,6 +1100,13 @@ def solveTree(fg, tree=None, eliminationOrder=None, backend=None, seed=0, orderi
                 pts, bw, _ = be.belief_read(tp.main[v], var.varType.manifold)
                 setValKDE(fg, v, pts, bw, True)
                 var.solvedCount += 1
+            if getattr(be, "run_ppe", None) is not None:
+                # setPPE! of every solved variable (FactorGraph.jl:200-213): one launch over the beliefs still resident
+                labels = list(fg.ls())
+                dims = [fg.getVariable(v).varType.dim for v in labels]
+                mean, mx, idx = be.run_ppe([tp.main[v] for v in labels], [fg.getVariable(v).varType.manifold for v in labels])
+                for i, v in enumerate(labels):
+                    fg.getVariable(v).ppe = MeanMaxPPE(mean[i, :dims[i]].copy(), mx[i, :dims[i]].copy(), mean[i, :dims[i]].copy(), int(idx[i]))
         finally:  # the program goes before its context, on the error path too
             if prog is not None:
                 prog.close()
