@@ -289,6 +289,30 @@ nbp_status nbp_run_ppe(nbp_ctx *ctx, const int32_t *slots, const int32_t *manifo
 /* host-buffer form, like nbp_kde_bandwidth: stages through slot 0 */
 nbp_status nbp_kde_ppe(nbp_ctx *ctx, int32_t manifold, const double *pts_NxP, int32_t n_pts, const double *bw_D,
                        double *mean_out_D, double *max_out_D, int32_t *max_index_out /* nullable */);
+/* ---- belief queries (both DEFINED by this library, unpinned against the Julia packages: DESIGN.md 8) ----------
+ * Density of resident beliefs at query points, the reference's getBelief(fg, :x)(pts): belief i is evaluated at the queries
+ * q_first[i] .. q_first[i+1]-1 (tangent coordinates, NBP_MAXD doubles each; SE(2): x, y, theta; entries beyond the manifold's
+ * dimension are not read).  p(q) = 1 / (c prod_d sqrt(2 pi) bw_d) sum_{j<c} exp(-1/2 sum_d (delta_d(q, x_j) / bw_d)^2), delta
+ * wrapped to [-pi, pi) on circular coordinates (there the mass a kernel has beyond +-pi is lost), j = 0 .. c-1 in that order in
+ * one lane: a value does not depend on the queries that travel with it.  All coordinates of the manifold enter.  A bandwidth entry
+ * that is not positive and finite: every density of that belief is NaN.  Queued on the library stream; one copy each way;
+ * synchronises. */
+nbp_status nbp_run_evaluate(nbp_ctx *ctx, const int32_t *slots, const int32_t *manifolds, int32_t n,
+                            const int32_t *q_first /* n+1, ascending, q_first[0]=0 */,
+                            const double *queries /* q_first[n] x NBP_MAXD */, double *dens_out /* q_first[n] */);
+/* host-buffer form: stages through slot 0 */
+nbp_status nbp_kde_evaluate(nbp_ctx *ctx, int32_t manifold, const double *pts_NxP, int32_t n_pts, const double *bw_D,
+                            const double *queries /* nq x NBP_MAXD */, int32_t nq, double *dens_out);
+/* mmd(p1, p2, varType; bw = [sigma]) (SolverUtilities.jl:25-47) of pairs of resident beliefs a (n points), b (m points) on one
+ * manifold: k(p, q) = exp(-sigma d(p, q)^2), d^2 = sum_d delta_d^2 in tangent coordinates (circular ones wrapped; the heading of
+ * SE(2) with weight 1), S_xy = sum_i sum_j k(x_i, y_j), mmd = Saa/(n n) + Sbb/(m m) - 2 Sab/(n m), evaluated as written with one
+ * summation order for the three sums: a belief against a bit-identical copy (or slots_a[i] == slots_b[i]) gives exactly 0.0.  No
+ * clamp at zero; the beliefs' bandwidths play no part.  sigma: finite, >= 0 (the reference's default is 0.001). */
+nbp_status nbp_run_mmd(nbp_ctx *ctx, const int32_t *slots_a, const int32_t *slots_b, const int32_t *manifolds, int32_t n,
+                       double sigma, double *mmd_out /* n */);
+/* host-buffer form: stages through slots 0 and 1 */
+nbp_status nbp_kde_mmd(nbp_ctx *ctx, int32_t manifold, const double *a_NxP, int32_t na, const double *b_NxP, int32_t nb,
+                       double sigma, double *mmd_out);
 /* ---- variable seam: AMP.manifoldProduct + rebandwidth (GraphProductOperations.jl:53-60) --- */
 nbp_status nbp_run_products(nbp_ctx *ctx, const nbp_product_desc *descs, int32_t n);
 /* ---- host-buffer entry points: one call per reference function ----------------------------------

@@ -192,6 +192,65 @@ class HipBackend:
                                          mean.ctypes.data_as(dp), mx.ctypes.data_as(dp), C.byref(idx)))
         return mean, mx, idx.value
 
+    def run_evaluate(self, slots, manifolds, queries):
+        """densities of resident beliefs at query points (nbp_run_evaluate): queries = one array (q_i x D or x 3, tangent
+        coordinates; may be empty) per belief -> one array of q_i densities per belief, from one launch"""
+        s = np.ascontiguousarray(slots, dtype=np.int32)
+        m = np.ascontiguousarray(manifolds, dtype=np.int32)
+        n = s.size
+        first = np.zeros(n + 1, dtype=np.int32)
+        rows = []
+        for i in range(n):
+            D = abi.MANIFOLD_DIM.get(int(m[i]), abi.MAXD)  # (an unknown manifold is the library's to refuse)
+            q = np.asarray(queries[i], dtype=np.float64)
+            q = q.reshape(-1, q.shape[-1] if q.ndim > 1 else D)
+            pad = np.zeros((q.shape[0], abi.MAXD))
+            pad[:, :min(D, q.shape[1])] = q[:, :D]
+            rows.append(pad)
+            first[i + 1] = first[i] + q.shape[0]
+        Q = np.ascontiguousarray(np.concatenate(rows)) if rows else np.zeros((0, abi.MAXD))
+        out = np.zeros(int(first[-1]))
+        ip, dp = C.POINTER(C.c_int32), C.POINTER(C.c_double)
+        self._check(self.lib.nbp_run_evaluate(self._ctx, s.ctypes.data_as(ip), m.ctypes.data_as(ip), n, first.ctypes.data_as(ip),
+                                              Q.ctypes.data_as(dp), out.ctypes.data_as(dp)))
+        return [out[first[i]:first[i + 1]] for i in range(n)]
+
+    def kde_evaluate(self, manifold, pts, bw, queries):
+        """densities of a belief held on the host at query points in tangent coordinates (nbp_kde_evaluate; clobbers slot 0)"""
+        dp = C.POINTER(C.c_double)
+        pts = np.ascontiguousarray(pts, dtype=np.float64).reshape(-1, abi.MANIFOLD_P[manifold])
+        bw = np.ascontiguousarray(bw, dtype=np.float64)
+        D = abi.MANIFOLD_DIM[manifold]
+        q = np.asarray(queries, dtype=np.float64)
+        q = q.reshape(-1, q.shape[-1] if q.ndim > 1 else D)
+        Q = np.zeros((q.shape[0], abi.MAXD))
+        Q[:, :D] = q[:, :D]
+        out = np.zeros(q.shape[0])
+        self._check(self.lib.nbp_kde_evaluate(self._ctx, manifold, pts.ctypes.data_as(dp), pts.shape[0], bw.ctypes.data_as(dp),
+                                              Q.ctypes.data_as(dp), q.shape[0], out.ctypes.data_as(dp)))
+        return out
+
+    def run_mmd(self, slots_a, slots_b, manifolds, sigma=0.001):
+        """mmd of pairs of resident beliefs (nbp_run_mmd) -> values[n], from one launch"""
+        a = np.ascontiguousarray(slots_a, dtype=np.int32)
+        b = np.ascontiguousarray(slots_b, dtype=np.int32)
+        m = np.ascontiguousarray(manifolds, dtype=np.int32)
+        out = np.zeros(a.size)
+        ip, dp = C.POINTER(C.c_int32), C.POINTER(C.c_double)
+        self._check(self.lib.nbp_run_mmd(self._ctx, a.ctypes.data_as(ip), b.ctypes.data_as(ip), m.ctypes.data_as(ip), a.size,
+                                         float(sigma), out.ctypes.data_as(dp)))
+        return out
+
+    def kde_mmd(self, manifold, a, b, sigma=0.001):
+        """mmd of two beliefs held on the host (nbp_kde_mmd; clobbers slots 0 and 1)"""
+        dp = C.POINTER(C.c_double)
+        a = np.ascontiguousarray(a, dtype=np.float64).reshape(-1, abi.MANIFOLD_P[manifold])
+        b = np.ascontiguousarray(b, dtype=np.float64).reshape(-1, abi.MANIFOLD_P[manifold])
+        out = C.c_double(0.0)
+        self._check(self.lib.nbp_kde_mmd(self._ctx, manifold, a.ctypes.data_as(dp), a.shape[0], b.ctypes.data_as(dp), b.shape[0],
+                                         float(sigma), C.byref(out)))
+        return out.value
+
     def conv(self, desc, var_pts, var_bw=None, mhidx_in=None, want_mhidx=False, want_bw=True):
         dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
         man = desc.manifold

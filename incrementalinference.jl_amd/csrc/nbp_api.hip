@@ -21,6 +21,7 @@
 #include "nbp_kernels.h"
 #include "nbp_fused.h"
 #include "nbp_ppe.h"
+#include "nbp_query.h"
 
 static thread_local std::string g_err;
 static nbp_status fail(nbp_status code, const std::string &msg) {
@@ -99,6 +100,9 @@ struct nbp_ctx {
   // point estimates (nbp_run_ppe): one record per belief of the batch, grown on demand
   nbp_ppe_rec *ppe = nullptr;
   size_t ppe_cap = 0;
+  // belief queries (nbp_run_evaluate / nbp_run_mmd): the queries going in and the values coming out, grown on demand
+  double *query = nullptr;
+  size_t query_cap = 0;
   // pinned host staging of the batched belief transfers (nbp_belief_write_batch / _read_batch): one copy per run of
   // consecutive slots, asynchronous on the library stream
   double *pin = nullptr;
@@ -360,6 +364,7 @@ nbp_status nbp_ctx_destroy(nbp_ctx *c) {
   if (c->lv_dbls) hipFree(c->lv_dbls);
   if (c->stage) hipFree(c->stage);
   if (c->ppe) hipFree(c->ppe);
+  if (c->query) hipFree(c->query);
   if (c->pin) hipHostFree(c->pin);
   for (auto &b : c->blob_cache) hipFree(b.first);
   c->blob_cache.clear();
@@ -1575,6 +1580,118 @@ nbp_status nbp_kde_ppe(nbp_ctx *c, int32_t manifold, const double *pts, int32_t 
     max_out[k] = max3[k];
   }
   return NBP_OK;
+}
+
+// the scratch of the belief queries holds at least `doubles` (called with the stream idle: stage_upload has waited)
+static nbp_status query_reserve(nbp_ctx *c, size_t doubles) {
+  if (doubles <= c->query_cap) return NBP_OK;
+  if (c->query) HIPCHK(hipFree(c->query));
+  c->query = nullptr;
+  c->query_cap = 0;
+  HIPCHK(hipMalloc(&c->query, sizeof(double) * doubles * 2));
+  c->query_cap = doubles * 2;
+  return NBP_OK;
+}
+
+// getBelief(fg, :x)(pts) for beliefs resident in slots: the density of each belief's KDE at its own run of query points
+// (nbp_query.h).  One workgroup per tile of at most NBP_QUERY_TILE queries of one belief; one copy each way.
+nbp_status nbp_run_evaluate(nbp_ctx *c, const int32_t *slots, const int32_t *manifolds, int32_t n, const int32_t *q_first,
+                            const double *queries, double *dens_out) {
+  if (!c || ((!slots || !manifolds || !q_first) && n > 0)) return fail(NBP_ERR_ARG, "null argument");
+  if (n <= 0) return NBP_OK;
+  HIPCHK(hipSetDevice(c->device));
+  if (q_first[0] != 0) return fail(NBP_ERR_ARG, "evaluate: q_first[0] must be 0");
+  for (int i = 0; i < n; i++) {
+    if (slots[i] < 0 || slots[i] >= c->n_slots) return fail(NBP_ERR_RANGE, "evaluate: slot out of range");
+    if (!manifold_ok(manifolds[i])) return fail(NBP_ERR_ARG, "evaluate: unknown manifold");
+    if (q_first[i + 1] < q_first[i]) return fail(NBP_ERR_ARG, "evaluate: q_first must not decrease");
+  }
+  const size_t Q = (size_t)q_first[n];
+  if (Q == 0) return NBP_OK;
+  if (!queries || !dens_out) return fail(NBP_ERR_ARG, "null argument");
+  std::vector<int32_t> ints(slots, slots + n);
+  ints.insert(ints.end(), manifolds, manifolds + n);
+  for (int i = 0; i < n; i++)
+    for (int32_t q = q_first[i]; q < q_first[i + 1]; q += NBP_QUERY_TILE) {
+      ints.push_back(i);
+      ints.push_back(q);
+      ints.push_back(std::min<int32_t>(NBP_QUERY_TILE, q_first[i + 1] - q));
+    }
+  const size_t tiles = (ints.size() - 2 * (size_t)n) / 3;
+  nbp_status rc = stage_upload(c, ints.data(), ints.size() * 4);  // (waits for the stream: the query buffer is free as well)
+  if (rc) return rc;
+  rc = query_reserve(c, Q * (NBP_MAXD + 1));
+  if (rc) return rc;
+  double *dq = c->query, *dd = c->query + Q * NBP_MAXD;
+  HIPCHK(hipMemcpyAsync(dq, queries, sizeof(double) * Q * NBP_MAXD, hipMemcpyHostToDevice, c->stream));
+  const int32_t *ds = (const int32_t *)c->stage;
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(nbp_eval_kernel, dim3((unsigned)tiles), dim3(NBP_QUERY_TILE), nbp_eval_lds_bytes(c->N), c->stream, ds + 2 * n, ds,
+                     ds + n, c->arena, c->N, c->S, dq, dd);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(dens_out, dd, sizeof(double) * Q, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return NBP_OK;
+}
+
+// host-buffer form: stages through slot 0 (which it clobbers), like nbp_kde_ppe
+nbp_status nbp_kde_evaluate(nbp_ctx *c, int32_t manifold, const double *pts, int32_t n_pts, const double *bw, const double *queries,
+                            int32_t nq, double *dens_out) {
+  if (!c || !pts || !bw || ((!queries || !dens_out) && nq > 0)) return fail(NBP_ERR_ARG, "null argument");
+  if (!manifold_ok(manifold)) return fail(NBP_ERR_ARG, "evaluate: unknown manifold");
+  if (n_pts < 1) return fail(NBP_ERR_ARG, "evaluate: a belief holds at least one point");
+  if (nq < 0) return fail(NBP_ERR_ARG, "evaluate: nq < 0");
+  nbp_status rc = nbp_belief_write(c, 0, manifold, pts, n_pts, bw, nullptr);
+  if (rc) return rc;
+  const int32_t slot = 0, q_first[2] = {0, nq};
+  return nbp_run_evaluate(c, &slot, &manifold, 1, q_first, queries, dens_out);
+}
+
+// mmd(p1, p2, varType; bw = [sigma]) (services/SolverUtilities.jl:25-47) for pairs of beliefs resident in slots: one workgroup per
+// pair (nbp_query.h), one copy back
+nbp_status nbp_run_mmd(nbp_ctx *c, const int32_t *slots_a, const int32_t *slots_b, const int32_t *manifolds, int32_t n, double sigma,
+                       double *mmd_out) {
+  if (!c || ((!slots_a || !slots_b || !manifolds || !mmd_out) && n > 0)) return fail(NBP_ERR_ARG, "null argument");
+  if (!(sigma >= 0.0 && sigma < INFINITY)) return fail(NBP_ERR_ARG, "mmd: sigma must be finite and not negative");
+  if (n <= 0) return NBP_OK;
+  HIPCHK(hipSetDevice(c->device));
+  for (int i = 0; i < n; i++) {
+    if (slots_a[i] < 0 || slots_a[i] >= c->n_slots || slots_b[i] < 0 || slots_b[i] >= c->n_slots)
+      return fail(NBP_ERR_RANGE, "mmd: slot out of range");
+    if (!manifold_ok(manifolds[i])) return fail(NBP_ERR_ARG, "mmd: unknown manifold");
+  }
+  std::vector<int32_t> ints(slots_a, slots_a + n);
+  ints.insert(ints.end(), slots_b, slots_b + n);
+  ints.insert(ints.end(), manifolds, manifolds + n);
+  nbp_status rc = stage_upload(c, ints.data(), ints.size() * 4);  // (waits for the stream: the query buffer is free as well)
+  if (rc) return rc;
+  rc = query_reserve(c, (size_t)n);
+  if (rc) return rc;
+  const int32_t *ds = (const int32_t *)c->stage;
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(nbp_mmd_kernel, dim3(n), dim3(c->Npad), nbp_mmd_lds_bytes(c->N), c->stream, ds, ds + n, ds + 2 * n, c->arena, c->N,
+                     c->S, sigma, c->query);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(mmd_out, c->query, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return NBP_OK;
+}
+
+// host-buffer form: stages through slots 0 and 1 (which it clobbers).  The bandwidths play no part in an mmd; the slots carry ones.
+nbp_status nbp_kde_mmd(nbp_ctx *c, int32_t manifold, const double *a, int32_t na, const double *b, int32_t nb, double sigma,
+                       double *mmd_out) {
+  if (!c || !a || !b || !mmd_out) return fail(NBP_ERR_ARG, "null argument");
+  if (!manifold_ok(manifold)) return fail(NBP_ERR_ARG, "mmd: unknown manifold");
+  if (na < 1 || nb < 1) return fail(NBP_ERR_ARG, "mmd: a belief holds at least one point");
+  if (!(sigma >= 0.0 && sigma < INFINITY)) return fail(NBP_ERR_ARG, "mmd: sigma must be finite and not negative");
+  if (c->n_slots < 2) return fail(NBP_ERR_RANGE, "mmd: the context needs two slots");
+  const double ones[NBP_MAXD] = {1.0, 1.0, 1.0};
+  nbp_status rc = nbp_belief_write(c, 0, manifold, a, na, ones, nullptr);
+  if (rc) return rc;
+  rc = nbp_belief_write(c, 1, manifold, b, nb, ones, nullptr);
+  if (rc) return rc;
+  const int32_t sa = 0, sb = 1;
+  return nbp_run_mmd(c, &sa, &sb, &manifold, 1, sigma, mmd_out);
 }
 
 nbp_status nbp_run_resample(nbp_ctx *c, const int32_t *slots, const int32_t *manifolds, int32_t n, uint64_t seed) {
