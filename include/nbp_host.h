@@ -197,6 +197,29 @@ enum nbp_cliq_status {
   NBP_CLIQ_DOWNSOLVED = 5, NBP_CLIQ_UPRECYCLED = 6, NBP_CLIQ_ERROR_STATUS = 7
 };
 
+/* ---- incremental solves: clique recycling between two trees of a growing graph --------------------------------------
+ * solveTree!(fg, oldtree) gives every clique of the new tree a status before anything is solved
+ * (setCliqueRecycling_StateMachine, CliqueStateMachine.jl:110-132), and the compiler reads it: UPRECYCLED and MARGINALIZED
+ * cliques run no up solve -- preUpSolve_StateMachine goes straight to postUpSolve (:309-317), and the up message is the
+ * separator beliefs their sub graph was copied with (prepCliqueMsgUp, TreeMessageUtils.jl:667-703) -- and MARGINALIZED ones
+ * no down solve either (:708-745); their children still receive the stored separator values.  A tree whose statuses are
+ * all NBP_CLIQ_NULL compiles as it always did. */
+/* setCliqueStatus!(cliq, status): legal until nbp_tree_plan_slots (the slot plan is sized from the schedules) */
+nbp_status nbp_tree_set_clique_status(nbp_tree *t, int32_t k, int32_t status);
+/* getCliqueStatus(cliq), getCliqueData(cliq).allmarginalized, .isCliqReused; every out pointer may be NULL */
+nbp_status nbp_tree_clique_status(const nbp_tree *t, int32_t k, int32_t *status, int32_t *allmarginalized, int32_t *reused);
+/* setCliqueRecycling_StateMachine for every clique of `t`: all frontals and separators marginalized and initialised in the
+ * graph (areCliqVariablesAllMarginalized, TreeBasedInitialization.jl:165-173) -> MARGINALIZED; otherwise, `incremental` and
+ * the similar clique of `old` (attemptTreeSimilarClique, JunctionTreeUtils.jl:1801-1849: the old clique that holds the first
+ * frontal, with the same frontals, separators and potentials) is DOWNSOLVED -> UPRECYCLED.  `old` is a tree of the same
+ * nbp_graph (ids are compared; the graph may have grown since) or NULL.  Legal until the slots of `t` are planned. */
+nbp_status nbp_tree_recycle(nbp_tree *t, const nbp_tree *old /* same nbp_graph, may be NULL */, int32_t incremental);
+/* calcCliquesRecycled(tree) (JunctionTreeUtils.jl:1775-1788): cliques, all-marginalized, reused, both */
+nbp_status nbp_tree_cliques_recycled(const nbp_tree *t, int32_t out[4]);
+/* After nbp_tree_schedule / nbp_tree_compile the statuses are what the solve leaves behind: NBP_CLIQ_DOWNSOLVED
+ * (NBP_CLIQ_UPSOLVED when params.downsolve is off), MARGINALIZED stays (CliqueStateMachine.jl:740-745) -- so the tree can
+ * be the `old` of the next one. */
+
 typedef struct nbp_clique_desc {
   int32_t clique_id;           /* CliqueId.value: keys the random streams                                     */
   int32_t nvars;               /* variables of the clique sub graph: the frontals first, then the separators,

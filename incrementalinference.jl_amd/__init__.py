@@ -8,14 +8,16 @@ from . import abi, bayestree, beliefquery, canonical, ppe, seeds  # noqa: F401
 from .backend import HipBackend, NbpError  # noqa: F401
 from .beliefquery import (Belief, density_numpy, getBelief, isapproxBeliefs, mmd, mmd_numpy, mmdVariables,  # noqa: F401
                           ppe_coords)
-from .bayestree import (buildTreeFromOrdering, buildTreeReset, getEliminationOrder,  # noqa: F401
-                        nestedDissectionOrder)
+from .bayestree import (areCliqVariablesAllMarginalized, attemptTreeSimilarClique, buildTreeFromOrdering,  # noqa: F401
+                        buildTreeReset, calcCliquesRecycled, getEliminationOrder, nestedDissectionOrder, setCliqueRecycling)
 from .canonical import (generateChainEuclid, generateCircularDoors, generateGraph_Kaess,  # noqa: F401
                         generateGraph_LineStep, generateMixtureChain, generateSE2Lattice)
 from .factorgraph import (AliasingScalarSampler, Circular, CircularCircular, ContinuousEuclid, ContinuousScalar,  # noqa: F401
                           EuclidDistance, LinearRelative, ManifoldFactor, ManifoldPrior, Mixture,
                           MsgPrior, MvNormal, Normal, PartialLinearRelative, PartialManifoldFactor, PartialPrior, PartialPriorPassThrough, Prior, Rayleigh, Uniform, PriorCircular, SolverParams,
-                          SpecialEuclidean2, addFactor, addVariable, deleteFactor, getSolverParams, initfg, isPartial)
+                          SpecialEuclidean2, addFactor, addVariable, defaultFixedLagOnTree, deleteFactor, deleteVariable,
+                          dontMarginalizeVariablesAll, fifoFreeze, getAddHistory, getSolverParams, initfg, isMarginalized,
+                          isPartial, setMarginalized, setfreeze, unfreezeVariablesAll)
 from .ppe import (MeanMaxPPE, calcPPE, getPPE, getPPEMax, getPPEMean, getPPESuggested, getPPESuggestedAll,  # noqa: F401
                   setPPE)
 from .solver import (TreeProgram, approxConv, approxConvBelief, approxConvBeliefPath, approxDeconv, findShortestPath,  # noqa: F401

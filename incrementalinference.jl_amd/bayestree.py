@@ -9,10 +9,16 @@ reference so that the same variable-update sequence is executed:
   compCliqAssocMatrices!       src/services/JunctionTreeUtils.jl:1294-1340
   setCliqMCIDs! and friends    src/services/JunctionTreeUtils.jl:1352-1523
   determineCliqVariableDownSequence  src/CliqueStateMachine/services/CliqStateMachineUtils.jl:424-462
+  attemptTreeSimilarClique / calcCliquesRecycled   src/services/JunctionTreeUtils.jl:1770-1849
+  setCliqueRecycling (setCliqueRecycling_StateMachine)   src/CliqueStateMachine/services/CliqueStateMachine.jl:110-132
 """
 from dataclasses import dataclass, field
 
 import numpy as np
+
+
+# CliqStatus (entities/BeliefTypes.jl:8) = enum nbp_cliq_status of include/nbp_host.h
+NULL, NO_INIT, INITIALIZED, UPSOLVED, MARGINALIZED, DOWNSOLVED, UPRECYCLED, ERROR_STATUS = range(8)
 
 
 @dataclass
@@ -32,6 +38,9 @@ class TreeClique:
     itervarIDs: list = field(default_factory=list)
     msgskipIDs: list = field(default_factory=list)
     directFrtlMsgIDs: list = field(default_factory=list)
+    status: int = NULL             # CliqStatus; UPRECYCLED / MARGINALIZED are read by the schedule compilers
+    allmarginalized: bool = False  # every variable of the clique is frozen: neither pass touches it
+    isCliqReused: bool = False     # the up solve is taken over from the same clique of an older tree
 
     @property
     def allIDs(self):
@@ -424,3 +433,53 @@ def downSchedule(fg, cliq, MCIters=3):
         iterFrtls = [v for v in iterFrtls if v not in skip]
         directs = [v for v in directs if v not in skip]
     return directs + iterFrtls * MCIters
+
+
+# ------------------------------------------------------------------------------------------------
+# clique recycling between two solves of a growing graph
+# ------------------------------------------------------------------------------------------------
+def areCliqVariablesAllMarginalized(fg, cliq):
+    """every frontal and separator is marginalized and initialised (TreeBasedInitialization.jl:165-173)"""
+    return all(fg.getVariable(v).ismargin and fg.getVariable(v).initialized for v in cliq.allIDs)
+
+
+def attemptTreeSimilarClique(oldtree, cliq):
+    """The clique of `oldtree` that holds `cliq`'s first frontal, when its frontals, its separators and its potentials
+    are the same sets as `cliq`'s; None otherwise (JunctionTreeUtils.jl:1801-1849)."""
+    cid = oldtree.frontals.get(cliq.frontalIDs[0]) if oldtree is not None else None
+    if cid is None:
+        return None
+    other = oldtree.cliques[cid]
+    same = (set(other.frontalIDs) == set(cliq.frontalIDs) and set(other.separatorIDs) == set(cliq.separatorIDs)
+            and set(other.potentials) == set(cliq.potentials))
+    return other if same else None
+
+
+def setCliqueRecycling(fg, tree, oldtree=None, incremental=True):
+    """setCliqueRecycling_StateMachine (CliqueStateMachine.jl:110-132) for every clique of `tree`: all variables
+    marginalized -> MARGINALIZED (this wins); otherwise, `incremental` and the similar clique of `oldtree` is DOWNSOLVED ->
+    UPRECYCLED, reused."""
+    olds = {k: attemptTreeSimilarClique(oldtree, cliq) for k, cliq in tree.cliques.items()}
+    oldstatus = {k: (o.status if o is not None else NULL) for k, o in olds.items()}
+    for k, cliq in tree.cliques.items():  # the reference's tree is fresh here; a prebuilt one starts over
+        cliq.status, cliq.allmarginalized, cliq.isCliqReused = NULL, False, False
+        if areCliqVariablesAllMarginalized(fg, cliq):
+            cliq.allmarginalized, cliq.status = True, MARGINALIZED
+        elif incremental and oldstatus[k] == DOWNSOLVED:
+            cliq.isCliqReused, cliq.status = True, UPRECYCLED
+    return tree
+
+
+def calcCliquesRecycled(tree):
+    """(cliques, all-marginalized, reused, both)   JunctionTreeUtils.jl:1775-1788"""
+    cl = list(tree.cliques.values())
+    return (len(cl), sum(c.allmarginalized for c in cl), sum(c.isCliqReused for c in cl),
+            sum(c.allmarginalized and c.isCliqReused for c in cl))
+
+
+def setSolvedStatuses(tree, downsolve=True):
+    """the statuses a whole-tree solve leaves behind: DOWNSOLVED (UPSOLVED without a down pass); MARGINALIZED stays
+    (CliqueStateMachine.jl:740-745)"""
+    for cliq in tree.cliques.values():
+        if cliq.status != MARGINALIZED:
+            cliq.status = DOWNSOLVED if downsolve else UPSOLVED

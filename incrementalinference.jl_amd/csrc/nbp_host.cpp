@@ -76,6 +76,9 @@ struct Clique {
   std::vector<int> jpriors;                // separators that get a MsgPrior in the message
   bool hasPriors = false;
   std::vector<int> Dslot;                  // slot of the KDE of each differential factor
+  // clique recycling (setCliqueRecycling_StateMachine): CliqStatus and the two flags calcCliquesRecycled counts
+  int status = NBP_CLIQ_NULL;
+  bool allmarginalized = false, reused = false;
   std::vector<int> all() const {
     std::vector<int> a = frontals;
     a.insert(a.end(), seps.begin(), seps.end());
@@ -122,6 +125,7 @@ struct nbp_tree {
   // rounds = the steps of a schedule grouped into sets of commuting steps (solver.TreeProgram._rounds)
   std::vector<std::vector<int>> usched, uiter, dsched;
   std::vector<std::vector<std::vector<int>>> urounds, drounds;
+  bool replan = false;  // a clique status changed since the rounds were planned
   std::map<MeasKey, uint64_t> meas_seed;  // (clique, tag, a, b, variable of a message) -> seed of the last fresh draw
   std::vector<char> isinit;               // the graph's initialised flags as the last compile found them (multihypo)
   // multi-rank compile (solver.TreeProgram(owner=, rank=)): owner[c] = rank of clique c (index c - 1); this rank compiles
@@ -960,6 +964,11 @@ void plan_rounds(nbp_tree *t) {
     t->uiter[k0] = c.upiter;
     drop_skipped_steps(t->usched[k0], t->uiter[k0], [&](int v) { return up_entries(t, c, v).empty() || g->vars[v].ismargin; });
     t->dsched[k0] = t->joint ? t->jdnsched[k0] : c.dnsched;  // (down steps are not filtered)
+    // a recycled or marginalized clique goes from preUpSolve straight to postUpSolve (CliqueStateMachine.jl:309-317): no update,
+    // and its up message is the separator beliefs its sub graph copy was filled with; a marginalized one is not down
+    // solved either (:708-745) -- its separator values still travel on to its children
+    if (c.status == NBP_CLIQ_UPRECYCLED || c.status == NBP_CLIQ_MARGINALIZED) { t->usched[k0].clear(); t->uiter[k0].clear(); }
+    if (c.status == NBP_CLIQ_MARGINALIZED) t->dsched[k0].clear();
     t->urounds[k0] = schedule_rounds(t->usched[k0], [&](int v) { return entry_reads(t, up_entries(t, c, v)); });
     t->drounds[k0] = schedule_rounds(t->dsched[k0], [&](int v) { return entry_reads(t, down_entries(t, c, v)); });
   }
@@ -1149,6 +1158,7 @@ int32_t nbp_tree_plan_slots(nbp_tree *t, int32_t snapshot) {
   if (!t) return hfail(NBP_ERR_ARG, "null argument");
   const nbp_graph *g = t->g;
   const int n = (int)g->vars.size();
+  if (t->replan) { plan_rounds(t); t->replan = false; }
   t->snapshot = snapshot;
   t->main_slot.resize(n);
   for (int v = 0; v < n; v++) t->main_slot[v] = v;
@@ -1187,10 +1197,9 @@ int32_t nbp_tree_plan_slots(nbp_tree *t, int32_t snapshot) {
       c.Dslot.clear();
       for (size_t i = 0; i < c.rel.size(); i++) c.Dslot.push_back(nxt++);
     }
-    // widest product of this clique; marginalized variables are never updated in the up solve (SolveTree.jl:61)
+    // widest product of this clique, over the steps that run (plan_rounds: no marginalized variable, no recycled clique)
     size_t maxf = 1;
-    for (int v : c.upsched)
-      if (!g->vars[v].ismargin) maxf = std::max(maxf, up_entries(t, c, v).size());
+    for (int v : t->usched[c.id - 1]) maxf = std::max(maxf, up_entries(t, c, v).size());
     for (int v : t->dsched[c.id - 1]) maxf = std::max(maxf, down_entries(t, c, v).size());
     t->scratch[c.id - 1] = nxt;
     t->maxf[c.id - 1] = (int)maxf;
@@ -1375,6 +1384,70 @@ nbp_status nbp_tree_schedule(nbp_tree *t, uint64_t seed) {
   for (const Clique &c : t->cl) edges += c.parent != 0;
   t->st.messages = ((g->sp.upsolve ? 1 : 0) + (g->sp.downsolve ? 1 : 0)) * edges;
   t->st.slots = t->n_slots;
+  // what the solve leaves behind, for a later tree to be matched against (CliqueStateMachine.jl:740-745)
+  for (Clique &c : t->cl)
+    if (c.status != NBP_CLIQ_MARGINALIZED) c.status = g->sp.downsolve ? NBP_CLIQ_DOWNSOLVED : NBP_CLIQ_UPSOLVED;
+  return NBP_OK;
+}
+
+// ---- clique recycling -----------------------------------------------------------------------------------------------
+static void clique_set_status(nbp_tree *t, Clique &c, int status, bool allmarginalized, bool reused) {
+  c.status = status;
+  c.allmarginalized = allmarginalized;
+  c.reused = reused;
+  t->replan = true;
+}
+nbp_status nbp_tree_set_clique_status(nbp_tree *t, int32_t k, int32_t status) {
+  if (!t || k < 1 || k > (int)t->cl.size()) return hfail(NBP_ERR_RANGE, "clique id");
+  if (status < NBP_CLIQ_NULL || status > NBP_CLIQ_ERROR_STATUS) return hfail(NBP_ERR_ARG, "unknown clique status");
+  if (!t->main_slot.empty()) return hfail(NBP_ERR_ARG, "clique statuses are set before the slots are planned");
+  clique_set_status(t, t->cl[k - 1], status, status == NBP_CLIQ_MARGINALIZED, status == NBP_CLIQ_UPRECYCLED);
+  return NBP_OK;
+}
+nbp_status nbp_tree_clique_status(const nbp_tree *t, int32_t k, int32_t *status, int32_t *allmarginalized, int32_t *reused) {
+  if (!t || k < 1 || k > (int)t->cl.size()) return hfail(NBP_ERR_RANGE, "clique id");
+  const Clique &c = t->cl[k - 1];
+  if (status) *status = c.status;
+  if (allmarginalized) *allmarginalized = c.allmarginalized;
+  if (reused) *reused = c.reused;
+  return NBP_OK;
+}
+nbp_status nbp_tree_recycle(nbp_tree *t, const nbp_tree *old, int32_t incremental) {
+  if (!t) return hfail(NBP_ERR_ARG, "null argument");
+  if (!t->main_slot.empty()) return hfail(NBP_ERR_ARG, "clique statuses are set before the slots are planned");
+  const nbp_graph *g = t->g;
+  auto same_set = [](std::vector<int> a, std::vector<int> b) {
+    std::sort(a.begin(), a.end());
+    std::sort(b.begin(), b.end());
+    return a == b;
+  };
+  std::vector<int> oldstatus(t->cl.size(), NBP_CLIQ_NULL);
+  for (const Clique &c : t->cl) {
+    // attemptTreeSimilarClique: the old clique that holds the first frontal, with equal frontals, separators, potentials
+    const int f0 = c.frontals[0];
+    if (!old || f0 >= (int)old->frontal_of.size() || old->frontal_of[f0] < 1) continue;
+    const Clique &cand = old->cl[old->frontal_of[f0] - 1];
+    if (same_set(cand.frontals, c.frontals) && same_set(cand.seps, c.seps) && same_set(cand.potentials, c.potentials))
+      oldstatus[c.id - 1] = cand.status;
+  }
+  for (Clique &c : t->cl) {  // (the reference's tree is fresh here; one that has statuses starts over)
+    bool allmarg = true;     // areCliqVariablesAllMarginalized
+    for (int v : c.all()) allmarg = allmarg && g->vars[v].ismargin && g->vars[v].initialized;
+    if (allmarg) clique_set_status(t, c, NBP_CLIQ_MARGINALIZED, true, false);
+    else if (incremental && oldstatus[c.id - 1] == NBP_CLIQ_DOWNSOLVED) clique_set_status(t, c, NBP_CLIQ_UPRECYCLED, false, true);
+    else clique_set_status(t, c, NBP_CLIQ_NULL, false, false);
+  }
+  return NBP_OK;
+}
+nbp_status nbp_tree_cliques_recycled(const nbp_tree *t, int32_t out[4]) {
+  if (!t || !out) return hfail(NBP_ERR_ARG, "null argument");
+  out[0] = (int32_t)t->cl.size();
+  out[1] = out[2] = out[3] = 0;
+  for (const Clique &c : t->cl) {
+    out[1] += c.allmarginalized;
+    out[2] += c.reused;
+    out[3] += c.allmarginalized && c.reused;
+  }
   return NBP_OK;
 }
 

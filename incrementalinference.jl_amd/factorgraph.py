@@ -8,6 +8,8 @@ factors    Prior, PriorCircular, ManifoldPrior, LinearRelative, CircularCircular
 graph      initfg, addVariable, addFactor(multihypo=, nullhypo=, inflation=), getVariable, ls, lsf
            (src/services/FactorGraph.jl:587-632, 824-875)
 params     SolverParams with the reference defaults (src/entities/SolverParams.jl:12-75)
+fixed lag  getAddHistory, deleteVariable, setfreeze, fifoFreeze, defaultFixedLagOnTree, dontMarginalizeVariablesAll /
+           unfreezeVariablesAll, isMarginalized, setMarginalized   (src/services/FGOSUtils.jl:164-211, 315-385)
 
 Only bookkeeping lives here; all particle arithmetic happens in libnbp behind include/nbp.h.
 """
@@ -368,6 +370,9 @@ class DifferentialRelative(_Factor):
 # ------------------------------------------------------------------------------------------------
 # SolverParams (entities/SolverParams.jl:12-75) -- hot-path knobs only
 # ------------------------------------------------------------------------------------------------
+QFL_UNLIMITED = 2 ** 63 - 1  # typemax(Int): nothing is older than the horizon
+
+
 @dataclass
 class SolverParams:
     N: int = 100
@@ -383,6 +388,9 @@ class SolverParams:
     limitfixeddown: bool = False  # skip marginalized frontals in the down solve (CliqStateMachineUtils.jl:499)
     productNiter: int = 1  # AMP.manifoldProduct(...; Niter=1), GraphProductOperations.jl:56
     useMsgLikelihoods: bool = False  # upward messages as joint likelihoods (SolverParams.jl:25, jointmsg.py)
+    isfixedlag: bool = False  # solveTree freezes the variables older than `qfl` first (SolverAPI.jl:383-386)
+    qfl: int = QFL_UNLIMITED  # quasi fixed-lag horizon, in variables of the add history (SolverParams.jl: typemax(Int))
+    incremental: bool = True  # recycle the cliques an old tree has already solved (solveTree(oldtree=), SolverParams.jl)
 
 
 @dataclass
@@ -435,6 +443,7 @@ class FactorGraph:
         self.variables = {}
         self.factors = {}
         self._adj = {}  # variable label -> [factor labels] in insertion order
+        self.addHistory = []  # every variable label ever added, in add order; deleteVariable leaves it alone (getAddHistory)
 
     # -- DFG-style accessors -------------------------------------------------------------------
     def ls(self, var=None):
@@ -472,6 +481,75 @@ def deleteFactor(fg, label):
     return f
 
 
+def getAddHistory(fg):
+    """getAddHistory(dfg): the labels of all variables in the order they were added, deleted ones included"""
+    return fg.addHistory
+
+
+def deleteVariable(fg, label):
+    """deleteVariable!(dfg, label): the variable and every factor on it go; the add history keeps the label"""
+    if label not in fg.variables:
+        raise KeyError(f"variable {label} not in graph")
+    for f in list(fg._adj[label]):
+        deleteFactor(fg, f)
+    del fg._adj[label]
+    return fg.variables.pop(label)
+
+
+def isMarginalized(fg, label):
+    """isMarginalized(dfg, sym)"""
+    return fg.getVariable(label).ismargin
+
+
+def setMarginalized(fg, label, val):
+    """setMarginalized!(dfg, sym, val)"""
+    fg.getVariable(label).ismargin = bool(val)
+
+
+def setfreeze(fg, syms):
+    """setfreeze!(dfg, sym | syms) (FGOSUtils.jl:169-183): the variable is marginalized -- inference no longer updates it.
+    A variable that is not initialised is left alone, with a warning."""
+    for sym in ([syms] if isinstance(syms, str) else list(syms)):
+        if not fg.isInitialized(sym):
+            import warnings
+            warnings.warn(f"Vertex {sym} is not initialized, and won't be frozen at this time.")
+            continue
+        fg.getVariable(sym).ismargin = True
+
+
+def fifoFreeze(fg):
+    """fifoFreeze!(dfg) (FGOSUtils.jl:193-211): freeze what is older than the last `qfl` entries of the add history --
+    history[1:(end - qfl)], less the variables that no longer exist (#966)"""
+    qfl = fg.solverParams.qfl
+    if qfl == 0:
+        import warnings
+        warnings.warn("Quasi fixed-lag is enabled but QFL horizon is zero. Please set a valid window with qfl")
+    tofreeze = [v for v in fg.addHistory[:max(0, len(fg.addHistory) - qfl)] if v in fg.variables]
+    if tofreeze:
+        setfreeze(fg, tofreeze)
+
+
+def dontMarginalizeVariablesAll(fg):
+    """dontMarginalizeVariablesAll!(dfg) (FGOSUtils.jl:320-328): fixed lag off, every variable free again"""
+    sp = fg.solverParams
+    sp.isfixedlag, sp.qfl, sp.limitfixeddown = False, QFL_UNLIMITED, False
+    for sym in fg.ls():
+        setMarginalized(fg, sym, False)
+
+
+def unfreezeVariablesAll(fg):
+    """unfreezeVariablesAll!(dfg) (FGOSUtils.jl:339-341)"""
+    dontMarginalizeVariablesAll(fg)
+
+
+def defaultFixedLagOnTree(fg, len=30, limitfixeddown=True):
+    """defaultFixedLagOnTree!(dfg, len; limitfixeddown) (FGOSUtils.jl:375-385): the defaults of fixed-lag operation on the
+    tree; by default the down solve does not reach the frozen variables either"""
+    sp = fg.solverParams
+    sp.isfixedlag, sp.qfl, sp.limitfixeddown = True, int(len), bool(limitfixeddown)
+    return sp
+
+
 def initfg(solverParams=None):
     return FactorGraph(solverParams)
 
@@ -488,6 +566,7 @@ def addVariable(fg, label, varType, N=None):
     v = DFGVariable(label, varType, False, np.tile(varType.identity(), (N, 1)), np.zeros(varType.dim))
     fg.variables[label] = v
     fg._adj[label] = []
+    fg.addHistory.append(label)
     return v
 
 

@@ -55,6 +55,7 @@ class CliqueDescC(C.Structure):
 
 
 CLIQ_UPSOLVED, CLIQ_DOWNSOLVED = 3, 5  # enum nbp_cliq_status
+CLIQ_NULL, CLIQ_MARGINALIZED, CLIQ_UPRECYCLED = 0, 4, 6
 
 HOST_EXPORTS = ["nbp_graph_create", "nbp_graph_destroy", "nbp_graph_add_variable", "nbp_graph_add_factor",
                 "nbp_graph_set_variable_flags", "nbp_graph_num_variables", "nbp_graph_num_factors",
@@ -65,7 +66,8 @@ HOST_EXPORTS = ["nbp_graph_create", "nbp_graph_destroy", "nbp_graph_add_variable
                 "nbp_clique_submit_batch", "nbp_clique_wait", "nbp_resident_write", "nbp_resident_read", "nbp_resident_copy",
                 "nbp_tree_partition", "nbp_tree_set_owner", "nbp_tree_num_segments", "nbp_tree_segment",
                 "nbp_tree_run_sharded", "nbp_tree_run_sharded_cb",
-                "nbp_graph_num_densities", "nbp_graph_density_factors", "nbp_graph_init_density_slot0", "nbp_tree_density_slot0"]
+                "nbp_graph_num_densities", "nbp_graph_density_factors", "nbp_graph_init_density_slot0", "nbp_tree_density_slot0",
+                "nbp_tree_set_clique_status", "nbp_tree_clique_status", "nbp_tree_recycle", "nbp_tree_cliques_recycled"]
 
 _declared = False
 
@@ -112,6 +114,10 @@ def _lib():
         lib.nbp_tree_segment.argtypes = [vp, i32, ip, ip, ip, ip, ip, C.POINTER(Xfer), C.POINTER(Xfer), i32]
         lib.nbp_tree_run_sharded.argtypes = [vp, vp, vp, vp]
         lib.nbp_tree_run_sharded_cb.argtypes = [vp, vp, XCHG_FN, vp]
+        lib.nbp_tree_set_clique_status.argtypes = [vp, i32, i32]
+        lib.nbp_tree_clique_status.argtypes = [vp, i32, ip, ip, ip]
+        lib.nbp_tree_recycle.argtypes = [vp, vp, i32]
+        lib.nbp_tree_cliques_recycled.argtypes = [vp, ip]
         lib.nbp_clique_slots.argtypes = [C.POINTER(CliqueDescC)]
         for fn in (lib.nbp_clique_upsolve, lib.nbp_clique_downsolve):
             fn.argtypes = [vp, C.POINTER(SolverParamsC), C.POINTER(CliqueDescC), C.c_uint64, C.POINTER(TreeBeliefC), ip]
@@ -491,6 +497,42 @@ class NativeTree:
 
     def density_slot0(self):
         return _check(self.lib.nbp_tree_density_slot0(self._t))
+
+    # -- clique recycling (bayestree.setCliqueRecycling in C++) ----------------------------------
+    def set_clique_status(self, k, status):
+        _check(self.lib.nbp_tree_set_clique_status(self._t, k, status))
+
+    def clique_status(self, k):
+        """-> (status, allmarginalized, isCliqReused) of clique k"""
+        st, am, ru = i32(), i32(), i32()
+        _check(self.lib.nbp_tree_clique_status(self._t, k, C.byref(st), C.byref(am), C.byref(ru)))
+        return st.value, bool(am.value), bool(ru.value)
+
+    def same_ids(self, old):
+        """do the ids of `old`'s graph name the same variables and factors in this tree's graph?  (true when the graph only
+        grew in between: ids are positions in the add order)"""
+        return (self.g.labels[:len(old.g.labels)] == old.g.labels and self.g.flabels[:len(old.g.flabels)] == old.g.flabels)
+
+    def recycle(self, old=None, incremental=True):
+        """nbp_tree_recycle against the NativeTree `old` (None: marginalized cliques only)"""
+        if old is not None and not self.same_ids(old):
+            raise ValueError("the old tree's graph numbers its variables or factors differently")
+        _check(self.lib.nbp_tree_recycle(self._t, old._t if old is not None else None, int(bool(incremental))))
+
+    def cliques_recycled(self):
+        out = (i32 * 4)()
+        _check(self.lib.nbp_tree_cliques_recycled(self._t, out))
+        return tuple(out)
+
+    def push_statuses(self, tree):
+        """the statuses of the Python tree -> this tree (for an old tree whose graph numbered things differently)"""
+        for k, c in tree.cliques.items():
+            if c.status != CLIQ_NULL:
+                self.set_clique_status(k, c.status)
+
+    def pull_statuses(self, tree):
+        for k, c in tree.cliques.items():
+            c.status, c.allmarginalized, c.isCliqReused = self.clique_status(k)
 
     def plan_slots(self, snapshot=False):
         self.n_slots = _check(self.lib.nbp_tree_plan_slots(self._t, int(snapshot)))

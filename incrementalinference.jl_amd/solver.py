@@ -668,6 +668,10 @@ class TreeProgram:
         # doFMCIteration skips marginalized variables (SolveTree.jl:61)
         full = [(v, it) for v, it in bayestree.upGibbsSchedule(cl, sp.gibbsIters, with_iteration=True)
                 if upf[v] and not fg.getVariable(v).ismargin]
+        if cl.status in (bayestree.UPRECYCLED, bayestree.MARGINALIZED):
+            # preUpSolve_StateMachine goes straight to postUpSolve (CliqueStateMachine.jl:309-317): nothing is updated and
+            # prepCliqueMsgUp sends up the separator beliefs the sub graph copy was filled with
+            full = []
         sched = [v for v, _ in full]
         # needFreshMeasurements = iter == 1 || alwaysFreshMeasurements (SolveTree.jl:119)
         self.upfresh[cid] = [it == 1 or sp.alwaysFreshMeasurements for _, it in full]
@@ -686,6 +690,8 @@ class TreeProgram:
             skip = {v for v in cl.frontalIDs if sp.limitfixeddown and fg.getVariable(v).ismargin}
             dsch = ([v for v in cl.frontalIDs if v not in itv and v not in skip and dnf[v]]
                     + [v for v in cl.frontalIDs if v in itv and v not in skip] * 3) if cl.parent >= 0 else []  # MCIters = 3
+        if cl.status == bayestree.MARGINALIZED:  # no down solve either (CliqueStateMachine.jl:708-745); its separator
+            dsch = []                            # values still travel on to the children
         self.dnfacs[cid] = dnf
         self.dnsched[cid] = dsch
         self.uprounds[cid] = self._rounds(sched, upf)
@@ -1049,10 +1055,20 @@ def _initialised_subgraph(fg):
     return sub
 
 
-def solveTree(fg, tree=None, eliminationOrder=None, backend=None, seed=0, ordering="qr", return_timing=False, native=None):
-    """solveTree!(dfg; eliminationOrder) -> tree   (SolverAPI.jl:326-493).
-    graphinit -> buildTreeReset! -> up pass -> down pass -> posteriors written back to `fg`."""
+def solveTree(fg, tree=None, eliminationOrder=None, backend=None, seed=0, ordering="qr", return_timing=False, native=None,
+              oldtree=None):
+    """solveTree!(dfg, oldtree; eliminationOrder) -> tree   (SolverAPI.jl:326-493).
+    fifoFreeze! (fixed lag) -> graphinit -> buildTreeReset! -> clique recycling against `oldtree` -> up pass -> down pass
+    -> posteriors written back to `fg`.  `tree`: use this prebuilt tree.  `oldtree`: the tree an earlier solveTree of the
+    (since grown) graph returned -- its DOWNSOLVED cliques that the new tree has too are not up-solved again
+    (SolverParams.incremental); cliques whose variables are all frozen are left alone whatever `oldtree` is."""
     sp = fg.solverParams
+    if oldtree is not None and getattr(sp, "useMsgLikelihoods", False):
+        raise ValueError("solveTree(oldtree=...) with useMsgLikelihoods: the joint message of a recycled clique has not been made "
+                         "to follow the reference (DESIGN.md 7a); solve without oldtree or without useMsgLikelihoods")
+    if sp.isfixedlag:  # SolverAPI.jl:383-386
+        from .factorgraph import fifoFreeze
+        fifoFreeze(fg)
     t0 = time.perf_counter()
     if sp.graphinit:
         # a backend INSTANCE is sized for the tree solve: graph initialisation makes its own from the same class
@@ -1078,10 +1094,31 @@ def solveTree(fg, tree=None, eliminationOrder=None, backend=None, seed=0, orderi
         from . import native_host
         ng = native_host.NativeGraph.from_fg(fg)
         tp = ng.build_tree(tree.eliminationOrder)
+        # setCliqueRecycling_StateMachine, CliqueStateMachine.jl:110-132, in libnbp: against the native twin of `oldtree` when
+        # its graph numbered the variables and factors as this one does (the graph only grew), from the labels otherwise
+        old = getattr(oldtree, "_native", None)
+        if old is not None and old._t and tp.same_ids(old):
+            tp.recycle(old, sp.incremental)
+        else:
+            bayestree.setCliqueRecycling(fg, tree, oldtree, sp.incremental)
+            tp.push_statuses(tree)
+        tp.pull_statuses(tree)
         tp.plan_slots(False)
         ng.place_densities(fg, tp.density_slot0())
     else:
+        bayestree.setCliqueRecycling(fg, tree, oldtree, sp.incremental)
         tp = TreeProgram(fg, tree, seed=seed)
+    # variables no schedule updates keep the host belief they have, bit for bit (a trip through a slot may re-normalise a
+    # rotation): main[v] is written by v's frontal clique alone -- in the up solve unless the clique is recycled or v
+    # frozen, in the down solve unless the clique is a root or marginalized, or v frozen under limitfixeddown
+    untouched = set()
+    for cl in tree.cliques.values():
+        skip_up = not sp.upsolve or cl.status in (bayestree.UPRECYCLED, bayestree.MARGINALIZED)
+        skip_dn = not sp.downsolve or cl.parent < 0 or cl.status == bayestree.MARGINALIZED
+        for v in cl.frontalIDs:
+            frozen = fg.getVariable(v).ismargin
+            if (skip_up or frozen) and (skip_dn or (frozen and sp.limitfixeddown)):
+                untouched.add(v)
     be, own = _make_backend(backend, sp.N, tp.n_slots)
     try:
         for v in fg.ls():
@@ -1097,8 +1134,9 @@ def solveTree(fg, tree=None, eliminationOrder=None, backend=None, seed=0, orderi
             t4 = time.perf_counter()
             for v in fg.ls():
                 var = fg.getVariable(v)
-                pts, bw, _ = be.belief_read(tp.main[v], var.varType.manifold)
-                setValKDE(fg, v, pts, bw, True)
+                if v not in untouched:
+                    pts, bw, _ = be.belief_read(tp.main[v], var.varType.manifold)
+                    setValKDE(fg, v, pts, bw, True)
                 var.solvedCount += 1
             if getattr(be, "run_ppe", None) is not None:
                 # setPPE! of every solved variable (FactorGraph.jl:200-213): one launch over the beliefs still resident
@@ -1113,6 +1151,10 @@ def solveTree(fg, tree=None, eliminationOrder=None, backend=None, seed=0, orderi
     finally:
         if own:
             be.close()
+    # what the solve leaves behind, for the next solve to recycle (the native host has set the same in nbp_tree_schedule)
+    bayestree.setSolvedStatuses(tree, sp.downsolve)
+    if use_native:
+        tree._native = tp  # kept with its graph: the `old` of nbp_tree_recycle when this tree comes back as `oldtree`
     if return_timing:
         st = tp.stats()
         st.setdefault("cliques", len(tree.cliques))
