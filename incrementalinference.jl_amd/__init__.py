@@ -20,6 +20,7 @@ from .factorgraph import (AliasingScalarSampler, Circular, CircularCircular, Con
                           isPartial, setMarginalized, setfreeze, unfreezeVariablesAll)
 from .ppe import (MeanMaxPPE, calcPPE, getPPE, getPPEMax, getPPEMean, getPPESuggested, getPPESuggestedAll,  # noqa: F401
                   setPPE)
+from .session import SolveSession  # noqa: F401
 from .solver import (TreeProgram, approxConv, approxConvBelief, approxConvBeliefPath, approxDeconv, findShortestPath,  # noqa: F401
                      product_desc, proposal_desc,
                      initAll, initVariable, localProduct, localProductAndUpdate, manikde, propagateBelief,

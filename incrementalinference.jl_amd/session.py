@@ -1,0 +1,294 @@
+"""Solve sessions: one device context that outlives a solve, with the beliefs resident between incremental solves.
+
+`solveTree(fg, oldtree=tree)` makes a context, uploads every belief, runs, reads every updated belief back and tears the
+context down -- and graph initialisation does the same once more in a context of its own.  On the loop a SLAM front end runs
+(solve, add a pose, solve again) that fixed cost is paid for the whole graph at every step.  A `SolveSession` keeps ONE backend
+instance; both schedule compilers put the belief of variable v in slot main[v] = its place in the add order, and main[v] is
+written by v's frontal clique alone, so the posteriors of the last solve lie exactly where the next program reads its inputs.
+What travels is what changed: new variables and host edits go up, the beliefs a program updated come down.  No new kernel: the
+hot path is host traffic that no longer happens."""
+import time
+
+from . import bayestree
+from .ppe import MeanMaxPPE
+from .solver import (TreeProgram, _initialised_subgraph, _make_backend, _refuse_joint_recycling, _runs_on_libnbp,
+                     _untouched_variables, initStages, passthrough_factors, setValKDE, write_densities)
+
+
+class _Resident:
+    """what the device holds in one variable slot: `label`'s belief, equal to the host arrays `val` and `bw` (kept referenced,
+    so that their identity can never be taken by another array) -- or, `pending`, newer than the host copy"""
+    __slots__ = ("label", "val", "bw", "pending")
+
+    def __init__(self, label, val, bw, pending=False):
+        self.label, self.val, self.bw, self.pending = label, val, bw, pending
+
+
+def _density_slots(fg):
+    return {f: fg.getFactor(f).fnc.slot for f in passthrough_factors(fg)}
+
+
+def _place_densities(fg, slots):
+    for f, s in slots.items():
+        fg.getFactor(f).fnc.slot = s
+
+
+class SolveSession:
+    """SolveSession(fg, backend=None, reserve=0): incremental solves of a growing graph in one device context.
+
+    `ses.solve(...)` is `solveTree(fg, oldtree=ses.tree, ...)` in every respect a caller can observe -- fifoFreeze, graph
+    initialisation, tree, clique recycling against the previous tree, up pass, down pass, posteriors, solvedCount, PPE and
+    clique statuses, with the same seeds -- but the beliefs stay on the device between solves.  `backend`: a factory
+    make(N, n_slots, side_ints=0), or None for HipBackend.  `reserve`: slots to start with (the context holds
+    max(reserve, 1.5 x the first solve's need); a solve that needs more replaces it by one of 1.5 x that need and uploads
+    everything again -- the policy looks at slot counts only, so it is the same on every backend).
+
+    Residency.  For every variable slot the session knows whose belief the device holds and which host arrays (`var.val`,
+    `var.bw`, by object identity) it equals.  Before a program runs, whatever is missing, stale or displaced is uploaded in one
+    batch; afterwards only the beliefs the program updated are read back, in one batch, and the arrays that come back are the
+    new tokens.  `setValKDE` / `initVariable` assign fresh arrays, so edits between solves are seen.  An edit IN PLACE
+    (`fg.getVal("x3")[:] = ...`) is not: call `ses.invalidate("x3")`.  Frozen, recycled and otherwise untouched variables are
+    neither uploaded nor read, and keep the `ppe` they have.  The beliefs graph initialisation produces stay on the device for
+    the tree program and reach the host with its results.
+
+    What "the same as solveTree" means.  Euclid(1-3) and Circular: bit-identical to `solveTree(oldtree=...)` with the same
+    seeds (a slot stores these coordinates as the host sees them).  SE(2): a slot stores the heading as theta, the host sees
+    cos and sin, and a write converts back with atan2 -- a belief that stayed resident can differ from its host round trip in
+    the last bit.  There the session is its own definition: bit-identical between the oracle backend and libnbp, held to the
+    reference's bands, not compared bit for bit with `solveTree`.
+
+    When a solve raises, the residency table is cleared (the host copy wins at the next solve), variables graph initialisation
+    had reached in that solve but whose beliefs never came back are uninitialised again, and the context stays usable.
+
+    `ses.tree`: the tree of the last solve (None before the first).  `ses.stats`: uploads, readbacks (beliefs, cumulative),
+    contexts, resyncs (table cleared: growth or renumbering), solves, slots (the last solve's need), capacity, and under
+    "last" the uploads, readbacks and resyncs of the last solve."""
+
+    def __init__(self, fg, backend=None, reserve=0):
+        if backend is not None and hasattr(backend, "slot_write"):
+            raise TypeError("SolveSession takes a backend factory (or None), not an instance: it sizes the context itself")
+        self.fg, self.backend, self.reserve = fg, backend, int(reserve)
+        self.tree = None
+        self._be = None
+        self._closed = False
+        self._table = {}    # variable slot -> _Resident
+        self._labels = []   # the labels of the subgraph the last solve worked on, in slot order
+        self.stats = {"uploads": 0, "readbacks": 0, "contexts": 0, "resyncs": 0, "solves": 0, "slots": 0, "capacity": 0,
+                      "last": {"uploads": 0, "readbacks": 0, "resyncs": 0}}
+
+    # ---- life cycle ---------------------------------------------------------------------------------------------------
+    def close(self):
+        """closes the context (programs go before it); harmless when repeated"""
+        self._closed = True
+        self._table.clear()
+        be, self._be = self._be, None
+        if be is not None:
+            be.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def invalidate(self, *labels):
+        """the host copy of these variables (no labels: of all) wins at the next solve; their stored PPE goes too"""
+        if not labels:
+            self._table.clear()
+        for s in [s for s, e in self._table.items() if e.label in labels]:
+            del self._table[s]
+        for v in (labels or self.fg.ls()):
+            if v in self.fg.variables:
+                self.fg.getVariable(v).ppe = None
+
+    # ---- the context and the table --------------------------------------------------------------------------------------
+    def _resync(self):
+        self._table.clear()
+        self.stats["resyncs"] += 1
+        self.stats["last"]["resyncs"] += 1
+
+    def _ensure_capacity(self, needed):
+        st, N = self.stats, self.fg.solverParams.N
+        if self._be is not None and needed <= st["capacity"] and self._be.N == N:
+            return
+        grown = self._be is not None
+        if grown:
+            self._be.close()
+            self._be = None
+            self._resync()
+        cap = needed + needed // 2 if grown else max(self.reserve, needed + needed // 2)
+        self._be, _ = _make_backend(self.backend, N, cap)
+        st["capacity"] = cap
+        st["contexts"] += 1
+
+    def _upload(self, graph, expected, V):
+        """make the device hold what a program with `V` variable slots expects: expected = [(label, slot)]"""
+        for s in [s for s in self._table if s >= V]:  # scratch of this program
+            del self._table[s]
+        todo = []
+        for label, slot in expected:
+            var, e = graph.getVariable(label), self._table.get(slot)
+            if e is not None and e.label == label and (e.pending or (e.val is var.val and e.bw is var.bw)):
+                continue
+            todo.append((label, slot, var))
+        if not todo:
+            return
+        be = self._be
+        mans = [var.varType.manifold for _, _, var in todo]
+        if getattr(be, "beliefs_write", None) is not None:
+            be.beliefs_write([s for _, s, _ in todo], mans, [(var.val, var.bw, None) for _, _, var in todo])
+        else:
+            for (_, slot, var), man in zip(todo, mans):
+                be.belief_write(slot, man, var.val, var.bw)
+        for label, slot, var in todo:
+            self._table[slot] = _Resident(label, var.val, var.bw)
+        self.stats["uploads"] += len(todo)
+        self.stats["last"]["uploads"] += len(todo)
+
+    def _readback(self, graph, wanted):
+        """the beliefs of wanted = [(label, slot)] -> the host graph (setValKDE); the new arrays become the table's tokens"""
+        if not wanted:
+            return
+        be = self._be
+        mans = [graph.getVariable(v).varType.manifold for v, _ in wanted]
+        if getattr(be, "beliefs_read", None) is not None:
+            got = be.beliefs_read([s for _, s in wanted], mans)
+        else:
+            got = [be.belief_read(s, m) for (_, s), m in zip(wanted, mans)]
+        for (v, slot), (pts, bw, _) in zip(wanted, got):
+            setValKDE(graph, v, pts, bw, True)
+            var = graph.getVariable(v)
+            self._table[slot] = _Resident(v, var.val, var.bw)
+        self.stats["readbacks"] += len(wanted)
+        self.stats["last"]["readbacks"] += len(wanted)
+
+    # ---- one solve ---------------------------------------------------------------------------------------------------------
+    def solve(self, seed=0, eliminationOrder=None, ordering="qr", return_timing=False):
+        """solveTree(fg, oldtree=ses.tree, ...) in the session's context -> tree (or (tree, timing) with return_timing: the
+        keys of solveTree's, plus upload_s and readback_s)"""
+        if self._closed:
+            raise RuntimeError("this SolveSession is closed")
+        whole, sp = self.fg, self.fg.solverParams
+        _refuse_joint_recycling(sp, self.tree)
+        if sp.isfixedlag:  # SolverAPI.jl:383-386
+            from .factorgraph import fifoFreeze
+            fifoFreeze(whole)
+        self.stats["last"] = {"uploads": 0, "readbacks": 0, "resyncs": 0}
+        T = dict.fromkeys(("init_s", "tree_s", "compile_s", "upload_s", "solve_s", "readback_s"), 0.0)
+        clock = time.perf_counter
+        pending = []  # initialised by this solve's init program, belief not on the host yet
+        try:
+            # -- plans first, on the host: the context is sized for both programs before either runs ------------------
+            t = clock()
+            plan, islot, n_init, istages = initStages(whole, seed) if sp.graphinit else ([], {}, 0, [])
+            init_dens = _density_slots(whole)
+            for sym, _, _ in plan:
+                whole.getVariable(sym).initialized = True
+                pending.append(sym)
+            T["init_s"] += clock() - t
+            t = clock()
+            fg = _initialised_subgraph(whole)
+            if fg is not whole and eliminationOrder is not None:
+                eliminationOrder = [v for v in eliminationOrder if v in fg.variables]
+            tree = bayestree.buildTreeReset(fg, eliminationOrder, ordering)
+            T["tree_s"] += clock() - t
+            t = clock()
+            use_native = _runs_on_libnbp(self.backend)
+            if use_native:
+                from . import native_host
+                ng = native_host.NativeGraph.from_fg(fg)
+                tp = ng.build_tree(tree.eliminationOrder)
+                old = getattr(self.tree, "_native", None)
+                if old is not None and old._t and tp.same_ids(old):
+                    tp.recycle(old, sp.incremental)
+                else:
+                    bayestree.setCliqueRecycling(fg, tree, self.tree, sp.incremental)
+                    tp.push_statuses(tree)
+                tp.pull_statuses(tree)
+                tp.plan_slots(False)
+                ng.place_densities(fg, tp.density_slot0())
+            else:
+                bayestree.setCliqueRecycling(fg, tree, self.tree, sp.incremental)
+                tp = TreeProgram(fg, tree, seed=seed)
+            tree_dens = _density_slots(fg)
+            untouched = _untouched_variables(fg, tree)
+            labels = fg.ls()
+            needed = max(n_init if plan else 0, tp.n_slots)
+            self.stats["slots"] = needed
+            self._ensure_capacity(needed)
+            if labels[:len(self._labels)] != self._labels and self._table:  # renumbered: nothing lies where it is expected
+                self._resync()
+            self._labels = labels
+            be = self._be
+            T["compile_s"] += clock() - t
+            # -- graph initialisation, in this context ---------------------------------------------------------------------
+            if plan:
+                t = clock()
+                _place_densities(whole, init_dens)
+                self._upload(whole, [(v, islot[v]) for v in whole.ls()], len(whole.ls()))
+                write_densities(whole, be)
+                prog = None
+                try:
+                    prog = be.program(istages)
+                    prog.run()
+                    be.synchronize()
+                finally:  # the program goes before its context, on the error path too
+                    if prog is not None:
+                        prog.close()
+                for sym in pending:
+                    self._table[islot[sym]] = _Resident(sym, None, None, pending=True)
+                T["init_s"] += clock() - t
+            # -- the tree program ------------------------------------------------------------------------------------------
+            t = clock()
+            _place_densities(fg, tree_dens)
+            moved = [v for v in pending if tp.main[v] != islot[v]]  # (init numbers the whole graph, the tree its subgraph)
+            self._readback(whole, [(v, islot[v]) for v in moved])
+            pending = [v for v in pending if v not in moved]
+            T["readback_s"] += clock() - t
+            t = clock()
+            self._upload(fg, [(v, tp.main[v]) for v in labels], len(labels))
+            write_densities(fg, be)
+            T["upload_s"] += clock() - t
+            prog = None
+            try:
+                t = clock()
+                prog = tp.compile(be, seed) if use_native else be.program(tp.stages, lazy_bandwidth=True)
+                T["compile_s"] += clock() - t
+                t = clock()
+                prog.run()
+                be.synchronize()
+                T["solve_s"] += clock() - t
+                t = clock()
+                self._readback(fg, [(v, tp.main[v]) for v in labels if v not in untouched or v in pending])
+                pending = []
+                for v in labels:
+                    fg.getVariable(v).solvedCount += 1
+                if getattr(be, "run_ppe", None) is not None:
+                    # setPPE! (FactorGraph.jl:200-213) of the beliefs that changed, in one launch over the resident beliefs
+                    stale = [v for v in labels if fg.getVariable(v).ppe is None]
+                    if stale:
+                        dims = [fg.getVariable(v).varType.dim for v in stale]
+                        mean, mx, idx = be.run_ppe([tp.main[v] for v in stale], [fg.getVariable(v).varType.manifold for v in stale])
+                        for i, v in enumerate(stale):
+                            fg.getVariable(v).ppe = MeanMaxPPE(mean[i, :dims[i]].copy(), mx[i, :dims[i]].copy(),
+                                                               mean[i, :dims[i]].copy(), int(idx[i]))
+                T["readback_s"] += clock() - t
+            finally:
+                if prog is not None:
+                    prog.close()
+        except BaseException:
+            self._table.clear()  # the device state is unknown: the host copy wins
+            for sym in pending:
+                whole.getVariable(sym).initialized = False
+            raise
+        bayestree.setSolvedStatuses(tree, sp.downsolve)
+        if use_native:
+            tree._native = tp
+        self.tree = tree
+        self.stats["solves"] += 1
+        if return_timing:
+            st = tp.stats()
+            st.setdefault("cliques", len(tree.cliques))
+            return tree, {**T, **st}
+        return tree

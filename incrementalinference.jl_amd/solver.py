@@ -1055,6 +1055,34 @@ def _initialised_subgraph(fg):
     return sub
 
 
+def _refuse_joint_recycling(sp, oldtree):
+    if oldtree is not None and getattr(sp, "useMsgLikelihoods", False):
+        raise ValueError("solveTree(oldtree=...) with useMsgLikelihoods: the joint message of a recycled clique has not been made "
+                         "to follow the reference (DESIGN.md 7a); solve without oldtree or without useMsgLikelihoods")
+
+
+def _runs_on_libnbp(backend):
+    """does a solve on `backend` (class, factory or instance) run on libnbp, with the schedule compiled by the native host?"""
+    return backend is None or backend is HipBackend or isinstance(backend, HipBackend) or getattr(backend, "is_hip", False)
+
+
+def _untouched_variables(fg, tree):
+    """The variables no schedule of `tree` (statuses set) updates.  They keep the host belief they have, bit for bit (a trip
+    through a slot may re-normalise a rotation): main[v] is written by v's frontal clique alone -- in the up solve unless the
+    clique is recycled or v frozen, in the down solve unless the clique is a root or marginalized, or v frozen under
+    limitfixeddown"""
+    sp = fg.solverParams
+    untouched = set()
+    for cl in tree.cliques.values():
+        skip_up = not sp.upsolve or cl.status in (bayestree.UPRECYCLED, bayestree.MARGINALIZED)
+        skip_dn = not sp.downsolve or cl.parent < 0 or cl.status == bayestree.MARGINALIZED
+        for v in cl.frontalIDs:
+            frozen = fg.getVariable(v).ismargin
+            if (skip_up or frozen) and (skip_dn or (frozen and sp.limitfixeddown)):
+                untouched.add(v)
+    return untouched
+
+
 def solveTree(fg, tree=None, eliminationOrder=None, backend=None, seed=0, ordering="qr", return_timing=False, native=None,
               oldtree=None):
     """solveTree!(dfg, oldtree; eliminationOrder) -> tree   (SolverAPI.jl:326-493).
@@ -1063,9 +1091,7 @@ def solveTree(fg, tree=None, eliminationOrder=None, backend=None, seed=0, orderi
     (since grown) graph returned -- its DOWNSOLVED cliques that the new tree has too are not up-solved again
     (SolverParams.incremental); cliques whose variables are all frozen are left alone whatever `oldtree` is."""
     sp = fg.solverParams
-    if oldtree is not None and getattr(sp, "useMsgLikelihoods", False):
-        raise ValueError("solveTree(oldtree=...) with useMsgLikelihoods: the joint message of a recycled clique has not been made "
-                         "to follow the reference (DESIGN.md 7a); solve without oldtree or without useMsgLikelihoods")
+    _refuse_joint_recycling(sp, oldtree)
     if sp.isfixedlag:  # SolverAPI.jl:383-386
         from .factorgraph import fifoFreeze
         fifoFreeze(fg)
@@ -1088,8 +1114,7 @@ def solveTree(fg, tree=None, eliminationOrder=None, backend=None, seed=0, orderi
     t2 = time.perf_counter()
     # the schedule is compiled by the native host (nbp_host.h) when the solve runs on libnbp, by the
     # Python mirror otherwise (oracle backend in the tests); both produce the same descriptors
-    use_native = native if native is not None else (backend is None or backend is HipBackend or isinstance(backend, HipBackend)
-                                                    or getattr(backend, "is_hip", False))
+    use_native = native if native is not None else _runs_on_libnbp(backend)
     if use_native:
         from . import native_host
         ng = native_host.NativeGraph.from_fg(fg)
@@ -1108,17 +1133,7 @@ def solveTree(fg, tree=None, eliminationOrder=None, backend=None, seed=0, orderi
     else:
         bayestree.setCliqueRecycling(fg, tree, oldtree, sp.incremental)
         tp = TreeProgram(fg, tree, seed=seed)
-    # variables no schedule updates keep the host belief they have, bit for bit (a trip through a slot may re-normalise a
-    # rotation): main[v] is written by v's frontal clique alone -- in the up solve unless the clique is recycled or v
-    # frozen, in the down solve unless the clique is a root or marginalized, or v frozen under limitfixeddown
-    untouched = set()
-    for cl in tree.cliques.values():
-        skip_up = not sp.upsolve or cl.status in (bayestree.UPRECYCLED, bayestree.MARGINALIZED)
-        skip_dn = not sp.downsolve or cl.parent < 0 or cl.status == bayestree.MARGINALIZED
-        for v in cl.frontalIDs:
-            frozen = fg.getVariable(v).ismargin
-            if (skip_up or frozen) and (skip_dn or (frozen and sp.limitfixeddown)):
-                untouched.add(v)
+    untouched = _untouched_variables(fg, tree)
     be, own = _make_backend(backend, sp.N, tp.n_slots)
     try:
         for v in fg.ls():
