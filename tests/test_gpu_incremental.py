@@ -70,6 +70,24 @@ def test_chain24_grown_by_four_poses(oracle_backend, hip_backend):
     assert getattr(trees[1], "_native", None) is not None  # recycled by nbp_tree_recycle against the old native tree
 
 
+def test_basic_incremental_recycle_native_host_equals_oracle_mirror(oracle_backend, hip_backend):
+    """testBasicRecycling.jl:141-169: a prior on lm3 changes the potentials of one clique, every other clique is recycled"""
+    solve = both_solvers(oracle_backend, hip_backend, 20)
+    (fa, order), (fb, _) = cases.recycle_graph(), cases.recycle_graph()
+    trees = solve((fa, fb), eliminationOrder=order)
+    cases.assert_ppe_band(fb, "first")
+    assert iif.calcCliquesRecycled(trees[1]) == (len(trees[1].cliques), 0, 0, 0)
+    for fg in (fa, fb):
+        iif.addFactor(fg, ["lm3"], iif.Prior(iif.Normal(3.0, 0.1)))
+    trees = solve((fa, fb), eliminationOrder=order, oldtree=trees)
+    cases.assert_ppe_band(fb, "second")
+    n = len(trees[1].cliques)
+    assert iif.calcCliquesRecycled(trees[1]) == (n, 0, n - 1, 0)
+    changed = trees[1].frontals["lm3"]  # its potentials gained the prior: not similar any more
+    assert [k for k, c in trees[1].cliques.items() if not c.isCliqReused] == [changed]
+    assert [(k, c.isCliqReused) for k, c in trees[0].cliques.items()] == [(k, c.isCliqReused) for k, c in trees[1].cliques.items()]
+
+
 def test_se2_chain_with_fixed_lag(oracle_backend, hip_backend):
     solve = both_solvers(oracle_backend, hip_backend, 400)
     fgs = (cases.se2_chain(12), cases.se2_chain(12))
