@@ -313,6 +313,31 @@ nbp_status nbp_run_mmd(nbp_ctx *ctx, const int32_t *slots_a, const int32_t *slot
 /* host-buffer form: stages through slots 0 and 1 */
 nbp_status nbp_kde_mmd(nbp_ctx *ctx, int32_t manifold, const double *a_NxP, int32_t na, const double *b_NxP, int32_t nb,
                        double sigma, double *mmd_out);
+/* ---- belief statistics ("Belief statistics") ----------------------------------------------------------------------
+ * calcMeanCovar (VariableStatistics.jl:39-44; Statistics.cov(vartype, pts), VariableStatistics.jl:12-19) for beliefs resident in
+ * slots.  mean = the mean nbp_run_ppe delivers, bit for bit; cov[d][e] = 1/(c-1) sum_i delta[i][d] delta[i][e] with
+ * delta[i][d] = x[i][d] - mean[d], wrapped to [-pi, pi) on circular coordinates; c = the count the slot holds.  Tangent coordinates
+ * (SE(2): x, y, theta: deviations in the world frame about the mean -- DEFINED here, unpinned against Manifolds.jl: DESIGN.md 8).
+ * cov is NBP_MAXD x NBP_MAXD per belief, row-major, symmetric bit for bit, rows and columns beyond the manifold's dimension zero;
+ * c < 2: the D x D block is NaN, the mean stands.  The bandwidth plays no part.  Queued on the library stream behind whatever runs
+ * there; one copy back; synchronises. */
+nbp_status nbp_run_meancov(nbp_ctx *ctx, const int32_t *slots, const int32_t *manifolds, int32_t n,
+                           double *mean_out /* n x NBP_MAXD */, double *cov_out /* n x NBP_MAXD x NBP_MAXD */);
+/* host-buffer form, like nbp_kde_ppe: stages through slot 0 */
+nbp_status nbp_kde_meancov(nbp_ctx *ctx, int32_t manifold, const double *pts_NxP, int32_t n_pts, double *mean_out_D,
+                           double *cov_out_DxD);
+/* kld(p, q) (attic/examples/FixedPointIllustrationsSquare.jl:53-62) of pairs of resident beliefs a (n points, bandwidth h_a) and
+ * b (m points, h_b) on one manifold: kld = Eaa - Eab, Eaa = 1/n sum_i l_a(a_i) (the self term stays in), Eab = 1/n sum_i l_b(a_i),
+ * l_p(x) = the logarithm of the density nbp_run_evaluate defines, formed as M + log(sum_j exp(e_j - M)) - log(m prod_d sqrt(2 pi) h_d)
+ * with e_j = -1/2 sum_d (delta_d(x, y_j) / h_d)^2 and M = max_j e_j, so that it is finite where the density underflows.  One
+ * function and one summation order behind both terms: a belief against a bit-identical copy (or slots_a[i] == slots_b[i]) gives
+ * exactly 0.0.  No clamp at zero; entropy(a) = -Eaa.  A bandwidth entry of either belief that is not positive and finite: kld and
+ * both terms are NaN.  DEFINED by this library, unpinned against KernelDensityEstimate.jl. */
+nbp_status nbp_run_kld(nbp_ctx *ctx, const int32_t *slots_a, const int32_t *slots_b, const int32_t *manifolds, int32_t n,
+                       double *kld_out /* n */, double *terms_out /* n x 2: Eaa, Eab; nullable */);
+/* host-buffer form: stages through slots 0 and 1 */
+nbp_status nbp_kde_kld(nbp_ctx *ctx, int32_t manifold, const double *a_NxP, int32_t na, const double *bw_a_D, const double *b_NxP,
+                       int32_t nb, const double *bw_b_D, double *kld_out, double *terms_out_2 /* nullable */);
 /* ---- variable seam: AMP.manifoldProduct + rebandwidth (GraphProductOperations.jl:53-60) --- */
 nbp_status nbp_run_products(nbp_ctx *ctx, const nbp_product_desc *descs, int32_t n);
 /* ---- host-buffer entry points: one call per reference function ----------------------------------

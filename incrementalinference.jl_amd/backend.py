@@ -251,6 +251,52 @@ class HipBackend:
                                          float(sigma), C.byref(out)))
         return out.value
 
+    def run_meancov(self, slots, manifolds):
+        """calcMeanCovar of resident beliefs (nbp_run_meancov) -> (mean[n, 3], cov[n, 3, 3]), tangent coordinates, entries beyond
+        the manifold's dimension zero; the mean is run_ppe's, bit for bit"""
+        s = np.ascontiguousarray(slots, dtype=np.int32)
+        m = np.ascontiguousarray(manifolds, dtype=np.int32)
+        n = s.size
+        mean, cov = np.zeros((n, abi.MAXD)), np.zeros((n, abi.MAXD, abi.MAXD))
+        ip, dp = C.POINTER(C.c_int32), C.POINTER(C.c_double)
+        self._check(self.lib.nbp_run_meancov(self._ctx, s.ctypes.data_as(ip), m.ctypes.data_as(ip), n, mean.ctypes.data_as(dp),
+                                             cov.ctypes.data_as(dp)))
+        return mean, cov
+
+    def kde_meancov(self, manifold, pts):
+        """calcMeanCovar of a belief held on the host (nbp_kde_meancov; clobbers slot 0) -> (mean[D], cov[D, D])"""
+        dp = C.POINTER(C.c_double)
+        pts = np.ascontiguousarray(pts, dtype=np.float64).reshape(-1, abi.MANIFOLD_P[manifold])
+        D = abi.MANIFOLD_DIM[manifold]
+        mean, cov = np.zeros(D), np.zeros((D, D))
+        self._check(self.lib.nbp_kde_meancov(self._ctx, manifold, pts.ctypes.data_as(dp), pts.shape[0], mean.ctypes.data_as(dp),
+                                             cov.ctypes.data_as(dp)))
+        return mean, cov
+
+    def run_kld(self, slots_a, slots_b, manifolds, terms=False):
+        """kld of pairs of resident beliefs (nbp_run_kld) -> values[n], from one launch; terms=True: (values[n], terms[n, 2]) with
+        terms = (Eaa, Eab), values = Eaa - Eab, entropy(a) = -Eaa"""
+        a = np.ascontiguousarray(slots_a, dtype=np.int32)
+        b = np.ascontiguousarray(slots_b, dtype=np.int32)
+        m = np.ascontiguousarray(manifolds, dtype=np.int32)
+        out, tm = np.zeros(a.size), np.zeros((a.size, 2))
+        ip, dp = C.POINTER(C.c_int32), C.POINTER(C.c_double)
+        self._check(self.lib.nbp_run_kld(self._ctx, a.ctypes.data_as(ip), b.ctypes.data_as(ip), m.ctypes.data_as(ip), a.size,
+                                         out.ctypes.data_as(dp), tm.ctypes.data_as(dp) if terms else None))
+        return (out, tm) if terms else out
+
+    def kde_kld(self, manifold, a, bw_a, b, bw_b, terms=False):
+        """kld of two beliefs held on the host (nbp_kde_kld; clobbers slots 0 and 1) -> value, or (value, (Eaa, Eab))"""
+        dp = C.POINTER(C.c_double)
+        a = np.ascontiguousarray(a, dtype=np.float64).reshape(-1, abi.MANIFOLD_P[manifold])
+        b = np.ascontiguousarray(b, dtype=np.float64).reshape(-1, abi.MANIFOLD_P[manifold])
+        bw_a, bw_b = np.ascontiguousarray(bw_a, dtype=np.float64), np.ascontiguousarray(bw_b, dtype=np.float64)
+        out, tm = C.c_double(0.0), np.zeros(2)
+        self._check(self.lib.nbp_kde_kld(self._ctx, manifold, a.ctypes.data_as(dp), a.shape[0], bw_a.ctypes.data_as(dp),
+                                         b.ctypes.data_as(dp), b.shape[0], bw_b.ctypes.data_as(dp), C.byref(out),
+                                         tm.ctypes.data_as(dp) if terms else None))
+        return (out.value, tm) if terms else out.value
+
     def conv(self, desc, var_pts, var_bw=None, mhidx_in=None, want_mhidx=False, want_bw=True):
         dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
         man = desc.manifold

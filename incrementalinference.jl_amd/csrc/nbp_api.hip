@@ -22,6 +22,7 @@
 #include "nbp_fused.h"
 #include "nbp_ppe.h"
 #include "nbp_query.h"
+#include "nbp_stats.h"
 
 static thread_local std::string g_err;
 static nbp_status fail(nbp_status code, const std::string &msg) {
@@ -100,7 +101,8 @@ struct nbp_ctx {
   // point estimates (nbp_run_ppe): one record per belief of the batch, grown on demand
   nbp_ppe_rec *ppe = nullptr;
   size_t ppe_cap = 0;
-  // belief queries (nbp_run_evaluate / nbp_run_mmd): the queries going in and the values coming out, grown on demand
+  // belief queries and statistics (nbp_run_evaluate / nbp_run_mmd / nbp_run_meancov / nbp_run_kld): the queries going in and the
+  // values coming out, grown on demand
   double *query = nullptr;
   size_t query_cap = 0;
   // pinned host staging of the batched belief transfers (nbp_belief_write_batch / _read_batch): one copy per run of
@@ -1692,6 +1694,110 @@ nbp_status nbp_kde_mmd(nbp_ctx *c, int32_t manifold, const double *a, int32_t na
   if (rc) return rc;
   const int32_t sa = 0, sb = 1;
   return nbp_run_mmd(c, &sa, &sb, &manifold, 1, sigma, mmd_out);
+}
+
+// calcMeanCovar (VariableStatistics.jl:39-44) of resident beliefs: one workgroup per belief (nbp_stats.h), one copy back
+nbp_status nbp_run_meancov(nbp_ctx *c, const int32_t *slots, const int32_t *manifolds, int32_t n, double *mean_out, double *cov_out) {
+  if (!c || ((!slots || !manifolds || !mean_out || !cov_out) && n > 0)) return fail(NBP_ERR_ARG, "null argument");
+  if (n <= 0) return NBP_OK;
+  HIPCHK(hipSetDevice(c->device));
+  for (int i = 0; i < n; i++) {
+    if (slots[i] < 0 || slots[i] >= c->n_slots) return fail(NBP_ERR_RANGE, "meancov: slot out of range");
+    if (!manifold_ok(manifolds[i])) return fail(NBP_ERR_ARG, "meancov: unknown manifold");
+  }
+  std::vector<int32_t> both(slots, slots + n);
+  both.insert(both.end(), manifolds, manifolds + n);
+  nbp_status rc = stage_upload(c, both.data(), both.size() * 4);  // (waits for the stream: the query buffer is free as well)
+  if (rc) return rc;
+  static_assert(sizeof(nbp_meancov_rec) == sizeof(double) * (NBP_MAXD + NBP_MAXD * NBP_MAXD), "nbp_meancov_rec is packed doubles");
+  rc = query_reserve(c, (size_t)n * (sizeof(nbp_meancov_rec) / sizeof(double)));
+  if (rc) return rc;
+  const int32_t *ds = (const int32_t *)c->stage;
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(nbp_meancov_kernel, dim3(n), dim3(c->Npad), nbp_meancov_lds_bytes(c->N), c->stream, ds, ds + n, c->arena, c->N, c->S,
+                     (nbp_meancov_rec *)c->query);
+  HIPCHK(hipGetLastError());
+  std::vector<nbp_meancov_rec> rec((size_t)n);
+  HIPCHK(hipMemcpyAsync(rec.data(), c->query, sizeof(nbp_meancov_rec) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  for (int i = 0; i < n; i++) {
+    memcpy(mean_out + (size_t)i * NBP_MAXD, rec[i].mean, sizeof(rec[i].mean));
+    memcpy(cov_out + (size_t)i * NBP_MAXD * NBP_MAXD, rec[i].cov, sizeof(rec[i].cov));
+  }
+  return NBP_OK;
+}
+
+// host-buffer form: stages through slot 0 (which it clobbers), like nbp_kde_ppe.  The bandwidth plays no part; the slot carries ones.
+nbp_status nbp_kde_meancov(nbp_ctx *c, int32_t manifold, const double *pts, int32_t n_pts, double *mean_out, double *cov_out) {
+  if (!c || !pts || !mean_out || !cov_out) return fail(NBP_ERR_ARG, "null argument");
+  if (!manifold_ok(manifold)) return fail(NBP_ERR_ARG, "meancov: unknown manifold");
+  if (n_pts < 1) return fail(NBP_ERR_ARG, "meancov: a belief holds at least one point");
+  const double ones[NBP_MAXD] = {1.0, 1.0, 1.0};
+  nbp_status rc = nbp_belief_write(c, 0, manifold, pts, n_pts, ones, nullptr);
+  if (rc) return rc;
+  const int32_t slot = 0;
+  double mean3[NBP_MAXD], cov9[NBP_MAXD * NBP_MAXD];
+  rc = nbp_run_meancov(c, &slot, &manifold, 1, mean3, cov9);
+  if (rc) return rc;
+  const int D = manifold_dim_h(manifold);
+  for (int k = 0; k < D; k++) {
+    mean_out[k] = mean3[k];
+    for (int e = 0; e < D; e++) cov_out[k * D + e] = cov9[k * NBP_MAXD + e];
+  }
+  return NBP_OK;
+}
+
+// kld(p, q) (attic/examples/FixedPointIllustrationsSquare.jl:53-62) for pairs of beliefs resident in slots: one workgroup per pair
+// (nbp_stats.h), one copy back
+nbp_status nbp_run_kld(nbp_ctx *c, const int32_t *slots_a, const int32_t *slots_b, const int32_t *manifolds, int32_t n, double *kld_out,
+                       double *terms_out) {
+  if (!c || ((!slots_a || !slots_b || !manifolds || !kld_out) && n > 0)) return fail(NBP_ERR_ARG, "null argument");
+  if (n <= 0) return NBP_OK;
+  HIPCHK(hipSetDevice(c->device));
+  for (int i = 0; i < n; i++) {
+    if (slots_a[i] < 0 || slots_a[i] >= c->n_slots || slots_b[i] < 0 || slots_b[i] >= c->n_slots)
+      return fail(NBP_ERR_RANGE, "kld: slot out of range");
+    if (!manifold_ok(manifolds[i])) return fail(NBP_ERR_ARG, "kld: unknown manifold");
+  }
+  std::vector<int32_t> ints(slots_a, slots_a + n);
+  ints.insert(ints.end(), slots_b, slots_b + n);
+  ints.insert(ints.end(), manifolds, manifolds + n);
+  nbp_status rc = stage_upload(c, ints.data(), ints.size() * 4);  // (waits for the stream: the query buffer is free as well)
+  if (rc) return rc;
+  static_assert(sizeof(nbp_kld_rec) == sizeof(double) * 3, "nbp_kld_rec is packed doubles");
+  rc = query_reserve(c, (size_t)n * 3);
+  if (rc) return rc;
+  const int32_t *ds = (const int32_t *)c->stage;
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(nbp_kld_kernel, dim3(n), dim3(c->Npad), nbp_kld_lds_bytes(c->N), c->stream, ds, ds + n, ds + 2 * n, c->arena, c->N,
+                     c->S, (nbp_kld_rec *)c->query);
+  HIPCHK(hipGetLastError());
+  std::vector<nbp_kld_rec> rec((size_t)n);
+  HIPCHK(hipMemcpyAsync(rec.data(), c->query, sizeof(nbp_kld_rec) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  for (int i = 0; i < n; i++) {
+    kld_out[i] = rec[i].kld;
+    if (terms_out) {
+      terms_out[2 * (size_t)i] = rec[i].eaa;
+      terms_out[2 * (size_t)i + 1] = rec[i].eab;
+    }
+  }
+  return NBP_OK;
+}
+
+// host-buffer form: stages through slots 0 and 1 (which it clobbers)
+nbp_status nbp_kde_kld(nbp_ctx *c, int32_t manifold, const double *a, int32_t na, const double *bw_a, const double *b, int32_t nb,
+                       const double *bw_b, double *kld_out, double *terms_out) {
+  if (!c || !a || !bw_a || !b || !bw_b || !kld_out) return fail(NBP_ERR_ARG, "null argument");
+  if (!manifold_ok(manifold)) return fail(NBP_ERR_ARG, "kld: unknown manifold");
+  if (na < 1 || nb < 1) return fail(NBP_ERR_ARG, "kld: a belief holds at least one point");
+  if (c->n_slots < 2) return fail(NBP_ERR_RANGE, "kld: the context needs two slots");
+  nbp_status rc = nbp_belief_write(c, 0, manifold, a, na, bw_a, nullptr);
+  if (rc) return rc;
+  rc = nbp_belief_write(c, 1, manifold, b, nb, bw_b, nullptr);
+  if (rc) return rc;
+  const int32_t sa = 0, sb = 1;
+  return nbp_run_kld(c, &sa, &sb, &manifold, 1, kld_out, terms_out);
 }
 
 nbp_status nbp_run_resample(nbp_ctx *c, const int32_t *slots, const int32_t *manifolds, int32_t n, uint64_t seed) {

@@ -163,6 +163,40 @@ class SolveSession:
         self.stats["readbacks"] += len(wanted)
         self.stats["last"]["readbacks"] += len(wanted)
 
+    # ---- statistics of the resident beliefs ------------------------------------------------------------------------------
+    def calcMeanCovar(self, labels=None):
+        """calcMeanCovar (VariableStatistics.jl:39-44) of the variables' current beliefs -> {label: (mu[D], Sigma[D, D])}; labels:
+        default every variable the last solve worked on.  On libnbp the beliefs the residency table holds as current are read
+        where they lie, in ONE launch (`run_meancov`): no belief travels and `stats` does not move.  A belief that is not
+        resident (edited on the host since, or invalidated) goes up first by the session's upload path and is counted as an
+        upload.  A variable that has no slot in the session's context (never part of a solve), or a backend without
+        `run_meancov`: `beliefstats.calcMeanCovar` on the host copy."""
+        from . import beliefstats
+        if self._closed:
+            raise RuntimeError("this SolveSession is closed")
+        labels = list(self._labels if labels is None else labels)
+        be = self._be
+        place = {v: i for i, v in enumerate(self._labels)}
+        out = {}
+        if be is None or getattr(be, "run_meancov", None) is None:
+            return {v: beliefstats.calcMeanCovar(self.fg, v) for v in labels}
+        here = [v for v in labels if v in place]
+        if here:
+            try:
+                self._upload(self.fg, [(v, place[v]) for v in here], len(self._labels))
+                mans = [self.fg.getVariable(v).varType.manifold for v in here]
+                mean, cov = be.run_meancov([place[v] for v in here], mans)
+            except BaseException:
+                self._table.clear()  # the device state is unknown: the host copy wins
+                raise
+            for i, v in enumerate(here):
+                D = self.fg.getVariable(v).varType.dim
+                out[v] = (mean[i, :D].copy(), cov[i, :D, :D].copy())
+        for v in labels:
+            if v not in place:
+                out[v] = beliefstats.calcMeanCovar(self.fg, v, backend=self.backend)
+        return {v: out[v] for v in labels}
+
     # ---- one solve ---------------------------------------------------------------------------------------------------------
     def solve(self, seed=0, eliminationOrder=None, ordering="qr", return_timing=False):
         """solveTree(fg, oldtree=ses.tree, ...) in the session's context -> tree (or (tree, timing) with return_timing: the
