@@ -408,7 +408,8 @@ nbp_status nbp_program_add_stage(nbp_program *prog, int32_t kind, const void *de
  * trees, the product and the fit of the result in one workgroup per variable, with nothing but the operand beliefs and
  * the new belief touching HBM -- when the round has at least NBP_FUSED_MIN updates (environment, read at nbp_ctx_create;
  * unset = never: the fused form trades time for traffic) and its factors are of a class the kernel is built
- * for; same particles and bandwidths as the three-launch form up to the rounding of sums taken in another order.
+ * for (the list stands above fused_plan, csrc/nbp_api.hip); the same particles, bandwidths and infoPerCoord as the three-launch
+ * form, bit for bit (one summation order in every geometry; tests/test_gpu_fused_update.py holds both forms to the oracle).
  * A stage range of nbp_program_run that ends between the two stages of a fused pair runs the pair in the three-launch form
  * (the proposals to their arena slots, their fits at the end of the range); a range that starts at the second stage of such a pair
  * fits every proposal of the pair again before the products (redundant after the previous range's end-of-range fits, never wrong). */

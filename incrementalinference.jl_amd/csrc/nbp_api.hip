@@ -2067,7 +2067,14 @@ static nbp_liveness product_liveness(const nbp_program *p) {
 //     exactly one product (the proposals never reach HBM; one that a later stage reads from its slot is written there too);
 //   * no proposal reads a slot another update of the round writes (the three-launch form runs all proposals before any
 //     product; fused, the updates of a round run in any order) -- rounds of commuting Gibbs steps satisfy this by construction;
-//   * class: LinearRelative / priors / message priors on Euclid(2), full (non-partial) densities, no label output.
+//   * class (proposals_uniform_class = NBP_CLS_LIN2, simple or not): Euclid(2) throughout; full (non-partial) LinearRelative,
+//     Prior, MsgPrior and pass-through proposals, with nullhypo, multihypo (nvars > 2), mixtures, injected / recorded
+//     hypothesis indices, stored measurements (meas_seed), a KDE as the measurement (meas_kde), either solve direction,
+//     operands of fewer than N points; 1 .. NBP_FUSED_MAXF inputs per product; skip_bandwidth only on the lone proposal of
+//     a pass-through product; a pass-through among several inputs, or alone with keep_count = 0;
+//   * refused: another manifold, partial proposals, relatives of another kind; products with label output, an old_slot
+//     (hence partial inputs), more than NBP_FUSED_MAXF inputs; Npad > 256; an LDS need above 158 KiB (nbp_program_finalize).
+//   The same bits as the three-launch form either way (tests/fused_cases.py keeps one round per entry of both lists).
 static bool fused_plan(const nbp_program *p, int s, std::vector<nbp_update_desc> &upd, int &Fmax) {
   const nbp_ctx *c = p->ctx;
   if (!c->fused_on || !p->use_fused || s + 1 >= p->n_user_stages || c->Npad > 256) return false;

@@ -10,9 +10,11 @@
 // (read once, coalesced) and the new belief (written once) touches memory: the algorithmic bytes of SURVEY 8(d).  The
 // phases are the SAME device functions the three kernels run (proposal_body, lcv_slot_coordinate, kd_build,
 // product_body), with the same random streams, in the one-lane-per-particle geometry (workgroup = Npad lanes): the
-// particles and bandwidths are those of the three-launch form at its throughput geometry, bit for bit
-// (tests/test_gpu_fused_update.py).  Used for the stages that fill the chip (nbp_api.hip: fused_plan); the launches that
-// cannot fill it keep the three-launch form, whose latency geometries spread ONE update over many CUs.
+// particles, bandwidths and infoPerCoord are those of the three-launch form in any of its geometries and of the oracle, bit
+// for bit (include/nbp.h, NBP_OPT_FUSED_UPDATES; tests/test_gpu_fused_update.py: every N from 8 to 256, F = 1 .. 4, both
+// instances below, every class of proposal fused_plan admits).  Used for the
+// stages that fill the chip (nbp_api.hip: fused_plan); the launches that cannot fill it keep the three-launch form, whose
+// latency geometries spread ONE update over many CUs.
 //
 // LDS of a workgroup (Fmax = largest F of the launch, SL = 3N + 8 doubles = one slot):
 //   tab[256] | slot[Fmax][SL] | bw[Fmax][3] | cen[Fmax][3] | transient area
@@ -137,16 +139,25 @@ __device__ __forceinline__ void update_body(const nbp_update_desc *uds, const nb
       }
     }
     if ((flags >> (1 + j)) & 1) {  // somebody reads this proposal from its arena slot later
+      // (a proposal nothing fitted -- skip_bandwidth, or a lone one whose fit nobody wants -- holds no bandwidth here: its
+      //  arena slot keeps the one it has, as the proposal kernel leaves it)
+      const bool has_bw = fit || pd->factor_kind == NBP_F_PASSTHROUGH;
       double *o = arena + S * pd->out_slot;
-      for (int i = tid; i < (int)SL; i += blockDim.x) o[i] = FL.slot[j * SL + i];
+      for (int i = tid; i < (int)SL; i += blockDim.x)
+        if (has_bw || i < 3 * N || i >= 3 * N + 3) o[i] = FL.slot[j * SL + i];
     }
   }
   NBP_TICK(51);  // fits of the proposals
   double *out = arena + S * d->out_slot;
   if (F == 1) {
     // a single density: AMP returns it (product_passthrough): points, bandwidth, count; infoPerCoord = ones(D)
+    // (an unfitted proposal's bandwidth is the one its arena slot holds: what the pass-through product of the three-launch
+    //  form hands on)
     const double *src = FL.slot;
-    for (int i = tid; i < 3 * N + 3; i += blockDim.x) out[i] = src[i];
+    const nbp_proposal_desc *pd = props + u->prop[0];
+    const bool has_bw = pd->factor_kind == NBP_F_PASSTHROUGH || (!pd->skip_bandwidth && (flags & NBP_UPD_FIT_OUT));
+    const double *bwsrc = has_bw ? src : arena + S * pd->out_slot;
+    for (int i = tid; i < 3 * N + 3; i += blockDim.x) out[i] = i < 3 * N ? src[i] : bwsrc[i];
     if (tid < 3) out[3 * N + 3 + tid] = (tid < D) ? 1.0 : 0.0;
     if (tid == 0) out[3 * N + 6] = src[3 * N + 6];
     return;

@@ -1,15 +1,21 @@
 """-m gpu: the fused variable-update kernel (csrc/nbp_fused.h: proposals, their bandwidth fits, KD trees, product and the
-fit of the result in one workgroup per variable) against the three-launch form of the same round (proposal kernel ->
-prep kernel -> product kernel).  Both run the same device functions with the same random streams; they differ in the
-launch geometry (one lane per particle throughout vs. the geometries the host picks per launch), i.e. in the order of
-floating-point sums -- the comparison is the one `test_batch_size_does_not_change_results` makes between geometries:
-points, bandwidths, infoPerCoord to 1e-9, and the oracle for the fused round itself."""
+fit of the result in one workgroup per variable) against the oracle and against the three-launch form of the same round
+(proposal kernel -> prep kernel -> product kernel).  All three run the same operations with the same random streams and
+one summation order (round 6), so the comparison is `np.array_equal` -- no tolerance -- on the points, the bandwidth and
+infoPerCoord of every output slot and of every proposal slot the program leaves written, and on the counters between the
+two device forms.  The cases are those of tests/fused_cases.py (its docstring lists what the planner accepts and what it
+refuses); tests/test_fused_cases.py runs them on the oracle alone.
+
+Sizes: every (N, F) of fused_cases.SIZES x SIZE_F lies under the LDS ceiling of nbp_program_finalize (158 KiB; N = 256
+with F = 4 needs 111 232 bytes) and must fuse -- none falls back; N = 257 and N = 512 (Npad > 256) are refused."""
 import os
 
 import numpy as np
 import pytest
 
-from parity_utils import abi, assert_points_close, iif, product_desc, rand_points, relative_factor_desc
+import fused_cases as fc
+from fused_cases import legacy_round as _round  # (test_gpu_product_first_label.py imports it from here)
+from parity_utils import abi, assert_points_close, iif, rand_points
 
 pytestmark = pytest.mark.gpu
 
@@ -29,23 +35,6 @@ def fused_min():
         os.environ.pop("NBP_FUSED_MIN", None)
     else:
         os.environ["NBP_FUSED_MIN"] = old
-
-
-def _round(nops, F):
-    """nops updates, each the product of F proposals on its own target: relatives from slot 0 / 1 and a prior"""
-    props, prods = [], []
-    stride = F + 1
-    for i in range(nops):
-        o = 4 + stride * i
-        ins = []
-        for j in range(F):
-            if j == F - 1 and F > 1:  # the last input of every product with several inputs is a prior
-                props.append(relative_factor_desc(abi.F_PRIOR, MAN, 1, 0, [2], o + j, 900 + 7 * i + j, [1.0, 1.0], [0.3, 0.3]))
-            else:
-                props.append(relative_factor_desc(abi.F_LINREL, MAN, 2, 1, [j % 2, 2], o + j, 900 + 7 * i + j, [1.0 - j, 1.0 - j], [0.1, 0.1]))
-            ins.append(o + j)
-        prods.append(product_desc(MAN, ins, o + F, 5000 + i))
-    return props, prods, stride
 
 
 def _run_round(hip_backend, nops, F, fused, lazy=False, read=(0, -1)):
@@ -179,26 +168,174 @@ def test_a_range_that_splits_a_fused_pair_runs_it_in_three_launches(hip_backend,
         assert np.all(a[1] > 0)
 
 
-def test_whole_solve_with_fused_rounds(hip_backend, fused_min):
-    """a chain solved with every round of >= 16 updates fused against the same solve in the three-launch form: same
-    random streams, geometry-level rounding differences only -- most variables stay particle-identical, all stay at the
-    truth"""
-    fused_min(16)
+def test_whole_solve_with_fused_rounds(oracle_backend, hip_backend, monkeypatch):
+    """a chain solved with every round of >= 16 updates fused, the same solve in the three-launch form and the oracle's solve
+    of the same graph and seed: every variable particle-identical among the three (and at the truth)"""
+    monkeypatch.setenv("NBP_FUSED_MIN", "16")
+    fused_rounds = []
+    close = iif.backend.HipProgram.close
 
-    def solve(fused):
+    def counting_close(prog):
+        if prog._p:
+            fused_rounds.append(prog.num_fused())
+        close(prog)
+
+    monkeypatch.setattr(iif.backend.HipProgram, "close", counting_close)
+
+    def solve(backend, fused=True):
         if not fused:
-            os.environ["NBP_NO_FUSED_UPDATE"] = "1"
+            monkeypatch.setenv("NBP_NO_FUSED_UPDATE", "1")
         try:
-            fg = iif.generateChainEuclid(160, vardims=2, priorEvery=20, N=100)
-            iif.solveTree(fg, eliminationOrder=iif.nestedDissectionOrder(fg), backend=hip_backend, seed=3)
+            fg, order = fc.chain_graph()
+            iif.solveTree(fg, eliminationOrder=order, backend=backend, seed=3)
         finally:
-            os.environ.pop("NBP_NO_FUSED_UPDATE", None)
-        return {v: fg.getVal(v) for v in fg.ls()}
+            monkeypatch.delenv("NBP_NO_FUSED_UPDATE", raising=False)
+        return {v: (fg.getVal(v), fg.getVariable(v).bw) for v in fg.ls()}
 
-    a, b = solve(True), solve(False)
-    same = 0
+    a = solve(hip_backend)  # (a solve closes two programs: graph initialisation, then the tree)
+    nfused = sum(fused_rounds)
+    assert nfused >= 1, fused_rounds
+    del fused_rounds[:]
+    b = solve(hip_backend, fused=False)
+    assert fused_rounds and sum(fused_rounds) == 0, fused_rounds
+    o = solve(oracle_backend)
+    print(f"whole solve: {nfused} fused rounds")
     for i, v in enumerate(sorted(a, key=lambda s: int(s[1:]))):
-        assert np.abs(a[v].mean(axis=0) - i).max() < 0.6, (v, a[v].mean(axis=0))
-        same += np.allclose(a[v], b[v], rtol=0, atol=0)
-    print(f"fused vs three-launch solve: {same} of {len(a)} variables particle-identical")
-    assert same >= len(a) // 2
+        assert np.abs(a[v][0].mean(axis=0) - i).max() < 0.6, (v, a[v][0].mean(axis=0))
+        for other, what in ((b, "three-launch solve"), (o, "oracle's solve")):
+            assert np.array_equal(a[v][0], other[v][0]), f"{v}: points differ from the {what}"
+            assert np.array_equal(a[v][1], other[v][1]), f"{v}: bandwidth differs from the {what}"
+
+
+# ---- the cases of fused_cases.py: fused form == three-launch form == oracle --------------------------------------------------
+def _set_form(monkeypatch, form):
+    monkeypatch.setenv("NBP_FUSED_MIN", "16")  # (read when the context is created)
+    if form == "p1":
+        monkeypatch.setenv("NBP_FUSED_P1_MIN", "1")  # one lane per particle, the form of rounds that fill the chip
+
+
+@pytest.fixture(scope="module")
+def refs(oracle_backend, hip_backend):
+    """case -> (the oracle's result, the three-launch form's): computed once per case and shared by the two forms of the
+    kernel (fused_updates = False: neither depends on NBP_FUSED_MIN / NBP_FUSED_P1_MIN)"""
+    done = {}
+
+    def get(case):
+        if case.name not in done:
+            done[case.name] = (case.run(oracle_backend), case.run(hip_backend, fused=False))
+        return done[case.name]
+
+    return get
+
+
+def _same(case, got, ref, what, lazy=False):
+    for k, ((p, bw, ipc), (q, bw2, ipc2)) in enumerate(zip(got["out"], ref["out"])):
+        assert np.array_equal(p, q), f"{case.name}: output {k}: points differ from {what}"
+        assert np.array_equal(bw, bw2), f"{case.name}: output {k}: bandwidth differs from {what}"
+        assert np.array_equal(ipc, ipc2), f"{case.name}: output {k}: infoPerCoord differs from {what}"
+    # the proposals are still in their slots when the program ends: written there by either form.  (A lone proposal's fit
+    # travels with the pass-through product, a proposal nothing reads is not fitted under lazy_bandwidth: no bandwidth then)
+    for k, ((p, bw, ipc), (q, bw2, ipc2)) in enumerate(zip(got["prop"], ref["prop"])):
+        assert np.array_equal(p, q), f"{case.name}: proposal {k}: points differ from {what}"
+        assert np.array_equal(ipc, ipc2), f"{case.name}: proposal {k}: infoPerCoord differs from {what}"
+        if case.F > 1 and not lazy:
+            assert np.array_equal(bw, bw2), f"{case.name}: proposal {k}: bandwidth differs from {what}"
+    assert np.array_equal(got["side"], ref["side"]), f"{case.name}: recorded hypotheses / labels differ from {what}"
+
+
+def _check(case, want_fused, refs, hip_backend):
+    orc, three = refs(case)
+    got = case.run(hip_backend)
+    assert three["nf"] == 0
+    assert got["nf"] == want_fused, f"{case.name}: {got['nf']} fused rounds, expected {want_fused}"
+    _same(case, three, orc, "the oracle (three-launch form)", case.lazy)
+    _same(case, got, orc, "the oracle", case.lazy)
+    _same(case, got, three, "the three-launch form", case.lazy)
+    for k in ("solves", "nonconverged", "nan_results", "residual_evals"):
+        assert got["diag"][k] == three["diag"][k], k
+    return got
+
+
+@pytest.mark.parametrize("form", ["p2", "p1"])
+@pytest.mark.parametrize("F", fc.SIZE_F)
+@pytest.mark.parametrize("N", fc.SIZES)
+def test_every_size_equals_the_oracle(N, F, form, refs, hip_backend, monkeypatch):
+    """the library's minimum N, every Npad with and without idle lanes, the ceiling N = 256: the round fuses wherever
+    nbp_update_lds_bytes admits it -- at every one of these sizes, none falls back -- and gives the oracle's bits"""
+    _set_form(monkeypatch, form)
+    admitted = fc.admits(N, F)
+    print(f"N = {N}, F = {F}: {fc.lds_bytes(max(F, 2), 2, N, fc.npad(N), 2)} bytes of LDS, {'fused' if admitted else 'falls back to three launches'}")
+    _check(fc.size_case(N, F), 1 if admitted else 0, refs, hip_backend)
+
+
+@pytest.mark.parametrize("F", fc.SIZE_F)
+@pytest.mark.parametrize("N", fc.SIZES_REFUSED)
+def test_more_than_256_particles_keep_the_three_launch_form(N, F, refs, hip_backend, monkeypatch):
+    _set_form(monkeypatch, "p2")
+    assert not fc.admits(N, F)
+    _check(fc.size_case(N, F), 0, refs, hip_backend)
+
+
+@pytest.mark.parametrize("form", ["p2", "p1"])
+@pytest.mark.parametrize("F", [2, 3])
+@pytest.mark.parametrize("N", fc.CLASS_N)
+@pytest.mark.parametrize("feature", list(fc.ACCEPTED))
+def test_every_accepted_input_class_equals_the_oracle(feature, N, F, form, refs, hip_backend, monkeypatch):
+    """one round per descriptor feature that proposals_uniform_class / fused_plan keep fused (fused_cases.ACCEPTED)"""
+    _set_form(monkeypatch, form)
+    _check(fc.accepted_case(feature, N, F), 1, refs, hip_backend)
+
+
+@pytest.mark.parametrize("form", ["p2", "p1"])
+@pytest.mark.parametrize("N", fc.CLASS_N)
+@pytest.mark.parametrize("feature", list(fc.ACCEPTED_F1))
+def test_single_density_updates_equal_the_oracle(feature, N, form, refs, hip_backend, monkeypatch):
+    """F = 1, the early return of the kernel: count and bandwidth handed on, infoPerCoord = ones -- skip_bandwidth, a
+    MsgPrior, a nullhypo prior, a mixture, a lone pass-through (full, or resampled to N)"""
+    _set_form(monkeypatch, form)
+    got = _check(fc.accepted_f1_case(feature, N), 1, refs, hip_backend)
+    assert all(np.array_equal(ipc, [1.0, 1.0]) for _, _, ipc in got["out"])
+
+
+@pytest.mark.parametrize("N", fc.CLASS_N)
+@pytest.mark.parametrize("feature", list(fc.REFUSED))
+def test_every_refused_input_class_keeps_the_three_launch_form(feature, N, refs, hip_backend, monkeypatch):
+    """one round per feature fused_plan refuses (fused_cases.REFUSED): no fused round, the oracle's bits all the same"""
+    _set_form(monkeypatch, "p2")
+    _check(fc.refused_case(feature, N), 0, refs, hip_backend)
+
+
+@pytest.mark.parametrize("form", ["p2", "p1"])
+@pytest.mark.parametrize("cnt", fc.BELOW)
+def test_operands_with_fewer_than_n_points(cnt, form, refs, hip_backend, monkeypatch):
+    """the relative's other variable and the MsgPrior's KDE hold 1, 2, 63, 150 of N = 200 points: `anyn_index` and the KDE
+    draw read the operand from the arena while the proposal goes to LDS"""
+    _set_form(monkeypatch, form)
+    _check(fc.below_case(cnt), 1, refs, hip_backend)
+
+
+@pytest.mark.parametrize("form", ["p2", "p1"])
+@pytest.mark.parametrize("F", [1, 2])
+def test_lazy_bandwidth_skips_the_fit_of_overwritten_outputs(F, form, refs, hip_backend, monkeypatch):
+    """two fused pairs, the second overwriting the outputs of the first, under lazy_bandwidth: the first outputs' fit (for
+    F = 1 the proposal's fit) is not made -- fewer likelihood evaluations than the eager program -- and the final beliefs
+    are the oracle's"""
+    _set_form(monkeypatch, form)
+    case = fc.lazy_case(F)
+    got = _check(case, 2, refs, hip_backend)
+    eager = case.run(hip_backend, lazy=False)
+    assert eager["nf"] == 2
+    _same(case, eager, got, "the lazy program", lazy=True)
+    assert got["diag"]["lcv_evals"] < eager["diag"]["lcv_evals"]
+
+
+@pytest.mark.parametrize("form", ["p2", "p1"])
+def test_several_write_back_flags_in_one_launch(form, refs, hip_backend, monkeypatch):
+    """F = 4; a STAGE_COPIES behind the round reads inputs 0, 2 and 3 of three different updates, the last of the launch
+    among them, and every proposal slot is overwritten afterwards, so that the launch carries exactly those three
+    write-back flags: the copies equal the three-launch form's and the oracle's"""
+    _set_form(monkeypatch, form)
+    case = fc.copies_case()
+    got = _check(case, 1, refs, hip_backend)
+    for pts, bw, _ in got["out"][case.nops:]:
+        assert np.abs(pts).max() > 0 and (bw > 0).all()
