@@ -303,6 +303,48 @@ nbp_status nbp_run_evaluate(nbp_ctx *ctx, const int32_t *slots, const int32_t *m
 /* host-buffer form: stages through slot 0 */
 nbp_status nbp_kde_evaluate(nbp_ctx *ctx, int32_t manifold, const double *pts_NxP, int32_t n_pts, const double *bw_D,
                             const double *queries /* nq x NBP_MAXD */, int32_t nq, double *dens_out);
+/* ---- marginal densities ("Marginal densities"; DEFINED by this library, unpinned: DESIGN.md 8) -----------------------
+ * For a coordinate set K of the manifold (at least one coordinate; 0-based here, where the reference's `partial` is 1-based):
+ * p_K(q) = 1 / (c prod_{d in K} sqrt(2 pi) bw_d) sum_{j<c} exp(-1/2 sum_{d in K} (delta_d(q, x_j) / bw_d)^2), the density above with
+ * the coordinates outside K dropped.  Only the bandwidth entries in K must be positive and finite (else every value is NaN); the
+ * others are not read, so the belief a lone partial factor leaves (bandwidth h0, h1, 0 on SE(2)) has a marginal on (0, 1).
+ *
+ * A grid descriptor asks for p_K of one resident belief on a regular grid: |K| = 1 (dims[1] = -1) or 2, n[a] points on axis a
+ * (1 .. NBP_GRID_MAX), point k of axis a at lo[a] + (double)k * step[a].  The output is row-major with the FIRST listed coordinate
+ * slowest; dims = {b, a} is the transpose of dims = {a, b} bit for bit.  The value is (sum_j E_0[k0][j] E_1[k1][j]) / norm with
+ * E_a[k][j] = exp(-1/2 (delta(g_a[k], x_j) / bw_a)^2), j = 0 .. c-1 in that order in one lane: it depends on the belief and its grid
+ * point alone.  flags & NBP_GRID_AUTO_EXTENT: lo and step are not read; a Euclidean axis spans min_j x - margin bw .. max_j x +
+ * margin bw (step = (hi - lo) / (n - 1), n >= 2), a circular axis lo = -pi, step = 2 pi / n (margin plays no part there).
+ * Fields that a 1-D grid or an automatic extent does not use are not read. */
+#define NBP_GRID_MAX 1024
+#define NBP_GRID_AUTO_EXTENT 1
+typedef struct nbp_grid_desc {
+  int32_t slot;
+  int32_t manifold;
+  int32_t dims[2];
+  int32_t n[2];
+  int32_t flags;
+  double lo[2];
+  double step[2];
+  double margin;
+} nbp_grid_desc;
+/* Grids of any number of resident beliefs (the same slot may appear in several descriptors) in one launch sequence with one copy
+ * back (a second, of 32 bytes a descriptor, where extent_out is given): descriptor i fills out[first[i] .. first[i+1]-1], first[0] = 0 and first[i+1] - first[i] = the points of grid i.  extent_out
+ * (nullable): the extent used, lo0, step0, lo1, step1 per descriptor (a 1-D grid: lo1 = step1 = 0).  NBP_ERR_RANGE, with the
+ * descriptor's index in the message and before anything is launched, for: a slot or a coordinate outside the context / manifold, a
+ * repeated coordinate, n outside 1 .. NBP_GRID_MAX, n < 2 on a Euclidean axis with automatic extent, a non-finite lo / step (explicit
+ * extent) or margin (automatic extent), offsets that do not match the grid sizes.  Queued on the library stream; synchronises. */
+nbp_status nbp_run_marginal_grid(nbp_ctx *ctx, const nbp_grid_desc *descs, int32_t n_desc, const int32_t *first /* n_desc+1 */,
+                                 double *out /* first[n_desc] */, double *extent_out /* n_desc x 4, nullable */);
+/* host-buffer form: stages through slot 0; desc->slot and desc->manifold are not read */
+nbp_status nbp_kde_marginal_grid(nbp_ctx *ctx, int32_t manifold, const double *pts_NxP, int32_t n_pts, const double *bw_D,
+                                 const nbp_grid_desc *desc, double *out, double *extent_out_4 /* nullable */);
+/* p_K at arbitrary query points: nbp_run_evaluate with one coordinate bit mask per belief (bit d = coordinate d; a non-empty subset
+ * of the manifold's coordinates, else NBP_ERR_RANGE naming the belief).  Queries are NBP_MAXD doubles each; entries outside the
+ * mask are not read.  With the full mask the values are those of nbp_run_evaluate bit for bit. */
+nbp_status nbp_run_evaluate_marginal(nbp_ctx *ctx, const int32_t *slots, const int32_t *manifolds, const int32_t *masks, int32_t n,
+                                     const int32_t *q_first /* n+1, ascending, q_first[0]=0 */,
+                                     const double *queries /* q_first[n] x NBP_MAXD */, double *dens_out /* q_first[n] */);
 /* mmd(p1, p2, varType; bw = [sigma]) (SolverUtilities.jl:25-47) of pairs of resident beliefs a (n points), b (m points) on one
  * manifold: k(p, q) = exp(-sigma d(p, q)^2), d^2 = sum_d delta_d^2 in tangent coordinates (circular ones wrapped; the heading of
  * SE(2) with weight 1), S_xy = sum_i sum_j k(x_i, y_j), mmd = Saa/(n n) + Sbb/(m m) - 2 Sab/(n m), evaluated as written with one

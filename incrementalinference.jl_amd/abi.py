@@ -67,6 +67,23 @@ class CopyDesc(C.Structure):
     _fields_ = [("src_slot", C.c_int32), ("dst_slot", C.c_int32)]
 
 
+class GridDesc(C.Structure):
+    """nbp_grid_desc: one marginal grid of one resident belief (coordinates 0-based; dims[1] = -1: a 1-D grid)"""
+    _fields_ = [
+        ("slot", C.c_int32),
+        ("manifold", C.c_int32),
+        ("dims", C.c_int32 * 2),
+        ("n", C.c_int32 * 2),
+        ("flags", C.c_int32),
+        ("lo", C.c_double * 2),
+        ("step", C.c_double * 2),
+        ("margin", C.c_double),
+    ]
+
+
+GRID_MAX, GRID_AUTO_EXTENT = 1024, 1
+
+
 class Xfer(C.Structure):
     _fields_ = [("peer", C.c_int32), ("slot", C.c_int32)]
 
@@ -99,7 +116,7 @@ EXPORTS = [
     "nbp_ctx_reserve_resident", "nbp_ctx_resident", "nbp_belief_write_batch_async", "nbp_belief_read_batch_begin", "nbp_belief_read_batch_end",
     "nbp_run_copies_async", "nbp_program_retire",
     "nbp_slot_write", "nbp_slot_read", "nbp_belief_write", "nbp_belief_read", "nbp_belief_write_batch", "nbp_belief_read_batch", "nbp_run_resample", "nbp_side_write", "nbp_side_read",
-    "nbp_run_proposals", "nbp_run_bandwidth", "nbp_run_ppe", "nbp_kde_ppe", "nbp_run_evaluate", "nbp_kde_evaluate", "nbp_run_mmd", "nbp_kde_mmd", "nbp_run_meancov", "nbp_kde_meancov", "nbp_run_kld", "nbp_kde_kld", "nbp_run_products", "nbp_run_copies", "nbp_run_deconv", "nbp_kde_bandwidth", "nbp_conv", "nbp_manifold_product",
+    "nbp_run_proposals", "nbp_run_bandwidth", "nbp_run_ppe", "nbp_kde_ppe", "nbp_run_evaluate", "nbp_kde_evaluate", "nbp_run_marginal_grid", "nbp_kde_marginal_grid", "nbp_run_evaluate_marginal", "nbp_run_mmd", "nbp_kde_mmd", "nbp_run_meancov", "nbp_kde_meancov", "nbp_run_kld", "nbp_kde_kld", "nbp_run_products", "nbp_run_copies", "nbp_run_deconv", "nbp_kde_bandwidth", "nbp_conv", "nbp_manifold_product",
     "nbp_program_create", "nbp_program_add_stage", "nbp_program_set_option", "nbp_program_finalize", "nbp_program_run",
     "nbp_program_reseed", "nbp_program_num_seeds", "nbp_program_set_seeds", "nbp_program_seed_order", "nbp_ctx_attach", "nbp_ctx_attached", "nbp_program_num_stages", "nbp_program_num_fused", "nbp_program_num_two_stream", "nbp_program_destroy",
     "nbp_timing_enable", "nbp_timing_read", "nbp_timing_read_n", "nbp_diag_read",
@@ -163,6 +180,9 @@ def load_library(path=None):
     lib.nbp_kde_ppe.argtypes = [vp, i32, dp, i32, dp, dp, dp, ip]
     lib.nbp_run_evaluate.argtypes = [vp, ip, ip, i32, ip, dp, dp]
     lib.nbp_kde_evaluate.argtypes = [vp, i32, dp, i32, dp, dp, i32, dp]
+    lib.nbp_run_marginal_grid.argtypes = [vp, C.POINTER(GridDesc), i32, ip, dp, dp]
+    lib.nbp_kde_marginal_grid.argtypes = [vp, i32, dp, i32, dp, C.POINTER(GridDesc), dp, dp]
+    lib.nbp_run_evaluate_marginal.argtypes = [vp, ip, ip, ip, i32, ip, dp, dp]
     lib.nbp_run_mmd.argtypes = [vp, ip, ip, ip, i32, C.c_double, dp]
     lib.nbp_kde_mmd.argtypes = [vp, i32, dp, i32, dp, i32, C.c_double, dp]
     lib.nbp_run_meancov.argtypes = [vp, ip, ip, i32, dp, dp]

@@ -230,6 +230,82 @@ class HipBackend:
                                               Q.ctypes.data_as(dp), q.shape[0], out.ctypes.data_as(dp)))
         return out
 
+    @staticmethod
+    def _grid_desc(slot, manifold, dims, n, extent=None, margin=4.0):
+        """one nbp_grid_desc: dims / n scalars or sequences of one or two (0-based coordinates); extent = ((lo0, step0), (lo1,
+        step1)) or (lo0, step0, lo1, step1) or, 1-D, (lo0, step0); None: the automatic extent with `margin`"""
+        dims, n = np.atleast_1d(dims).astype(int).tolist(), np.atleast_1d(n).astype(int).tolist()
+        if len(dims) not in (1, 2) or len(n) != len(dims):
+            raise ValueError("a marginal grid has one or two coordinates and as many sizes")
+        g = abi.GridDesc(slot=int(slot), manifold=int(manifold), margin=float(margin))
+        g.dims[0], g.dims[1] = dims[0], dims[1] if len(dims) > 1 else -1
+        g.n[0], g.n[1] = n[0], n[1] if len(n) > 1 else 1
+        if extent is None:
+            g.flags = abi.GRID_AUTO_EXTENT
+        else:
+            e = np.asarray(extent, dtype=np.float64).reshape(-1)
+            if e.size != 2 * len(dims):
+                raise ValueError("an extent is (lo, step) per axis")
+            for a in range(len(dims)):
+                g.lo[a], g.step[a] = e[2 * a], e[2 * a + 1]
+        return g
+
+    def run_marginal_grid(self, grids, return_extent=False):
+        """marginal densities of resident beliefs on regular grids (nbp_run_marginal_grid), all in one call: grids = [(slot,
+        manifold, dims, n[, extent[, margin]])] as `_grid_desc` takes them, or ready `abi.GridDesc`s -> one array per grid of shape
+        (n0,) or (n0, n1), the first listed coordinate slowest; return_extent: also [(lo0, step0, lo1, step1)] as used"""
+        descs = [g if isinstance(g, abi.GridDesc) else self._grid_desc(*g) for g in grids]
+        nd = len(descs)
+        arr = (abi.GridDesc * max(nd, 1))(*descs)
+        shapes = [(g.n[0],) if g.dims[1] == -1 else (g.n[0], g.n[1]) for g in descs]
+        first = np.zeros(nd + 1, dtype=np.int64)
+        for i, sh in enumerate(shapes):
+            first[i + 1] = first[i] + max(int(np.prod(sh)), 0)
+        first = first.astype(np.int32)
+        out, ext = np.zeros(int(first[-1])), np.zeros((nd, 4))
+        ip, dp = C.POINTER(C.c_int32), C.POINTER(C.c_double)
+        self._check(self.lib.nbp_run_marginal_grid(self._ctx, arr, nd, first.ctypes.data_as(ip), out.ctypes.data_as(dp),
+                                                   ext.ctypes.data_as(dp)))
+        res = [out[first[i]:first[i + 1]].reshape(sh) for i, sh in enumerate(shapes)]
+        return (res, ext) if return_extent else res
+
+    def kde_marginal_grid(self, manifold, pts, bw, dims, n, extent=None, margin=4.0):
+        """the marginal grid of a belief held on the host (nbp_kde_marginal_grid; clobbers slot 0) -> (grid, (lo0, step0, lo1,
+        step1)); dims 0-based"""
+        dp = C.POINTER(C.c_double)
+        pts = np.ascontiguousarray(pts, dtype=np.float64).reshape(-1, abi.MANIFOLD_P[manifold])
+        bw = np.ascontiguousarray(bw, dtype=np.float64)
+        g = self._grid_desc(0, manifold, dims, n, extent, margin)
+        shape = (g.n[0],) if g.dims[1] == -1 else (g.n[0], g.n[1])
+        out, ext = np.zeros(max(int(np.prod(shape)), 0)), np.zeros(4)
+        self._check(self.lib.nbp_kde_marginal_grid(self._ctx, manifold, pts.ctypes.data_as(dp), pts.shape[0], bw.ctypes.data_as(dp),
+                                                   C.byref(g), out.ctypes.data_as(dp), ext.ctypes.data_as(dp)))
+        return out.reshape(shape), ext
+
+    def run_evaluate_marginal(self, slots, manifolds, masks, queries):
+        """marginal densities of resident beliefs at query points (nbp_run_evaluate_marginal): masks = one coordinate bit mask
+        per belief (bit d = coordinate d); queries as in run_evaluate (q_i x D or x 3; entries outside the mask are not read)"""
+        s = np.ascontiguousarray(slots, dtype=np.int32)
+        m = np.ascontiguousarray(manifolds, dtype=np.int32)
+        k = np.ascontiguousarray(masks, dtype=np.int32)
+        n = s.size
+        first = np.zeros(n + 1, dtype=np.int32)
+        rows = []
+        for i in range(n):
+            D = abi.MANIFOLD_DIM.get(int(m[i]), abi.MAXD)  # (an unknown manifold is the library's to refuse)
+            q = np.asarray(queries[i], dtype=np.float64)
+            q = q.reshape(-1, q.shape[-1] if q.ndim > 1 else D)
+            pad = np.zeros((q.shape[0], abi.MAXD))
+            pad[:, :min(D, q.shape[1])] = q[:, :D]
+            rows.append(pad)
+            first[i + 1] = first[i] + q.shape[0]
+        Q = np.ascontiguousarray(np.concatenate(rows)) if rows else np.zeros((0, abi.MAXD))
+        out = np.zeros(int(first[-1]))
+        ip, dp = C.POINTER(C.c_int32), C.POINTER(C.c_double)
+        self._check(self.lib.nbp_run_evaluate_marginal(self._ctx, s.ctypes.data_as(ip), m.ctypes.data_as(ip), k.ctypes.data_as(ip), n,
+                                                       first.ctypes.data_as(ip), Q.ctypes.data_as(dp), out.ctypes.data_as(dp)))
+        return [out[first[i]:first[i + 1]] for i in range(n)]
+
     def run_mmd(self, slots_a, slots_b, manifolds, sigma=0.001):
         """mmd of pairs of resident beliefs (nbp_run_mmd) -> values[n], from one launch"""
         a = np.ascontiguousarray(slots_a, dtype=np.int32)

@@ -146,6 +146,12 @@ class Belief:
             if own:
                 be.close()
 
+    def marginal(self, dims):
+        """belief.marginal(dims): the marginal density on the 1-BASED coordinates `dims` (marginal.py) -- callable at host points,
+        with a `.grid(n, extent=None, margin=4.0, backend=None)` method; a partial belief has one on its partial coordinates"""
+        from .marginal import Marginal
+        return Marginal(self, dims)
+
 
 def getBelief(fg, label):
     """getBelief(dfg, label): the variable's current belief, callable at query points"""

@@ -23,6 +23,7 @@
 #include "nbp_ppe.h"
 #include "nbp_query.h"
 #include "nbp_stats.h"
+#include "nbp_marginal.h"
 
 static thread_local std::string g_err;
 static nbp_status fail(nbp_status code, const std::string &msg) {
@@ -101,8 +102,8 @@ struct nbp_ctx {
   // point estimates (nbp_run_ppe): one record per belief of the batch, grown on demand
   nbp_ppe_rec *ppe = nullptr;
   size_t ppe_cap = 0;
-  // belief queries and statistics (nbp_run_evaluate / nbp_run_mmd / nbp_run_meancov / nbp_run_kld): the queries going in and the
-  // values coming out, grown on demand
+  // belief queries and statistics (nbp_run_evaluate / nbp_run_mmd / nbp_run_meancov / nbp_run_kld / nbp_run_marginal_grid): the
+  // queries going in and the values coming out, grown on demand
   double *query = nullptr;
   size_t query_cap = 0;
   // pinned host staging of the batched belief transfers (nbp_belief_write_batch / _read_batch): one copy per run of
@@ -1647,6 +1648,142 @@ nbp_status nbp_kde_evaluate(nbp_ctx *c, int32_t manifold, const double *pts, int
   if (rc) return rc;
   const int32_t slot = 0, q_first[2] = {0, nq};
   return nbp_run_evaluate(c, &slot, &manifold, 1, q_first, queries, dens_out);
+}
+
+// ---- marginal densities (nbp_marginal.h) ---------------------------------------------------------------------------------------
+// One descriptor of nbp_run_marginal_grid: NBP_OK and its number of grid points, or the refusal (nothing has been launched)
+static nbp_status grid_desc_check(const nbp_ctx *c, const nbp_grid_desc &g, int i, int64_t *points) {
+  const std::string who = "marginal grid: descriptor " + std::to_string(i) + ": ";
+  if (g.slot < 0 || g.slot >= c->n_slots) return fail(NBP_ERR_RANGE, who + "slot out of range");
+  if (!manifold_ok(g.manifold)) return fail(NBP_ERR_ARG, who + "unknown manifold");
+  if (g.flags & ~NBP_GRID_AUTO_EXTENT) return fail(NBP_ERR_ARG, who + "unknown flag");
+  const int D = manifold_dim_h(g.manifold), axes = g.dims[1] == -1 ? 1 : 2;
+  const bool autoext = g.flags & NBP_GRID_AUTO_EXTENT;
+  int64_t pts = 1;
+  for (int a = 0; a < axes; a++) {
+    if (g.dims[a] < 0 || g.dims[a] >= D) return fail(NBP_ERR_RANGE, who + "coordinate outside the manifold");
+    if (a == 1 && g.dims[1] == g.dims[0]) return fail(NBP_ERR_RANGE, who + "repeated coordinate");
+    if (g.n[a] < 1 || g.n[a] > NBP_GRID_MAX) return fail(NBP_ERR_RANGE, who + "n outside 1 .. " + std::to_string(NBP_GRID_MAX));
+    const bool circ = (g.manifold == NBP_CIRCULAR && g.dims[a] == 0) || (g.manifold == NBP_SE2 && g.dims[a] == 2);
+    if (autoext && !circ && g.n[a] < 2) return fail(NBP_ERR_RANGE, who + "automatic extent of a Euclidean axis needs n >= 2");
+    if (!autoext && !(std::isfinite(g.lo[a]) && std::isfinite(g.step[a]))) return fail(NBP_ERR_RANGE, who + "lo / step not finite");
+    pts *= g.n[a];
+  }
+  if (autoext && !std::isfinite(g.margin)) return fail(NBP_ERR_RANGE, who + "margin not finite");
+  *points = pts;
+  return NBP_OK;
+}
+
+// p_K of resident beliefs on regular grids: one workgroup per tile of one descriptor's grid (nbp_marginal.h); the descriptors, the
+// offsets and the tile table go up in one staging copy, the grids come back in one copy (the extents, 32 bytes a descriptor, in a
+// second one where the caller asks for them)
+nbp_status nbp_run_marginal_grid(nbp_ctx *c, const nbp_grid_desc *descs, int32_t n, const int32_t *first, double *out,
+                                 double *extent_out) {
+  if (!c || ((!descs || !first) && n > 0)) return fail(NBP_ERR_ARG, "null argument");
+  if (n <= 0) return NBP_OK;
+  HIPCHK(hipSetDevice(c->device));
+  if (first[0] != 0) return fail(NBP_ERR_RANGE, "marginal grid: descriptor 0: first[0] must be 0");
+  std::vector<int32_t> tiles;
+  for (int i = 0; i < n; i++) {
+    int64_t pts = 0;
+    nbp_status rc = grid_desc_check(c, descs[i], i, &pts);
+    if (rc) return rc;
+    if ((int64_t)first[i + 1] - (int64_t)first[i] != pts)
+      return fail(NBP_ERR_RANGE, "marginal grid: descriptor " + std::to_string(i) + ": offsets do not match the grid size");
+    const bool two = descs[i].dims[1] != -1;
+    const int t0 = two ? NBP_GRID_TILE : NBP_GRID_TILE1;
+    for (int32_t k0 = 0; k0 < descs[i].n[0]; k0 += t0)
+      for (int32_t k1 = 0; k1 < (two ? descs[i].n[1] : 1); k1 += NBP_GRID_TILE) {
+        tiles.push_back(i);
+        tiles.push_back(k0);
+        tiles.push_back(k1);
+      }
+  }
+  if (!out) return fail(NBP_ERR_ARG, "null argument");
+  const size_t total = (size_t)first[n], n_tiles = tiles.size() / 3;
+  // staging: descriptors (8-byte aligned) | first | tiles
+  const size_t off_first = sizeof(nbp_grid_desc) * (size_t)n, off_tiles = off_first + 4 * ((size_t)n + 1);
+  std::vector<char> blob(off_tiles + 4 * tiles.size());
+  memcpy(blob.data(), descs, off_first);
+  memcpy(blob.data() + off_first, first, 4 * ((size_t)n + 1));
+  memcpy(blob.data() + off_tiles, tiles.data(), 4 * tiles.size());
+  nbp_status rc = stage_upload(c, blob.data(), blob.size());  // (waits for the stream: the query buffer is free as well)
+  if (rc) return rc;
+  rc = query_reserve(c, total + 4 * (size_t)n);
+  if (rc) return rc;
+  const char *ds = (const char *)c->stage;
+  double *dgrid = c->query, *dext = c->query + total;
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(nbp_marginal_grid_kernel, dim3((unsigned)n_tiles), dim3(NBP_GRID_LANES), 0, c->stream, (const nbp_grid_desc *)ds,
+                     (const int32_t *)(ds + off_first), (const int32_t *)(ds + off_tiles), c->arena, c->N, c->S, dgrid, dext);
+  HIPCHK(hipGetLastError());
+  // straight into the caller's buffers (a staging vector of the grids' size costs more than the kernel: profiles/marginal_grid_kernel.txt)
+  HIPCHK(hipMemcpyAsync(out, dgrid, sizeof(double) * total, hipMemcpyDeviceToHost, c->stream));
+  if (extent_out) HIPCHK(hipMemcpyAsync(extent_out, dext, sizeof(double) * 4 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return NBP_OK;
+}
+
+// host-buffer form: stages through slot 0 (which it clobbers), like nbp_kde_evaluate
+nbp_status nbp_kde_marginal_grid(nbp_ctx *c, int32_t manifold, const double *pts, int32_t n_pts, const double *bw,
+                                 const nbp_grid_desc *desc, double *out, double *extent_out) {
+  if (!c || !pts || !bw || !desc || !out) return fail(NBP_ERR_ARG, "null argument");
+  if (!manifold_ok(manifold)) return fail(NBP_ERR_ARG, "marginal grid: unknown manifold");
+  if (n_pts < 1) return fail(NBP_ERR_ARG, "marginal grid: a belief holds at least one point");
+  nbp_grid_desc g = *desc;
+  g.slot = 0;
+  g.manifold = manifold;
+  int64_t pts_n = 0;
+  nbp_status rc = grid_desc_check(c, g, 0, &pts_n);  // (before slot 0 is touched)
+  if (rc) return rc;
+  rc = nbp_belief_write(c, 0, manifold, pts, n_pts, bw, nullptr);
+  if (rc) return rc;
+  const int32_t first[2] = {0, (int32_t)pts_n};
+  return nbp_run_marginal_grid(c, &g, 1, first, out, extent_out);
+}
+
+// p_K at query points: nbp_run_evaluate's launch with the masked instance of its kernel
+nbp_status nbp_run_evaluate_marginal(nbp_ctx *c, const int32_t *slots, const int32_t *manifolds, const int32_t *masks, int32_t n,
+                                     const int32_t *q_first, const double *queries, double *dens_out) {
+  if (!c || ((!slots || !manifolds || !masks || !q_first) && n > 0)) return fail(NBP_ERR_ARG, "null argument");
+  if (n <= 0) return NBP_OK;
+  HIPCHK(hipSetDevice(c->device));
+  if (q_first[0] != 0) return fail(NBP_ERR_ARG, "evaluate marginal: q_first[0] must be 0");
+  for (int i = 0; i < n; i++) {
+    const std::string who = "evaluate marginal: belief " + std::to_string(i) + ": ";
+    if (slots[i] < 0 || slots[i] >= c->n_slots) return fail(NBP_ERR_RANGE, who + "slot out of range");
+    if (!manifold_ok(manifolds[i])) return fail(NBP_ERR_ARG, who + "unknown manifold");
+    if (q_first[i + 1] < q_first[i]) return fail(NBP_ERR_ARG, who + "q_first must not decrease");
+    if (masks[i] == 0) return fail(NBP_ERR_RANGE, who + "empty mask");
+    if (masks[i] < 0 || (masks[i] >> manifold_dim_h(manifolds[i])) != 0) return fail(NBP_ERR_RANGE, who + "coordinate outside the manifold");
+  }
+  const size_t Q = (size_t)q_first[n];
+  if (Q == 0) return NBP_OK;
+  if (!queries || !dens_out) return fail(NBP_ERR_ARG, "null argument");
+  std::vector<int32_t> ints(slots, slots + n);
+  ints.insert(ints.end(), manifolds, manifolds + n);
+  ints.insert(ints.end(), masks, masks + n);
+  for (int i = 0; i < n; i++)
+    for (int32_t q = q_first[i]; q < q_first[i + 1]; q += NBP_QUERY_TILE) {
+      ints.push_back(i);
+      ints.push_back(q);
+      ints.push_back(std::min<int32_t>(NBP_QUERY_TILE, q_first[i + 1] - q));
+    }
+  const size_t tiles = (ints.size() - 3 * (size_t)n) / 3;
+  nbp_status rc = stage_upload(c, ints.data(), ints.size() * 4);  // (waits for the stream: the query buffer is free as well)
+  if (rc) return rc;
+  rc = query_reserve(c, Q * (NBP_MAXD + 1));
+  if (rc) return rc;
+  double *dq = c->query, *dd = c->query + Q * NBP_MAXD;
+  HIPCHK(hipMemcpyAsync(dq, queries, sizeof(double) * Q * NBP_MAXD, hipMemcpyHostToDevice, c->stream));
+  const int32_t *ds = (const int32_t *)c->stage;
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(nbp_eval_marginal_kernel, dim3((unsigned)tiles), dim3(NBP_QUERY_TILE), nbp_eval_lds_bytes(c->N), c->stream,
+                     ds + 3 * n, ds, ds + n, ds + 2 * n, c->arena, c->N, c->S, dq, dd);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(dens_out, dd, sizeof(double) * Q, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return NBP_OK;
 }
 
 // mmd(p1, p2, varType; bw = [sigma]) (services/SolverUtilities.jl:25-47) for pairs of beliefs resident in slots: one workgroup per

@@ -197,6 +197,43 @@ class SolveSession:
                 out[v] = beliefstats.calcMeanCovar(self.fg, v, backend=self.backend)
         return {v: out[v] for v in labels}
 
+    def marginalGrid(self, labels=None, dims=(1,), n=64, margin=4.0):
+        """The marginal densities of the variables' current beliefs on regular grids with the automatic extent (marginal.py) ->
+        {label: (grid, axes)}.  dims: one or two coordinates, 1-BASED like the reference's `partial`; n: points per axis (a scalar:
+        the same on both); labels: default every variable the last solve worked on whose manifold has the coordinates `dims`.  On
+        libnbp all of them are served where they lie by ONE `run_marginal_grid`: no belief travels and `stats` does not move
+        (a belief that is not resident goes up first and is counted, as in `calcMeanCovar`).  A variable without a slot in the
+        session's context, or a backend without `run_marginal_grid`: `marginal.marginalGrid` on the host copy."""
+        from . import marginal
+        if self._closed:
+            raise RuntimeError("this SolveSession is closed")
+        dims = tuple(int(d) for d in (dims if hasattr(dims, "__len__") else (dims,)))
+        nn = [int(v) for v in (n if hasattr(n, "__len__") else (n,))]
+        nn = nn * len(dims) if len(nn) == 1 else nn
+        if labels is None:
+            labels = [v for v in self._labels if self.fg.getVariable(v).varType.dim >= max(dims)]
+        labels = list(labels)
+        be = self._be
+        place = {v: i for i, v in enumerate(self._labels)}
+        if be is None or getattr(be, "run_marginal_grid", None) is None:
+            return {v: marginal.marginalGrid(self.fg, v, dims, nn, None, margin) for v in labels}
+        out = {}
+        here = [v for v in labels if v in place]
+        if here:
+            try:
+                self._upload(self.fg, [(v, place[v]) for v in here], len(self._labels))
+                grids, ext = be.run_marginal_grid([(place[v], self.fg.getVariable(v).varType.manifold, [d - 1 for d in dims], nn, None,
+                                                    margin) for v in here], return_extent=True)
+            except BaseException:
+                self._table.clear()  # the device state is unknown: the host copy wins
+                raise
+            for i, v in enumerate(here):
+                out[v] = (grids[i].copy(), marginal.grid_axes(ext[i], nn))
+        for v in labels:
+            if v not in place:
+                out[v] = marginal.marginalGrid(self.fg, v, dims, nn, None, margin, backend=self.backend)
+        return {v: out[v] for v in labels}
+
     # ---- one solve ---------------------------------------------------------------------------------------------------------
     def solve(self, seed=0, eliminationOrder=None, ordering="qr", return_timing=False):
         """solveTree(fg, oldtree=ses.tree, ...) in the session's context -> tree (or (tree, timing) with return_timing: the
