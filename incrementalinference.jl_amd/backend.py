@@ -19,6 +19,29 @@ class NbpError(RuntimeError):
     (reference: CliqStateMachineUtils.jl:184-246, test/testCSMMonitor.jl:51)."""
 
 
+def _i32(seq):
+    """a sequence as a contiguous int32 array and the pointer to it that libnbp takes (the pointer holds a reference to the array)"""
+    a = np.ascontiguousarray(seq, dtype=np.int32)
+    return a, a.ctypes.data_as(C.POINTER(C.c_int32))
+
+
+def _pack_queries(manifolds, queries, all_columns=False):
+    """one array of queries per belief (q_i x D or x 3, or flat: rows of D) -> (the padded Q x 3 array, first[n + 1]): the layout of
+    nbp_run_evaluate.  all_columns: the assignment covers all D columns whatever the queries' width, as kde_evaluate has always
+    made it (numpy broadcasts one column and refuses any other narrower width); else narrower queries are zero-padded"""
+    first = np.zeros(len(manifolds) + 1, dtype=np.int32)
+    rows = []
+    for i, m in enumerate(manifolds):
+        D = abi.MANIFOLD_DIM.get(int(m), abi.MAXD)  # (an unknown manifold is the library's to refuse)
+        q = np.asarray(queries[i], dtype=np.float64)
+        q = q.reshape(-1, q.shape[-1] if q.ndim > 1 else D)
+        pad = np.zeros((q.shape[0], abi.MAXD))
+        pad[:, :D if all_columns else min(D, q.shape[1])] = q[:, :D]
+        rows.append(pad)
+        first[i + 1] = first[i] + q.shape[0]
+    return (np.ascontiguousarray(np.concatenate(rows)) if rows else np.zeros((0, abi.MAXD))), first
+
+
 def _as_array(descs, ctype):
     if isinstance(descs, C.Array):
         return descs, len(descs)
@@ -122,8 +145,8 @@ class HipBackend:
         return [(p[:cnt[i]], b, q) for i, (p, b, q) in enumerate(out)]
 
     def side_write(self, offset, ints):
-        a = np.ascontiguousarray(ints, dtype=np.int32)
-        self._check(self.lib.nbp_side_write(self._ctx, offset, a.ctypes.data_as(C.POINTER(C.c_int32)), a.size))
+        a, ap = _i32(ints)
+        self._check(self.lib.nbp_side_write(self._ctx, offset, ap, a.size))
 
     def side_read(self, offset, n):
         a = np.empty(n, dtype=np.int32)
@@ -145,33 +168,27 @@ class HipBackend:
 
     def run_deconv(self, descs, meas_slots=None):
         arr, n = _as_array(descs, abi.ProposalDesc)
-        ms = np.ascontiguousarray(meas_slots if meas_slots is not None else [-1] * n, dtype=np.int32)
-        self._check(self.lib.nbp_run_deconv(self._ctx, arr, ms.ctypes.data_as(C.POINTER(C.c_int32)), n))
+        _, msp = _i32(meas_slots if meas_slots is not None else [-1] * n)
+        self._check(self.lib.nbp_run_deconv(self._ctx, arr, msp, n))
 
     def run_bandwidth(self, slots, manifolds):
-        s = np.ascontiguousarray(slots, dtype=np.int32)
-        m = np.ascontiguousarray(manifolds, dtype=np.int32)
-        ip = C.POINTER(C.c_int32)
-        self._check(self.lib.nbp_run_bandwidth(self._ctx, s.ctypes.data_as(ip), m.ctypes.data_as(ip), s.size))
+        (s, sp), (_, mp) = _i32(slots), _i32(manifolds)
+        self._check(self.lib.nbp_run_bandwidth(self._ctx, sp, mp, s.size))
 
     def run_ppe(self, slots, manifolds):
         """calcPPE of resident beliefs (nbp_run_ppe) -> (mean[n, 3], max[n, 3], max_index[n]): the manifold mean and the point
         of the belief at which its own KDE is greatest, in tangent coordinates (entries beyond the manifold's dimension zero)"""
-        s = np.ascontiguousarray(slots, dtype=np.int32)
-        m = np.ascontiguousarray(manifolds, dtype=np.int32)
+        (s, sp), (_, mp) = _i32(slots), _i32(manifolds)
         n = s.size
         mean, mx, idx = np.zeros((n, abi.MAXD)), np.zeros((n, abi.MAXD)), np.zeros(n, dtype=np.int32)
         ip, dp = C.POINTER(C.c_int32), C.POINTER(C.c_double)
-        self._check(self.lib.nbp_run_ppe(self._ctx, s.ctypes.data_as(ip), m.ctypes.data_as(ip), n, mean.ctypes.data_as(dp),
-                                         mx.ctypes.data_as(dp), idx.ctypes.data_as(ip)))
+        self._check(self.lib.nbp_run_ppe(self._ctx, sp, mp, n, mean.ctypes.data_as(dp), mx.ctypes.data_as(dp), idx.ctypes.data_as(ip)))
         return mean, mx, idx
 
     def run_resample(self, slots, manifolds, seed=0):
         """sample(oldBel, N - Npts): top beliefs with fewer than N points up to N, in place"""
-        s = np.ascontiguousarray(slots, dtype=np.int32)
-        m = np.ascontiguousarray(manifolds, dtype=np.int32)
-        ip = C.POINTER(C.c_int32)
-        self._check(self.lib.nbp_run_resample(self._ctx, s.ctypes.data_as(ip), m.ctypes.data_as(ip), s.size, C.c_uint64(seed)))
+        (s, sp), (_, mp) = _i32(slots), _i32(manifolds)
+        self._check(self.lib.nbp_run_resample(self._ctx, sp, mp, s.size, C.c_uint64(seed)))
 
     # ---- host-buffer entry points (one call per reference function) -------------------------------
     def kde_bandwidth(self, manifold, pts):
@@ -192,42 +209,34 @@ class HipBackend:
                                          mean.ctypes.data_as(dp), mx.ctypes.data_as(dp), C.byref(idx)))
         return mean, mx, idx.value
 
+    def _run_evaluate(self, slots, manifolds, masks, queries):
+        """run_evaluate (masks None) and run_evaluate_marginal: one packing of the queries, one slicing of the densities"""
+        (s, sp), (m, mp) = _i32(slots), _i32(manifolds)
+        n = s.size
+        Q, first = _pack_queries(m, queries)
+        out = np.zeros(int(first[-1]))
+        ip, dp = C.POINTER(C.c_int32), C.POINTER(C.c_double)
+        tail = (n, first.ctypes.data_as(ip), Q.ctypes.data_as(dp), out.ctypes.data_as(dp))
+        if masks is None:
+            self._check(self.lib.nbp_run_evaluate(self._ctx, sp, mp, *tail))
+        else:
+            self._check(self.lib.nbp_run_evaluate_marginal(self._ctx, sp, mp, _i32(masks)[1], *tail))
+        return [out[first[i]:first[i + 1]] for i in range(n)]
+
     def run_evaluate(self, slots, manifolds, queries):
         """densities of resident beliefs at query points (nbp_run_evaluate): queries = one array (q_i x D or x 3, tangent
         coordinates; may be empty) per belief -> one array of q_i densities per belief, from one launch"""
-        s = np.ascontiguousarray(slots, dtype=np.int32)
-        m = np.ascontiguousarray(manifolds, dtype=np.int32)
-        n = s.size
-        first = np.zeros(n + 1, dtype=np.int32)
-        rows = []
-        for i in range(n):
-            D = abi.MANIFOLD_DIM.get(int(m[i]), abi.MAXD)  # (an unknown manifold is the library's to refuse)
-            q = np.asarray(queries[i], dtype=np.float64)
-            q = q.reshape(-1, q.shape[-1] if q.ndim > 1 else D)
-            pad = np.zeros((q.shape[0], abi.MAXD))
-            pad[:, :min(D, q.shape[1])] = q[:, :D]
-            rows.append(pad)
-            first[i + 1] = first[i] + q.shape[0]
-        Q = np.ascontiguousarray(np.concatenate(rows)) if rows else np.zeros((0, abi.MAXD))
-        out = np.zeros(int(first[-1]))
-        ip, dp = C.POINTER(C.c_int32), C.POINTER(C.c_double)
-        self._check(self.lib.nbp_run_evaluate(self._ctx, s.ctypes.data_as(ip), m.ctypes.data_as(ip), n, first.ctypes.data_as(ip),
-                                              Q.ctypes.data_as(dp), out.ctypes.data_as(dp)))
-        return [out[first[i]:first[i + 1]] for i in range(n)]
+        return self._run_evaluate(slots, manifolds, None, queries)
 
     def kde_evaluate(self, manifold, pts, bw, queries):
         """densities of a belief held on the host at query points in tangent coordinates (nbp_kde_evaluate; clobbers slot 0)"""
         dp = C.POINTER(C.c_double)
         pts = np.ascontiguousarray(pts, dtype=np.float64).reshape(-1, abi.MANIFOLD_P[manifold])
         bw = np.ascontiguousarray(bw, dtype=np.float64)
-        D = abi.MANIFOLD_DIM[manifold]
-        q = np.asarray(queries, dtype=np.float64)
-        q = q.reshape(-1, q.shape[-1] if q.ndim > 1 else D)
-        Q = np.zeros((q.shape[0], abi.MAXD))
-        Q[:, :D] = q[:, :D]
-        out = np.zeros(q.shape[0])
+        Q, first = _pack_queries([manifold], [queries], all_columns=True)
+        out = np.zeros(int(first[1]))
         self._check(self.lib.nbp_kde_evaluate(self._ctx, manifold, pts.ctypes.data_as(dp), pts.shape[0], bw.ctypes.data_as(dp),
-                                              Q.ctypes.data_as(dp), q.shape[0], out.ctypes.data_as(dp)))
+                                              Q.ctypes.data_as(dp), int(first[1]), out.ctypes.data_as(dp)))
         return out
 
     @staticmethod
@@ -285,36 +294,13 @@ class HipBackend:
     def run_evaluate_marginal(self, slots, manifolds, masks, queries):
         """marginal densities of resident beliefs at query points (nbp_run_evaluate_marginal): masks = one coordinate bit mask
         per belief (bit d = coordinate d); queries as in run_evaluate (q_i x D or x 3; entries outside the mask are not read)"""
-        s = np.ascontiguousarray(slots, dtype=np.int32)
-        m = np.ascontiguousarray(manifolds, dtype=np.int32)
-        k = np.ascontiguousarray(masks, dtype=np.int32)
-        n = s.size
-        first = np.zeros(n + 1, dtype=np.int32)
-        rows = []
-        for i in range(n):
-            D = abi.MANIFOLD_DIM.get(int(m[i]), abi.MAXD)  # (an unknown manifold is the library's to refuse)
-            q = np.asarray(queries[i], dtype=np.float64)
-            q = q.reshape(-1, q.shape[-1] if q.ndim > 1 else D)
-            pad = np.zeros((q.shape[0], abi.MAXD))
-            pad[:, :min(D, q.shape[1])] = q[:, :D]
-            rows.append(pad)
-            first[i + 1] = first[i] + q.shape[0]
-        Q = np.ascontiguousarray(np.concatenate(rows)) if rows else np.zeros((0, abi.MAXD))
-        out = np.zeros(int(first[-1]))
-        ip, dp = C.POINTER(C.c_int32), C.POINTER(C.c_double)
-        self._check(self.lib.nbp_run_evaluate_marginal(self._ctx, s.ctypes.data_as(ip), m.ctypes.data_as(ip), k.ctypes.data_as(ip), n,
-                                                       first.ctypes.data_as(ip), Q.ctypes.data_as(dp), out.ctypes.data_as(dp)))
-        return [out[first[i]:first[i + 1]] for i in range(n)]
+        return self._run_evaluate(slots, manifolds, masks, queries)
 
     def run_mmd(self, slots_a, slots_b, manifolds, sigma=0.001):
         """mmd of pairs of resident beliefs (nbp_run_mmd) -> values[n], from one launch"""
-        a = np.ascontiguousarray(slots_a, dtype=np.int32)
-        b = np.ascontiguousarray(slots_b, dtype=np.int32)
-        m = np.ascontiguousarray(manifolds, dtype=np.int32)
+        (a, ap), (_, bp), (_, mp) = _i32(slots_a), _i32(slots_b), _i32(manifolds)
         out = np.zeros(a.size)
-        ip, dp = C.POINTER(C.c_int32), C.POINTER(C.c_double)
-        self._check(self.lib.nbp_run_mmd(self._ctx, a.ctypes.data_as(ip), b.ctypes.data_as(ip), m.ctypes.data_as(ip), a.size,
-                                         float(sigma), out.ctypes.data_as(dp)))
+        self._check(self.lib.nbp_run_mmd(self._ctx, ap, bp, mp, a.size, float(sigma), out.ctypes.data_as(C.POINTER(C.c_double))))
         return out
 
     def kde_mmd(self, manifold, a, b, sigma=0.001):
@@ -330,13 +316,11 @@ class HipBackend:
     def run_meancov(self, slots, manifolds):
         """calcMeanCovar of resident beliefs (nbp_run_meancov) -> (mean[n, 3], cov[n, 3, 3]), tangent coordinates, entries beyond
         the manifold's dimension zero; the mean is run_ppe's, bit for bit"""
-        s = np.ascontiguousarray(slots, dtype=np.int32)
-        m = np.ascontiguousarray(manifolds, dtype=np.int32)
+        (s, sp), (_, mp) = _i32(slots), _i32(manifolds)
         n = s.size
         mean, cov = np.zeros((n, abi.MAXD)), np.zeros((n, abi.MAXD, abi.MAXD))
-        ip, dp = C.POINTER(C.c_int32), C.POINTER(C.c_double)
-        self._check(self.lib.nbp_run_meancov(self._ctx, s.ctypes.data_as(ip), m.ctypes.data_as(ip), n, mean.ctypes.data_as(dp),
-                                             cov.ctypes.data_as(dp)))
+        dp = C.POINTER(C.c_double)
+        self._check(self.lib.nbp_run_meancov(self._ctx, sp, mp, n, mean.ctypes.data_as(dp), cov.ctypes.data_as(dp)))
         return mean, cov
 
     def kde_meancov(self, manifold, pts):
@@ -352,13 +336,10 @@ class HipBackend:
     def run_kld(self, slots_a, slots_b, manifolds, terms=False):
         """kld of pairs of resident beliefs (nbp_run_kld) -> values[n], from one launch; terms=True: (values[n], terms[n, 2]) with
         terms = (Eaa, Eab), values = Eaa - Eab, entropy(a) = -Eaa"""
-        a = np.ascontiguousarray(slots_a, dtype=np.int32)
-        b = np.ascontiguousarray(slots_b, dtype=np.int32)
-        m = np.ascontiguousarray(manifolds, dtype=np.int32)
+        (a, ap), (_, bp), (_, mp) = _i32(slots_a), _i32(slots_b), _i32(manifolds)
         out, tm = np.zeros(a.size), np.zeros((a.size, 2))
-        ip, dp = C.POINTER(C.c_int32), C.POINTER(C.c_double)
-        self._check(self.lib.nbp_run_kld(self._ctx, a.ctypes.data_as(ip), b.ctypes.data_as(ip), m.ctypes.data_as(ip), a.size,
-                                         out.ctypes.data_as(dp), tm.ctypes.data_as(dp) if terms else None))
+        dp = C.POINTER(C.c_double)
+        self._check(self.lib.nbp_run_kld(self._ctx, ap, bp, mp, a.size, out.ctypes.data_as(dp), tm.ctypes.data_as(dp) if terms else None))
         return (out, tm) if terms else out
 
     def kde_kld(self, manifold, a, bw_a, b, bw_b, terms=False):

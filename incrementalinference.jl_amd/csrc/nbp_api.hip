@@ -99,11 +99,8 @@ struct nbp_ctx {
   // staging for immediate-mode calls
   void *stage = nullptr;
   size_t stage_bytes = 0;
-  // point estimates (nbp_run_ppe): one record per belief of the batch, grown on demand
-  nbp_ppe_rec *ppe = nullptr;
-  size_t ppe_cap = 0;
-  // belief queries and statistics (nbp_run_evaluate / nbp_run_mmd / nbp_run_meancov / nbp_run_kld / nbp_run_marginal_grid): the
-  // queries going in and the values coming out, grown on demand
+  // point estimates, belief queries and statistics (nbp_run_ppe / nbp_run_evaluate / nbp_run_mmd / nbp_run_meancov / nbp_run_kld /
+  // nbp_run_marginal_grid): the queries going in and the values or records coming out, grown on demand
   double *query = nullptr;
   size_t query_cap = 0;
   // pinned host staging of the batched belief transfers (nbp_belief_write_batch / _read_batch): one copy per run of
@@ -182,6 +179,43 @@ static int manifold_dim_h(int m) { return m == NBP_SE2 ? 3 : (m == NBP_CIRCULAR 
 static int manifold_P_h(int m) { return m == NBP_SE2 ? 6 : manifold_dim_h(m); }
 static bool manifold_ok(int m) { return m >= NBP_EUCLID1 && m <= NBP_SE2; }
 static double wrap_h(double a) { return nbpm_wrap_pi(a); }  // (include/nbp_math.h)
+
+// ---- helpers of the batches over resident beliefs (used far below; the templates need C++ linkage, so they stand here) ----------
+#define NBPCHK(...)                    \
+  do {                                 \
+    nbp_status rc_ = (__VA_ARGS__);    \
+    if (rc_) return rc_;               \
+  } while (0)
+struct refusal {
+  nbp_status code;
+  const char *what;  // nullptr: none
+};
+static refusal no_refusal(int) { return {NBP_OK, nullptr}; }
+
+template <class K, class... A>
+static nbp_status launch_checked(nbp_ctx *c, K kernel, size_t blocks, int lanes, size_t lds, A... args) {
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(lanes), lds, c->stream, args...);
+  HIPCHK(hipGetLastError());
+  return NBP_OK;
+}
+
+// selects the device; then, element by element and in this order: every slot column, the manifold, what `extra(i)` refuses
+// (no_refusal: nothing more)
+template <class Extra>
+static nbp_status batch_check(nbp_ctx *c, const char *who, std::initializer_list<const int32_t *> slot_cols, const int32_t *manifolds,
+                              int n, Extra extra) {
+  HIPCHK(hipSetDevice(c->device));
+  for (int i = 0; i < n; i++) {
+    refusal r{NBP_OK, nullptr};
+    for (const int32_t *s : slot_cols)
+      if (s[i] < 0 || s[i] >= c->n_slots) r = {NBP_ERR_RANGE, "slot out of range"};
+    if (!r.what && !manifold_ok(manifolds[i])) r = {NBP_ERR_ARG, "unknown manifold"};
+    if (!r.what) r = extra(i);
+    if (r.what) return fail(r.code, std::string(who) + ": belief " + std::to_string(i) + ": " + r.what);
+  }
+  return NBP_OK;
+}
 
 extern "C" {
 
@@ -366,7 +400,6 @@ nbp_status nbp_ctx_destroy(nbp_ctx *c) {
   if (c->lv_ints) hipFree(c->lv_ints);
   if (c->lv_dbls) hipFree(c->lv_dbls);
   if (c->stage) hipFree(c->stage);
-  if (c->ppe) hipFree(c->ppe);
   if (c->query) hipFree(c->query);
   if (c->pin) hipHostFree(c->pin);
   for (auto &b : c->blob_cache) hipFree(b.first);
@@ -1510,20 +1543,83 @@ nbp_status nbp_run_copies_async(nbp_ctx *c, const nbp_copy_desc *descs, int32_t 
   return rc;
 }
 
+// ---- batches over resident beliefs -------------------------------------------------------------------------------------------
+// Every nbp_run_* below is one sequence: the device selected and the columns checked (batch_check), the columns staged in
+// one copy and the result scratch reserved (stage_columns), one launch (launch_checked), the results copied back and the stream
+// waited for (query_fetch).  The nbp_kde_* forms put their host buffers into slot 0 (and 1) first (kde_check, kde_write).
+// the scratch of the belief queries holds at least `doubles` (called with the stream idle: stage_upload has waited)
+static nbp_status query_reserve(nbp_ctx *c, size_t doubles) {
+  if (doubles <= c->query_cap) return NBP_OK;
+  if (c->query) HIPCHK(hipFree(c->query));
+  c->query = nullptr;
+  c->query_cap = 0;
+  HIPCHK(hipMalloc(&c->query, sizeof(double) * doubles * 2));
+  c->query_cap = doubles * 2;
+  return NBP_OK;
+}
+
+struct stage_col {
+  const void *p;
+  size_t bytes;
+};
+// columns of any plain type in ONE staging copy, each starting on an 8-byte boundary, dev[k] = where column k lies on the device
+// (int32 columns but for the grid descriptors: cast there); then c->query holds `scratch` doubles
+// (stage_upload waits for the stream: the query scratch is free as well)
+static nbp_status stage_columns(nbp_ctx *c, std::initializer_list<stage_col> cols, const int32_t **dev, size_t scratch) {
+  std::vector<char> blob;
+  std::vector<size_t> off;
+  for (const stage_col &col : cols) {
+    off.push_back(blob.size());
+    blob.resize(blob.size() + (col.bytes + 7) / 8 * 8);
+    if (col.bytes) memcpy(blob.data() + off.back(), col.p, col.bytes);
+  }
+  NBPCHK(stage_upload(c, blob.data(), blob.size()));
+  for (size_t o : off) *dev++ = (const int32_t *)((const char *)c->stage + o);
+  return query_reserve(c, scratch);
+}
+
+// the one copy back, and the wait for it
+static nbp_status query_fetch(nbp_ctx *c, void *dst, const void *src, size_t bytes) {
+  HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return NBP_OK;
+}
+
+// Host-buffer forms: the beliefs go through slot 0 (and slot 1), which they clobber.  bw == nullptr: the bandwidth plays no part
+// in the query, the slot carries ones.
+struct host_belief {
+  const double *pts;
+  int32_t n;
+  const double *bw;
+};
+static nbp_status kde_check(const nbp_ctx *c, const char *who, int32_t manifold, std::initializer_list<host_belief> bels) {
+  if (!manifold_ok(manifold)) return fail(NBP_ERR_ARG, std::string(who) + ": unknown manifold");
+  for (const host_belief &b : bels)
+    if (b.n < 1) return fail(NBP_ERR_ARG, std::string(who) + ": a belief holds at least one point");
+  if (bels.size() == 2 && c->n_slots < 2) return fail(NBP_ERR_RANGE, std::string(who) + ": the context needs two slots");
+  return NBP_OK;
+}
+static nbp_status kde_write(nbp_ctx *c, int32_t manifold, std::initializer_list<host_belief> bels) {
+  const double ones[NBP_MAXD] = {1.0, 1.0, 1.0};
+  int32_t slot = 0;
+  for (const host_belief &b : bels) {
+    NBPCHK(nbp_belief_write(c, slot++, manifold, b.pts, b.n, b.bw ? b.bw : ones, nullptr));
+  }
+  return NBP_OK;
+}
+static nbp_status kde_stage(nbp_ctx *c, const char *who, int32_t manifold, std::initializer_list<host_belief> bels) {
+  NBPCHK(kde_check(c, who, manifold, bels));
+  return kde_write(c, manifold, bels);
+}
+
 nbp_status nbp_run_bandwidth(nbp_ctx *c, const int32_t *slots, const int32_t *manifolds, int32_t n) {
   if (!c || ((!slots || !manifolds) && n > 0)) return fail(NBP_ERR_ARG, "null argument");
   if (n <= 0) return NBP_OK;
-  HIPCHK(hipSetDevice(c->device));
-  for (int i = 0; i < n; i++) {
-    if (slots[i] < 0 || slots[i] >= c->n_slots) return fail(NBP_ERR_RANGE, "bandwidth: slot out of range");
-    if (!manifold_ok(manifolds[i])) return fail(NBP_ERR_ARG, "bandwidth: unknown manifold");
-  }
+  NBPCHK(batch_check(c, "bandwidth", {slots}, manifolds, n, no_refusal));
   nbp_fits fits;
   for (int i = 0; i < n; i++) fits.push(slots[i], manifolds[i]);
-  nbp_status rc = stage_with_fits(c, nullptr, 0, fits);
-  if (rc) return rc;
-  rc = launch_bandwidth(c, ctx_env(c), fits_dev(fits, c->stage));
-  if (rc) return rc;
+  NBPCHK(stage_with_fits(c, nullptr, 0, fits));
+  NBPCHK(launch_bandwidth(c, ctx_env(c), fits_dev(fits, c->stage)));
   HIPCHK(hipStreamSynchronize(c->stream));
   return NBP_OK;
 }
@@ -1533,29 +1629,13 @@ nbp_status nbp_run_ppe(nbp_ctx *c, const int32_t *slots, const int32_t *manifold
                        int32_t *max_index_out) {
   if (!c || ((!slots || !manifolds || !mean_out || !max_out) && n > 0)) return fail(NBP_ERR_ARG, "null argument");
   if (n <= 0) return NBP_OK;
-  HIPCHK(hipSetDevice(c->device));
-  for (int i = 0; i < n; i++) {
-    if (slots[i] < 0 || slots[i] >= c->n_slots) return fail(NBP_ERR_RANGE, "ppe: slot out of range");
-    if (!manifold_ok(manifolds[i])) return fail(NBP_ERR_ARG, "ppe: unknown manifold");
-  }
-  std::vector<int32_t> both(slots, slots + n);
-  both.insert(both.end(), manifolds, manifolds + n);
-  nbp_status rc = stage_upload(c, both.data(), both.size() * 4);  // (waits for the stream: the record buffer is free as well)
-  if (rc) return rc;
-  if ((size_t)n > c->ppe_cap) {
-    if (c->ppe) HIPCHK(hipFree(c->ppe));
-    c->ppe = nullptr;
-    c->ppe_cap = 0;
-    HIPCHK(hipMalloc(&c->ppe, sizeof(nbp_ppe_rec) * (size_t)n * 2));
-    c->ppe_cap = (size_t)n * 2;
-  }
-  const int32_t *ds = (const int32_t *)c->stage;
-  (void)hipGetLastError();
-  hipLaunchKernelGGL(nbp_ppe_kernel, dim3(n), dim3(c->Npad), nbp_ppe_lds_bytes(c->N), c->stream, ds, ds + n, c->arena, c->N, c->S, c->ppe);
-  HIPCHK(hipGetLastError());
+  NBPCHK(batch_check(c, "ppe", {slots}, manifolds, n, no_refusal));
+  static_assert(sizeof(nbp_ppe_rec) % sizeof(double) == 0, "nbp_ppe_rec fills whole doubles of the query scratch");
+  const int32_t *d[2];
+  NBPCHK(stage_columns(c, {{slots, 4 * (size_t)n}, {manifolds, 4 * (size_t)n}}, d, (size_t)n * (sizeof(nbp_ppe_rec) / sizeof(double))));
+  NBPCHK(launch_checked(c, nbp_ppe_kernel, n, c->Npad, nbp_ppe_lds_bytes(c->N), d[0], d[1], c->arena, c->N, c->S, (nbp_ppe_rec *)c->query));
   std::vector<nbp_ppe_rec> rec((size_t)n);
-  HIPCHK(hipMemcpyAsync(rec.data(), c->ppe, sizeof(nbp_ppe_rec) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
+  NBPCHK(query_fetch(c, rec.data(), c->query, sizeof(nbp_ppe_rec) * (size_t)n));
   for (int i = 0; i < n; i++) {
     for (int k = 0; k < NBP_MAXD; k++) {
       mean_out[(size_t)i * NBP_MAXD + k] = rec[i].mean[k];
@@ -1570,14 +1650,10 @@ nbp_status nbp_run_ppe(nbp_ctx *c, const int32_t *slots, const int32_t *manifold
 nbp_status nbp_kde_ppe(nbp_ctx *c, int32_t manifold, const double *pts, int32_t n_pts, const double *bw, double *mean_out,
                        double *max_out, int32_t *max_index_out) {
   if (!c || !pts || !bw || !mean_out || !max_out) return fail(NBP_ERR_ARG, "null argument");
-  if (!manifold_ok(manifold)) return fail(NBP_ERR_ARG, "ppe: unknown manifold");
-  if (n_pts < 1) return fail(NBP_ERR_ARG, "ppe: a belief holds at least one point");
-  nbp_status rc = nbp_belief_write(c, 0, manifold, pts, n_pts, bw, nullptr);
-  if (rc) return rc;
+  NBPCHK(kde_stage(c, "ppe", manifold, {{pts, n_pts, bw}}));
   const int32_t slot = 0;
   double mean3[NBP_MAXD], max3[NBP_MAXD];
-  rc = nbp_run_ppe(c, &slot, &manifold, 1, mean3, max3, max_index_out);
-  if (rc) return rc;
+  NBPCHK(nbp_run_ppe(c, &slot, &manifold, 1, mean3, max3, max_index_out));
   for (int k = 0; k < manifold_dim_h(manifold); k++) {
     mean_out[k] = mean3[k];
     max_out[k] = max3[k];
@@ -1585,67 +1661,51 @@ nbp_status nbp_kde_ppe(nbp_ctx *c, int32_t manifold, const double *pts, int32_t 
   return NBP_OK;
 }
 
-// the scratch of the belief queries holds at least `doubles` (called with the stream idle: stage_upload has waited)
-static nbp_status query_reserve(nbp_ctx *c, size_t doubles) {
-  if (doubles <= c->query_cap) return NBP_OK;
-  if (c->query) HIPCHK(hipFree(c->query));
-  c->query = nullptr;
-  c->query_cap = 0;
-  HIPCHK(hipMalloc(&c->query, sizeof(double) * doubles * 2));
-  c->query_cap = doubles * 2;
-  return NBP_OK;
+// The launch of both point-density forms, behind their argument checks: one workgroup per tile of at most NBP_QUERY_TILE queries of
+// one belief, one copy each way.  masks == nullptr: nbp_eval_kernel; else its masked instance.
+static nbp_status run_point_density(nbp_ctx *c, const int32_t *slots, const int32_t *manifolds, const int32_t *masks, int32_t n,
+                                    const int32_t *q_first, const double *queries, double *dens_out) {
+  const size_t Q = (size_t)q_first[n];
+  if (Q == 0) return NBP_OK;
+  if (!queries || !dens_out) return fail(NBP_ERR_ARG, "null argument");
+  std::vector<int32_t> tiles;  // (belief of the batch, first query, number of queries <= NBP_QUERY_TILE)
+  for (int i = 0; i < n; i++)
+    for (int32_t q = q_first[i]; q < q_first[i + 1]; q += NBP_QUERY_TILE) {
+      tiles.push_back(i);
+      tiles.push_back(q);
+      tiles.push_back(std::min<int32_t>(NBP_QUERY_TILE, q_first[i + 1] - q));
+    }
+  const int32_t *d[4];
+  NBPCHK(stage_columns(c, {{slots, 4 * (size_t)n}, {manifolds, 4 * (size_t)n}, {masks, masks ? 4 * (size_t)n : 0}, {tiles.data(), 4 * tiles.size()}},
+                                d, Q * (NBP_MAXD + 1)));
+  double *dq = c->query, *dd = c->query + Q * NBP_MAXD;
+  HIPCHK(hipMemcpyAsync(dq, queries, sizeof(double) * Q * NBP_MAXD, hipMemcpyHostToDevice, c->stream));
+  const size_t n_tiles = tiles.size() / 3, lds = nbp_eval_lds_bytes(c->N);
+  NBPCHK(masks ? launch_checked(c, nbp_eval_marginal_kernel, n_tiles, NBP_QUERY_TILE, lds, d[3], d[0], d[1], d[2], c->arena, c->N, c->S, dq, dd)
+             : launch_checked(c, nbp_eval_kernel, n_tiles, NBP_QUERY_TILE, lds, d[3], d[0], d[1], c->arena, c->N, c->S, dq, dd));
+  return query_fetch(c, dens_out, dd, sizeof(double) * Q);
 }
 
 // getBelief(fg, :x)(pts) for beliefs resident in slots: the density of each belief's KDE at its own run of query points
-// (nbp_query.h).  One workgroup per tile of at most NBP_QUERY_TILE queries of one belief; one copy each way.
+// (nbp_query.h)
 nbp_status nbp_run_evaluate(nbp_ctx *c, const int32_t *slots, const int32_t *manifolds, int32_t n, const int32_t *q_first,
                             const double *queries, double *dens_out) {
   if (!c || ((!slots || !manifolds || !q_first) && n > 0)) return fail(NBP_ERR_ARG, "null argument");
   if (n <= 0) return NBP_OK;
-  HIPCHK(hipSetDevice(c->device));
   if (q_first[0] != 0) return fail(NBP_ERR_ARG, "evaluate: q_first[0] must be 0");
-  for (int i = 0; i < n; i++) {
-    if (slots[i] < 0 || slots[i] >= c->n_slots) return fail(NBP_ERR_RANGE, "evaluate: slot out of range");
-    if (!manifold_ok(manifolds[i])) return fail(NBP_ERR_ARG, "evaluate: unknown manifold");
-    if (q_first[i + 1] < q_first[i]) return fail(NBP_ERR_ARG, "evaluate: q_first must not decrease");
-  }
-  const size_t Q = (size_t)q_first[n];
-  if (Q == 0) return NBP_OK;
-  if (!queries || !dens_out) return fail(NBP_ERR_ARG, "null argument");
-  std::vector<int32_t> ints(slots, slots + n);
-  ints.insert(ints.end(), manifolds, manifolds + n);
-  for (int i = 0; i < n; i++)
-    for (int32_t q = q_first[i]; q < q_first[i + 1]; q += NBP_QUERY_TILE) {
-      ints.push_back(i);
-      ints.push_back(q);
-      ints.push_back(std::min<int32_t>(NBP_QUERY_TILE, q_first[i + 1] - q));
-    }
-  const size_t tiles = (ints.size() - 2 * (size_t)n) / 3;
-  nbp_status rc = stage_upload(c, ints.data(), ints.size() * 4);  // (waits for the stream: the query buffer is free as well)
-  if (rc) return rc;
-  rc = query_reserve(c, Q * (NBP_MAXD + 1));
-  if (rc) return rc;
-  double *dq = c->query, *dd = c->query + Q * NBP_MAXD;
-  HIPCHK(hipMemcpyAsync(dq, queries, sizeof(double) * Q * NBP_MAXD, hipMemcpyHostToDevice, c->stream));
-  const int32_t *ds = (const int32_t *)c->stage;
-  (void)hipGetLastError();
-  hipLaunchKernelGGL(nbp_eval_kernel, dim3((unsigned)tiles), dim3(NBP_QUERY_TILE), nbp_eval_lds_bytes(c->N), c->stream, ds + 2 * n, ds,
-                     ds + n, c->arena, c->N, c->S, dq, dd);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(dens_out, dd, sizeof(double) * Q, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return NBP_OK;
+  NBPCHK(batch_check(c, "evaluate", {slots}, manifolds, n, [&](int i) {
+    return q_first[i + 1] < q_first[i] ? refusal{NBP_ERR_ARG, "q_first must not decrease"} : refusal{NBP_OK, nullptr};
+  }));
+  return run_point_density(c, slots, manifolds, nullptr, n, q_first, queries, dens_out);
 }
 
 // host-buffer form: stages through slot 0 (which it clobbers), like nbp_kde_ppe
 nbp_status nbp_kde_evaluate(nbp_ctx *c, int32_t manifold, const double *pts, int32_t n_pts, const double *bw, const double *queries,
                             int32_t nq, double *dens_out) {
   if (!c || !pts || !bw || ((!queries || !dens_out) && nq > 0)) return fail(NBP_ERR_ARG, "null argument");
-  if (!manifold_ok(manifold)) return fail(NBP_ERR_ARG, "evaluate: unknown manifold");
-  if (n_pts < 1) return fail(NBP_ERR_ARG, "evaluate: a belief holds at least one point");
+  NBPCHK(kde_check(c, "evaluate", manifold, {{pts, n_pts, bw}}));
   if (nq < 0) return fail(NBP_ERR_ARG, "evaluate: nq < 0");
-  nbp_status rc = nbp_belief_write(c, 0, manifold, pts, n_pts, bw, nullptr);
-  if (rc) return rc;
+  NBPCHK(kde_write(c, manifold, {{pts, n_pts, bw}}));
   const int32_t slot = 0, q_first[2] = {0, nq};
   return nbp_run_evaluate(c, &slot, &manifold, 1, q_first, queries, dens_out);
 }
@@ -1686,8 +1746,7 @@ nbp_status nbp_run_marginal_grid(nbp_ctx *c, const nbp_grid_desc *descs, int32_t
   std::vector<int32_t> tiles;
   for (int i = 0; i < n; i++) {
     int64_t pts = 0;
-    nbp_status rc = grid_desc_check(c, descs[i], i, &pts);
-    if (rc) return rc;
+    NBPCHK(grid_desc_check(c, descs[i], i, &pts));
     if ((int64_t)first[i + 1] - (int64_t)first[i] != pts)
       return fail(NBP_ERR_RANGE, "marginal grid: descriptor " + std::to_string(i) + ": offsets do not match the grid size");
     const bool two = descs[i].dims[1] != -1;
@@ -1700,23 +1759,14 @@ nbp_status nbp_run_marginal_grid(nbp_ctx *c, const nbp_grid_desc *descs, int32_t
       }
   }
   if (!out) return fail(NBP_ERR_ARG, "null argument");
-  const size_t total = (size_t)first[n], n_tiles = tiles.size() / 3;
-  // staging: descriptors (8-byte aligned) | first | tiles
-  const size_t off_first = sizeof(nbp_grid_desc) * (size_t)n, off_tiles = off_first + 4 * ((size_t)n + 1);
-  std::vector<char> blob(off_tiles + 4 * tiles.size());
-  memcpy(blob.data(), descs, off_first);
-  memcpy(blob.data() + off_first, first, 4 * ((size_t)n + 1));
-  memcpy(blob.data() + off_tiles, tiles.data(), 4 * tiles.size());
-  nbp_status rc = stage_upload(c, blob.data(), blob.size());  // (waits for the stream: the query buffer is free as well)
-  if (rc) return rc;
-  rc = query_reserve(c, total + 4 * (size_t)n);
-  if (rc) return rc;
-  const char *ds = (const char *)c->stage;
+  const size_t total = (size_t)first[n];
+  // staging: descriptors | first | tiles
+  const int32_t *d[3];
+  NBPCHK(stage_columns(c, {{descs, sizeof(nbp_grid_desc) * (size_t)n}, {first, 4 * ((size_t)n + 1)}, {tiles.data(), 4 * tiles.size()}}, d,
+                                total + 4 * (size_t)n));
   double *dgrid = c->query, *dext = c->query + total;
-  (void)hipGetLastError();
-  hipLaunchKernelGGL(nbp_marginal_grid_kernel, dim3((unsigned)n_tiles), dim3(NBP_GRID_LANES), 0, c->stream, (const nbp_grid_desc *)ds,
-                     (const int32_t *)(ds + off_first), (const int32_t *)(ds + off_tiles), c->arena, c->N, c->S, dgrid, dext);
-  HIPCHK(hipGetLastError());
+  NBPCHK(launch_checked(c, nbp_marginal_grid_kernel, tiles.size() / 3, NBP_GRID_LANES, 0, (const nbp_grid_desc *)d[0], d[1], d[2], c->arena,
+                      c->N, c->S, dgrid, dext));
   // straight into the caller's buffers (a staging vector of the grids' size costs more than the kernel: profiles/marginal_grid_kernel.txt)
   HIPCHK(hipMemcpyAsync(out, dgrid, sizeof(double) * total, hipMemcpyDeviceToHost, c->stream));
   if (extent_out) HIPCHK(hipMemcpyAsync(extent_out, dext, sizeof(double) * 4 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
@@ -1728,16 +1778,13 @@ nbp_status nbp_run_marginal_grid(nbp_ctx *c, const nbp_grid_desc *descs, int32_t
 nbp_status nbp_kde_marginal_grid(nbp_ctx *c, int32_t manifold, const double *pts, int32_t n_pts, const double *bw,
                                  const nbp_grid_desc *desc, double *out, double *extent_out) {
   if (!c || !pts || !bw || !desc || !out) return fail(NBP_ERR_ARG, "null argument");
-  if (!manifold_ok(manifold)) return fail(NBP_ERR_ARG, "marginal grid: unknown manifold");
-  if (n_pts < 1) return fail(NBP_ERR_ARG, "marginal grid: a belief holds at least one point");
+  NBPCHK(kde_check(c, "marginal grid", manifold, {{pts, n_pts, bw}}));
   nbp_grid_desc g = *desc;
   g.slot = 0;
   g.manifold = manifold;
   int64_t pts_n = 0;
-  nbp_status rc = grid_desc_check(c, g, 0, &pts_n);  // (before slot 0 is touched)
-  if (rc) return rc;
-  rc = nbp_belief_write(c, 0, manifold, pts, n_pts, bw, nullptr);
-  if (rc) return rc;
+  NBPCHK(grid_desc_check(c, g, 0, &pts_n));  // (before slot 0 is touched)
+  NBPCHK(kde_write(c, manifold, {{pts, n_pts, bw}}));
   const int32_t first[2] = {0, (int32_t)pts_n};
   return nbp_run_marginal_grid(c, &g, 1, first, out, extent_out);
 }
@@ -1747,43 +1794,14 @@ nbp_status nbp_run_evaluate_marginal(nbp_ctx *c, const int32_t *slots, const int
                                      const int32_t *q_first, const double *queries, double *dens_out) {
   if (!c || ((!slots || !manifolds || !masks || !q_first) && n > 0)) return fail(NBP_ERR_ARG, "null argument");
   if (n <= 0) return NBP_OK;
-  HIPCHK(hipSetDevice(c->device));
   if (q_first[0] != 0) return fail(NBP_ERR_ARG, "evaluate marginal: q_first[0] must be 0");
-  for (int i = 0; i < n; i++) {
-    const std::string who = "evaluate marginal: belief " + std::to_string(i) + ": ";
-    if (slots[i] < 0 || slots[i] >= c->n_slots) return fail(NBP_ERR_RANGE, who + "slot out of range");
-    if (!manifold_ok(manifolds[i])) return fail(NBP_ERR_ARG, who + "unknown manifold");
-    if (q_first[i + 1] < q_first[i]) return fail(NBP_ERR_ARG, who + "q_first must not decrease");
-    if (masks[i] == 0) return fail(NBP_ERR_RANGE, who + "empty mask");
-    if (masks[i] < 0 || (masks[i] >> manifold_dim_h(manifolds[i])) != 0) return fail(NBP_ERR_RANGE, who + "coordinate outside the manifold");
-  }
-  const size_t Q = (size_t)q_first[n];
-  if (Q == 0) return NBP_OK;
-  if (!queries || !dens_out) return fail(NBP_ERR_ARG, "null argument");
-  std::vector<int32_t> ints(slots, slots + n);
-  ints.insert(ints.end(), manifolds, manifolds + n);
-  ints.insert(ints.end(), masks, masks + n);
-  for (int i = 0; i < n; i++)
-    for (int32_t q = q_first[i]; q < q_first[i + 1]; q += NBP_QUERY_TILE) {
-      ints.push_back(i);
-      ints.push_back(q);
-      ints.push_back(std::min<int32_t>(NBP_QUERY_TILE, q_first[i + 1] - q));
-    }
-  const size_t tiles = (ints.size() - 3 * (size_t)n) / 3;
-  nbp_status rc = stage_upload(c, ints.data(), ints.size() * 4);  // (waits for the stream: the query buffer is free as well)
-  if (rc) return rc;
-  rc = query_reserve(c, Q * (NBP_MAXD + 1));
-  if (rc) return rc;
-  double *dq = c->query, *dd = c->query + Q * NBP_MAXD;
-  HIPCHK(hipMemcpyAsync(dq, queries, sizeof(double) * Q * NBP_MAXD, hipMemcpyHostToDevice, c->stream));
-  const int32_t *ds = (const int32_t *)c->stage;
-  (void)hipGetLastError();
-  hipLaunchKernelGGL(nbp_eval_marginal_kernel, dim3((unsigned)tiles), dim3(NBP_QUERY_TILE), nbp_eval_lds_bytes(c->N), c->stream,
-                     ds + 3 * n, ds, ds + n, ds + 2 * n, c->arena, c->N, c->S, dq, dd);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(dens_out, dd, sizeof(double) * Q, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return NBP_OK;
+  NBPCHK(batch_check(c, "evaluate marginal", {slots}, manifolds, n, [&](int i) {
+    if (q_first[i + 1] < q_first[i]) return refusal{NBP_ERR_ARG, "q_first must not decrease"};
+    if (masks[i] == 0) return refusal{NBP_ERR_RANGE, "empty mask"};
+    if (masks[i] < 0 || (masks[i] >> manifold_dim_h(manifolds[i])) != 0) return refusal{NBP_ERR_RANGE, "coordinate outside the manifold"};
+    return refusal{NBP_OK, nullptr};
+  }));
+  return run_point_density(c, slots, manifolds, masks, n, q_first, queries, dens_out);
 }
 
 // mmd(p1, p2, varType; bw = [sigma]) (services/SolverUtilities.jl:25-47) for pairs of beliefs resident in slots: one workgroup per
@@ -1793,42 +1811,19 @@ nbp_status nbp_run_mmd(nbp_ctx *c, const int32_t *slots_a, const int32_t *slots_
   if (!c || ((!slots_a || !slots_b || !manifolds || !mmd_out) && n > 0)) return fail(NBP_ERR_ARG, "null argument");
   if (!(sigma >= 0.0 && sigma < INFINITY)) return fail(NBP_ERR_ARG, "mmd: sigma must be finite and not negative");
   if (n <= 0) return NBP_OK;
-  HIPCHK(hipSetDevice(c->device));
-  for (int i = 0; i < n; i++) {
-    if (slots_a[i] < 0 || slots_a[i] >= c->n_slots || slots_b[i] < 0 || slots_b[i] >= c->n_slots)
-      return fail(NBP_ERR_RANGE, "mmd: slot out of range");
-    if (!manifold_ok(manifolds[i])) return fail(NBP_ERR_ARG, "mmd: unknown manifold");
-  }
-  std::vector<int32_t> ints(slots_a, slots_a + n);
-  ints.insert(ints.end(), slots_b, slots_b + n);
-  ints.insert(ints.end(), manifolds, manifolds + n);
-  nbp_status rc = stage_upload(c, ints.data(), ints.size() * 4);  // (waits for the stream: the query buffer is free as well)
-  if (rc) return rc;
-  rc = query_reserve(c, (size_t)n);
-  if (rc) return rc;
-  const int32_t *ds = (const int32_t *)c->stage;
-  (void)hipGetLastError();
-  hipLaunchKernelGGL(nbp_mmd_kernel, dim3(n), dim3(c->Npad), nbp_mmd_lds_bytes(c->N), c->stream, ds, ds + n, ds + 2 * n, c->arena, c->N,
-                     c->S, sigma, c->query);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(mmd_out, c->query, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return NBP_OK;
+  NBPCHK(batch_check(c, "mmd", {slots_a, slots_b}, manifolds, n, no_refusal));
+  const int32_t *d[3];
+  NBPCHK(stage_columns(c, {{slots_a, 4 * (size_t)n}, {slots_b, 4 * (size_t)n}, {manifolds, 4 * (size_t)n}}, d, (size_t)n));
+  NBPCHK(launch_checked(c, nbp_mmd_kernel, n, c->Npad, nbp_mmd_lds_bytes(c->N), d[0], d[1], d[2], c->arena, c->N, c->S, sigma, c->query));
+  return query_fetch(c, mmd_out, c->query, sizeof(double) * (size_t)n);
 }
 
 // host-buffer form: stages through slots 0 and 1 (which it clobbers).  The bandwidths play no part in an mmd; the slots carry ones.
 nbp_status nbp_kde_mmd(nbp_ctx *c, int32_t manifold, const double *a, int32_t na, const double *b, int32_t nb, double sigma,
                        double *mmd_out) {
   if (!c || !a || !b || !mmd_out) return fail(NBP_ERR_ARG, "null argument");
-  if (!manifold_ok(manifold)) return fail(NBP_ERR_ARG, "mmd: unknown manifold");
-  if (na < 1 || nb < 1) return fail(NBP_ERR_ARG, "mmd: a belief holds at least one point");
   if (!(sigma >= 0.0 && sigma < INFINITY)) return fail(NBP_ERR_ARG, "mmd: sigma must be finite and not negative");
-  if (c->n_slots < 2) return fail(NBP_ERR_RANGE, "mmd: the context needs two slots");
-  const double ones[NBP_MAXD] = {1.0, 1.0, 1.0};
-  nbp_status rc = nbp_belief_write(c, 0, manifold, a, na, ones, nullptr);
-  if (rc) return rc;
-  rc = nbp_belief_write(c, 1, manifold, b, nb, ones, nullptr);
-  if (rc) return rc;
+  NBPCHK(kde_stage(c, "mmd", manifold, {{a, na, nullptr}, {b, nb, nullptr}}));
   const int32_t sa = 0, sb = 1;
   return nbp_run_mmd(c, &sa, &sb, &manifold, 1, sigma, mmd_out);
 }
@@ -1837,26 +1832,14 @@ nbp_status nbp_kde_mmd(nbp_ctx *c, int32_t manifold, const double *a, int32_t na
 nbp_status nbp_run_meancov(nbp_ctx *c, const int32_t *slots, const int32_t *manifolds, int32_t n, double *mean_out, double *cov_out) {
   if (!c || ((!slots || !manifolds || !mean_out || !cov_out) && n > 0)) return fail(NBP_ERR_ARG, "null argument");
   if (n <= 0) return NBP_OK;
-  HIPCHK(hipSetDevice(c->device));
-  for (int i = 0; i < n; i++) {
-    if (slots[i] < 0 || slots[i] >= c->n_slots) return fail(NBP_ERR_RANGE, "meancov: slot out of range");
-    if (!manifold_ok(manifolds[i])) return fail(NBP_ERR_ARG, "meancov: unknown manifold");
-  }
-  std::vector<int32_t> both(slots, slots + n);
-  both.insert(both.end(), manifolds, manifolds + n);
-  nbp_status rc = stage_upload(c, both.data(), both.size() * 4);  // (waits for the stream: the query buffer is free as well)
-  if (rc) return rc;
+  NBPCHK(batch_check(c, "meancov", {slots}, manifolds, n, no_refusal));
   static_assert(sizeof(nbp_meancov_rec) == sizeof(double) * (NBP_MAXD + NBP_MAXD * NBP_MAXD), "nbp_meancov_rec is packed doubles");
-  rc = query_reserve(c, (size_t)n * (sizeof(nbp_meancov_rec) / sizeof(double)));
-  if (rc) return rc;
-  const int32_t *ds = (const int32_t *)c->stage;
-  (void)hipGetLastError();
-  hipLaunchKernelGGL(nbp_meancov_kernel, dim3(n), dim3(c->Npad), nbp_meancov_lds_bytes(c->N), c->stream, ds, ds + n, c->arena, c->N, c->S,
-                     (nbp_meancov_rec *)c->query);
-  HIPCHK(hipGetLastError());
+  const int32_t *d[2];
+  NBPCHK(stage_columns(c, {{slots, 4 * (size_t)n}, {manifolds, 4 * (size_t)n}}, d, (size_t)n * (sizeof(nbp_meancov_rec) / sizeof(double))));
+  NBPCHK(launch_checked(c, nbp_meancov_kernel, n, c->Npad, nbp_meancov_lds_bytes(c->N), d[0], d[1], c->arena, c->N, c->S,
+                      (nbp_meancov_rec *)c->query));
   std::vector<nbp_meancov_rec> rec((size_t)n);
-  HIPCHK(hipMemcpyAsync(rec.data(), c->query, sizeof(nbp_meancov_rec) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
+  NBPCHK(query_fetch(c, rec.data(), c->query, sizeof(nbp_meancov_rec) * (size_t)n));
   for (int i = 0; i < n; i++) {
     memcpy(mean_out + (size_t)i * NBP_MAXD, rec[i].mean, sizeof(rec[i].mean));
     memcpy(cov_out + (size_t)i * NBP_MAXD * NBP_MAXD, rec[i].cov, sizeof(rec[i].cov));
@@ -1867,15 +1850,10 @@ nbp_status nbp_run_meancov(nbp_ctx *c, const int32_t *slots, const int32_t *mani
 // host-buffer form: stages through slot 0 (which it clobbers), like nbp_kde_ppe.  The bandwidth plays no part; the slot carries ones.
 nbp_status nbp_kde_meancov(nbp_ctx *c, int32_t manifold, const double *pts, int32_t n_pts, double *mean_out, double *cov_out) {
   if (!c || !pts || !mean_out || !cov_out) return fail(NBP_ERR_ARG, "null argument");
-  if (!manifold_ok(manifold)) return fail(NBP_ERR_ARG, "meancov: unknown manifold");
-  if (n_pts < 1) return fail(NBP_ERR_ARG, "meancov: a belief holds at least one point");
-  const double ones[NBP_MAXD] = {1.0, 1.0, 1.0};
-  nbp_status rc = nbp_belief_write(c, 0, manifold, pts, n_pts, ones, nullptr);
-  if (rc) return rc;
+  NBPCHK(kde_stage(c, "meancov", manifold, {{pts, n_pts, nullptr}}));
   const int32_t slot = 0;
   double mean3[NBP_MAXD], cov9[NBP_MAXD * NBP_MAXD];
-  rc = nbp_run_meancov(c, &slot, &manifold, 1, mean3, cov9);
-  if (rc) return rc;
+  NBPCHK(nbp_run_meancov(c, &slot, &manifold, 1, mean3, cov9));
   const int D = manifold_dim_h(manifold);
   for (int k = 0; k < D; k++) {
     mean_out[k] = mean3[k];
@@ -1890,28 +1868,14 @@ nbp_status nbp_run_kld(nbp_ctx *c, const int32_t *slots_a, const int32_t *slots_
                        double *terms_out) {
   if (!c || ((!slots_a || !slots_b || !manifolds || !kld_out) && n > 0)) return fail(NBP_ERR_ARG, "null argument");
   if (n <= 0) return NBP_OK;
-  HIPCHK(hipSetDevice(c->device));
-  for (int i = 0; i < n; i++) {
-    if (slots_a[i] < 0 || slots_a[i] >= c->n_slots || slots_b[i] < 0 || slots_b[i] >= c->n_slots)
-      return fail(NBP_ERR_RANGE, "kld: slot out of range");
-    if (!manifold_ok(manifolds[i])) return fail(NBP_ERR_ARG, "kld: unknown manifold");
-  }
-  std::vector<int32_t> ints(slots_a, slots_a + n);
-  ints.insert(ints.end(), slots_b, slots_b + n);
-  ints.insert(ints.end(), manifolds, manifolds + n);
-  nbp_status rc = stage_upload(c, ints.data(), ints.size() * 4);  // (waits for the stream: the query buffer is free as well)
-  if (rc) return rc;
+  NBPCHK(batch_check(c, "kld", {slots_a, slots_b}, manifolds, n, no_refusal));
   static_assert(sizeof(nbp_kld_rec) == sizeof(double) * 3, "nbp_kld_rec is packed doubles");
-  rc = query_reserve(c, (size_t)n * 3);
-  if (rc) return rc;
-  const int32_t *ds = (const int32_t *)c->stage;
-  (void)hipGetLastError();
-  hipLaunchKernelGGL(nbp_kld_kernel, dim3(n), dim3(c->Npad), nbp_kld_lds_bytes(c->N), c->stream, ds, ds + n, ds + 2 * n, c->arena, c->N,
-                     c->S, (nbp_kld_rec *)c->query);
-  HIPCHK(hipGetLastError());
+  const int32_t *d[3];
+  NBPCHK(stage_columns(c, {{slots_a, 4 * (size_t)n}, {slots_b, 4 * (size_t)n}, {manifolds, 4 * (size_t)n}}, d, (size_t)n * 3));
+  NBPCHK(launch_checked(c, nbp_kld_kernel, n, c->Npad, nbp_kld_lds_bytes(c->N), d[0], d[1], d[2], c->arena, c->N, c->S,
+                      (nbp_kld_rec *)c->query));
   std::vector<nbp_kld_rec> rec((size_t)n);
-  HIPCHK(hipMemcpyAsync(rec.data(), c->query, sizeof(nbp_kld_rec) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
+  NBPCHK(query_fetch(c, rec.data(), c->query, sizeof(nbp_kld_rec) * (size_t)n));
   for (int i = 0; i < n; i++) {
     kld_out[i] = rec[i].kld;
     if (terms_out) {
@@ -1926,13 +1890,7 @@ nbp_status nbp_run_kld(nbp_ctx *c, const int32_t *slots_a, const int32_t *slots_
 nbp_status nbp_kde_kld(nbp_ctx *c, int32_t manifold, const double *a, int32_t na, const double *bw_a, const double *b, int32_t nb,
                        const double *bw_b, double *kld_out, double *terms_out) {
   if (!c || !a || !bw_a || !b || !bw_b || !kld_out) return fail(NBP_ERR_ARG, "null argument");
-  if (!manifold_ok(manifold)) return fail(NBP_ERR_ARG, "kld: unknown manifold");
-  if (na < 1 || nb < 1) return fail(NBP_ERR_ARG, "kld: a belief holds at least one point");
-  if (c->n_slots < 2) return fail(NBP_ERR_RANGE, "kld: the context needs two slots");
-  nbp_status rc = nbp_belief_write(c, 0, manifold, a, na, bw_a, nullptr);
-  if (rc) return rc;
-  rc = nbp_belief_write(c, 1, manifold, b, nb, bw_b, nullptr);
-  if (rc) return rc;
+  NBPCHK(kde_stage(c, "kld", manifold, {{a, na, bw_a}, {b, nb, bw_b}}));
   const int32_t sa = 0, sb = 1;
   return nbp_run_kld(c, &sa, &sb, &manifold, 1, kld_out, terms_out);
 }
@@ -1940,19 +1898,10 @@ nbp_status nbp_kde_kld(nbp_ctx *c, int32_t manifold, const double *a, int32_t na
 nbp_status nbp_run_resample(nbp_ctx *c, const int32_t *slots, const int32_t *manifolds, int32_t n, uint64_t seed) {
   if (!c || ((!slots || !manifolds) && n > 0)) return fail(NBP_ERR_ARG, "null argument");
   if (n <= 0) return NBP_OK;
-  HIPCHK(hipSetDevice(c->device));
-  for (int i = 0; i < n; i++) {
-    if (slots[i] < 0 || slots[i] >= c->n_slots) return fail(NBP_ERR_RANGE, "resample: slot out of range");
-    if (!manifold_ok(manifolds[i])) return fail(NBP_ERR_ARG, "resample: unknown manifold");
-  }
-  std::vector<int32_t> both(slots, slots + n);
-  both.insert(both.end(), manifolds, manifolds + n);
-  nbp_status rc = stage_upload(c, both.data(), both.size() * 4);
-  if (rc) return rc;
-  const int32_t *ds = (const int32_t *)c->stage;
-  (void)hipGetLastError();
-  hipLaunchKernelGGL(nbp_resample_kernel, dim3(n), dim3(256), 0, c->stream, ds, ds + n, c->arena, c->N, c->S, seed);
-  HIPCHK(hipGetLastError());
+  NBPCHK(batch_check(c, "resample", {slots}, manifolds, n, no_refusal));
+  const int32_t *d[2];
+  NBPCHK(stage_columns(c, {{slots, 4 * (size_t)n}, {manifolds, 4 * (size_t)n}}, d, 0));
+  NBPCHK(launch_checked(c, nbp_resample_kernel, n, 256, 0, d[0], d[1], c->arena, c->N, c->S, seed));
   HIPCHK(hipStreamSynchronize(c->stream));
   return NBP_OK;
 }

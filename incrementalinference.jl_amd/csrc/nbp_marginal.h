@@ -1,10 +1,10 @@
 // nbp_marginal.h -- marginal densities of resident beliefs: on a regular 1-D or 2-D grid over a subset K of the manifold's
 // coordinates (the x-y picture of a pose, the 1-D picture of one coordinate) and at arbitrary query points.  DESIGN.md 3 holds
 // the definitions; coordinates are tangent coordinates at the identity (SE(2): x, y, theta), as in nbp_query.h.
-//   marginal  p_K(q) = 1 / (c prod_{d in K} sqrt(2 pi) h_d) * sum_{j < c} exp(-1/2 sum_{d in K} (delta_d(q, x_j) / h_d)^2), delta
-//             wrapped to [-pi, pi) on circular coordinates: the density of nbp_query.h with the coordinates outside K dropped
-//             (integrating a coordinate out of a product-kernel KDE is dropping it).  Only the bandwidth entries IN K must be
-//             positive and finite (else every value is NaN); the others are not read: a partial belief has a marginal.
+//   marginal  p_K(q) = 1 / norm * sum_{j < c} exp(e(q, x_j)), e and norm the exponent and the normalisation of nbp_kde.h over the
+//             coordinates in K: the density of nbp_query.h with the coordinates outside K dropped (integrating a coordinate out
+//             of a product-kernel KDE is dropping it).  Only the bandwidth entries IN K must be positive and finite (else every
+//             value is NaN); the others are not read: a partial belief has a marginal.
 //   grid      point k of axis a is lo_a + (double)k * step_a; the output is row-major, the first listed coordinate slowest.
 //             E_a[k][j] = exp_nonpos(-1/2 (((g_a[k] - x_j[d_a]) wrapped where circular) * (1 / h_a))^2), the per-axis arithmetic
 //             of nbp_eval_kernel; 2-D value = (sum_j E_0[k0][j] * E_1[k1][j]) / norm, 1-D value = (sum_j E_0[k0][j]) / norm,
@@ -18,9 +18,8 @@
 // (grid point, particle) pair is one multiplication and one addition.  DEFINED here, unpinned against KernelDensityEstimate.jl
 // (DESIGN.md 8).
 #pragma once
-#include "nbp_query.h"
-
-#define NBP_TU_MARGINAL 16384  // the marginal kernels (nbp_k_marginal.hip)
+#include "nbp_kde.h"
+#include "nbp_query.h"  // eval_body; NBP_TU_MARGINAL
 
 #define NBP_GRID_TILE 32    // 2-D: grid points per axis of one tile
 #define NBP_GRID_RB 4       // 2-D: a lane owns RB x RB points of the tile (8 x 8 lanes: one wave per tile)
@@ -102,7 +101,7 @@ nbp_marginal_grid_kernel(NBP_GRID_ARGS) {
     extent[4 * gi + 3] = st1;
   }
   double *o = out + first[gi];
-  const bool valid = h0 > 0.0 && h0 < INFINITY && h1 > 0.0 && h1 < INFINITY;
+  const bool valid = kde_bw_ok(h0) & kde_bw_ok(h1);
   const double qnan = __longlong_as_double(0x7ff8000000000000ll);
   double norm = (double)c;  // the eval kernel's order: ascending coordinates
   if (!two) {
@@ -171,58 +170,11 @@ nbp_marginal_grid_kernel(NBP_GRID_ARGS) {
     }
 }
 
-// nbp_eval_kernel's loop with the coordinates outside the mask skipped: the same exp_nonpos of the summed exponent, the same
-// operations in the same order on the coordinates that stay, so that the full mask delivers nbp_eval_kernel's values bit for bit.
+// nbp_eval_kernel's body with the belief's mask in place of the constant 7: one function, so the full mask delivers
+// nbp_eval_kernel's values bit for bit.
 __global__ void __launch_bounds__(NBP_QUERY_TILE)
 nbp_eval_marginal_kernel(NBP_EVAL_MARGINAL_ARGS) {
-  extern __shared__ double smem[];
-  double *tab = smem, *X = smem + NBP_EXPTAB;
-  const int b = tiles[3 * blockIdx.x], q0 = tiles[3 * blockIdx.x + 1], nq = tiles[3 * blockIdx.x + 2];
-  const double *s = arena + S * slots[b];
-  const int M = manifolds[b], D = mani_dim(M), t = threadIdx.x, K = masks[b];
-  const bool k0 = K & 1, k1 = D > 1 && (K & 2), k2 = D > 2 && (K & 4);  // block-uniform
-  const int c = slot_count(s, N);
-  nbp_exp_tab_init(tab);
-  for (int i = t; i < c; i += blockDim.x)
-    for (int k = 0; k < D; k++) X[k * N + i] = s[k * N + i];
-  __syncthreads();
-  const double h0 = k0 ? s[3 * N] : 1.0, h1 = k1 ? s[3 * N + 1] : 1.0, h2 = k2 ? s[3 * N + 2] : 1.0;
-  const bool valid = h0 > 0.0 && h0 < INFINITY && h1 > 0.0 && h1 < INFINITY && h2 > 0.0 && h2 < INFINITY;
-  if (t >= nq) return;
-  double p = __longlong_as_double(0x7ff8000000000000ll);
-  if (valid) {
-    const double *q = queries + (size_t)NBP_MAXD * (size_t)(q0 + t);
-    const double r0 = 1.0 / h0, r1 = 1.0 / h1, r2 = 1.0 / h2;
-    const bool c0 = is_circ(M, 0), c2 = is_circ(M, 2);
-    const double x0 = k0 ? q[0] : 0.0, x1 = k1 ? q[1] : 0.0, x2 = k2 ? q[2] : 0.0;
-    p = 0.0;
-    for (int j = 0; j < c; j++) {
-      double e = 0.0;  // (0 + d d = d d exactly: the first coordinate that stays enters as in the eval kernel)
-      if (k0) {
-        double d0 = x0 - X[j];
-        if (c0) d0 = wrap_pi(d0);
-        d0 *= r0;
-        e = d0 * d0;
-      }
-      if (k1) {
-        const double d1 = (x1 - X[N + j]) * r1;
-        e += d1 * d1;
-      }
-      if (k2) {
-        double d2 = x2 - X[2 * N + j];
-        if (c2) d2 = wrap_pi(d2);
-        d2 *= r2;
-        e += d2 * d2;
-      }
-      p += exp_nonpos(-0.5 * e, tab);
-    }
-    double norm = (double)c;
-    if (k0) norm *= NBP_SQRT_2PI * h0;
-    if (k1) norm *= NBP_SQRT_2PI * h1;
-    if (k2) norm *= NBP_SQRT_2PI * h2;
-    p /= norm;
-  }
-  dens[q0 + t] = p;
+  eval_body(tiles, slots, manifolds, arena, N, S, queries, dens, masks[tiles[3 * blockIdx.x]]);
 }
 #else
 __global__ void nbp_marginal_grid_kernel(NBP_GRID_ARGS);

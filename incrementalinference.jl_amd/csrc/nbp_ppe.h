@@ -2,12 +2,13 @@
 // every setValKDE! (services/FactorGraph.jl:200-213).  DESIGN.md 3 holds the definition:
 //   mean[d]   = mean(M, pts, GeodesicInterpolation()) of coordinate d over the points the belief holds (mean_geodesic_coord, the
 //               function the proposals' spread statistics call, in the workgroup shape they call it in)
-//   p_i       = sum_{j < c} exp(-1/2 sum_d (delta_d(i, j) / h_d)^2), delta wrapped to [-pi, pi) on circular coordinates, the self
-//               term included, no normalisation, j = 0 .. c - 1 in that order (one lane adds one p_i: reproducible bit for bit)
+//   p_i       = sum_{j < c} exp(e(x_i, x_j)), e the exponent of nbp_kde.h over all D coordinates, the self term included, no
+//               normalisation, j = 0 .. c - 1 in that order (one lane adds one p_i: reproducible bit for bit)
 //   max_index = the smallest i whose p_i is the greatest (Julia's argmax); max = that point, copied
 // A bandwidth entry that is not a positive finite number: max = NaN, max_index = -1; the mean is delivered all the same.
 #pragma once
 #include "nbp_kernels.h"
+#include "nbp_kde.h"
 
 #define NBP_TU_PPE 2048  // the point-estimate kernel (nbp_k_ppe.hip)
 
@@ -40,7 +41,7 @@ nbp_ppe_kernel(NBP_PPE_ARGS) {
   const double mu1 = D > 1 ? mean_geodesic_coord(X + N, c, M, 1, red) : 0.0;
   const double mu2 = D > 2 ? mean_geodesic_coord(X + 2 * N, c, M, 2, red) : 0.0;
   const double h0 = s[3 * N], h1 = D > 1 ? s[3 * N + 1] : 1.0, h2 = D > 2 ? s[3 * N + 2] : 1.0;
-  const bool valid = h0 > 0.0 && h0 < INFINITY && h1 > 0.0 && h1 < INFINITY && h2 > 0.0 && h2 < INFINITY;  // block-uniform
+  const bool valid = kde_bw_ok(h0) & kde_bw_ok(h1) & kde_bw_ok(h2);  // block-uniform
   double p = -INFINITY;
   int best = 0x7fffffff;
   if (valid && n < c) {
@@ -49,23 +50,7 @@ nbp_ppe_kernel(NBP_PPE_ARGS) {
     const double x0 = X[n], x1 = D > 1 ? X[N + n] : 0.0, x2 = D > 2 ? X[2 * N + n] : 0.0;
     p = 0.0;
     best = n;
-    for (int j = 0; j < c; j++) {
-      double d0 = x0 - X[j];
-      if (c0) d0 = wrap_pi(d0);
-      d0 *= r0;
-      double q = d0 * d0;
-      if (D > 1) {
-        const double d1 = (x1 - X[N + j]) * r1;
-        q += d1 * d1;
-      }
-      if (D > 2) {
-        double d2 = x2 - X[2 * N + j];
-        if (c2) d2 = wrap_pi(d2);
-        d2 *= r2;
-        q += d2 * d2;
-      }
-      p += exp_nonpos(-0.5 * q, tab);
-    }
+    for (int j = 0; j < c; j++) p += exp_nonpos(kde_exponent(x0, x1, x2, X, N, j, true, D > 1, D > 2, c0, c2, r0, r1, r2), tab);
   }
   // argmax on (value, index): the greater value, the lower index among equals -- inside the wave, then across the waves
 #pragma unroll

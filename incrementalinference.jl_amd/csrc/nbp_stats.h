@@ -10,9 +10,9 @@
 //                observation); the mean is delivered all the same.  The bandwidth plays no part.
 //   SE(2): the deviations are taken in the world frame about the mean, heading wrapped -- not the Lie-algebra coordinates at the
 //                mean of Manifolds.jl's cov(M, pts; basis).  DEFINED here, unpinned.
-//   l_p(x)     = M + log(sum_{j < m} exp(e_j - M)) - log(m prod_d sqrt(2 pi) h_d) for a belief p of m points y_j and bandwidth h,
-//                e_j = -1/2 sum_d (delta_d(x, y_j) / h_d)^2, M = max_j e_j; j = 0 .. m - 1 in that order in one lane (two passes:
-//                the maximum, then the sum).  The logarithm of the density nbp_run_evaluate defines, finite where that density
+//   l_p(x)     = M + log(sum_{j < m} exp(e_j - M)) - log(norm) for a belief p of m points y_j and bandwidth h, e_j = e(x, y_j) and
+//                norm the exponent and the normalisation of nbp_kde.h, M = max_j e_j; j = 0 .. m - 1 in that order in one lane (two
+//                passes: the maximum, then the sum).  The logarithm of the density nbp_run_evaluate defines, finite where that density
 //                underflows to zero.
 //   kld(a, b)  = Eaa - Eab, Eaa = (1 / n) sum_{i < n} l_a(a_i) (the self term stays in), Eab = (1 / n) sum_{i < n} l_b(a_i); both
 //                means in one summation order (lane i, block_sum), both l from one device function: a belief against a
@@ -21,7 +21,7 @@
 //                from memory of KernelDensityEstimate.jl's direct kld and is unpinned.
 #pragma once
 #include "nbp_kernels.h"
-#include "nbp_query.h"  // NBP_SQRT_2PI
+#include "nbp_kde.h"
 
 #define NBP_TU_STATS 8192  // the belief-statistics kernels (nbp_k_stats.hip)
 
@@ -104,37 +104,16 @@ nbp_meancov_kernel(NBP_MEANCOV_ARGS) {
   }
 }
 
-// e_j of the definition: -1/2 sum_d (delta_d(x, y_j) r_d)^2 with r_d = 1 / h_d (the kernel of nbp_eval_kernel)
-__device__ __forceinline__ double stats_log_kernel(double x0, double x1, double x2, const double *Y, int N, int j, int D, bool c0,
-                                                   bool c2, double r0, double r1, double r2) {
-  double d0 = x0 - Y[j];
-  if (c0) d0 = wrap_pi(d0);
-  d0 *= r0;
-  double e = d0 * d0;
-  if (D > 1) {
-    const double d1 = (x1 - Y[N + j]) * r1;
-    e += d1 * d1;
-  }
-  if (D > 2) {
-    double d2 = x2 - Y[2 * N + j];
-    if (c2) d2 = wrap_pi(d2);
-    d2 *= r2;
-    e += d2 * d2;
-  }
-  return -0.5 * e;
-}
-
 // l_p(x): the one function, and the one order, behind Eaa and Eab.  cnt >= 1; h positive and finite (the caller has checked).
 __device__ __forceinline__ double stats_log_density(double x0, double x1, double x2, const double *Y, int N, int cnt, int D, bool c0,
                                                     bool c2, double h0, double h1, double h2, const double *tab) {
   const double r0 = 1.0 / h0, r1 = 1.0 / h1, r2 = 1.0 / h2;
+  const bool k1 = D > 1, k2 = D > 2;
   double mx = -INFINITY;
-  for (int j = 0; j < cnt; j++) mx = fmax(mx, stats_log_kernel(x0, x1, x2, Y, N, j, D, c0, c2, r0, r1, r2));
+  for (int j = 0; j < cnt; j++) mx = fmax(mx, kde_exponent(x0, x1, x2, Y, N, j, true, k1, k2, c0, c2, r0, r1, r2));
   double acc = 0.0;
-  for (int j = 0; j < cnt; j++) acc += exp_nonpos(stats_log_kernel(x0, x1, x2, Y, N, j, D, c0, c2, r0, r1, r2) - mx, tab);
-  double norm = (double)cnt * (NBP_SQRT_2PI * h0);
-  if (D > 1) norm *= NBP_SQRT_2PI * h1;
-  if (D > 2) norm *= NBP_SQRT_2PI * h2;
+  for (int j = 0; j < cnt; j++) acc += exp_nonpos(kde_exponent(x0, x1, x2, Y, N, j, true, k1, k2, c0, c2, r0, r1, r2) - mx, tab);
+  const double norm = kde_norm(cnt, true, k1, k2, h0, h1, h2);
   return mx + nbpm_log(acc) - nbpm_log(norm);
 }
 
@@ -156,8 +135,7 @@ nbp_kld_kernel(NBP_KLD_ARGS) {
   __syncthreads();
   const double ha0 = sa[3 * N], ha1 = D > 1 ? sa[3 * N + 1] : 1.0, ha2 = D > 2 ? sa[3 * N + 2] : 1.0;
   const double hb0 = sb[3 * N], hb1 = D > 1 ? sb[3 * N + 1] : 1.0, hb2 = D > 2 ? sb[3 * N + 2] : 1.0;
-  const bool valid = ha0 > 0.0 && ha0 < INFINITY && ha1 > 0.0 && ha1 < INFINITY && ha2 > 0.0 && ha2 < INFINITY &&
-                     hb0 > 0.0 && hb0 < INFINITY && hb1 > 0.0 && hb1 < INFINITY && hb2 > 0.0 && hb2 < INFINITY;  // block-uniform
+  const bool valid = kde_bw_ok(ha0) & kde_bw_ok(ha1) & kde_bw_ok(ha2) & kde_bw_ok(hb0) & kde_bw_ok(hb1) & kde_bw_ok(hb2);  // block-uniform
   double la = 0.0, lb = 0.0;
   if (valid && n < ca) {
     const bool c0 = is_circ(M, 0), c2 = is_circ(M, 2);

@@ -164,75 +164,70 @@ class SolveSession:
         self.stats["last"]["readbacks"] += len(wanted)
 
     # ---- statistics of the resident beliefs ------------------------------------------------------------------------------
-    def calcMeanCovar(self, labels=None):
-        """calcMeanCovar (VariableStatistics.jl:39-44) of the variables' current beliefs -> {label: (mu[D], Sigma[D, D])}; labels:
-        default every variable the last solve worked on.  On libnbp the beliefs the residency table holds as current are read
-        where they lie, in ONE launch (`run_meancov`): no belief travels and `stats` does not move.  A belief that is not
-        resident (edited on the host since, or invalidated) goes up first by the session's upload path and is counted as an
-        upload.  A variable that has no slot in the session's context (never part of a solve), or a backend without
-        `run_meancov`: `beliefstats.calcMeanCovar` on the host copy."""
-        from . import beliefstats
+    def _query_resident(self, labels, method, args, pick, host):
+        """One query of the variables' current beliefs -> {label: result} in the order of `labels` (default: every variable the
+        last solve worked on).  On a backend that has `method`, the beliefs the residency table holds as current are read where
+        they lie, in ONE call `method(*args(here, place))` -- here: the labels that have a slot, place: label -> slot -- and
+        `pick(result, i, label)` is what that call holds for here[i]: no belief travels and `stats` does not move.  A belief that
+        is not resident (edited on the host since, or invalidated) goes up first by the session's upload path and is counted as
+        an upload.  `host(label, **kw)` is the same query on the host copy: for every label where there is no context or the
+        backend lacks `method`, and with backend=self.backend for a variable that has no slot in the session's context (never
+        part of a solve)."""
         if self._closed:
             raise RuntimeError("this SolveSession is closed")
         labels = list(self._labels if labels is None else labels)
         be = self._be
         place = {v: i for i, v in enumerate(self._labels)}
+        if be is None or getattr(be, method, None) is None:
+            return {v: host(v) for v in labels}
         out = {}
-        if be is None or getattr(be, "run_meancov", None) is None:
-            return {v: beliefstats.calcMeanCovar(self.fg, v) for v in labels}
         here = [v for v in labels if v in place]
         if here:
             try:
                 self._upload(self.fg, [(v, place[v]) for v in here], len(self._labels))
-                mans = [self.fg.getVariable(v).varType.manifold for v in here]
-                mean, cov = be.run_meancov([place[v] for v in here], mans)
+                res = getattr(be, method)(*args(here, place))
             except BaseException:
                 self._table.clear()  # the device state is unknown: the host copy wins
                 raise
             for i, v in enumerate(here):
-                D = self.fg.getVariable(v).varType.dim
-                out[v] = (mean[i, :D].copy(), cov[i, :D, :D].copy())
+                out[v] = pick(res, i, v)
         for v in labels:
             if v not in place:
-                out[v] = beliefstats.calcMeanCovar(self.fg, v, backend=self.backend)
+                out[v] = host(v, backend=self.backend)
         return {v: out[v] for v in labels}
+
+    def calcMeanCovar(self, labels=None):
+        """calcMeanCovar (VariableStatistics.jl:39-44) of the variables' current beliefs -> {label: (mu[D], Sigma[D, D])}, served
+        by ONE `run_meancov` launch where libnbp holds the beliefs (`_query_resident`); on the host copy,
+        `beliefstats.calcMeanCovar`."""
+        from . import beliefstats
+        var = self.fg.getVariable
+
+        def pick(res, i, v):
+            D = var(v).varType.dim
+            return res[0][i, :D].copy(), res[1][i, :D, :D].copy()
+        return self._query_resident(labels, "run_meancov",
+                                    lambda here, place: ([place[v] for v in here], [var(v).varType.manifold for v in here]), pick,
+                                    lambda v, **kw: beliefstats.calcMeanCovar(self.fg, v, **kw))
 
     def marginalGrid(self, labels=None, dims=(1,), n=64, margin=4.0):
         """The marginal densities of the variables' current beliefs on regular grids with the automatic extent (marginal.py) ->
         {label: (grid, axes)}.  dims: one or two coordinates, 1-BASED like the reference's `partial`; n: points per axis (a scalar:
-        the same on both); labels: default every variable the last solve worked on whose manifold has the coordinates `dims`.  On
-        libnbp all of them are served where they lie by ONE `run_marginal_grid`: no belief travels and `stats` does not move
-        (a belief that is not resident goes up first and is counted, as in `calcMeanCovar`).  A variable without a slot in the
-        session's context, or a backend without `run_marginal_grid`: `marginal.marginalGrid` on the host copy."""
+        the same on both); labels: default every variable the last solve worked on whose manifold has the coordinates `dims`.
+        Served by ONE `run_marginal_grid` where libnbp holds the beliefs (`_query_resident`); on the host copy,
+        `marginal.marginalGrid`."""
         from . import marginal
-        if self._closed:
-            raise RuntimeError("this SolveSession is closed")
         dims = tuple(int(d) for d in (dims if hasattr(dims, "__len__") else (dims,)))
         nn = [int(v) for v in (n if hasattr(n, "__len__") else (n,))]
         nn = nn * len(dims) if len(nn) == 1 else nn
-        if labels is None:
-            labels = [v for v in self._labels if self.fg.getVariable(v).varType.dim >= max(dims)]
-        labels = list(labels)
-        be = self._be
-        place = {v: i for i, v in enumerate(self._labels)}
-        if be is None or getattr(be, "run_marginal_grid", None) is None:
-            return {v: marginal.marginalGrid(self.fg, v, dims, nn, None, margin) for v in labels}
-        out = {}
-        here = [v for v in labels if v in place]
-        if here:
-            try:
-                self._upload(self.fg, [(v, place[v]) for v in here], len(self._labels))
-                grids, ext = be.run_marginal_grid([(place[v], self.fg.getVariable(v).varType.manifold, [d - 1 for d in dims], nn, None,
-                                                    margin) for v in here], return_extent=True)
-            except BaseException:
-                self._table.clear()  # the device state is unknown: the host copy wins
-                raise
-            for i, v in enumerate(here):
-                out[v] = (grids[i].copy(), marginal.grid_axes(ext[i], nn))
-        for v in labels:
-            if v not in place:
-                out[v] = marginal.marginalGrid(self.fg, v, dims, nn, None, margin, backend=self.backend)
-        return {v: out[v] for v in labels}
+        var = self.fg.getVariable
+        if labels is None:  # (a generator: read behind the closed check)
+            labels = (v for v in self._labels if var(v).varType.dim >= max(dims))
+        return self._query_resident(labels, "run_marginal_grid",
+                                    lambda here, place: ([(place[v], var(v).varType.manifold, [d - 1 for d in dims], nn, None, margin)
+                                                          for v in here], True),
+                                    lambda res, i, v: (res[0][i].copy(), marginal.grid_axes(res[1][i], nn)),
+                                    lambda v, **kw: marginal.marginalGrid(self.fg, v, dims, nn, None, margin, **kw))
 
     # ---- one solve ---------------------------------------------------------------------------------------------------------
     def solve(self, seed=0, eliminationOrder=None, ordering="qr", return_timing=False):
