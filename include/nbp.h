@@ -380,6 +380,38 @@ nbp_status nbp_run_kld(nbp_ctx *ctx, const int32_t *slots_a, const int32_t *slot
 /* host-buffer form: stages through slots 0 and 1 */
 nbp_status nbp_kde_kld(nbp_ctx *ctx, int32_t manifold, const double *a_NxP, int32_t na, const double *bw_a_D, const double *b_NxP,
                        int32_t nb, const double *bw_b_D, double *kld_out, double *terms_out_2 /* nullable */);
+/* ---- heatmap densities ("Heatmap densities"; the deviations from the reference: DESIGN.md 8) --------------------------
+ * HeatmapGridDensity / LevelSetGridNormal (ext/HeatmapSampler.jl:123-242): a scalar field on a regular x-y grid turned into a
+ * samplable density, the measurement model of the pass-through prior (NBP_F_PASSTHROUGH).  data[i * ny + j] is the field at
+ * (x[i], y[j]).  The arithmetic -- cell weights and the fixed-order prefix sum, the inverse-CDF draws, the bilinear formula, the
+ * weights exp(-(d - dmin)) -- is written once in csrc/nbp_heatmap.h and restated in heatmap.py.  Everything runs on the context's
+ * stream; a call with host outputs returns after they are filled.  A heatmap does not outlive its context: nbp_ctx_destroy frees
+ * what it holds on the device, after which only nbp_heatmap_destroy accepts the handle.
+ *
+ * nbp_heatmap_create   sampleHeatmap(field, x, y, 0) and the bandwidth of fitKDE (:123-159): checks the grid ON THE HOST, before
+ *                      anything is allocated or launched -- nx, ny >= 2, nx * ny <= 2^26, x and y strictly increasing with uniform
+ *                      spacing (|x[i+1] - x[i] - dx| <= 1e-9 |dx|, dx = (x[nx-1] - x[0]) / (nx - 1)), every datum finite, at least
+ *                      one positive, bw_factor positive and finite: else NBP_ERR_INVALID (the sizes are looked at before the
+ *                      pointers) --, uploads the field and leaves cdf and total on the device.  h = bw_factor * 0.5 * (dx + dy).
+ * nbp_heatmap_build    sample(density_, N), the interpolation and the weights (:179-199): M pre-samples (1 <= M <= 2^26) under
+ *                      `seed`; may be called again: replaces the pre-samples.  Host outputs (all nullable): the cell index, the
+ *                      point, the field value and the weight of every pre-sample.
+ * nbp_heatmap_draw     the density as this library holds it (:205-209 keeps the M weighted pre-samples; a belief here is
+ *                      unweighted and a slot holds at most N points): n points drawn from the pre-samples by weight under `seed`,
+ *                      bandwidth (h, h); jitter != 0 adds h * randn, which is AMP.sample(hgd, n) (:113).  slot >= 0: the points
+ *                      also become the NBP_EUCLID2 belief of that slot (rows 0 and 1, count n, bandwidth (h, h), infoPerCoord 0,
+ *                      the layout nbp_belief_write leaves); n > N is refused then.  slot = -1: no slot.  Before a build:
+ *                      NBP_ERR_INVALID.  Host outputs nullable: the pre-sample taken, the point, the bandwidth.
+ * nbp_heatmap_info     h twice, total, wtotal and M (0 before a build; wtotal then 0); outputs nullable. */
+#define NBP_ERR_INVALID (-5)
+typedef struct nbp_heatmap nbp_heatmap;
+nbp_status nbp_heatmap_create(nbp_ctx *ctx, const double *data /* nx x ny */, int32_t nx, int32_t ny, const double *x, const double *y,
+                              double bw_factor, nbp_heatmap **out);
+nbp_status nbp_heatmap_build(nbp_heatmap *hm, int32_t M, uint64_t seed, int32_t *cell_M, double *pre_Mx2, double *d_M, double *W_M);
+nbp_status nbp_heatmap_draw(nbp_heatmap *hm, int32_t n, uint64_t seed, int32_t jitter, int32_t slot /* -1: none */, int32_t *pick_n,
+                            double *pts_nx2, double *bw_2);
+nbp_status nbp_heatmap_info(const nbp_heatmap *hm, double *bw_2, double *total, double *wtotal, int32_t *M);
+nbp_status nbp_heatmap_destroy(nbp_heatmap *hm);
 /* ---- variable seam: AMP.manifoldProduct + rebandwidth (GraphProductOperations.jl:53-60) --- */
 nbp_status nbp_run_products(nbp_ctx *ctx, const nbp_product_desc *descs, int32_t n);
 /* ---- host-buffer entry points: one call per reference function ----------------------------------

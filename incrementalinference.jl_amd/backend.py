@@ -354,6 +354,56 @@ class HipBackend:
                                          tm.ctypes.data_as(dp) if terms else None))
         return (out.value, tm) if terms else out.value
 
+    # ---- heatmap densities (nbp_heatmap_*; heatmap.py) -------------------------------------------------------------------------
+    def heatmap_create(self, data, x, y, bw_factor=0.7):
+        """nbp_heatmap_create: the field data[i, j] at (x[i], y[j]) -> a handle (heatmap_destroy it); the library checks the grid"""
+        dp = C.POINTER(C.c_double)
+        data = np.ascontiguousarray(data, dtype=np.float64)
+        x, y = np.ascontiguousarray(x, dtype=np.float64).reshape(-1), np.ascontiguousarray(y, dtype=np.float64).reshape(-1)
+        if data.ndim != 2 or data.shape != (x.size, y.size):
+            raise ValueError("heatmap: data must be len(x) by len(y)")
+        hm = C.c_void_p()
+        self._check(self.lib.nbp_heatmap_create(self._ctx, data.ctypes.data_as(dp), x.size, y.size, x.ctypes.data_as(dp),
+                                                y.ctypes.data_as(dp), float(bw_factor), C.byref(hm)))
+        return hm
+
+    def heatmap_build(self, hm, M, seed=0, outputs=True):
+        """nbp_heatmap_build: M pre-samples under `seed` -> (cell[M], pre[M, 2], d[M], W[M]), or None with outputs=False"""
+        ip, dp = C.POINTER(C.c_int32), C.POINTER(C.c_double)
+        M = int(M)
+        if not outputs or M < 1:
+            self._check(self.lib.nbp_heatmap_build(hm, M, C.c_uint64(seed), None, None, None, None))
+            return None
+        cell, pre, d, W = np.zeros(M, dtype=np.int32), np.zeros((M, 2)), np.zeros(M), np.zeros(M)
+        self._check(self.lib.nbp_heatmap_build(hm, M, C.c_uint64(seed), cell.ctypes.data_as(ip), pre.ctypes.data_as(dp),
+                                               d.ctypes.data_as(dp), W.ctypes.data_as(dp)))
+        return cell, pre, d, W
+
+    def heatmap_draw(self, hm, n, seed=0, jitter=0, slot=-1, outputs=True):
+        """nbp_heatmap_draw: n points of the density under `seed` -> (pick[n], points[n, 2], bw[2]); slot >= 0: they also become
+        the EUCLID2 belief of that slot; outputs=False (with a slot): nothing comes back to the host but the bandwidth"""
+        ip, dp = C.POINTER(C.c_int32), C.POINTER(C.c_double)
+        n, bw = int(n), np.zeros(2)
+        if not outputs or n < 1:
+            self._check(self.lib.nbp_heatmap_draw(hm, n, C.c_uint64(seed), int(jitter), int(slot), None, None, bw.ctypes.data_as(dp)))
+            return None, None, bw
+        pick, pts = np.zeros(n, dtype=np.int32), np.zeros((n, 2))
+        self._check(self.lib.nbp_heatmap_draw(hm, n, C.c_uint64(seed), int(jitter), int(slot), pick.ctypes.data_as(ip),
+                                              pts.ctypes.data_as(dp), bw.ctypes.data_as(dp)))
+        return pick, pts, bw
+
+    def heatmap_info(self, hm):
+        """-> (bw[2], total, wtotal, M): M = 0 (and wtotal = 0) before a build"""
+        dp = C.POINTER(C.c_double)
+        bw, total, wtotal, M = np.zeros(2), C.c_double(0), C.c_double(0), C.c_int32(0)
+        self._check(self.lib.nbp_heatmap_info(hm, bw.ctypes.data_as(dp), C.byref(total), C.byref(wtotal), C.byref(M)))
+        return bw, total.value, wtotal.value, M.value
+
+    def heatmap_destroy(self, hm):
+        if hm:
+            self._check(self.lib.nbp_heatmap_destroy(hm))
+            hm.value = None
+
     def conv(self, desc, var_pts, var_bw=None, mhidx_in=None, want_mhidx=False, want_bw=True):
         dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
         man = desc.manifold

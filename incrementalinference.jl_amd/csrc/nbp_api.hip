@@ -24,6 +24,7 @@
 #include "nbp_query.h"
 #include "nbp_stats.h"
 #include "nbp_marginal.h"
+#include "nbp_heatmap.h"
 
 static thread_local std::string g_err;
 static nbp_status fail(nbp_status code, const std::string &msg) {
@@ -74,6 +75,7 @@ extern "C" nbp_status nbp_internal_fail(nbp_status code, const char *msg) { retu
 struct nbp_program;
 struct nbp_comm;
 struct nbp_ctx {
+  std::vector<nbp_heatmap *> heatmaps;  // live heatmap densities: their device memory is freed (ctx = null) by nbp_ctx_destroy
   std::vector<nbp_program *> programs;  // live programs: detached (device blob freed, ctx = null) by nbp_ctx_destroy
   std::vector<nbp_comm *> comms;        // live communicators: shut down (and detached) by nbp_ctx_destroy
   void *attached = nullptr;             // an object of the layer above (nbp_ctx_attach: the native host's plan cache) ...
@@ -372,6 +374,7 @@ nbp_status nbp_ctx_create(int32_t device, int32_t N, int32_t n_slots, void *aren
 static void program_detach(nbp_program *p);
 static void program_delete(nbp_program *p);  // detach + delete (defined behind the type)
 static void ctx_detach_comms(nbp_ctx *c);
+static void heatmap_release(nbp_heatmap *hm);  // frees the device memory, leaves the context
 static void reap_retired(nbp_ctx *c);
 
 nbp_status nbp_ctx_attach(nbp_ctx *c, void *obj, void (*destroy)(void *)) {
@@ -391,6 +394,7 @@ nbp_status nbp_ctx_destroy(nbp_ctx *c) {
   c->attached = nullptr;
   for (nbp_program *p : c->programs) program_detach(p);  // a program outliving its context must not touch it
   c->programs.clear();
+  while (!c->heatmaps.empty()) heatmap_release(c->heatmaps.back());  // likewise a heatmap density: its handle stays valid for nbp_heatmap_destroy
   ctx_detach_comms(c);  // likewise a communicator: shut down now, its handle stays valid for nbp_comm_destroy
   for (auto &v : c->ev)
     for (auto &p : v) { hipEventDestroy(p.first); hipEventDestroy(p.second); }
@@ -1893,6 +1897,204 @@ nbp_status nbp_kde_kld(nbp_ctx *c, int32_t manifold, const double *a, int32_t na
   NBPCHK(kde_stage(c, "kld", manifold, {{a, na, bw_a}, {b, nb, bw_b}}));
   const int32_t sa = 0, sb = 1;
   return nbp_run_kld(c, &sa, &sb, &manifold, 1, kld_out, terms_out);
+}
+
+// ---- heatmap densities (nbp_heatmap.h) -------------------------------------------------------------------------------------------
+struct nbp_heatmap {
+  nbp_ctx *ctx = nullptr;  // null: the context was destroyed
+  int nx = 0, ny = 0, M = 0;
+  double h = 0, dx = 0, dy = 0, total = 0, wtotal = 0;
+  double *data = nullptr, *x = nullptr, *y = nullptr, *cdf = nullptr, *t2 = nullptr, *p2 = nullptr;  // field, axes, scan(w), tile totals
+  int *lastpos = nullptr;                                                                              // last cell with w > 0 ...
+  int lastpos_h = -1;                                                                                  // ... as the host found it
+  int cap = 0;                                                                                         // pre-samples the buffers below hold
+  int32_t *cell = nullptr;
+  double2 *pre = nullptr;
+  double *d = nullptr, *W = nullptr, *wcdf = nullptr, *wt2 = nullptr, *wp2 = nullptr;
+  unsigned long long *dmin_key = nullptr;
+  int dcap = 0;  // drawn points the buffers below hold
+  int32_t *pick = nullptr;
+  double2 *pts = nullptr;
+};
+static void heatmap_free_pre(nbp_heatmap *hm) {
+  for (void *p : {(void *)hm->cell, (void *)hm->pre, (void *)hm->d, (void *)hm->W, (void *)hm->wcdf, (void *)hm->wt2, (void *)hm->wp2})
+    if (p) hipFree(p);
+  hm->cell = nullptr; hm->pre = nullptr; hm->d = hm->W = hm->wcdf = hm->wt2 = hm->wp2 = nullptr;
+  hm->cap = hm->M = 0;
+}
+static void heatmap_release(nbp_heatmap *hm) {
+  nbp_ctx *c = hm->ctx;
+  if (!c) return;
+  hipSetDevice(c->device);
+  if (c->stream) hipStreamSynchronize(c->stream);
+  heatmap_free_pre(hm);
+  for (void *p : {(void *)hm->data, (void *)hm->x, (void *)hm->y, (void *)hm->cdf, (void *)hm->t2, (void *)hm->p2, (void *)hm->lastpos,
+                  (void *)hm->dmin_key, (void *)hm->pick, (void *)hm->pts})
+    if (p) hipFree(p);
+  hm->data = hm->x = hm->y = hm->cdf = hm->t2 = hm->p2 = nullptr;
+  hm->lastpos = nullptr; hm->dmin_key = nullptr; hm->pick = nullptr; hm->pts = nullptr;
+  hm->dcap = 0;
+  c->heatmaps.erase(std::remove(c->heatmaps.begin(), c->heatmaps.end(), hm), c->heatmaps.end());
+  hm->ctx = nullptr;
+}
+// scan(in) -> out (nbp_heatmap.h: totals, tiles, apply), n <= NBP_HM_MAX_CELLS checked by the callers
+static nbp_status heatmap_scan(nbp_ctx *c, const double *in, int n, double *t2, double *p2, double *out) {
+  const size_t tiles = ((size_t)n + NBP_HM_TILE - 1) / NBP_HM_TILE;
+  NBPCHK(launch_checked(c, nbp_hm_scan_totals_kernel, tiles, NBP_HM_LANES, 0, in, n, t2));
+  NBPCHK(launch_checked(c, nbp_hm_scan_tiles_kernel, 1, NBP_HM_LANES, 0, (const double *)t2, (int)tiles, p2));
+  return launch_checked(c, nbp_hm_scan_apply_kernel, tiles, NBP_HM_LANES, 0, in, n, (const double *)t2, (const double *)p2, out);
+}
+// dx of the definition and the refusal of an axis that is not strictly increasing and uniform to 1e-9 of its spacing
+static bool heatmap_axis(const double *x, int n, double *dx) {
+  const double s = (x[n - 1] - x[0]) / (double)(n - 1);
+  if (!(std::isfinite(x[0]) && std::isfinite(s) && s > 0.0)) return false;
+  for (int i = 0; i + 1 < n; i++)
+    if (!(x[i + 1] > x[i]) || !(std::fabs((x[i + 1] - x[i]) - s) <= 1e-9 * std::fabs(s))) return false;
+  *dx = s;
+  return true;
+}
+
+nbp_status nbp_heatmap_create(nbp_ctx *c, const double *data, int32_t nx, int32_t ny, const double *x, const double *y, double bw_factor,
+                              nbp_heatmap **out) {
+  if (!c || !out) return fail(NBP_ERR_ARG, "null argument");
+  *out = nullptr;
+  if (nx < 2 || ny < 2) return fail(NBP_ERR_INVALID, "heatmap: nx, ny >= 2");
+  if ((int64_t)nx * (int64_t)ny > NBP_HM_MAX_CELLS) return fail(NBP_ERR_INVALID, "heatmap: more than 2^26 cells");
+  if (!data || !x || !y) return fail(NBP_ERR_ARG, "null argument");
+  if (!(std::isfinite(bw_factor) && bw_factor > 0.0)) return fail(NBP_ERR_INVALID, "heatmap: bw_factor must be positive and finite");
+  double dx = 0, dy = 0;
+  if (!heatmap_axis(x, nx, &dx)) return fail(NBP_ERR_INVALID, "heatmap: x is not strictly increasing with uniform spacing");
+  if (!heatmap_axis(y, ny, &dy)) return fail(NBP_ERR_INVALID, "heatmap: y is not strictly increasing with uniform spacing");
+  const int n = nx * ny;
+  bool finite = true;
+  int lastpos = -1;  // the last cell with w > 0
+  for (int i = 0; i < n; i++) {
+    finite &= std::isfinite(data[i]);
+    lastpos = data[i] > 0.0 ? i : lastpos;
+  }
+  if (!finite) return fail(NBP_ERR_INVALID, "heatmap: the field holds a value that is not finite");
+  if (lastpos < 0) return fail(NBP_ERR_INVALID, "heatmap: no positive cell");
+  const double h = bw_factor * 0.5 * (dx + dy);
+  if (!(std::isfinite(h) && h > 0.0)) return fail(NBP_ERR_INVALID, "heatmap: the bandwidth is not positive and finite");
+  HIPCHK(hipSetDevice(c->device));
+  nbp_heatmap *hm = new nbp_heatmap;
+  hm->ctx = c;
+  hm->nx = nx; hm->ny = ny; hm->dx = dx; hm->dy = dy; hm->h = h; hm->lastpos_h = lastpos;
+  c->heatmaps.push_back(hm);
+  const size_t tiles = ((size_t)n + NBP_HM_TILE - 1) / NBP_HM_TILE;
+  auto body = [&]() -> nbp_status {
+    HIPCHK(hipMalloc(&hm->data, sizeof(double) * (size_t)n));
+    HIPCHK(hipMalloc(&hm->cdf, sizeof(double) * (size_t)n));
+    HIPCHK(hipMalloc(&hm->x, sizeof(double) * (size_t)nx));
+    HIPCHK(hipMalloc(&hm->y, sizeof(double) * (size_t)ny));
+    HIPCHK(hipMalloc(&hm->t2, sizeof(double) * tiles));
+    HIPCHK(hipMalloc(&hm->p2, sizeof(double) * tiles));
+    HIPCHK(hipMalloc(&hm->lastpos, sizeof(int)));
+    HIPCHK(hipMalloc(&hm->dmin_key, sizeof(unsigned long long)));
+    HIPCHK(hipMemcpyAsync(hm->data, data, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(hm->x, x, sizeof(double) * (size_t)nx, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(hm->y, y, sizeof(double) * (size_t)ny, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(hm->lastpos, &hm->lastpos_h, sizeof(int), hipMemcpyHostToDevice, c->stream));
+    NBPCHK(heatmap_scan(c, hm->data, n, hm->t2, hm->p2, hm->cdf));
+    HIPCHK(hipMemcpyAsync(&hm->total, hm->cdf + (n - 1), sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (!(std::isfinite(hm->total) && hm->total > 0.0)) return fail(NBP_ERR_INVALID, "heatmap: the sum of the positive cells is not positive and finite");
+    return NBP_OK;
+  };
+  const nbp_status rc = body();
+  if (rc) {
+    const std::string msg = g_err;
+    heatmap_release(hm);
+    delete hm;
+    return fail(rc, msg);
+  }
+  *out = hm;
+  return NBP_OK;
+}
+
+nbp_status nbp_heatmap_build(nbp_heatmap *hm, int32_t M, uint64_t seed, int32_t *cell_M, double *pre_Mx2, double *d_M, double *W_M) {
+  if (!hm) return fail(NBP_ERR_ARG, "null argument");
+  nbp_ctx *c = hm->ctx;
+  if (!c) return fail(NBP_ERR_ARG, "heatmap: the context was destroyed");
+  if (M < 1 || M > NBP_HM_MAX_CELLS) return fail(NBP_ERR_INVALID, "heatmap build: M outside 1 .. 2^26");
+  HIPCHK(hipSetDevice(c->device));
+  hm->M = 0;  // (a build that fails leaves no pre-samples)
+  hm->wtotal = 0;
+  if (M > hm->cap) {
+    HIPCHK(hipStreamSynchronize(c->stream));
+    heatmap_free_pre(hm);
+    const size_t tiles = ((size_t)M + NBP_HM_TILE - 1) / NBP_HM_TILE;
+    HIPCHK(hipMalloc(&hm->cell, sizeof(int32_t) * (size_t)M));
+    HIPCHK(hipMalloc(&hm->pre, sizeof(double2) * (size_t)M));
+    HIPCHK(hipMalloc(&hm->d, sizeof(double) * (size_t)M));
+    HIPCHK(hipMalloc(&hm->W, sizeof(double) * (size_t)M));
+    HIPCHK(hipMalloc(&hm->wcdf, sizeof(double) * (size_t)M));
+    HIPCHK(hipMalloc(&hm->wt2, sizeof(double) * tiles));
+    HIPCHK(hipMalloc(&hm->wp2, sizeof(double) * tiles));
+    hm->cap = M;
+  }
+  const size_t blocks = ((size_t)M + NBP_HM_LANES - 1) / NBP_HM_LANES;
+  HIPCHK(hipMemsetAsync(hm->dmin_key, 0xFF, sizeof(unsigned long long), c->stream));
+  NBPCHK(launch_checked(c, nbp_hm_presample_kernel, blocks, NBP_HM_LANES, 0, (const double *)hm->data, (const double *)hm->x,
+                        (const double *)hm->y, (const double *)hm->cdf, (const int *)hm->lastpos, hm->nx, hm->ny, hm->dx, hm->dy, hm->h,
+                        (int)M, seed, hm->cell, hm->pre, hm->d, hm->dmin_key));
+  NBPCHK(launch_checked(c, nbp_hm_weight_kernel, blocks, NBP_HM_LANES, 0, (const double *)hm->d, (const unsigned long long *)hm->dmin_key,
+                        (int)M, hm->W));
+  NBPCHK(heatmap_scan(c, hm->W, M, hm->wt2, hm->wp2, hm->wcdf));
+  HIPCHK(hipMemcpyAsync(&hm->wtotal, hm->wcdf + (M - 1), sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (cell_M) HIPCHK(hipMemcpyAsync(cell_M, hm->cell, sizeof(int32_t) * (size_t)M, hipMemcpyDeviceToHost, c->stream));
+  if (pre_Mx2) HIPCHK(hipMemcpyAsync(pre_Mx2, hm->pre, sizeof(double2) * (size_t)M, hipMemcpyDeviceToHost, c->stream));
+  if (d_M) HIPCHK(hipMemcpyAsync(d_M, hm->d, sizeof(double) * (size_t)M, hipMemcpyDeviceToHost, c->stream));
+  if (W_M) HIPCHK(hipMemcpyAsync(W_M, hm->W, sizeof(double) * (size_t)M, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  hm->M = M;
+  return NBP_OK;
+}
+
+nbp_status nbp_heatmap_draw(nbp_heatmap *hm, int32_t n, uint64_t seed, int32_t jitter, int32_t slot, int32_t *pick_n, double *pts_nx2,
+                            double *bw_2) {
+  if (!hm) return fail(NBP_ERR_ARG, "null argument");
+  nbp_ctx *c = hm->ctx;
+  if (!c) return fail(NBP_ERR_ARG, "heatmap: the context was destroyed");
+  if (hm->M < 1) return fail(NBP_ERR_INVALID, "heatmap draw: no pre-samples (nbp_heatmap_build comes first)");
+  if (n < 1 || n > NBP_HM_MAX_CELLS) return fail(NBP_ERR_INVALID, "heatmap draw: n outside 1 .. 2^26");
+  if (slot < -1 || slot >= c->n_slots) return fail(NBP_ERR_RANGE, "heatmap draw: slot out of range");
+  if (slot >= 0 && n > c->N) return fail(NBP_ERR_INVALID, "heatmap draw: a slot holds at most N points");
+  HIPCHK(hipSetDevice(c->device));
+  if (n > hm->dcap) {
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (hm->pick) HIPCHK(hipFree(hm->pick));
+    if (hm->pts) HIPCHK(hipFree(hm->pts));
+    hm->pick = nullptr; hm->pts = nullptr; hm->dcap = 0;
+    HIPCHK(hipMalloc(&hm->pick, sizeof(int32_t) * (size_t)n));
+    HIPCHK(hipMalloc(&hm->pts, sizeof(double2) * (size_t)n));
+    hm->dcap = n;
+  }
+  double *s = slot >= 0 ? c->arena + c->S * slot : nullptr;
+  if (s) HIPCHK(hipMemsetAsync(s, 0, sizeof(double) * (size_t)c->S, c->stream));
+  NBPCHK(launch_checked(c, nbp_hm_draw_kernel, ((size_t)n + NBP_HM_LANES - 1) / NBP_HM_LANES, NBP_HM_LANES, 0, (const double *)hm->wcdf,
+                        (const double2 *)hm->pre, hm->M, hm->h, (int)n, seed, (int)(jitter != 0), hm->pick, hm->pts, s, c->N));
+  if (pick_n) HIPCHK(hipMemcpyAsync(pick_n, hm->pick, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+  if (pts_nx2) HIPCHK(hipMemcpyAsync(pts_nx2, hm->pts, sizeof(double2) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+  if (pick_n || pts_nx2) HIPCHK(hipStreamSynchronize(c->stream));
+  if (bw_2) bw_2[0] = bw_2[1] = hm->h;
+  return NBP_OK;
+}
+
+nbp_status nbp_heatmap_info(const nbp_heatmap *hm, double *bw_2, double *total, double *wtotal, int32_t *M) {
+  if (!hm) return fail(NBP_ERR_ARG, "null argument");
+  if (bw_2) bw_2[0] = bw_2[1] = hm->h;
+  if (total) *total = hm->total;
+  if (wtotal) *wtotal = hm->wtotal;
+  if (M) *M = hm->M;
+  return NBP_OK;
+}
+
+nbp_status nbp_heatmap_destroy(nbp_heatmap *hm) {
+  if (!hm) return NBP_OK;
+  heatmap_release(hm);
+  delete hm;
+  return NBP_OK;
 }
 
 nbp_status nbp_run_resample(nbp_ctx *c, const int32_t *slots, const int32_t *manifolds, int32_t n, uint64_t seed) {

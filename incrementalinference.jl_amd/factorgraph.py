@@ -325,6 +325,13 @@ class PartialPriorPassThrough(_Factor):
         self.points, self.bw = pts, np.atleast_1d(np.asarray(bw, dtype=float))
         self.slot = None  # device slot of the density, set by whoever plans the slots
 
+    @classmethod
+    def fromDensity(cls, varType, Z, partial=(1, 2)):
+        """PartialPriorPassThrough(Z, partial) of the reference with Z a HeatmapGridDensity or a LevelSetGridNormal (heatmap.py): the
+        factor reads `Z.heatmap.densityFnc` there, the heatmap's points and bandwidth here"""
+        Z = getattr(Z, "heatmap", Z)
+        return cls(varType, Z.points, Z.bw, partial)
+
     def components(self):
         return [(1.0, np.zeros(1), np.zeros((1, 1)))]
 
