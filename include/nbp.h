@@ -380,6 +380,53 @@ nbp_status nbp_run_kld(nbp_ctx *ctx, const int32_t *slots_a, const int32_t *slot
 /* host-buffer form: stages through slots 0 and 1 */
 nbp_status nbp_kde_kld(nbp_ctx *ctx, int32_t manifold, const double *a_NxP, int32_t na, const double *bw_a_D, const double *b_NxP,
                        int32_t nb, const double *bw_b_D, double *kld_out, double *terms_out_2 /* nullable */);
+/* ---- modes of a belief ("Modes of a belief"; DEFINED by this library, unpinned: DESIGN.md 8) -----------------------
+ * Mean-shift over the belief's own KDE at the bandwidth g = bw_scale * bw.  Every point x_i of the belief is a start y <- x_i;
+ * one iteration is  w_j = exp(e(y, x_j)) (the exponent of nbp_run_evaluate with g in place of bw),  S = sum_j w_j,
+ * m_d = sum_j w_j delta_d(x_j, y) (delta wrapped to [-pi, pi) on circular coordinates),  y_d <- y_d + m_d / S (wrapped on circular
+ * coordinates); j = 0 .. c-1 in that order in one lane, one rounding per written operation: a trajectory depends on the belief
+ * and the options alone.  A start stops after the first iteration with max_d |m_d / S| / g_d <= tol (converged) or after max_iter
+ * iterations.  A start is a point of the belief, so S >= 1 at its first iteration, and a mean-shift step does not decrease the
+ * density: S never vanishes.
+ * The end points are merged by leader clustering in index order: the lowest unassigned i becomes a leader, every unassigned k > i
+ * with max_d |delta_d(y_k, y_i)| / g_d <= merge joins it.  Modes are ranked by member count, descending, equal counts by the lower
+ * leader index.  Record r of a belief is the mode of rank r: the leader's end point, the member count, the KDE at bandwidth g at that
+ * point (S there / (c prod_d sqrt(2 pi) g_d)) and the leader's index; records from n_modes on (at most NBP_MODES_MAX are kept)
+ * hold NaN, count 0 and leader -1.  n_modes is the true number of modes, also above NBP_MODES_MAX.  labels: the rank of each
+ * point's mode (rows beyond the belief's count: -1); iters: the iterations each start took (rows beyond the count: 0).  A bandwidth
+ * entry bw_d or g_d that is not positive and finite: n_modes = 0, labels -1, iters 0, every record empty.
+ * Options: bw_scale, merge positive and finite, tol positive, max_iter >= 1, else NBP_ERR_ARG; merge < 1000 tol is NBP_ERR_RANGE (a
+ * stopped start may still sit tol rho / (1 - rho) from its fixed point, rho the contraction rate).  opts == NULL: the defaults
+ * below.  The fitted bandwidth is the leave-one-out one and under-smooths for mode finding: hence bw_scale = 2.
+ * Argument errors as nbp_run_ppe's, before anything is launched.  Queued on the library stream; one copy back; synchronises. */
+#define NBP_MODES_MAX 32
+#define NBP_MODES_BW_SCALE 2.0
+#define NBP_MODES_TOL 1e-6
+#define NBP_MODES_MAX_ITER 500
+#define NBP_MODES_MERGE 1e-2
+typedef struct nbp_modes_opts {
+  double bw_scale;
+  double tol;
+  double merge;
+  int32_t max_iter;
+  int32_t pad;
+} nbp_modes_opts;
+typedef struct nbp_mode_rec {
+  double location[NBP_MAXD]; /* tangent coordinates, entries beyond the manifold's dimension zero */
+  double density;
+  int32_t count;
+  int32_t leader;
+} nbp_mode_rec;
+nbp_status nbp_run_modes(nbp_ctx *ctx, const int32_t *slots, const int32_t *manifolds, int32_t n, const nbp_modes_opts *opts /* nullable */,
+                         nbp_mode_rec *recs_out /* n x NBP_MODES_MAX */, int32_t *n_modes_out /* n */,
+                         int32_t *labels_out /* n x N, nullable */, int32_t *iters_out /* n x N, nullable */,
+                         int32_t *n_unconverged_out /* n, nullable */);
+/* host-buffer form, like nbp_kde_ppe: stages through slot 0; labels_out / iters_out hold n_pts entries (a belief of more than N
+ * points keeps its first N, as in nbp_belief_write: the entries beyond them are -1 / 0) */
+nbp_status nbp_kde_modes(nbp_ctx *ctx, int32_t manifold, const double *pts_NxP, int32_t n_pts, const double *bw_D,
+                         const nbp_modes_opts *opts /* nullable */, nbp_mode_rec *recs_out /* NBP_MODES_MAX */, int32_t *n_modes_out,
+                         int32_t *labels_out /* n_pts, nullable */, int32_t *iters_out /* n_pts, nullable */,
+                         int32_t *n_unconverged_out /* nullable */);
 /* ---- heatmap densities ("Heatmap densities"; the deviations from the reference: DESIGN.md 8) --------------------------
  * HeatmapGridDensity / LevelSetGridNormal (ext/HeatmapSampler.jl:123-242): a scalar field on a regular x-y grid turned into a
  * samplable density, the measurement model of the pass-through prior (NBP_F_PASSTHROUGH).  data[i * ny + j] is the field at

@@ -333,6 +333,47 @@ class HipBackend:
                                              cov.ctypes.data_as(dp)))
         return mean, cov
 
+    _MODE_REC = np.dtype([("location", np.float64, (abi.MAXD,)), ("density", np.float64), ("count", np.int32), ("leader", np.int32)])
+
+    @staticmethod
+    def _modes_opts(bw_scale, tol, max_iter, merge):
+        return abi.ModesOpts(bw_scale=float(bw_scale), tol=float(tol), merge=float(merge), max_iter=int(max_iter), pad=0)
+
+    def run_modes(self, slots, manifolds, bw_scale=abi.MODES_BW_SCALE, tol=abi.MODES_TOL, max_iter=abi.MODES_MAX_ITER,
+                  merge=abi.MODES_MERGE):
+        """the modes of resident beliefs (nbp_run_modes: mean-shift from every point, merging and ranking in one launch) ->
+        (recs[n, 32], n_modes[n], labels[n, N], iters[n, N], n_unconverged[n]); recs is a structured array with the fields
+        location[3], density, count, leader, mode r of belief i in recs[i, r]; rows of labels / iters beyond a belief's count
+        hold -1 / 0"""
+        assert self._MODE_REC.itemsize == C.sizeof(abi.ModeRec)
+        (s, sp), (_, mp) = _i32(slots), _i32(manifolds)
+        n = s.size
+        recs = np.zeros((n, abi.MODES_MAX), dtype=self._MODE_REC)
+        nm, unc = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+        lab, its = np.zeros((n, self.N), dtype=np.int32), np.zeros((n, self.N), dtype=np.int32)
+        ip = C.POINTER(C.c_int32)
+        opts = self._modes_opts(bw_scale, tol, max_iter, merge)
+        self._check(self.lib.nbp_run_modes(self._ctx, sp, mp, n, C.byref(opts), recs.ctypes.data_as(C.POINTER(abi.ModeRec)),
+                                           nm.ctypes.data_as(ip), lab.ctypes.data_as(ip), its.ctypes.data_as(ip), unc.ctypes.data_as(ip)))
+        return recs, nm, lab, its, unc
+
+    def kde_modes(self, manifold, pts, bw, bw_scale=abi.MODES_BW_SCALE, tol=abi.MODES_TOL, max_iter=abi.MODES_MAX_ITER,
+                  merge=abi.MODES_MERGE):
+        """the modes of a belief held on the host (nbp_kde_modes; clobbers slot 0) -> (recs[32], n_modes, labels[c], iters[c],
+        n_unconverged)"""
+        dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+        pts = np.ascontiguousarray(pts, dtype=np.float64).reshape(-1, abi.MANIFOLD_P[manifold])
+        bw = np.ascontiguousarray(bw, dtype=np.float64)
+        c = pts.shape[0]
+        recs = np.zeros(abi.MODES_MAX, dtype=self._MODE_REC)
+        nm, unc = C.c_int32(0), C.c_int32(0)
+        lab, its = np.zeros(max(c, 1), dtype=np.int32), np.zeros(max(c, 1), dtype=np.int32)
+        opts = self._modes_opts(bw_scale, tol, max_iter, merge)
+        self._check(self.lib.nbp_kde_modes(self._ctx, manifold, pts.ctypes.data_as(dp), c, bw.ctypes.data_as(dp), C.byref(opts),
+                                           recs.ctypes.data_as(C.POINTER(abi.ModeRec)), C.byref(nm), lab.ctypes.data_as(ip),
+                                           its.ctypes.data_as(ip), C.byref(unc)))
+        return recs, nm.value, lab[:c], its[:c], unc.value
+
     def run_kld(self, slots_a, slots_b, manifolds, terms=False):
         """kld of pairs of resident beliefs (nbp_run_kld) -> values[n], from one launch; terms=True: (values[n], terms[n, 2]) with
         terms = (Eaa, Eab), values = Eaa - Eab, entropy(a) = -Eaa"""

@@ -152,6 +152,12 @@ class Belief:
         from .marginal import Marginal
         return Marginal(self, dims)
 
+    def modes(self, bwScale=abi.MODES_BW_SCALE, tol=abi.MODES_TOL, maxIter=abi.MODES_MAX_ITER, merge=abi.MODES_MERGE, backend=None):
+        """belief.modes(): the modes of the belief's KDE by mean-shift from every one of its points (modes.py) -> BeliefModes;
+        `backend` as in `__call__` (nbp_kde_modes, through slot 0)"""
+        from .modes import belief_modes
+        return belief_modes(self.manifold, self.pts, self.bw, bwScale, tol, maxIter, merge, backend)
+
 
 def getBelief(fg, label):
     """getBelief(dfg, label): the variable's current belief, callable at query points"""

@@ -16,7 +16,7 @@
 #include <rccl/rccl.h>  // types and prototypes only: the entry points are resolved with dlsym (see rccl_api)
 
 #ifndef NBP_TU
-#define NBP_TU 0  // host code: the kernels live in the nbp_k_*.hip files (-DNBP_TU=0xFFFF: single-file build with every kernel)
+#define NBP_TU 0  // host code: the kernels live in the nbp_k_*.hip files (-DNBP_TU=0x1FFFF: single-file build with every kernel)
 #endif
 #include "nbp_kernels.h"
 #include "nbp_fused.h"
@@ -25,6 +25,7 @@
 #include "nbp_stats.h"
 #include "nbp_marginal.h"
 #include "nbp_heatmap.h"
+#include "nbp_modes.h"
 
 static thread_local std::string g_err;
 static nbp_status fail(nbp_status code, const std::string &msg) {
@@ -1897,6 +1898,68 @@ nbp_status nbp_kde_kld(nbp_ctx *c, int32_t manifold, const double *a, int32_t na
   NBPCHK(kde_stage(c, "kld", manifold, {{a, na, bw_a}, {b, nb, bw_b}}));
   const int32_t sa = 0, sb = 1;
   return nbp_run_kld(c, &sa, &sb, &manifold, 1, kld_out, terms_out);
+}
+
+// ---- modes of beliefs (nbp_modes.h) ----------------------------------------------------------------------------------------------
+// the options as given, or the defaults; refused before anything is launched
+static nbp_status modes_opts_check(const nbp_modes_opts *opts, nbp_modes_opts *o) {
+  *o = opts ? *opts : nbp_modes_opts{NBP_MODES_BW_SCALE, NBP_MODES_TOL, NBP_MODES_MERGE, NBP_MODES_MAX_ITER, 0};
+  o->pad = 0;
+  if (!(o->bw_scale > 0.0 && o->bw_scale < INFINITY)) return fail(NBP_ERR_ARG, "modes: bw_scale must be positive and finite");
+  if (!(o->tol > 0.0 && o->tol < INFINITY)) return fail(NBP_ERR_ARG, "modes: tol must be positive and finite");
+  if (!(o->merge > 0.0 && o->merge < INFINITY)) return fail(NBP_ERR_ARG, "modes: merge must be positive and finite");
+  if (o->max_iter < 1) return fail(NBP_ERR_ARG, "modes: max_iter must be at least 1");
+  if (o->merge < 1000.0 * o->tol) return fail(NBP_ERR_RANGE, "modes: merge must be at least 1000 tol");
+  return NBP_OK;
+}
+
+// mean-shift modes of resident beliefs: one workgroup per belief (nbp_modes.h), one copy back.  The query scratch holds
+// hdr[n][2] | recs[n][NBP_MODES_MAX] | labels[n][N] | iters[n][N], each part starting on a whole double; the copy ends behind the last part asked for
+nbp_status nbp_run_modes(nbp_ctx *c, const int32_t *slots, const int32_t *manifolds, int32_t n, const nbp_modes_opts *opts,
+                         nbp_mode_rec *recs_out, int32_t *n_modes_out, int32_t *labels_out, int32_t *iters_out, int32_t *n_unconverged_out) {
+  if (!c || ((!slots || !manifolds || !recs_out || !n_modes_out) && n > 0)) return fail(NBP_ERR_ARG, "null argument");
+  if (n <= 0) return NBP_OK;
+  nbp_modes_opts o;
+  NBPCHK(modes_opts_check(opts, &o));
+  NBPCHK(batch_check(c, "modes", {slots}, manifolds, n, no_refusal));
+  static_assert(sizeof(nbp_mode_rec) % sizeof(double) == 0, "nbp_mode_rec fills whole doubles of the query scratch");
+  const size_t hdr_d = (size_t)n, rec_d = (size_t)n * NBP_MODES_MAX * (sizeof(nbp_mode_rec) / sizeof(double));
+  const size_t row_d = ((size_t)n * (size_t)c->N + 1) / 2;
+  const int32_t *d[2];
+  NBPCHK(stage_columns(c, {{slots, 4 * (size_t)n}, {manifolds, 4 * (size_t)n}}, d, hdr_d + rec_d + 2 * row_d));
+  int32_t *dh = (int32_t *)c->query, *dl = (int32_t *)(c->query + hdr_d + rec_d), *di = (int32_t *)(c->query + hdr_d + rec_d + row_d);
+  NBPCHK(launch_checked(c, nbp_modes_kernel, n, c->Npad, nbp_modes_lds_bytes(c->N), d[0], d[1], c->arena, c->N, c->S, o,
+                        (nbp_mode_rec *)(c->query + hdr_d), dh, dl, di));
+  std::vector<double> back(hdr_d + rec_d + (iters_out ? 2 * row_d : (labels_out ? row_d : 0)));
+  NBPCHK(query_fetch(c, back.data(), c->query, sizeof(double) * back.size()));
+  const int32_t *hh = (const int32_t *)back.data();
+  for (int i = 0; i < n; i++) {
+    n_modes_out[i] = hh[2 * i];
+    if (n_unconverged_out) n_unconverged_out[i] = hh[2 * i + 1];
+  }
+  memcpy(recs_out, back.data() + hdr_d, sizeof(double) * rec_d);
+  if (labels_out) memcpy(labels_out, back.data() + hdr_d + rec_d, sizeof(int32_t) * (size_t)n * (size_t)c->N);
+  if (iters_out) memcpy(iters_out, back.data() + hdr_d + rec_d + row_d, sizeof(int32_t) * (size_t)n * (size_t)c->N);
+  return NBP_OK;
+}
+
+// host-buffer form: stages through slot 0 (which it clobbers), like nbp_kde_ppe.  A belief of more than N points keeps its first N
+// (nbp_belief_write): the rows of labels_out / iters_out beyond them are -1 / 0.
+nbp_status nbp_kde_modes(nbp_ctx *c, int32_t manifold, const double *pts, int32_t n_pts, const double *bw, const nbp_modes_opts *opts,
+                         nbp_mode_rec *recs_out, int32_t *n_modes_out, int32_t *labels_out, int32_t *iters_out, int32_t *n_unconverged_out) {
+  if (!c || !pts || !bw || !recs_out || !n_modes_out) return fail(NBP_ERR_ARG, "null argument");
+  nbp_modes_opts o;
+  NBPCHK(modes_opts_check(opts, &o));
+  NBPCHK(kde_stage(c, "modes", manifold, {{pts, n_pts, bw}}));
+  const int32_t slot = 0;
+  std::vector<int32_t> lab(labels_out ? (size_t)c->N : 0), its(iters_out ? (size_t)c->N : 0);
+  NBPCHK(nbp_run_modes(c, &slot, &manifold, 1, &o, recs_out, n_modes_out, labels_out ? lab.data() : nullptr, iters_out ? its.data() : nullptr,
+                       n_unconverged_out));
+  for (int i = 0; i < n_pts; i++) {
+    if (labels_out) labels_out[i] = i < c->N ? lab[i] : -1;
+    if (iters_out) iters_out[i] = i < c->N ? its[i] : 0;
+  }
+  return NBP_OK;
 }
 
 // ---- heatmap densities (nbp_heatmap.h) -------------------------------------------------------------------------------------------

@@ -9,7 +9,7 @@ What travels is what changed: new variables and host edits go up, the beliefs a 
 hot path is host traffic that no longer happens."""
 import time
 
-from . import bayestree
+from . import abi, bayestree
 from .ppe import MeanMaxPPE
 from .solver import (TreeProgram, _initialised_subgraph, _make_backend, _refuse_joint_recycling, _runs_on_libnbp,
                      _untouched_variables, initStages, passthrough_factors, setValKDE, write_densities)
@@ -228,6 +228,18 @@ class SolveSession:
                                                           for v in here], True),
                                     lambda res, i, v: (res[0][i].copy(), marginal.grid_axes(res[1][i], nn)),
                                     lambda v, **kw: marginal.marginalGrid(self.fg, v, dims, nn, None, margin, **kw))
+
+    def getBeliefModes(self, labels=None, bwScale=abi.MODES_BW_SCALE, tol=abi.MODES_TOL, maxIter=abi.MODES_MAX_ITER, merge=abi.MODES_MERGE):
+        """The modes of the variables' current beliefs (modes.py: mean-shift from every point, merged and ranked) ->
+        {label: BeliefModes}, served by ONE `run_modes` launch where libnbp holds the beliefs (`_query_resident`); on the host
+        copy, `modes.getBeliefModes`."""
+        from . import modes
+        kw = modes._options(bwScale, tol, maxIter, merge)
+        var = self.fg.getVariable
+        return self._query_resident(labels, "run_modes",
+                                    lambda here, place: ([place[v] for v in here], [var(v).varType.manifold for v in here], *kw.values()),
+                                    lambda res, i, v: modes.modes_from_records(var(v).varType.manifold, *(r[i] for r in res)),
+                                    lambda v, **k: modes.getBeliefModes(self.fg, v, bwScale, tol, maxIter, merge, **k))
 
     # ---- one solve ---------------------------------------------------------------------------------------------------------
     def solve(self, seed=0, eliminationOrder=None, ordering="qr", return_timing=False):
