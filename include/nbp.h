@@ -427,6 +427,63 @@ nbp_status nbp_kde_modes(nbp_ctx *ctx, int32_t manifold, const double *pts_NxP, 
                          const nbp_modes_opts *opts /* nullable */, nbp_mode_rec *recs_out /* NBP_MODES_MAX */, int32_t *n_modes_out,
                          int32_t *labels_out /* n_pts, nullable */, int32_t *iters_out /* n_pts, nullable */,
                          int32_t *n_unconverged_out /* nullable */);
+/* ---- factor likelihoods ("Factor likelihoods"; DEFINED by this library, unpinned: DESIGN.md 8) ----------------------
+ * The likelihood of a factor's measurement model under the current beliefs of its variables: which association of a multihypo
+ * factor won, which Mixture component explains the data, which factor disagrees with the solution.  One ITEM is (measurement
+ * model, slot A, slot B); slot_b = -1 for a unary factor (NBP_F_PRIOR).  n_a, n_b: the counts the slots hold (n_b = 1 for a unary
+ * item).  A Monte-Carlo sum over the particles: bandwidths are never read.
+ * Predicted measurement zhat(a_i, b_j), the root of the factor's residual, in tangent coordinates (SE(2): x, y, theta):
+ *   NBP_F_LINREL      b - a, D coordinates
+ *   NBP_F_CIRCULAR    wrap_pi(b - a)
+ *   NBP_F_SE2         (c dx + s dy, -s dx + c dy, wrap_pi(b_th - a_th)), (s, c) = sincos(a_th), dx, dy = b_xy - a_xy
+ *   NBP_F_EUCLIDDIST  sqrt(sum_d (b_d - a_d)^2)
+ *   NBP_F_PRIOR       a_i
+ *   partial_mask != 0 only the masked coordinates of the above, in ascending order: popcount(mask) dimensions (zd), as in
+ *                     nbp_proposal_desc; admitted where the samplers admit it (Prior, SE(2), LinearRelative with one or two bits)
+ * Component log-density log p_c(z); comp[c] = weight, mean[3], L[3][3] as the samplers read it, the family in comp[c][12] when zd = 1:
+ *   Gaussian          delta = z - mean, wrapped to [-pi, pi) on circular coordinates (Circular; theta of SE(2)); L u = delta by
+ *                     forward substitution (u_0 = delta_0 / L_00, u_1 = (delta_1 - L_10 u_0) / L_11,
+ *                     u_2 = ((delta_2 - L_20 u_0) - L_21 u_1) / L_22); log p = -1/2 sum_k u_k^2 - (zd log(2 pi) / 2 + sum_k log L_kk),
+ *                     the squares added in ascending order
+ *   Uniform(a, a + w) -log w on [a, a + w], else -inf                (mean[0] = a, L[0][0] = w)
+ *   Rayleigh(sigma)   (log z - 2 log sigma) - z^2 / (2 sigma^2) for z > 0, else -inf
+ *   Uniform and Rayleigh are evaluated at zhat as formed, with no further wrap.
+ * Sums, one rounding per written operation:
+ *   e_ijc = log(w_c / sum w) + log p_c(zhat_ij)
+ *   pass 1: M = max_ijc e_ijc (exact in any order)
+ *   pass 2: S_c = sum_i sum_j exp(e_ijc - M); a term with e_ijc - M < -700 counts as zero; j = 0 .. n_b - 1 in that order in the
+ *           lane that owns i, the lanes combined by the library's fixed-order block sum (no atomics)
+ *   loglik = (M + log(sum_c S_c)) - log(n_a n_b);  comp_loglik[c] = (M + log S_c) - log(n_a n_b) (S_c = 0: -inf): the logsumexp of
+ *           comp_loglik over c is loglik.  Entries c >= ncomp are NaN.
+ * The result is finite where every density underflows (a factor 10^4 sigma off: about -5e7, not -inf).  M = -inf (nothing in the
+ * support of a Uniform / Rayleigh model): loglik = -inf.  A belief without points (host-buffer form only: a slot always holds at
+ * least one) gives NaN.
+ * Posterior weights are host arithmetic on these numbers:
+ *   hypotheses of a multihypo factor: pi_k proportional to p_k exp(l_k), p_k the normalised fractional entries of `multihypo`, l_k the
+ *           loglik of the item with variable k in its role; the null hypothesis has no likelihood and stays out (nullhypo is ignored)
+ *   Mixture responsibilities: exp(comp_loglik[c] - loglik)
+ *   both formed by max-shift; all -inf gives NaN.
+ * Refused before anything is launched, naming the item -- NBP_ERR_ARG: NBP_F_MSGPRIOR, NBP_F_PASSTHROUGH (and measurements held as
+ * a KDE, which this descriptor cannot name), NBP_DIST_TABLE or an unknown family; an L with a non-zero above the diagonal or a
+ * diagonal entry that is not positive and finite; a Uniform width or Rayleigh sigma that is not positive and finite; a weight that is
+ * negative or not finite, or weights without a positive sum; ncomp outside 1 .. NBP_MAXC; a kind / manifold pair, a mask or a slot_b
+ * the samplers do not admit for the kind.  NBP_ERR_RANGE: a slot out of range; a mask outside the manifold's coordinates.
+ * n = 0 returns NBP_OK.  Queued on the library stream; one upload of the descriptors, one copy back; synchronises. */
+typedef struct nbp_likelihood_desc {
+  int32_t kind;         /* enum nbp_factor                                                     */
+  int32_t manifold;     /* enum nbp_manifold of the factor's variables                         */
+  int32_t slot_a;       /* the belief in the first role (getVariableOrder)                     */
+  int32_t slot_b;       /* the belief in the second role; -1: unary                            */
+  int32_t ncomp;        /* 1, or the number of Mixture components                              */
+  int32_t partial_mask; /* 0: full factor, else as nbp_proposal_desc.partial_mask              */
+  double comp[NBP_MAXC][NBP_COMP_STRIDE]; /* measurement model, see NBP_COMP_STRIDE            */
+} nbp_likelihood_desc;
+nbp_status nbp_run_factor_likelihood(nbp_ctx *ctx, const nbp_likelihood_desc *descs, int32_t n, double *loglik_out /* n */,
+                                     double *comp_loglik_out /* n x NBP_MAXC, nullable */);
+/* host-buffer form, like nbp_kde_kld: stages through slots 0 and 1 (a unary item: slot 0), which it clobbers; desc->slot_a / slot_b
+ * are not read; b_NxP is not read for a unary item */
+nbp_status nbp_factor_likelihood(nbp_ctx *ctx, const nbp_likelihood_desc *desc, const double *a_NxP, int32_t na, const double *b_NxP,
+                                 int32_t nb, double *loglik_out, double *comp_loglik_out /* NBP_MAXC, nullable */);
 /* ---- heatmap densities ("Heatmap densities"; the deviations from the reference: DESIGN.md 8) --------------------------
  * HeatmapGridDensity / LevelSetGridNormal (ext/HeatmapSampler.jl:123-242): a scalar field on a regular x-y grid turned into a
  * samplable density, the measurement model of the pass-through prior (NBP_F_PASSTHROUGH).  data[i * ny + j] is the field at

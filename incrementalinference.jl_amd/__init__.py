@@ -4,13 +4,15 @@ clique Gibbs schedule).  Compute lives in csrc/libnbp.so (hand-written HIP, gfx9
 C ABI of include/nbp.h; this package is the host-side mirror of the reference's API for that
 path.  There is no CPU fallback: the compute entry points raise when libnbp.so or a GPU is
 missing."""
-from . import abi, bayestree, beliefquery, beliefstats, canonical, heatmap, marginal, modes, ppe, seeds  # noqa: F401
+from . import abi, bayestree, beliefquery, beliefstats, canonical, heatmap, likelihood, marginal, modes, ppe, seeds  # noqa: F401
 from .backend import HipBackend, NbpError  # noqa: F401
 from .beliefquery import (Belief, density_numpy, getBelief, isapproxBeliefs, mmd, mmd_numpy, mmdVariables,  # noqa: F401
                           ppe_coords)
 from .beliefstats import (calcMeanCovar, calcMeanCovarAll, entropy, kld, kld_numpy, meancov_numpy)  # noqa: F401
 from .marginal import (Marginal, grid_axes, grid_extent_numpy, marginal_density_numpy, marginal_grid_numpy, marginalGrid)  # noqa: F401
 from .modes import BeliefModes, getBeliefModes, getBeliefModesAll, modes_numpy  # noqa: F401
+from .likelihood import (FactorLikelihood, FactorLikelihoods, factor_likelihood_numpy, factorLikelihood,  # noqa: F401
+                         factorLikelihoodAll, likelihood_desc)
 from .heatmap import HeatmapGridDensity, LevelSetGridNormal, heatmap_density_numpy, sample  # noqa: F401
 from .bayestree import (areCliqVariablesAllMarginalized, attemptTreeSimilarClique, buildTreeFromOrdering,  # noqa: F401
                         buildTreeReset, calcCliquesRecycled, getEliminationOrder, nestedDissectionOrder, setCliqueRecycling)

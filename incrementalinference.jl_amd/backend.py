@@ -374,6 +374,29 @@ class HipBackend:
                                            its.ctypes.data_as(ip), C.byref(unc)))
         return recs, nm.value, lab[:c], its[:c], unc.value
 
+    def run_factor_likelihood(self, descs):
+        """the likelihood of factors under resident beliefs (nbp_run_factor_likelihood: every item in one launch); descs: a
+        sequence (or ctypes array) of abi.LikelihoodDesc -> (loglik[n], comp_loglik[n, 4]); entries of comp_loglik beyond an item's
+        ncomp are NaN"""
+        arr, n = _as_array(descs, abi.LikelihoodDesc)
+        dp = C.POINTER(C.c_double)
+        ll, cl = np.zeros(n), np.zeros((n, abi.MAXC))
+        self._check(self.lib.nbp_run_factor_likelihood(self._ctx, arr, n, ll.ctypes.data_as(dp), cl.ctypes.data_as(dp)))
+        return ll, cl
+
+    def factor_likelihood(self, desc, a, b=None):
+        """the likelihood of one factor under beliefs held on the host (nbp_factor_likelihood; clobbers slots 0 and 1); a, b: host
+        points (n x P) of the two roles, b None for a unary factor -> (loglik, comp_loglik[4])"""
+        dp = C.POINTER(C.c_double)
+        P = abi.MANIFOLD_P[desc.manifold]
+        a = np.ascontiguousarray(a, dtype=np.float64).reshape(-1, P)
+        b = None if b is None else np.ascontiguousarray(b, dtype=np.float64).reshape(-1, P)
+        ll, cl = C.c_double(0.0), np.zeros(abi.MAXC)
+        self._check(self.lib.nbp_factor_likelihood(self._ctx, C.byref(desc), a.ctypes.data_as(dp), a.shape[0],
+                                                   b.ctypes.data_as(dp) if b is not None else None, b.shape[0] if b is not None else 0,
+                                                   C.byref(ll), cl.ctypes.data_as(dp)))
+        return ll.value, cl
+
     def run_kld(self, slots_a, slots_b, manifolds, terms=False):
         """kld of pairs of resident beliefs (nbp_run_kld) -> values[n], from one launch; terms=True: (values[n], terms[n, 2]) with
         terms = (Eaa, Eab), values = Eaa - Eab, entropy(a) = -Eaa"""

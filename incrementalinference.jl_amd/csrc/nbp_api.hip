@@ -16,7 +16,7 @@
 #include <rccl/rccl.h>  // types and prototypes only: the entry points are resolved with dlsym (see rccl_api)
 
 #ifndef NBP_TU
-#define NBP_TU 0  // host code: the kernels live in the nbp_k_*.hip files (-DNBP_TU=0x1FFFF: single-file build with every kernel)
+#define NBP_TU 0  // host code: the kernels live in the nbp_k_*.hip files (-DNBP_TU=0x3FFFF: single-file build with every kernel)
 #endif
 #include "nbp_kernels.h"
 #include "nbp_fused.h"
@@ -26,6 +26,7 @@
 #include "nbp_marginal.h"
 #include "nbp_heatmap.h"
 #include "nbp_modes.h"
+#include "nbp_likelihood.h"
 
 static thread_local std::string g_err;
 static nbp_status fail(nbp_status code, const std::string &msg) {
@@ -1960,6 +1961,113 @@ nbp_status nbp_kde_modes(nbp_ctx *c, int32_t manifold, const double *pts, int32_
     if (iters_out) iters_out[i] = i < c->N ? its[i] : 0;
   }
   return NBP_OK;
+}
+
+// ---- factor likelihoods (nbp_likelihood.h) -----------------------------------------------------------------------------------------
+// what nbp_run_factor_likelihood refuses in one descriptor (the slots apart)
+static refusal likelihood_refusal(const nbp_likelihood_desc &p) {
+  const auto posfin = [](double v) { return v > 0.0 && v < INFINITY; };
+  if (p.kind == NBP_F_MSGPRIOR || p.kind == NBP_F_PASSTHROUGH) return {NBP_ERR_ARG, "message priors and pass-through priors have no density in closed form"};
+  if (p.kind < NBP_F_PRIOR || p.kind > NBP_F_EUCLIDDIST) return {NBP_ERR_ARG, "unknown factor kind"};
+  if (p.kind == NBP_F_CIRCULAR && p.manifold != NBP_CIRCULAR) return {NBP_ERR_ARG, "CircularCircular needs Circular variables"};
+  if (p.kind == NBP_F_SE2 && p.manifold != NBP_SE2) return {NBP_ERR_ARG, "SE2 factor needs SE2 variables"};
+  if ((p.kind == NBP_F_LINREL || p.kind == NBP_F_EUCLIDDIST) && p.manifold > NBP_EUCLID3)
+    return {NBP_ERR_ARG, "LinearRelative and EuclidDistance need Euclid variables"};
+  if (p.kind == NBP_F_PRIOR && p.slot_b != -1) return {NBP_ERR_ARG, "a prior is unary: slot_b must be -1"};
+  if (p.ncomp < 1 || p.ncomp > NBP_MAXC) return {NBP_ERR_ARG, "ncomp outside 1 .. NBP_MAXC"};
+  const int D = manifold_dim_h(p.manifold);
+  int zd = (p.kind == NBP_F_CIRCULAR || p.kind == NBP_F_EUCLIDDIST) ? 1 : D;
+  if (p.partial_mask) {
+    if (p.partial_mask < 0 || p.partial_mask >= (1 << D)) return {NBP_ERR_RANGE, "partial_mask outside the manifold's coordinates"};
+    zd = __builtin_popcount(p.partial_mask);
+    if (p.kind == NBP_F_LINREL) {
+      if (zd > 2) return {NBP_ERR_ARG, "partial LinearRelative: one or two partial coordinates"};
+    } else if (p.kind != NBP_F_PRIOR && p.kind != NBP_F_SE2)
+      return {NBP_ERR_ARG, "partial_mask is supported for Prior, LinearRelative and SE(2) ManifoldFactor factors"};
+  }
+  double wsum = 0.0;
+  for (int c = 0; c < p.ncomp; c++) {
+    const double *q = p.comp[c];
+    if (!(q[0] >= 0.0 && q[0] < INFINITY)) return {NBP_ERR_ARG, "a component weight is negative or not finite"};
+    wsum += q[0];
+    const double fam = zd == 1 ? q[12] : 0.0;
+    if (fam == (double)NBP_DIST_TABLE) return {NBP_ERR_ARG, "an alias table has no density"};
+    if (fam != (double)NBP_DIST_GAUSSIAN && fam != (double)NBP_DIST_UNIFORM && fam != (double)NBP_DIST_RAYLEIGH)
+      return {NBP_ERR_ARG, "unknown measurement family"};
+    if (fam == (double)NBP_DIST_UNIFORM) {
+      if (!posfin(q[4])) return {NBP_ERR_ARG, "the width of a Uniform is not positive and finite"};
+    } else if (fam == (double)NBP_DIST_RAYLEIGH) {
+      if (!posfin(q[4])) return {NBP_ERR_ARG, "the sigma of a Rayleigh is not positive and finite"};
+    } else {
+      for (int i = 0; i < zd; i++) {
+        if (!posfin(q[4 + 3 * i + i])) return {NBP_ERR_ARG, "a diagonal entry of L is not positive and finite"};
+        for (int j = i + 1; j < zd; j++)
+          if (q[4 + 3 * i + j] != 0.0) return {NBP_ERR_ARG, "L has a non-zero above the diagonal"};
+      }
+    }
+  }
+  if (!(wsum > 0.0 && wsum < INFINITY)) return {NBP_ERR_ARG, "the component weights have no positive sum"};
+  return {NBP_OK, nullptr};
+}
+
+// item by item, in nbp_run_ppe's order: the slots, the manifold, then the rest of the descriptor
+static nbp_status likelihood_check(nbp_ctx *c, const nbp_likelihood_desc *descs, int n) {
+  HIPCHK(hipSetDevice(c->device));
+  for (int i = 0; i < n; i++) {
+    const nbp_likelihood_desc &p = descs[i];
+    refusal r{NBP_OK, nullptr};
+    if (p.slot_a < 0 || p.slot_a >= c->n_slots) r = {NBP_ERR_RANGE, "slot_a out of range"};
+    else if (p.slot_b != -1 && (p.slot_b < 0 || p.slot_b >= c->n_slots)) r = {NBP_ERR_RANGE, "slot_b out of range"};
+    else if (!manifold_ok(p.manifold)) r = {NBP_ERR_ARG, "unknown manifold"};
+    else r = likelihood_refusal(p);
+    if (!r.what && p.kind != NBP_F_PRIOR && p.slot_b == -1) r = {NBP_ERR_RANGE, "slot_b out of range (a relative factor has two roles)"};
+    if (r.what) return fail(r.code, "factor_likelihood: item " + std::to_string(i) + ": " + r.what);
+  }
+  return NBP_OK;
+}
+
+// one workgroup per item (nbp_likelihood.h), one upload of the descriptors, one copy back
+nbp_status nbp_run_factor_likelihood(nbp_ctx *c, const nbp_likelihood_desc *descs, int32_t n, double *loglik_out, double *comp_loglik_out) {
+  if (!c || ((!descs || !loglik_out) && n > 0)) return fail(NBP_ERR_ARG, "null argument");
+  if (n <= 0) return NBP_OK;
+  NBPCHK(likelihood_check(c, descs, n));
+  static_assert(sizeof(nbp_likelihood_rec) == sizeof(double) * (1 + NBP_MAXC), "nbp_likelihood_rec is packed doubles");
+  static_assert(sizeof(nbp_likelihood_desc) % 8 == 0, "nbp_likelihood_desc keeps its doubles aligned in an array");
+  const int32_t *d[1];
+  NBPCHK(stage_columns(c, {{descs, sizeof(nbp_likelihood_desc) * (size_t)n}}, d, (size_t)n * (1 + NBP_MAXC)));
+  NBPCHK(launch_checked(c, nbp_likelihood_kernel, n, c->Npad, nbp_likelihood_lds_bytes(c->N), (const nbp_likelihood_desc *)d[0], c->arena,
+                        c->N, c->S, (nbp_likelihood_rec *)c->query));
+  std::vector<nbp_likelihood_rec> rec((size_t)n);
+  NBPCHK(query_fetch(c, rec.data(), c->query, sizeof(nbp_likelihood_rec) * (size_t)n));
+  for (int i = 0; i < n; i++) {
+    loglik_out[i] = rec[i].loglik;
+    if (comp_loglik_out)
+      for (int k = 0; k < NBP_MAXC; k++) comp_loglik_out[(size_t)i * NBP_MAXC + k] = rec[i].comp_loglik[k];
+  }
+  return NBP_OK;
+}
+
+// host-buffer form: stages through slots 0 and 1 (which it clobbers), like nbp_kde_kld; the descriptor's own slots are not read
+nbp_status nbp_factor_likelihood(nbp_ctx *c, const nbp_likelihood_desc *desc, const double *a, int32_t na, const double *b, int32_t nb,
+                                 double *loglik_out, double *comp_loglik_out) {
+  if (!c || !desc || !a || !loglik_out) return fail(NBP_ERR_ARG, "null argument");
+  nbp_likelihood_desc p = *desc;
+  const bool unary = p.kind == NBP_F_PRIOR;
+  if (!unary && !b) return fail(NBP_ERR_ARG, "null argument");
+  p.slot_a = 0;
+  p.slot_b = unary ? -1 : 1;
+  if (!unary && c->n_slots < 2) return fail(NBP_ERR_RANGE, "factor_likelihood: the context needs two slots");
+  NBPCHK(likelihood_check(c, &p, 1));
+  if (na < 0 || (!unary && nb < 0)) return fail(NBP_ERR_ARG, "factor_likelihood: a negative count");
+  if (na == 0 || (!unary && nb == 0)) {  // a belief without points: NaN, nothing launched
+    *loglik_out = NAN;
+    if (comp_loglik_out)
+      for (int k = 0; k < NBP_MAXC; k++) comp_loglik_out[k] = NAN;
+    return NBP_OK;
+  }
+  if (unary) NBPCHK(kde_write(c, p.manifold, {{a, na, nullptr}}));
+  else NBPCHK(kde_write(c, p.manifold, {{a, na, nullptr}, {b, nb, nullptr}}));
+  return nbp_run_factor_likelihood(c, &p, 1, loglik_out, comp_loglik_out);
 }
 
 // ---- heatmap densities (nbp_heatmap.h) -------------------------------------------------------------------------------------------

@@ -241,6 +241,50 @@ class SolveSession:
                                     lambda res, i, v: modes.modes_from_records(var(v).varType.manifold, *(r[i] for r in res)),
                                     lambda v, **k: modes.getBeliefModes(self.fg, v, bwScale, tol, maxIter, merge, **k))
 
+    def _query_resident_factors(self, plans, method, run, host):
+        """The factor-shaped sibling of `_query_resident`: one query of factors, each reading the current beliefs of SEVERAL
+        variables -> {factor label: result}.  plans: objects with `.label` and `.roles` (tuples of variable labels, None for an
+        empty role).  On a backend that has `method`, the factors whose variables all have a slot are served where the beliefs
+        lie by ONE call `run(be, plans_here, place)` -- place: variable label -> slot --: no belief travels and `stats` does not
+        move; a belief that is not resident goes up first by the session's upload path and is counted as an upload.
+        `host(plan, **kw)` is the same query on the host copy: for every factor where there is no context or the backend lacks
+        `method`, and with backend=self.backend for a factor with a variable that has no slot in the session's context."""
+        if self._closed:
+            raise RuntimeError("this SolveSession is closed")
+        be = self._be
+        if be is None or getattr(be, method, None) is None:
+            return {p.label: host(p) for p in plans}
+        place = {v: i for i, v in enumerate(self._labels)}
+        need = lambda p: [v for r in p.roles for v in r if v is not None]  # noqa: E731
+        here = [p for p in plans if all(v in place for v in need(p))]
+        out = {}
+        if here:
+            want = []
+            for p in here:
+                want += [v for v in need(p) if v not in want]
+            try:
+                self._upload(self.fg, [(v, place[v]) for v in want], len(self._labels))
+                out.update(run(be, here, place))
+            except BaseException:
+                self._table.clear()  # the device state is unknown: the host copy wins
+                raise
+        for p in plans:
+            if p.label not in out:
+                out[p.label] = host(p, backend=self.backend)
+        return {p.label: out[p.label] for p in plans}
+
+    def factorLikelihoods(self, labels=None):
+        """The likelihood of the factors `labels` (default: every factor of the graph, the unsupported ones listed in the result's
+        `.skipped`; a named unsupported factor is a ValueError) under the variables' current beliefs (likelihood.py) ->
+        FactorLikelihoods {label: FactorLikelihood} in natural order, served by ONE `run_factor_likelihood` launch for every item
+        of every factor where libnbp holds the beliefs (`_query_resident_factors`); on the host copy,
+        `likelihood.factorLikelihood`."""
+        from . import likelihood
+        plans, skipped = likelihood.plan_factors(self.fg, labels, skip_unsupported=labels is None)
+        res = self._query_resident_factors(plans, "run_factor_likelihood", likelihood.run_plans,
+                                           lambda p, **kw: likelihood.factorLikelihood(self.fg, p.label, **kw))
+        return likelihood.FactorLikelihoods(res.items(), skipped=skipped)
+
     # ---- one solve ---------------------------------------------------------------------------------------------------------
     def solve(self, seed=0, eliminationOrder=None, ordering="qr", return_timing=False):
         """solveTree(fg, oldtree=ses.tree, ...) in the session's context -> tree (or (tree, timing) with return_timing: the
