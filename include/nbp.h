@@ -39,6 +39,7 @@ extern "C" {
                         products whose node statistics do not fit the 160 KB LDS keep them in HBM/L2 */
 #define NBP_MAXD 3   /* tangent dimension                                                   */
 #define NBP_MAXC 4   /* Mixture components                                                  */
+#define NBP_MAXK 8   /* groups (modes) per belief in nbp_run_factor_mode_likelihood          */
 #define NBP_MAXN 512 /* particles per belief                                                */
 #define NBP_COMP_STRIDE 13 /* per component: weight, mean[3], sqrt-cov L[3][3] row-major    */
 /* Family of a SCALAR measurement component, carried in its last slot (comp[c][12] = L[2][2], which a one-dimensional
@@ -484,6 +485,46 @@ nbp_status nbp_run_factor_likelihood(nbp_ctx *ctx, const nbp_likelihood_desc *de
  * are not read; b_NxP is not read for a unary item */
 nbp_status nbp_factor_likelihood(nbp_ctx *ctx, const nbp_likelihood_desc *desc, const double *a_NxP, int32_t na, const double *b_NxP,
                                  int32_t nb, double *loglik_out, double *comp_loglik_out /* NBP_MAXC, nullable */);
+/* ---- factor likelihoods, mode by mode ("Joint hypotheses"; DEFINED by this library, unpinned: DESIGN.md 8) ----------
+ * Which mode of one variable belongs with which mode of another: the likelihood of a factor's measurement model given "a is in its
+ * group k and b is in its group l", for every pair of groups at once.  One ITEM is (measurement model, slot A, slot B, label row of
+ * A, label row of B).  The measurement model is an nbp_likelihood_desc, read exactly as nbp_run_factor_likelihood reads it: zhat,
+ * log p_c, e_ijc, the wrap rules, one rounding per written operation and the cut-off at -700 are those defined above.
+ * labels holds n_rows rows of N int32 each (N: the context's particle count).  Entry i of a row is the group of particle i, in
+ * -1 .. NBP_MAXK - 1; -1 leaves the particle out of both roles.  The kernel reads the first n_a (n_b) entries of a row, the count
+ * its slot holds.  Row index -1 stands for "every point in group 0".  A unary item has one column: row_b is -1 and n_l = 1.
+ * With n_k, n_l the member counts of group k of A and group l of B:
+ *   pass 1: M_kl = max over i in k, j in l, c of e_ijc (exact in any order): one maximum per cell, so a cell 10^4 sigma off stays
+ *           finite (about -5e7)
+ *   pass 2: S_klc = sum_{i in k} sum_{j in l} exp(e_ijc - M_kl); j ascending in the lane that owns i, the lanes combined by the
+ *           library's fixed-order block sum with an exact zero in every lane that is not a member, the components then added in
+ *           ascending c.  Adding an exact zero changes nothing: a masked sum and a skipped term in the same order are one number.
+ *   table_out[i][k][l] = (M_kl + log sum_c S_klc) - log((double)n_k (double)n_l);  M_kl = -inf: -inf;  no member pair (n_k = 0 or
+ *           n_l = 0, which includes every unused row and column of the NBP_MAXK x NBP_MAXK output): NaN
+ *   counts_out[i][0][k] = n_k, counts_out[i][1][l] = n_l (a unary item: 1, 0, 0, ...)
+ * Two identities: with every label 0 (or both rows -1) table_out[i][0][0] is nbp_run_factor_likelihood's loglik of the same item
+ * BIT FOR BIT (the same maximum, scan, block sum and order over the components); with no point left out,
+ * logsumexp_kl(T[k][l] + log(n_k n_l)) - log(n_a n_b) is that loglik up to rounding.
+ * The joint score of a choice of one mode per variable -- the sum of the cells the choice picks, a multihypo factor entering as
+ * logsumexp_h(log p_h + T_h) -- and its maximisation are host arithmetic on these tables (jointmodes.py).
+ * Refused before anything is launched, naming the item or the row: everything nbp_run_factor_likelihood refuses, through the same
+ * check; NBP_ERR_ARG: a label outside -1 .. NBP_MAXK - 1 in a row that an item names (the counts live on the device, so all N
+ * entries of such a row are looked at; a row no item names is not read), row_b != -1 on a unary item; NBP_ERR_RANGE: a row index
+ * outside -1 .. n_rows - 1.  labels may be NULL when n_rows = 0.
+ * n = 0 returns NBP_OK.  Queued on the library stream; one upload of the descriptors, the row indices and the label rows, one
+ * launch, one copy back; synchronises. */
+nbp_status nbp_run_factor_mode_likelihood(nbp_ctx *ctx, const nbp_likelihood_desc *descs, const int32_t *row_a /* n */,
+                                          const int32_t *row_b /* n */, int32_t n, const int32_t *labels /* n_rows x N */,
+                                          int32_t n_rows, double *table_out /* n x NBP_MAXK x NBP_MAXK */,
+                                          int32_t *counts_out /* n x 2 x NBP_MAXK, nullable */);
+/* host-buffer form, like nbp_factor_likelihood: stages through slots 0 and 1 (a unary item: slot 0), which it clobbers;
+ * desc->slot_a / slot_b are not read; labels_a (na entries) and labels_b (nb entries) may each be NULL: every point in group 0;
+ * b_NxP and labels_b are not read for a unary item.  A belief of more than N points keeps its first N, as in nbp_belief_write.
+ * A belief without points: every cell NaN, every count 0, nothing launched. */
+nbp_status nbp_factor_mode_likelihood(nbp_ctx *ctx, const nbp_likelihood_desc *desc, const double *a_NxP, int32_t na,
+                                      const int32_t *labels_a /* na, nullable */, const double *b_NxP, int32_t nb,
+                                      const int32_t *labels_b /* nb, nullable */, double *table_out /* NBP_MAXK x NBP_MAXK */,
+                                      int32_t *counts_out /* 2 x NBP_MAXK, nullable */);
 /* ---- heatmap densities ("Heatmap densities"; the deviations from the reference: DESIGN.md 8) --------------------------
  * HeatmapGridDensity / LevelSetGridNormal (ext/HeatmapSampler.jl:123-242): a scalar field on a regular x-y grid turned into a
  * samplable density, the measurement model of the pass-through prior (NBP_F_PASSTHROUGH).  data[i * ny + j] is the field at

@@ -397,6 +397,41 @@ class HipBackend:
                                                    C.byref(ll), cl.ctypes.data_as(dp)))
         return ll.value, cl
 
+    def run_factor_mode_likelihood(self, descs, row_a, row_b, labels):
+        """the likelihood of factors under resident beliefs, mode by mode (nbp_run_factor_mode_likelihood: every item in one launch);
+        descs: a sequence (or ctypes array) of abi.LikelihoodDesc; row_a, row_b: per item the row of `labels` (n_rows x N, int32,
+        entries in -1 .. 7) that groups the particles of its role, -1: every point in group 0 ->
+        (table[n, 8, 8], counts[n, 2, 8]); a cell without a member pair is NaN"""
+        arr, n = _as_array(descs, abi.LikelihoodDesc)
+        (ra, rap), (rb, rbp) = _i32(row_a), _i32(row_b)
+        if ra.size != n or rb.size != n:
+            raise ValueError("run_factor_mode_likelihood: one row index per item and role")
+        lab = np.ascontiguousarray(labels, dtype=np.int32).reshape(-1, self.N)
+        dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+        tab, cnt = np.zeros((n, abi.MAXK, abi.MAXK)), np.zeros((n, 2, abi.MAXK), dtype=np.int32)
+        self._check(self.lib.nbp_run_factor_mode_likelihood(self._ctx, arr, rap, rbp, n, lab.ctypes.data_as(ip), lab.shape[0],
+                                                            tab.ctypes.data_as(dp), cnt.ctypes.data_as(ip)))
+        return tab, cnt
+
+    def factor_mode_likelihood(self, desc, a, labels_a=None, b=None, labels_b=None):
+        """the mode-by-mode likelihood of one factor under beliefs held on the host (nbp_factor_mode_likelihood; clobbers slots 0
+        and 1); a, b: host points (n x P) of the two roles, b None for a unary factor; labels_*: one group per point, None: every
+        point in group 0 -> (table[8, 8], counts[2, 8])"""
+        dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+        P = abi.MANIFOLD_P[desc.manifold]
+        a = np.ascontiguousarray(a, dtype=np.float64).reshape(-1, P)
+        b = None if b is None else np.ascontiguousarray(b, dtype=np.float64).reshape(-1, P)
+        la = None if labels_a is None else np.ascontiguousarray(labels_a, dtype=np.int32).reshape(-1)
+        lb = None if labels_b is None or b is None else np.ascontiguousarray(labels_b, dtype=np.int32).reshape(-1)
+        if (la is not None and la.size != a.shape[0]) or (lb is not None and lb.size != b.shape[0]):
+            raise ValueError("factor_mode_likelihood: one label per point")
+        tab, cnt = np.zeros((abi.MAXK, abi.MAXK)), np.zeros((2, abi.MAXK), dtype=np.int32)
+        self._check(self.lib.nbp_factor_mode_likelihood(
+            self._ctx, C.byref(desc), a.ctypes.data_as(dp), a.shape[0], la.ctypes.data_as(ip) if la is not None else None,
+            b.ctypes.data_as(dp) if b is not None else None, b.shape[0] if b is not None else 0,
+            lb.ctypes.data_as(ip) if lb is not None else None, tab.ctypes.data_as(dp), cnt.ctypes.data_as(ip)))
+        return tab, cnt
+
     def run_kld(self, slots_a, slots_b, manifolds, terms=False):
         """kld of pairs of resident beliefs (nbp_run_kld) -> values[n], from one launch; terms=True: (values[n], terms[n, 2]) with
         terms = (Eaa, Eab), values = Eaa - Eab, entropy(a) = -Eaa"""

@@ -2070,6 +2070,78 @@ nbp_status nbp_factor_likelihood(nbp_ctx *c, const nbp_likelihood_desc *desc, co
   return nbp_run_factor_likelihood(c, &p, 1, loglik_out, comp_loglik_out);
 }
 
+// the same likelihood group by group (nbp_mode_likelihood_kernel): one upload of the descriptors, the row indices and the label rows,
+// one launch, one copy back.  The query scratch holds table[n][8][8] | counts[n][2][8] (int32).
+nbp_status nbp_run_factor_mode_likelihood(nbp_ctx *c, const nbp_likelihood_desc *descs, const int32_t *row_a, const int32_t *row_b, int32_t n,
+                                          const int32_t *labels, int32_t n_rows, double *table_out, int32_t *counts_out) {
+  if (!c || ((!descs || !row_a || !row_b || !table_out) && n > 0) || (n > 0 && n_rows > 0 && !labels)) return fail(NBP_ERR_ARG, "null argument");
+  if (n <= 0) return NBP_OK;
+  if (n_rows < 0) return fail(NBP_ERR_ARG, "factor_mode_likelihood: a negative number of label rows");
+  NBPCHK(likelihood_check(c, descs, n));
+  const size_t N = (size_t)c->N;
+  std::vector<char> seen((size_t)n_rows, 0);
+  for (int i = 0; i < n; i++) {
+    const std::string who = "factor_mode_likelihood: item " + std::to_string(i) + ": ";
+    if (row_a[i] < -1 || row_a[i] >= n_rows) return fail(NBP_ERR_RANGE, who + "row_a outside -1 .. n_rows - 1");
+    if (row_b[i] < -1 || row_b[i] >= n_rows) return fail(NBP_ERR_RANGE, who + "row_b outside -1 .. n_rows - 1");
+    if (descs[i].kind == NBP_F_PRIOR && row_b[i] != -1) return fail(NBP_ERR_ARG, who + "a prior is unary: row_b must be -1");
+    for (int r : {row_a[i], row_b[i]}) {
+      if (r < 0 || seen[(size_t)r]) continue;
+      seen[(size_t)r] = 1;
+      for (size_t k = 0; k < N; k++)
+        if (labels[(size_t)r * N + k] < -1 || labels[(size_t)r * N + k] >= NBP_MAXK)
+          return fail(NBP_ERR_ARG, "factor_mode_likelihood: label row " + std::to_string(r) + ": entry " + std::to_string(k) + " outside -1 .. NBP_MAXK - 1");
+    }
+  }
+  const size_t tab_d = (size_t)n * NBP_MAXK * NBP_MAXK, cnt_d = (size_t)n * NBP_MAXK;  // (2 x NBP_MAXK int32 = NBP_MAXK doubles per item)
+  const int32_t *d[4];
+  NBPCHK(stage_columns(c, {{descs, sizeof(nbp_likelihood_desc) * (size_t)n}, {row_a, 4 * (size_t)n}, {row_b, 4 * (size_t)n},
+                           {labels, 4 * (size_t)n_rows * N}}, d, tab_d + cnt_d));
+  NBPCHK(launch_checked(c, nbp_mode_likelihood_kernel, n, c->Npad, nbp_mode_likelihood_lds_bytes(c->N), (const nbp_likelihood_desc *)d[0], d[1],
+                        d[2], d[3], c->arena, c->N, c->S, c->query, (int32_t *)(c->query + tab_d)));
+  std::vector<double> back(tab_d + (counts_out ? cnt_d : 0));
+  NBPCHK(query_fetch(c, back.data(), c->query, sizeof(double) * back.size()));
+  memcpy(table_out, back.data(), sizeof(double) * tab_d);
+  if (counts_out) memcpy(counts_out, back.data() + tab_d, sizeof(double) * cnt_d);
+  return NBP_OK;
+}
+
+// host-buffer form: stages through slots 0 and 1 (which it clobbers), like nbp_factor_likelihood; the label rows are padded with -1
+nbp_status nbp_factor_mode_likelihood(nbp_ctx *c, const nbp_likelihood_desc *desc, const double *a, int32_t na, const int32_t *labels_a,
+                                      const double *b, int32_t nb, const int32_t *labels_b, double *table_out, int32_t *counts_out) {
+  if (!c || !desc || !a || !table_out) return fail(NBP_ERR_ARG, "null argument");
+  nbp_likelihood_desc p = *desc;
+  const bool unary = p.kind == NBP_F_PRIOR;
+  if (!unary && !b) return fail(NBP_ERR_ARG, "null argument");
+  p.slot_a = 0;
+  p.slot_b = unary ? -1 : 1;
+  if (!unary && c->n_slots < 2) return fail(NBP_ERR_RANGE, "factor_mode_likelihood: the context needs two slots");
+  NBPCHK(likelihood_check(c, &p, 1));
+  if (na < 0 || (!unary && nb < 0)) return fail(NBP_ERR_ARG, "factor_mode_likelihood: a negative count");
+  const int N = c->N;
+  std::vector<int32_t> rows;
+  int32_t ra = -1, rb = -1, n_rows = 0;
+  const auto row = [&](const int32_t *lab, int32_t cnt) {
+    rows.resize((size_t)(n_rows + 1) * (size_t)N, -1);
+    for (int i = 0; i < cnt && i < N; i++) rows[(size_t)n_rows * (size_t)N + i] = lab[i];
+    return n_rows++;
+  };
+  if (labels_a) ra = row(labels_a, na);
+  if (!unary && labels_b) rb = row(labels_b, nb);
+  for (size_t k = 0; k < rows.size(); k++)
+    if (rows[k] < -1 || rows[k] >= NBP_MAXK)
+      return fail(NBP_ERR_ARG, "factor_mode_likelihood: label row " + std::to_string(k / (size_t)N) + ": entry " + std::to_string(k % (size_t)N) + " outside -1 .. NBP_MAXK - 1");
+  if (na == 0 || (!unary && nb == 0)) {  // a belief without points: NaN, nothing launched
+    for (int k = 0; k < NBP_MAXK * NBP_MAXK; k++) table_out[k] = NAN;
+    if (counts_out)
+      for (int k = 0; k < 2 * NBP_MAXK; k++) counts_out[k] = 0;
+    return NBP_OK;
+  }
+  if (unary) NBPCHK(kde_write(c, p.manifold, {{a, na, nullptr}}));
+  else NBPCHK(kde_write(c, p.manifold, {{a, na, nullptr}, {b, nb, nullptr}}));
+  return nbp_run_factor_mode_likelihood(c, &p, &ra, &rb, 1, rows.data(), n_rows, table_out, counts_out);
+}
+
 // ---- heatmap densities (nbp_heatmap.h) -------------------------------------------------------------------------------------------
 struct nbp_heatmap {
   nbp_ctx *ctx = nullptr;  // null: the context was destroyed

@@ -27,6 +27,10 @@ struct nbp_likelihood_rec {
 };
 
 #define NBP_LIKELIHOOD_ARGS const nbp_likelihood_desc *descs, const double *arena, int N, int64_t S, nbp_likelihood_rec *out
+// the grouped kernel: the label rows of the two roles (-1: every point in group 0), table[n][8][8] and counts[n][2][8] out
+#define NBP_MODE_LIKELIHOOD_ARGS                                                                                                 \
+  const nbp_likelihood_desc *descs, const int32_t *row_a, const int32_t *row_b, const int32_t *labels, const double *arena, int N, \
+      int64_t S, double *table, int32_t *counts
 #if NBP_TU & NBP_TU_LIKELIHOOD
 // what a lane and a component bring to the pair loop: the lane's point (and the sine and cosine of its heading, formed once), the
 // coordinates the mask keeps and whether each is circular (block-uniform), the component's parameters (block-uniform)
@@ -250,8 +254,147 @@ nbp_likelihood_kernel(NBP_LIKELIHOOD_ARGS) {
     r->loglik = tot > 0.0 ? (Mx + nbpm_log(tot)) - ln : -INFINITY;
   }
 }
+
+// ---- the same likelihood, group by group ("Joint hypotheses"; include/nbp.h, nbp_run_factor_mode_likelihood) ---------
+// Every particle of A and of B carries a label in -1 .. NBP_MAXK - 1 (the rank of its mode); cell (k, l) of the item's table is
+// the likelihood over the pairs with a_i in group k and b_j in group l:
+//   pass 1   M_kl = max over i in k, j in l, c of e_ijc
+//   pass 2   S_klc = sum_{i in k} sum_{j in l} exp(e_ijc - M_kl): j ascending in the lane that owns i, the lanes added by block_sum
+//            with an exact zero in every lane outside k, the components added in ascending c
+//   T[k, l]  (M_kl + log sum_c S_klc) - log(n_k n_l); -inf where M_kl = -inf; NaN where n_k = 0 or n_l = 0
+// One workgroup per item, 64 ceil(N / 64) lanes.  LDS: exp table | B[3][N] | red | M[8][8] | S[8][8] | wave counts[8][16] |
+// counts[16].  B is staged SORTED BY GROUP, stably (a point's place: the points of lower groups, the points of its group in the
+// waves before, the points of its group in the lanes before: ballots, no atomics), and the points labelled -1 are not staged.  So
+// column l is one contiguous run of B in ascending j, and lik_scan walks it exactly as the ungrouped kernel walks the whole of B:
+// a lane keeps ONE accumulator per pass, nothing is indexed at run time and nothing is selected inside the pair loop.  Skipping
+// the pairs of other groups and adding an exact zero for them are the same number, so with one group on either side the cell is
+// nbp_likelihood_kernel's loglik bit for bit.  The reductions run per PRESENT cell (the counts are block-uniform): a unimodal
+// pair makes one block_max and ncomp block_sums, as the ungrouped kernel does.  Row -1: every point within the count in group 0.
+__global__ void __launch_bounds__(512)
+nbp_mode_likelihood_kernel(NBP_MODE_LIKELIHOOD_ARGS) {
+  extern __shared__ double smem[];
+  double *tab = smem, *B = smem + NBP_EXPTAB, *red = B + 3 * N, *Mt = red + NBP_RED, *St = Mt + NBP_MAXK * NBP_MAXK;
+  int *cntw = (int *)(St + NBP_MAXK * NBP_MAXK), *cnt = cntw + 8 * 2 * NBP_MAXK;
+  const nbp_likelihood_desc *d = descs + blockIdx.x;
+  const int kind = d->kind, M = d->manifold, D = mani_dim(M), n = threadIdx.x, ncomp = d->ncomp;
+  const int lane = n & 63, w = n >> 6, nw = (blockDim.x + 63) >> 6;
+  const bool unary = kind == NBP_F_PRIOR;
+  const double *sa = arena + S * d->slot_a, *sb = unary ? sa : arena + S * d->slot_b;
+  const int ca = slot_count(sa, N), cb = unary ? 1 : slot_count(sb, N);
+  const int ra = row_a[blockIdx.x], rb = unary ? -1 : row_b[blockIdx.x];
+  nbp_exp_tab_init(tab);
+  // the groups of this lane's a_i and b_j (the host has checked the range; anything else counts as -1 here as well)
+  int la = -1, lb = -1;
+  if (n < ca) la = ra < 0 ? 0 : labels[(size_t)ra * N + n];
+  if (n < cb) lb = rb < 0 ? 0 : labels[(size_t)rb * N + n];
+  if ((unsigned)la >= NBP_MAXK) la = -1;
+  if ((unsigned)lb >= NBP_MAXK) lb = -1;
+  if (n < NBP_MAXK * NBP_MAXK) St[n] = 0.0;
+  // members per wave, and this lane's rank among the lanes of its wave in the same group of B
+  const unsigned long long below = (1ull << lane) - 1ull;
+  int rank = 0;
+  for (int g = 0; g < NBP_MAXK; g++) {
+    const unsigned long long ma = __ballot(la == g), mb = __ballot(lb == g);
+    if (lane == 0) {
+      cntw[w * 2 * NBP_MAXK + g] = __popcll(ma);
+      cntw[w * 2 * NBP_MAXK + NBP_MAXK + g] = __popcll(mb);
+    }
+    if (lb == g) rank = __popcll(mb & below);
+  }
+  __syncthreads();
+  if (n < 2 * NBP_MAXK) {
+    int t = 0;
+    for (int i = 0; i < nw; i++) t += cntw[i * 2 * NBP_MAXK + n];
+    cnt[n] = t;
+    counts[(size_t)blockIdx.x * 2 * NBP_MAXK + n] = t;
+  }
+  __syncthreads();
+  if (!unary && lb >= 0) {
+    int pos = rank;
+    for (int g = 0; g < lb; g++) pos += cnt[NBP_MAXK + g];
+    for (int i = 0; i < w; i++) pos += cntw[i * 2 * NBP_MAXK + NBP_MAXK + lb];
+    for (int k = 0; k < D; k++) B[k * N + pos] = sb[k * N + n];  // (pos < the members of B <= cb <= N)
+  }
+  __syncthreads();
+  // the coordinates of the measurement, the lane's point: as nbp_likelihood_kernel forms them
+  const int full = (kind == NBP_F_CIRCULAR || kind == NBP_F_EUCLIDDIST) ? 1 : (1 << D) - 1;
+  const int mask = d->partial_mask ? d->partial_mask : full;
+  const int zd = __popc(mask);
+  lik_lane l;
+  l.D = D;
+  l.s0 = __ffs(mask) - 1;
+  const int rest = mask & (mask - 1);
+  l.s1 = rest ? __ffs(rest) - 1 : 0;
+  l.s2 = 2;
+  const bool cf0 = kind == NBP_F_CIRCULAR || (unary && is_circ(M, 0)), cf2 = kind == NBP_F_SE2 || (unary && is_circ(M, 2));
+  l.z0c = l.s0 == 0 ? cf0 : (l.s0 == 2 && cf2);
+  l.z1c = l.s1 == 2 && cf2;
+  l.z2c = cf2;
+  const bool mine = n < ca;
+  l.a0 = mine ? sa[n] : 0.0;
+  l.a1 = (mine && D > 1) ? sa[N + n] : 0.0;
+  l.a2 = (mine && D > 2) ? sa[2 * N + n] : 0.0;
+  l.sn = 0.0;
+  l.cs = 1.0;
+  if (kind == NBP_F_SE2) sincos_fast(l.a2, &l.sn, &l.cs);
+  double wsum = 0.0;
+  for (int c = 0; c < ncomp; c++) wsum += d->comp[c][0];
+
+  // ---- pass 1: the maximum of every present cell ----
+  int at = 0;
+  for (int g = 0; g < NBP_MAXK; g++) {  // (column g of the table: B[at .. at + ng))
+    const int ng = cnt[NBP_MAXK + g];
+    if (ng == 0) continue;  // (block-uniform)
+    double mx = -INFINITY;
+    for (int c = 0; c < ncomp; c++) {
+      const int fam = zd == 1 ? (int)d->comp[c][12] : NBP_DIST_GAUSSIAN;
+      const lik_comp k = lik_component(d, c, zd, fam, wsum);
+      mx = fmax(mx, lik_scan_kind<0>(kind, zd, fam, l, k, B + at, N, ng, 0.0, tab));
+    }
+    for (int r = 0; r < NBP_MAXK; r++) {
+      if (cnt[r] == 0) continue;
+      const double m = block_max(la == r ? mx : -INFINITY, red);
+      if (n == 0) Mt[r * NBP_MAXK + g] = m;
+    }
+    at += ng;
+  }
+  __syncthreads();
+
+  // ---- pass 2: the sums of every present cell relative to its own maximum, the components added in ascending c ----
+  at = 0;
+  for (int g = 0; g < NBP_MAXK; g++) {
+    const int ng = cnt[NBP_MAXK + g];
+    if (ng == 0) continue;
+    const double Mx = la >= 0 ? Mt[la * NBP_MAXK + g] : INFINITY;  // (a lane outside every group adds zeros, and they are masked)
+    for (int c = 0; c < ncomp; c++) {
+      const int fam = zd == 1 ? (int)d->comp[c][12] : NBP_DIST_GAUSSIAN;
+      const lik_comp k = lik_component(d, c, zd, fam, wsum);
+      const double s = lik_scan_kind<1>(kind, zd, fam, l, k, B + at, N, ng, Mx, tab);
+      for (int r = 0; r < NBP_MAXK; r++) {
+        if (cnt[r] == 0) continue;
+        const double t = block_sum(la == r ? s : 0.0, red);
+        if (n == 0) St[r * NBP_MAXK + g] += t;
+      }
+    }
+    at += ng;
+  }
+  __syncthreads();
+  if (n < NBP_MAXK * NBP_MAXK) {
+    const int r = n / NBP_MAXK, g = n % NBP_MAXK, nr = cnt[r], ng = cnt[NBP_MAXK + g];
+    double v = __longlong_as_double(0x7ff8000000000000ll);
+    if (nr > 0 && ng > 0) {
+      const double Mx = Mt[n], tot = Mx > -INFINITY ? St[n] : 0.0;
+      v = tot > 0.0 ? (Mx + nbpm_log(tot)) - nbpm_log((double)nr * (double)ng) : -INFINITY;
+    }
+    table[(size_t)blockIdx.x * NBP_MAXK * NBP_MAXK + n] = v;
+  }
+}
 #else
 __global__ void nbp_likelihood_kernel(NBP_LIKELIHOOD_ARGS);
+__global__ void nbp_mode_likelihood_kernel(NBP_MODE_LIKELIHOOD_ARGS);
 #endif
 
 static inline size_t nbp_likelihood_lds_bytes(int N) { return ((size_t)NBP_EXPTAB + 3 * (size_t)N + NBP_RED + NBP_MAXC) * 8; }
+static inline size_t nbp_mode_likelihood_lds_bytes(int N) {
+  return ((size_t)NBP_EXPTAB + 3 * (size_t)N + NBP_RED + 2 * NBP_MAXK * NBP_MAXK) * 8 + ((size_t)8 * 2 * NBP_MAXK + 2 * NBP_MAXK) * 4;
+}

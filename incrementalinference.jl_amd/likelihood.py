@@ -220,21 +220,9 @@ def predicted_measurement(desc, A, B=None, dtype=np.float64):
     return [f[k] for k in sel], [circ[k] for k in sel]
 
 
-def factor_likelihood_numpy(desc, A, B=None, dtype=np.float64):
-    """the definition on the host, in the arithmetic `dtype` (np.longdouble: the measure of a case's conditioning).  desc: an
-    abi.LikelihoodDesc (or anything with its fields; the slots are not read); A, B: the host points of the two roles (n x P; SE(2)
-    also n x 3 tangent coordinates), B None for a prior -> (loglik, comp_loglik[4]), entries beyond ncomp NaN"""
-    check_desc(desc)
+def pair_terms(desc, A, B=None, dtype=np.float64):
+    """e_ijc of the definition -> [ncomp arrays of shape (n_a, n_b)] (a prior: (n_a, 1)), in the arithmetic `dtype`"""
     T = dtype
-    unary = desc.kind in _UNARY
-    if not unary and B is None:
-        raise ValueError("a relative factor has two roles")
-    M = desc.manifold
-    na = _coords(M, A, T).shape[0]
-    nb = 1 if unary else _coords(M, B, T).shape[0]
-    cl = np.full(abi.MAXC, np.nan, dtype=T)
-    if na == 0 or nb == 0:
-        return T(np.nan), cl
     z, circ = predicted_measurement(desc, A, B, T)
     zd, ncomp = len(z), desc.ncomp
     wsum = T(0)
@@ -265,6 +253,31 @@ def factor_likelihood_numpy(desc, A, B=None, dtype=np.float64):
                     s = np.log(q[4 + 3 * k + k]) if k == 0 else s + np.log(q[4 + 3 * k + k])
                 lp = T(-0.5) * acc - (T(zd) * T(_HALF_LOG_2PI) + s)
             e.append((logw + lp).astype(T))
+    return e
+
+
+def shifted_exp(dl, T):
+    """exp(e - M) as pass 2 takes it: a term below exp(-700) counts as zero"""
+    return np.where(dl >= -700, np.exp(np.maximum(dl, T(-745))), T(0))
+
+
+def factor_likelihood_numpy(desc, A, B=None, dtype=np.float64):
+    """the definition on the host, in the arithmetic `dtype` (np.longdouble: the measure of a case's conditioning).  desc: an
+    abi.LikelihoodDesc (or anything with its fields; the slots are not read); A, B: the host points of the two roles (n x P; SE(2)
+    also n x 3 tangent coordinates), B None for a prior -> (loglik, comp_loglik[4]), entries beyond ncomp NaN"""
+    check_desc(desc)
+    T = dtype
+    unary = desc.kind in _UNARY
+    if not unary and B is None:
+        raise ValueError("a relative factor has two roles")
+    M = desc.manifold
+    na = _coords(M, A, T).shape[0]
+    nb = 1 if unary else _coords(M, B, T).shape[0]
+    cl = np.full(abi.MAXC, np.nan, dtype=T)
+    if na == 0 or nb == 0:
+        return T(np.nan), cl
+    e, ncomp = pair_terms(desc, A, B, T), desc.ncomp
+    with np.errstate(divide="ignore", invalid="ignore"):
         Mx = max(x.max() for x in e)
         if not Mx > -np.inf:
             cl[:ncomp] = -np.inf
@@ -272,8 +285,7 @@ def factor_likelihood_numpy(desc, A, B=None, dtype=np.float64):
         ln = np.log(T(na) * T(nb))
         tot = T(0)
         for c in range(ncomp):
-            dl = e[c] - Mx
-            w = np.where(dl >= -700, np.exp(np.maximum(dl, T(-745))), T(0))
+            w = shifted_exp(e[c] - Mx, T)
             S = block_sum_numpy(np.cumsum(w, axis=1)[:, -1])  # (a cumulative sum along j is the running sum in j order)
             tot = tot + S
             cl[c] = (Mx + np.log(S)) - ln if S > 0 else -np.inf

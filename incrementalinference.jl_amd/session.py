@@ -285,6 +285,23 @@ class SolveSession:
                                            lambda p, **kw: likelihood.factorLikelihood(self.fg, p.label, **kw))
         return likelihood.FactorLikelihoods(res.items(), skipped=skipped)
 
+    def jointModes(self, labels=None, maxModes=abi.MAXK, bwScale=abi.MODES_BW_SCALE, tol=abi.MODES_TOL, maxIter=abi.MODES_MAX_ITER,
+                   merge=abi.MODES_MERGE):
+        """The joint hypothesis of the graph under the variables' current beliefs (jointmodes.py): which mode of one variable
+        belongs with which mode of another, and the weight of every combination -> JointModes.  labels: the factors that enter
+        (default: every factor, the unsupported ones listed in `.skipped`; a named unsupported factor is a ValueError).  Where
+        libnbp holds the beliefs, the modes come from ONE `run_modes` launch (`getBeliefModes` through `_query_resident`) and the
+        tables from ONE `run_factor_mode_likelihood` launch (`_query_resident_factors`): no belief travels and `stats` does not
+        move.  On the host copy, `jointmodes.jointModes`."""
+        from . import jointmodes, likelihood
+        maxModes = jointmodes._check_max_modes(maxModes)
+        plans, skipped = likelihood.plan_factors(self.fg, labels, skip_unsupported=labels is None)
+        modes = self.getBeliefModes(jointmodes._plan_variables(plans), bwScale, tol, maxIter, merge)
+        res = self._query_resident_factors(plans, "run_factor_mode_likelihood",
+                                           lambda be, here, place: jointmodes.run_mode_plans(be, here, place, modes, maxModes),
+                                           lambda p, **kw: jointmodes.factorModeLikelihood(self.fg, p.label, modes, maxModes, **kw))
+        return jointmodes.joint_from_tables(modes, res, skipped, maxModes)
+
     # ---- one solve ---------------------------------------------------------------------------------------------------------
     def solve(self, seed=0, eliminationOrder=None, ordering="qr", return_timing=False):
         """solveTree(fg, oldtree=ses.tree, ...) in the session's context -> tree (or (tree, timing) with return_timing: the
