@@ -557,6 +557,13 @@ nbp_status nbp_heatmap_draw(nbp_heatmap *hm, int32_t n, uint64_t seed, int32_t j
                             double *pts_nx2, double *bw_2);
 nbp_status nbp_heatmap_info(const nbp_heatmap *hm, double *bw_2, double *total, double *wtotal, int32_t *M);
 nbp_status nbp_heatmap_destroy(nbp_heatmap *hm);
+/* Self-tests of the two primitives every heatmap density is built on (csrc/nbp_heatmap.h; tests/test_gpu_heatmap_scan.py), host
+ * buffers in and out.  scan_eval: out[n] = SCAN(w), w = in where 0 < in, else 0 -- the launches nbp_heatmap_create and
+ * nbp_heatmap_build make, all n sums back.  search_eval: idx_out[k] = SEARCH(cdf, t[k]), k < nt, one lane per probe; cdf is any
+ * n doubles, not necessarily a scan.  n (and nt) outside 1 .. 2^26: NBP_ERR_INVALID (the sizes are looked at before the
+ * pointers); a null pointer: NBP_ERR_ARG.  Neither keeps anything on the device. */
+nbp_status nbp_heatmap_scan_eval(nbp_ctx *ctx, const double *in, int32_t n, double *out);
+nbp_status nbp_heatmap_search_eval(nbp_ctx *ctx, const double *cdf, int32_t n, const double *t, int32_t nt, int32_t *idx_out);
 /* ---- variable seam: AMP.manifoldProduct + rebandwidth (GraphProductOperations.jl:53-60) --- */
 nbp_status nbp_run_products(nbp_ctx *ctx, const nbp_product_desc *descs, int32_t n);
 /* ---- host-buffer entry points: one call per reference function ----------------------------------

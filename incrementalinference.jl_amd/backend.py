@@ -503,6 +503,24 @@ class HipBackend:
             self._check(self.lib.nbp_heatmap_destroy(hm))
             hm.value = None
 
+    def heatmap_scan_eval(self, a):
+        """nbp_heatmap_scan_eval: the device's scan (csrc/nbp_heatmap.h) of w = a where 0 < a, else 0 -> all len(a) sums"""
+        dp = C.POINTER(C.c_double)
+        a = np.ascontiguousarray(a, dtype=np.float64).reshape(-1)
+        out = np.empty_like(a)
+        self._check(self.lib.nbp_heatmap_scan_eval(self._ctx, a.ctypes.data_as(dp), a.size, out.ctypes.data_as(dp)))
+        return out
+
+    def heatmap_search_eval(self, cdf, t):
+        """nbp_heatmap_search_eval: the device's search of every probe t[k] in cdf (any array of doubles) -> int32 indices"""
+        ip, dp = C.POINTER(C.c_int32), C.POINTER(C.c_double)
+        cdf = np.ascontiguousarray(cdf, dtype=np.float64).reshape(-1)
+        t = np.ascontiguousarray(t, dtype=np.float64).reshape(-1)
+        idx = np.empty(t.size, dtype=np.int32)
+        self._check(self.lib.nbp_heatmap_search_eval(self._ctx, cdf.ctypes.data_as(dp), cdf.size, t.ctypes.data_as(dp), t.size,
+                                                     idx.ctypes.data_as(ip)))
+        return idx
+
     def conv(self, desc, var_pts, var_bw=None, mhidx_in=None, want_mhidx=False, want_bw=True):
         dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
         man = desc.manifold

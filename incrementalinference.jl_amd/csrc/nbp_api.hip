@@ -2340,6 +2340,59 @@ nbp_status nbp_heatmap_destroy(nbp_heatmap *hm) {
   return NBP_OK;
 }
 
+// ---- self-tests of SCAN and SEARCH (nbp_heatmap.h): the whole scan and the search at given probes, back on the host ---------------
+nbp_status nbp_heatmap_scan_eval(nbp_ctx *c, const double *in, int32_t n, double *out) {
+  if (!c) return fail(NBP_ERR_ARG, "null argument");
+  if (n < 1 || n > NBP_HM_MAX_CELLS) return fail(NBP_ERR_INVALID, "heatmap scan_eval: n outside 1 .. 2^26");
+  if (!in || !out) return fail(NBP_ERR_ARG, "null argument");
+  HIPCHK(hipSetDevice(c->device));
+  const size_t tiles = ((size_t)n + NBP_HM_TILE - 1) / NBP_HM_TILE;
+  double *d_in = nullptr, *d_out = nullptr, *t2 = nullptr, *p2 = nullptr;
+  auto body = [&]() -> nbp_status {
+    HIPCHK(hipMalloc(&d_in, sizeof(double) * (size_t)n));
+    HIPCHK(hipMalloc(&d_out, sizeof(double) * (size_t)n));
+    HIPCHK(hipMalloc(&t2, sizeof(double) * tiles));
+    HIPCHK(hipMalloc(&p2, sizeof(double) * tiles));
+    HIPCHK(hipMemcpyAsync(d_in, in, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    NBPCHK(heatmap_scan(c, d_in, n, t2, p2, d_out));
+    HIPCHK(hipMemcpyAsync(out, d_out, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return NBP_OK;
+  };
+  const nbp_status rc = body();
+  if (rc) hipStreamSynchronize(c->stream);  // (nothing of the stream may still read what is freed below)
+  for (void *p : {(void *)d_in, (void *)d_out, (void *)t2, (void *)p2})
+    if (p) hipFree(p);
+  return rc;
+}
+
+nbp_status nbp_heatmap_search_eval(nbp_ctx *c, const double *cdf, int32_t n, const double *t, int32_t nt, int32_t *idx_out) {
+  if (!c) return fail(NBP_ERR_ARG, "null argument");
+  if (n < 1 || n > NBP_HM_MAX_CELLS) return fail(NBP_ERR_INVALID, "heatmap search_eval: n outside 1 .. 2^26");
+  if (nt < 1 || nt > NBP_HM_MAX_CELLS) return fail(NBP_ERR_INVALID, "heatmap search_eval: nt outside 1 .. 2^26");
+  if (!cdf || !t || !idx_out) return fail(NBP_ERR_ARG, "null argument");
+  HIPCHK(hipSetDevice(c->device));
+  double *d_cdf = nullptr, *d_t = nullptr;
+  int32_t *d_idx = nullptr;
+  auto body = [&]() -> nbp_status {
+    HIPCHK(hipMalloc(&d_cdf, sizeof(double) * (size_t)n));
+    HIPCHK(hipMalloc(&d_t, sizeof(double) * (size_t)nt));
+    HIPCHK(hipMalloc(&d_idx, sizeof(int32_t) * (size_t)nt));
+    HIPCHK(hipMemcpyAsync(d_cdf, cdf, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(d_t, t, sizeof(double) * (size_t)nt, hipMemcpyHostToDevice, c->stream));
+    NBPCHK(launch_checked(c, nbp_hm_search_eval_kernel, ((size_t)nt + NBP_HM_LANES - 1) / NBP_HM_LANES, NBP_HM_LANES, 0,
+                          (const double *)d_cdf, (int)n, (const double *)d_t, (int)nt, d_idx));
+    HIPCHK(hipMemcpyAsync(idx_out, d_idx, sizeof(int32_t) * (size_t)nt, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return NBP_OK;
+  };
+  const nbp_status rc = body();
+  if (rc) hipStreamSynchronize(c->stream);
+  for (void *p : {(void *)d_cdf, (void *)d_t, (void *)d_idx})
+    if (p) hipFree(p);
+  return rc;
+}
+
 nbp_status nbp_run_resample(nbp_ctx *c, const int32_t *slots, const int32_t *manifolds, int32_t n, uint64_t seed) {
   if (!c || ((!slots || !manifolds) && n > 0)) return fail(NBP_ERR_ARG, "null argument");
   if (n <= 0) return NBP_OK;

@@ -65,6 +65,7 @@ static __host__ __device__ __forceinline__ double hm_bilinear(const double *data
 #define NBP_HM_DRAW_ARGS                                                                                                \
   const double *wcdf, const double2 *pre, int M, double h, int n, uint64_t seed, int jitter, int32_t *pick, double2 *pts, \
       double *slot, int N
+#define NBP_HM_SEARCH_ARGS const double *cdf, int n, const double *t, int nt, int32_t *idx
 #if NBP_TU & NBP_TU_HEATMAP
 __device__ __forceinline__ double hm_weight(double v) { return v > 0.0 ? v : 0.0; }  // (NaN never arrives: the host refuses it)
 
@@ -257,6 +258,13 @@ nbp_hm_draw_kernel(NBP_HM_DRAW_ARGS) {
     }
   }
 }
+
+// the self-test of SEARCH (nbp_heatmap_search_eval): one lane per probe, cdf any array of n doubles
+__global__ void __launch_bounds__(NBP_HM_LANES)
+nbp_hm_search_eval_kernel(NBP_HM_SEARCH_ARGS) {
+  const int k = blockIdx.x * NBP_HM_LANES + threadIdx.x;
+  if (k < nt) idx[k] = hm_search(cdf, n, t[k]);
+}
 #else
 __global__ void nbp_hm_scan_totals_kernel(NBP_HM_TOTALS_ARGS);
 __global__ void nbp_hm_scan_tiles_kernel(NBP_HM_TILES_ARGS);
@@ -264,4 +272,5 @@ __global__ void nbp_hm_scan_apply_kernel(NBP_HM_APPLY_ARGS);
 __global__ void nbp_hm_presample_kernel(NBP_HM_PRE_ARGS);
 __global__ void nbp_hm_weight_kernel(NBP_HM_WEIGHT_ARGS);
 __global__ void nbp_hm_draw_kernel(NBP_HM_DRAW_ARGS);
+__global__ void nbp_hm_search_eval_kernel(NBP_HM_SEARCH_ARGS);
 #endif

@@ -36,6 +36,7 @@ BM_ATOL = 1e-14  # tests/test_nbp_math.py::test_box_muller_pair
 EPS = 2.0 ** -52
 W_RTOL = mc.DENS_RTOL
 MARGIN = 1e-9
+SEED3R = 2  # of the 65 x 4161 grid
 N_CTX = 150  # the context's N of the device tests (the pass-through case of the reference runs its solver with N = 150 here)
 
 
@@ -54,8 +55,10 @@ def _case(name, nx, ny, xr, yr, M, n, seed, **kw):
 
 
 # 17 x 241 = 4097 = 64 * 64 + 1: one more than a multiple of the segment (64) and of the tile (4096), the block sizes of the two
-# levels a sum of this length has; 257 x 1021 would be the third level's (64^3 + 1) and is beyond the largest grid a test may use --
-# test_heatmap.py runs the sum itself at 64^3 + 1 and 64^3 + 64^2 + 64 + 1 against a tile-by-tile restatement instead.
+# levels a sum of this length has.  The third and the fourth level (more than 64 and more than 4096 tiles: 64^3 + 1 and 2^24 + 1
+# cells) are LEVEL_CASES below; the sum and the search by themselves, at every boundary of every level up to 2^26 elements, are
+# tests/test_gpu_heatmap_scan.py (nbp_heatmap_scan_eval / nbp_heatmap_search_eval against scan_numpy / search_numpy), and
+# test_heatmap.py ties scan_numpy to a wave-by-wave walk of the kernels before the device is compared with it.
 STAGE_CASES = [
     _case("2 x 2", 2, 2, (-1.0, 1.0), (0.0, 3.0), M=1, n=1, seed=1),
     _case("3 x 2", 3, 2, (0.0, 1.0), (-2.0, -1.0), M=63, n=1, seed=1),
@@ -66,6 +69,75 @@ STAGE_CASES = [
     _case("300 x 257", 300, 257, (-3.0, 26.9), (5.0, 30.6), M=1000, n=N_CTX, seed=2, nonpositive=0.1),
     _case("17 x 241 = 64^2 + 1 cells", 17, 241, (0.0, 1.6), (100.0, 124.0), M=10000, n=120, seed=1),
 ]
+
+
+# ---- the third and the fourth level of the sum through the real path (built on first use: the large ones are 134 MB and more) -----
+# Which lengths reach what.  nbp_hm_scan_tiles_kernel forms a P3 carry from 65 tiles on (n > 64^3) and a P4 carry from 4097 tiles
+# on (n > 2^24), but a carry is the one INTO the next segment: the first element whose sum contains the P3 carry of the tile totals
+# is element 64 of tile 65 (n >= 64^3 + 64^2 + 64 + 1), and the first that contains a P4 carry is element 64 of tile 4161
+# (n >= 2^24 + 64^3 + 64^2 + 64 + 1).  At 64^3 + 1 and 2^24 + 1 cells the kernel computes the carry and nothing reads it.  So each
+# level has two grids: the first length with the extra level, and one some tiles past the first element that depends on it.
+LEVEL3_CELLS, LEVEL4_CELLS = 64 ** 3 + 1, 2 ** 24 + 1
+LEVEL3_READ, LEVEL4_READ = 64 ** 3 + 64 ** 2 + 64, 2 ** 24 + 64 ** 3 + 64 ** 2 + 64  # the first element that reads the P3 / P4 carry
+LEVEL4_M = 100_000
+PRE_LEVEL3_MS, PRE_LEVEL3_N = (64 ** 3 + 1, 64 ** 3 + 2 * 64 ** 2 + 1), 200_000  # the pre-sample axis: STAGE_CASES[2], 65 and 67 tiles of weights
+
+# Which margins the level-3 grids need: `cell` needs none -- the device's cdf is scan_numpy's bit for bit (asserted on its own in
+# test_gpu_heatmap_scan.py) and ua * total is the same product on both sides, so the two searches see the same bits (the argument
+# of test_every_M_and_n_on_one_grid).  Nor could a seed provide one: a cell is 3.8e-6 of the total wide, so each of the 10^5 draws
+# lies within 1e-9 of an end of its interval with probability 5e-4, about 50 of them on any seed.  `pre` -> `d` needs the grid
+# margin (a point an ulp across a grid line or a side of the box reads another cell) and `pick` needs its own (the device's W are
+# the restatement's to W_RTOL only, so wcdf differs in its last bits): test_heatmap.py asserts those two.
+
+
+def _level3_grid():
+    """65 x 4033 = 64^3 + 1 cells (65 tiles), a tenth of them <= 0, M = 100 000: every stage as for STAGE_CASES"""
+    return _case("65 x 4033 = 64^3 + 1 cells", 65, 4033, (-3.2, 3.2), (0.0, 403.2), M=100_000, n=N_CTX, seed=2, nonpositive=0.1)
+
+
+def _level3_grid_read():
+    """65 x 4161 = 270 465 cells (67 tiles): the cells from 266 304 on, 1.5 % of them, lie behind the P3 carry"""
+    return _case("65 x 4161: 67 tiles", 65, 4161, (-3.2, 3.2), (0.0, 416.0), M=100_000, n=N_CTX, seed=SEED3R, nonpositive=0.1)
+
+
+def _level4(nx, ny, name, zero_cols):
+    data = np.random.default_rng(100 + nx * ny).uniform(0.1, 2.0, (nx, ny))
+    data[100:120] = -data[100:120]
+    if zero_cols:
+        data[:, ny - zero_cols:] = 0.0
+    return dict(name=name, data=data, x=np.linspace(-12.8, 12.8, nx), y=np.linspace(0.0, 0.1 * (ny - 1), ny), M=LEVEL4_M, n=1, seed=3,
+                seed2=1003)
+
+
+def _level4_grid():
+    """257 x 65281 = 2^24 + 1 cells: rows 100-119 negative (20 x 65281 cells: whole tiles, a run longer than 64 tiles), the last
+    5281 columns of every row zero (a run longer than a tile in every row, and the trailing one).  Only indices and bit-equal
+    sums are asked of it (total, cell) and `pre` to its tolerance: no margin is needed (see above on `cell`)."""
+    return _level4(257, 65281, "257 x 65281 = 2^24 + 1 cells", 5281)
+
+
+def _level4_grid_read():
+    """257 x 67400 = 17 321 800 cells (4229 tiles), rows 100-119 negative: the cells from 17 043 520 on, 1.6 % of them, lie behind
+    the P4 carry, and `total` with them"""
+    return _level4(257, 67400, "257 x 67400: 4229 tiles", 0)
+
+
+_LEVEL_BUILDERS = [("65 x 4033 = 64^3 + 1 cells", _level3_grid), ("65 x 4161: 67 tiles", _level3_grid_read),
+                   ("257 x 65281 = 2^24 + 1 cells", _level4_grid), ("257 x 67400: 4229 tiles", _level4_grid_read)]
+LEVEL_CASES = [name for name, _ in _LEVEL_BUILDERS]
+LEVEL3_CASES, LEVEL4_CASES = LEVEL_CASES[:2], LEVEL_CASES[2:]
+_level_built = {}
+
+
+def level_case(name):
+    """the case of that name; the level-3 grids are kept (2 MB each, the CPU and the device test share them), the level-4 grids
+    are built anew for whoever asks (134 MB and more: one test each)"""
+    if name in _level_built:
+        return _level_built[name]
+    case = dict(_LEVEL_BUILDERS)[name]()
+    if case["data"].size <= 1 << 20:
+        _level_built[name] = case
+    return case
 
 
 def restate(case, **kw):

@@ -1,6 +1,6 @@
 """Heatmap densities on the CPU: `heatmap_density_numpy`, the host restatement of csrc/nbp_heatmap.h, alone -- its pieces against
-their definitions, the conditions under which tests/test_gpu_heatmap.py may ask for equal indices, and the known answers of
-tests/heatmap_cases.py.  Nothing here runs libnbp."""
+their definitions, the conditions under which tests/test_gpu_heatmap.py and tests/test_gpu_heatmap_scan.py may ask for equal
+indices, and the known answers of tests/heatmap_cases.py.  Nothing here runs libnbp."""
 import math
 import types
 
@@ -30,6 +30,31 @@ def _ks(v):
     return v
 
 
+def tiles_kernel(t2):
+    """nbp_hm_scan_tiles_kernel walked wave by wave: T2 -> l2 (kept in p2) and T3; T3 -> l3 and T4; P4 = l4; P3 = l3 + P4[.];
+    P2 = l2 + P3[.] -- m <= 2^14 tile totals -> P2 = scan(T2), the carries as the kernel forms them"""
+    m = t2.size
+    assert m <= 1 << 14
+    p2, t3, p3, t4 = np.zeros(m), np.zeros(256), np.zeros(256), np.zeros(4)
+    nseg2 = -(-m // 64)
+    nseg3 = -(-nseg2 // 64)
+    for src, cnt_all, dst, tot in ((t2, m, p2, t3), (t3, nseg2, p3, t4)):
+        for s in range(-(-cnt_all // 64)):
+            cnt = min(64, cnt_all - s * 64)
+            v = np.zeros(64)
+            v[:cnt] = src[s * 64:s * 64 + cnt]
+            r = _ks(v)
+            dst[s * 64:s * 64 + cnt], tot[s] = r[:cnt], r[cnt - 1]
+    v = np.zeros(64)
+    v[:nseg3] = t4[:nseg3]
+    p4 = _ks(v)
+    for t in range(64, nseg2):
+        p3[t] = p3[t] + p4[t // 64 - 1]
+    for i in range(64, m):
+        p2[i] = p2[i] + p3[i // 64 - 1]
+    return p2
+
+
 def scan_by_tiles(a):
     """the three scan kernels of csrc/nbp_heatmap.h walked tile by tile, wave by wave (zero-padded segments, the carries as the
     kernels form them): what the recursive definition must agree with bit for bit"""
@@ -49,23 +74,7 @@ def scan_by_tiles(a):
         return l, t1
     seg_of = [segments(b) for b in range(tiles)]
     t2 = np.array([_ks(t1)[min(64, -(-(n - b * 4096) // 64)) - 1] for b, (_, t1) in enumerate(seg_of)])
-    m, p2, t3, p3, t4 = tiles, np.zeros(tiles), np.zeros(256), np.zeros(256), np.zeros(4)
-    nseg2 = -(-m // 64)
-    nseg3 = -(-nseg2 // 64)
-    for src, cnt_all, dst, tot in ((t2, m, p2, t3), (t3, nseg2, p3, t4)):
-        for s in range(-(-cnt_all // 64)):
-            cnt = min(64, cnt_all - s * 64)
-            v = np.zeros(64)
-            v[:cnt] = src[s * 64:s * 64 + cnt]
-            r = _ks(v)
-            dst[s * 64:s * 64 + cnt], tot[s] = r[:cnt], r[cnt - 1]
-    v = np.zeros(64)
-    v[:nseg3] = t4[:nseg3]
-    p4 = _ks(v)
-    for t in range(64, nseg2):
-        p3[t] = p3[t] + p4[t // 64 - 1]
-    for i in range(64, m):
-        p2[i] = p2[i] + p3[i // 64 - 1]
+    p2 = tiles_kernel(t2)
     out = np.zeros(n)
     for b, (l, t1) in enumerate(seg_of):
         l1 = _ks(t1)
@@ -95,6 +104,18 @@ def test_scan_is_the_documented_order(n):
         assert abs(s[i] - exact) <= 30 * 2.0 ** -53 * exact
     if n <= 64:  # one segment: the plain Kogge-Stone sums
         assert np.array_equal(s, _ks(np.concatenate([a, np.zeros(64 - n)]))[:n])
+
+
+@pytest.mark.parametrize("m", [64, 65, 4096, 4097, 16384])
+def test_tiles_kernel_walk_is_the_scan_of_the_tile_totals(m):
+    """the second kernel alone, up to the 2^14 tile totals of 2^26 elements (scan_by_tiles takes too long there): scan_numpy's
+    third and fourth level are the kernel's own carry order -- m = 64: no carry; 65: the first P3 carry; 4096: nseg3 = 1 still;
+    4097: the first P4 carry; 16384: four segments at the fourth level.  tests/test_gpu_heatmap_scan.py then holds the device to
+    scan_numpy at the lengths these m belong to."""
+    rng = np.random.default_rng(m)
+    t2 = rng.uniform(0, 1, m) * np.exp(rng.normal(0, 3, m))
+    t2[rng.uniform(size=m) < 0.2] = 0.0
+    assert np.array_equal(tiles_kernel(t2), hm.scan_numpy(t2))
 
 
 def test_search_is_the_first_element_above():
@@ -147,6 +168,23 @@ def test_stage_cases_are_decidable_and_consistent(case):
     J = hc.restate(case, jitter=1)
     assert np.array_equal(J["pick"], R["pick"]) and np.abs((J["points"] - R["points"]) / R["h"]).max() < 6
     assert not np.array_equal(J["points"], R["points"])
+
+
+@pytest.mark.parametrize("name", hc.LEVEL3_CASES)
+def test_level3_grids_are_decidable_where_a_criterion_needs_it(name):
+    """64^3 + 1 cells and 67 tiles of cells, M = 100 000: the grid and the pick margins (what `d` and `pick` of check_stages need)
+    exceed MARGIN on the seed chosen; the cell margin is printed -- no criterion needs it and no seed has it (heatmap_cases)"""
+    case = hc.level_case(name)
+    assert case["data"].size >= hc.LEVEL3_CELLS and 0.05 < np.mean(~(case["data"] > 0)) < 0.15
+    R = hc.restate(case)
+    cell_m, grid_m, pick_m = hc.margins(case, R)
+    print(name, "margins (cell, grid, pick):", (cell_m, grid_m, pick_m))
+    assert min(grid_m, pick_m) > hc.MARGIN, (grid_m, pick_m)
+    flat = case["data"].reshape(-1)
+    assert np.all(flat[R["cell"]] > 0) and R["total"] == R["cdf"][-1] > 0
+    assert np.array_equal(R["points"], R["pre"][R["pick"]]) and R["points"].shape == (case["n"], 2)
+    if case["data"].size > hc.LEVEL3_READ:
+        assert np.sum(R["cell"] >= hc.LEVEL3_READ) > 1000  # pre-samples do land behind the P3 carry
 
 
 def test_offset_field_keeps_its_weights():
