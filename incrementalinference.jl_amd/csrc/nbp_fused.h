@@ -54,7 +54,7 @@ __host__ __device__ inline size_t nbp_update_lds_layout(int Fmax, int D, int N, 
   const size_t tr = o;
   // transient area: the largest of the four phases (all in doubles)
   const size_t prop = 3 * (size_t)N + NBP_RED + ((size_t)N + 1) / 2;
-  const size_t fit = 2 * (size_t)N + (size_t)P * Npad + (size_t)(P * Npad / 64) * 2 * N + NBP_RED + NBP_FITTAB;
+  const size_t fit = 2 * (size_t)N + (size_t)P * Npad + (size_t)(P * Npad / 64) * 2 * N + NBP_RED + NBP_EXPTAB;
   const size_t kd = nbp_update_kd_doubles(D, N, Npad, P) + ((size_t)N + 1) / 2 /* idx */;
   const size_t bulk = (size_t)Fmax * D * N;
   const size_t prodL = 3 * bulk + (circ ? 2 * (size_t)Fmax * N : 0) + (size_t)Fmax * N /* lg */ + 6 * (size_t)Fmax + N + 2 * (size_t)Fmax * Npad /* uu */ +
@@ -71,33 +71,6 @@ __host__ __device__ inline size_t nbp_update_lds_layout(int Fmax, int D, int N, 
 }
 static inline size_t nbp_update_lds_bytes(int Fmax, int D, int N, int Npad, int P, bool circ) {
   return nbp_update_lds_layout(Fmax, D, N, Npad, P, circ, nullptr, nullptr);
-}
-
-// a wave-uniform pointer that arrived in vector registers (function arguments do) back into scalar registers: the
-// descriptor reads and the branches on them stay scalar
-template <class T>
-__device__ __forceinline__ T *uniform_ptr(T *p) {
-  const unsigned long long v = (unsigned long long)p;
-  const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v), hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(v >> 32));
-  return (T *)(((unsigned long long)hi << 32) | lo);
-}
-// One proposal as a real call.  Inlined into the update kernel the proposal's registers (the Nelder-Mead simplex, ~150
-// VGPRs) are allocated together with everything the other phases keep live and the kernel spills; as a function it gets
-// the allocation of the stand-alone proposal kernel, and nothing but uniform values is live across the call.  The LDS
-// areas are passed as offsets into the kernel's dynamic LDS, so that the callee still addresses them as LDS (ds_read /
-// ds_write) instead of through generic pointers.
-template <int FIXK, int FIXM>
-__device__ __attribute__((noinline)) void proposal_call(const nbp_proposal_desc *d, int out_off, int tr_off, double *arena, int N, int Npad,
-                                                        int64_t S, int32_t *side, nbp_counters *ctr) {
-  extern __shared__ double smem[];
-  N = __builtin_amdgcn_readfirstlane(N);
-  Npad = __builtin_amdgcn_readfirstlane(Npad);
-  out_off = __builtin_amdgcn_readfirstlane(out_off);
-  tr_off = __builtin_amdgcn_readfirstlane(tr_off);
-  const unsigned long long s64 = (unsigned long long)S;
-  S = (int64_t)(((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(s64 >> 32)) << 32) |
-                (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)s64));
-  proposal_body<FIXK, FIXM>(uniform_ptr(d), smem + out_off, uniform_ptr(arena), N, Npad, S, uniform_ptr(side), uniform_ptr(ctr), smem + tr_off);
 }
 
 // FIXK / FIXM: the class of the launch (proposals_uniform_class): every relative factor is a full factor of kind FIXK on
@@ -119,11 +92,7 @@ __device__ __forceinline__ void update_body(const nbp_update_desc *uds, const nb
   NBP_TICK_INIT();
   // ---- proposalbeliefs!: the F proposals of the update, one after the other, one lane per particle -----------------
   for (int j = 0; j < F; j++) {
-#ifdef NBP_X_PROPCALL
-    proposal_call<FIXK, FIXM>(props + u->prop[j], (int)(FL.slot + j * SL - smem), (int)(FL.tr - smem), arena, N, Npad, S, side, ctr);
-#else
     proposal_body<FIXK, FIXM>(props + u->prop[j], FL.slot + j * SL, arena, N, Npad, S, side, ctr, FL.tr);
-#endif
     __syncthreads();
   }
   NBP_TICK(50);  // proposals
@@ -231,9 +200,7 @@ __device__ __forceinline__ void update_body(const nbp_update_desc *uds, const nb
 #else
 #define NBP_UPDATE_KERNEL(NAME, K_, M_, P_, WAVES) __global__ void NAME(NBP_UPDATE_ARGS);
 #endif
-#ifndef NBP_W_UPD_E2
 #define NBP_W_UPD_E2 4
-#endif
 // _p1: one lane per particle (workgroup = Npad lanes; N <= 256), for rounds with thousands of updates; _p2: two helper
 // rows (2 Npad lanes), for the rounds that fill the chip only with twice the lanes per update
 NBP_UPDATE_KERNEL(nbp_update_kernel_lin2_p1, NBP_F_LINREL, NBP_EUCLID2, 1, NBP_W_UPD_E2)

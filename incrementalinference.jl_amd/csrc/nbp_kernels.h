@@ -421,23 +421,17 @@ __global__ void nbp_proposal_kernel(NBP_PROPOSAL_ARGS);
 #else
 #define NBP_PROPOSAL_UNIFORM(NAME, K_, M_, WAVES) __global__ void NAME(NBP_PROPOSAL_ARGS);
 #endif
-#ifndef NBP_W_LIN2
 #define NBP_W_LIN2 3
-#endif
 NBP_PROPOSAL_UNIFORM(nbp_proposal_kernel_lin2, NBP_F_LINREL, NBP_EUCLID2, NBP_W_LIN2)
 // Euclid(3) instance at FIVE waves per SIMD (96 VGPRs, 44 B of scratch per lane; 120 VGPRs = four waves per SIMD without the cap):
 // BASELINE's config 5 runs N = 300, i.e. workgroups of five waves, of which a CU holds three at four waves per SIMD (15 waves, two
 // waves of every workgroup on one SIMD) and four at five.  975 proposals at N = 300: 1018 -> 747 us, 4000: 3630 -> 3010 us; a lone
 // proposal and N = 200 unchanged (168 / 499 us); config 5 415 -> 404 ms per solve (profiles/r04_lcv_five_wave_rows.txt, section 5)
-#ifndef NBP_W_LIN3
 #define NBP_W_LIN3 5
-#endif
 NBP_PROPOSAL_UNIFORM(nbp_proposal_kernel_lin3, NBP_F_LINREL, NBP_EUCLID3, NBP_W_LIN3)
 // CircularCircular on the circle (config 3, incl. its multihypo sightings) and ManifoldFactor on SE(2) (config 4)
 NBP_PROPOSAL_UNIFORM(nbp_proposal_kernel_circ, NBP_F_CIRCULAR, NBP_CIRCULAR, 3)
-#ifndef NBP_W_SE2
 #define NBP_W_SE2 2  // (3: 168 VGPRs and 80 B of scratch per lane; measured, profiles/r04_lcv_five_wave_rows.txt section 5)
-#endif
 NBP_PROPOSAL_UNIFORM(nbp_proposal_kernel_se2, NBP_F_SE2, NBP_SE2, NBP_W_SE2)
 
 // ================================================================================================
@@ -655,12 +649,8 @@ __device__ __forceinline__ void proposal_wave_body(const nbp_proposal_desc *d, d
 #define NBP_PROPOSAL_WAVE(NAME, M_, NC_, WAVES) __global__ void NAME(NBP_PROPOSAL_WAVE_ARGS);
 #endif
 #define NBP_PW_WAVES 4
-#ifndef NBP_WW_LIN2
 #define NBP_WW_LIN2 5  // 94 VGPRs
-#endif
-#ifndef NBP_WW_LIN3
 #define NBP_WW_LIN3 3  // 133 / 140 VGPRs
-#endif
 NBP_PROPOSAL_WAVE(nbp_proposal_wave_kernel_lin2, NBP_EUCLID2, 4, NBP_WW_LIN2)
 NBP_PROPOSAL_WAVE(nbp_proposal_wave_kernel_lin3, NBP_EUCLID3, 4, NBP_WW_LIN3)
 NBP_PROPOSAL_WAVE(nbp_proposal_wave_kernel_lin3n5, NBP_EUCLID3, 5, NBP_WW_LIN3)
@@ -734,8 +724,8 @@ __device__ __forceinline__ void lcv_slot_coordinate(double *s, int M, int k, int
   const int N = slot_count(s, Ncap);  // manikde! of the points the belief holds (Ncap = slot capacity = stride)
   const int P = blockDim.x / Npad;
   // the table of lcv_exp first: its address is then a constant of the kernel (one shift for the address of an entry)
-  double *tab = smem, *X = smem + NBP_FITTAB, *part = X + 2 * N, *red = part + P * Npad + (blockDim.x >> 6) * 2 * N;
-  nbp_fit_tab_init(tab);
+  double *tab = smem, *X = smem + NBP_EXPTAB, *part = X + 2 * N, *red = part + P * Npad + (blockDim.x >> 6) * 2 * N;
+  nbp_exp_tab_init(tab);
   // circular coordinates are staged wrapped (the identity for stored beliefs): every pair difference of
   // the fit is then within (-2pi, 2pi), which is what circ_sqdist relies on
   if (n < N) {
@@ -760,9 +750,7 @@ __device__ __forceinline__ void lcv_slot_coordinate(double *s, int M, int k, int
 // ================================================================================================
 #define NBP_BANDWIDTH_ARGS const int32_t *slots, const int32_t *manifolds, double *arena, int N, int Npad, int64_t S, nbp_counters *ctr
 #if NBP_TU & NBP_TU_PREP
-#ifndef NBP_W_PREP
 #define NBP_W_PREP 4
-#endif
 __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(NBP_W_PREP)))
 nbp_bandwidth_kernel(NBP_BANDWIDTH_ARGS) {
   extern __shared__ double smem[];  // grid (jobs, 3)
@@ -801,7 +789,7 @@ template <int DEPTH> __global__ void nbp_bandwidth_kernel_spec(NBP_BANDWIDTH_ARG
 
 // exp table | X[2N] | part[P][Npad] | acc[NW][2N] | red     (NW = P*Npad/64 waves)
 static inline size_t nbp_bandwidth_lds_bytes(int N, int Npad, int P) {
-  return (2 * (size_t)N + (size_t)P * Npad + (size_t)(P * Npad / 64) * 2 * N + NBP_RED + NBP_FITTAB) * 8;
+  return (2 * (size_t)N + (size_t)P * Npad + (size_t)(P * Npad / 64) * 2 * N + NBP_RED + NBP_EXPTAB) * 8;
 }
 
 #if NBP_TU & NBP_TU_PROPOSAL
@@ -1906,15 +1894,9 @@ __global__ void nbp_product_kernel_t2(NBP_PRODUCT_ARGS);
 // waves per SIMD of the single-manifold kernels, measured (profiles/r02_product_waves.txt): Euclid(1/2) are faster at 4
 // (Euclid(2) then spills 76 B per lane; at 3 it is spill-free but 16 % slower on the 10 000-variable chain), Euclid(3),
 // Circular and SE(2) at 3 (140-168 VGPRs: no scratch on Euclid(3), 36 / 120 B on the circular ones; 1-3 % faster)
-#ifndef NBP_W_E2
 #define NBP_W_E2 4
-#endif
-#ifndef NBP_W_SE
 #define NBP_W_SE 2
-#endif
-#ifndef NBP_W_CI
 #define NBP_W_CI 2  // (two waves: no spill -- three spilled 12 B per lane -- and 2 % faster on config 3)
-#endif
 #define NBP_UNIFORM_WAVES(MANI) ((MANI) == NBP_EUCLID1 ? 4 : (MANI) == NBP_EUCLID2 ? NBP_W_E2 : (MANI) == NBP_SE2 ? NBP_W_SE : (MANI) == NBP_CIRCULAR ? NBP_W_CI : 3)
 // the throughput geometry of a single-manifold batch, in two instances: node sums from the KD workspace, and `_xs` (from the
 // sorted coordinates, product_kernel_uniform)

@@ -37,7 +37,7 @@ BASE = 6
 NOPS = 16  # with NBP_FUSED_MIN = 16 the smallest round that fuses
 
 # ---- the LDS need of a fused workgroup, restated from nbp_update_lds_layout (csrc/nbp_fused.h) ---------------------------
-NBP_EXPTAB, NBP_RED, NBP_FITTAB, NBP_KD_PARTS = 256, 64, 256, 512
+NBP_EXPTAB, NBP_RED, NBP_KD_PARTS = 256, 64, 512
 LDS_CEILING = 158 * 1024
 
 
@@ -54,7 +54,7 @@ def lds_bytes(Fmax, D, N, Npad, P, circ=False):
     o = NBP_EXPTAB + Fmax * SL + Fmax * 3 + Fmax * 3
     tr = (o + 1) & ~1
     prop = 3 * N + NBP_RED + (N + 1) // 2
-    fit = 2 * N + P * Npad + (P * Npad // 64) * 2 * N + NBP_RED + NBP_FITTAB
+    fit = 2 * N + P * Npad + (P * Npad // 64) * 2 * N + NBP_RED + NBP_EXPTAB
     kd = kd_doubles(D, N, Npad, P) + (N + 1) // 2
     bulk = Fmax * D * N
     prod = 3 * bulk + (2 * Fmax * N if circ else 0) + Fmax * N + 6 * Fmax + N + 2 * Fmax * Npad + (Fmax * Npad * 2 + 1) // 2

@@ -10,8 +10,8 @@
 __global__ void __launch_bounds__(1024) k_vals(const double *pts, int N, int Npad, int circ, const double *hs, int nh, double *out) {
   extern __shared__ double smem[];
   const int P = blockDim.x / Npad, n = threadIdx.x;
-  double *tab = smem, *X = smem + NBP_FITTAB, *part = X + 2 * N, *red = part + P * Npad + (blockDim.x >> 6) * 2 * N;
-  nbp_fit_tab_init(tab);
+  double *tab = smem, *X = smem + NBP_EXPTAB, *part = X + 2 * N, *red = part + P * Npad + (blockDim.x >> 6) * 2 * N;
+  nbp_exp_tab_init(tab);
   if (n < N) X[n] = X[n + N] = pts[n];
   double *acc = part + P * Npad;
   for (int q = n; q < (int)(blockDim.x >> 6) * 2 * N; q += blockDim.x) acc[q] = 0.0;
@@ -49,7 +49,7 @@ int main(int argc, char **argv) {
         hipMalloc(&dp, N * 8); hipMalloc(&dh, hs.size() * 8); hipMalloc(&dout, hs.size() * 32);
         hipMemcpy(dp, p.data(), N * 8, hipMemcpyHostToDevice);
         hipMemcpy(dh, hs.data(), hs.size() * 8, hipMemcpyHostToDevice);
-        const size_t lds = (2 * (size_t)N + (size_t)P * Npad + (size_t)(P * Npad / 64) * 2 * N + NBP_RED + NBP_FITTAB) * 8;
+        const size_t lds = (2 * (size_t)N + (size_t)P * Npad + (size_t)(P * Npad / 64) * 2 * N + NBP_RED + NBP_EXPTAB) * 8;
         k_vals<<<1, P * Npad, lds>>>(dp, N, Npad, circ, dh, (int)hs.size(), dout);
         std::vector<double> o(hs.size() * 4);
         hipMemcpy(o.data(), dout, o.size() * 8, hipMemcpyDeviceToHost);
