@@ -171,6 +171,7 @@ __device__ __forceinline__ void sincos_fast(double a, double *sn, double *cs) { 
 // `tab` = the 256-entry table of nbp_lcv_table.h staged in LDS (nbp_exp_tab_init), read through lcv_tab_scaled; the
 // bandwidth fit's lcv_exp reads the same table
 #include "nbp_lcv_table.h"
+#include "nbp_lcv_pairs.h"
 #define NBP_EXPTAB NBP_LCVTAB
 __device__ __forceinline__ void nbp_exp_tab_init(double *tab) {
   for (int q = threadIdx.x; q < NBP_LCVTAB; q += blockDim.x) tab[q] = __longlong_as_double((long long)NBP_LCV_TAB[q]);
@@ -1475,6 +1476,13 @@ __device__ __forceinline__ double neg_loo_ll(const double *x, int N, int Npad, b
 //   the sums: <= N / 4 + 2 additions of positive terms per lane, u each; v_log_f32: 1 ulp of |log2| <= 46: 64 u; slack 34 u
 //   => bound E = u (24 X + 314 + N / 4)   (lcv_f32_bound; the differences measured are ~1e-3 of it: rounding errors do not
 //      line up over N^2 terms)
+//   Pairs once (ONCE, one-row workgroups of the throughput kernels; nbp_lcv_pairs.h): the waves of the full chunks of 64
+//   visit every unordered pair among them once and add its term to both ends -- the lane's own sum (four accumulators in
+//   turn) and a sum that travels round the wave with the partner.  The terms are the same three operations; what changes in
+//   the derivation is "the sums": a point's sum is its own sum plus one travelling sum per block, added in a fixed order, and
+//   the longest chain of additions of positive terms behind it is a travelling sum's 63 and the <= 3 rows from its own on:
+//   66, for every N (the own sums: <= 44 + 2 + 3; the partial chunk's points: N / 4 + 2 as before)
+//   => E = u (24 X + 312 + max(N / 4 + 2, 66))   (lcv_f32_bound<true>)
 // Returns NaN when some point's sum is below 2^-40 (an isolated point: its nearest neighbour decides the sum and the bound
 // above does not cover it) -- the caller then evaluates in double precision.
 // LDS: the scaled points live in the first row of the partner accumulators (all zero between evaluations, restored here).
@@ -1553,9 +1561,58 @@ __device__ __forceinline__ float loo_f32_redealt(const float4 *x4, int ga, int g
 // |f_single - f_double| <= this (see above; u = 2^-24): u (24 X + 250 + N / 4) for the sums + 64 u for log2 in single precision
 // (circular coordinates: the differences of the integer angles are exact and their conversion rounds like the subtraction it
 // replaces; what is left of the representation term is the grid itself, 2 pi / 2^32 per angle: xmax = 0.0125 stands for it)
+// ONCE (the kernels whose one-row workgroups visit every pair once, nbp_lcv_pairs.h): the longest chain of additions is 66
+// there -- a travelling sum's 63 round the wave and the rows added after it -- whatever N: 66 instead of N / 4 + 2
+template <bool ONCE = false>
 __device__ __forceinline__ double lcv_f32_bound(double xmax, double h, int N) {
+  if (ONCE) return 5.9604644775390625e-8 * (24.0 * (xmax * (0.84932180028801907 / h)) + 312.0 + fmax(0.25 * (double)N + 2.0, 66.0));
   return 5.9604644775390625e-8 * (24.0 * (xmax * (0.84932180028801907 / h)) + 314.0 + 0.25 * (double)N);
 }
+// ---- every unordered pair ONCE (nbp_lcv_pairs.h: the schedule; one-row workgroups of at most four waves) -----------------
+// wave_ror:1: lane l takes the value of lane l - 1 (mod 64).  The coordinate moves by a plain DPP move; the travelling sum
+// with an old value of zero, which lets the compiler fold its rotation into the addition (v_add_f32_dpp).
+__device__ __forceinline__ float lcv_ror(float v) { return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x13C, 0xF, 0xF, false)); }
+__device__ __forceinline__ float lcv_ror_sum(float v) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x13C, 0xF, 0xF, false)); }
+template <bool CIRC>
+__device__ __forceinline__ float loo_f32_pair(float xi, float y, float K) {
+  // (circular: the integer angles rotate as they are; the difference modulo 2^32 is taken after the rotation, as in loo_f32_quad)
+  const float d = CIRC ? (float)(int)(__float_as_uint(xi) - __float_as_uint(y)) * K : xi - y;
+  return __builtin_amdgcn_exp2f(-d * d);
+}
+// one block of the schedule: y = the met chunk's coordinate of this lane; the own sums go to o0 .. o3 in turn, the travelling
+// sum -- ONE chain of k.nboth additions -- is returned where it stands after the last both-ends offset
+template <bool CIRC>
+__device__ __forceinline__ float loo_f32_block(const nbp_lcv_block k, float xi, float y, float K, float &o0, float &o1, float &o2, float &o3) {
+  if (k.t0) y = lcv_ror(y);
+  float e = loo_f32_pair<CIRC>(xi, y, K), ps = e;
+  o0 += e;
+  int s = 1;
+  for (; s + 3 < k.nboth; s += 4) {
+    y = lcv_ror(y); e = loo_f32_pair<CIRC>(xi, y, K); o1 += e; ps = lcv_ror_sum(ps) + e;
+    y = lcv_ror(y); e = loo_f32_pair<CIRC>(xi, y, K); o2 += e; ps = lcv_ror_sum(ps) + e;
+    y = lcv_ror(y); e = loo_f32_pair<CIRC>(xi, y, K); o3 += e; ps = lcv_ror_sum(ps) + e;
+    y = lcv_ror(y); e = loo_f32_pair<CIRC>(xi, y, K); o0 += e; ps = lcv_ror_sum(ps) + e;
+  }
+  for (; s < k.nboth; s++) {
+    y = lcv_ror(y); e = loo_f32_pair<CIRC>(xi, y, K); o1 += e; ps = lcv_ror_sum(ps) + e;
+  }
+  if (k.n > k.nboth) o2 += loo_f32_pair<CIRC>(xi, lcv_ror(y), K);  // the diagonal's t = 32: the own end only
+  return ps;
+}
+// all blocks of full wave w (uniform), lane l: the own sum of point 64 w + l over its partners in full chunks; the travelling
+// sums into `rows` (one writer per entry; read and cleared by neg_loo_ll_f32 after its barrier)
+template <bool CIRC>
+__device__ __forceinline__ void loo_f32_once(const float *xf, float *rows, int W, int w, int l, float xi, float K, float &o0, float &o1, float &o2,
+                                             float &o3) {
+  const int nb = nbp_lcv_blocks(W);
+#pragma unroll 1
+  for (int b = 0; b < nb; b++) {
+    const nbp_lcv_block k = nbp_lcv_block_of(W, w, b);
+    const float ps = loo_f32_block<CIRC>(k, xi, b ? xf[64 * k.chunk + l] : xi, K, o0, o1, o2, o3);
+    rows[nbp_lcv_slot(W, b, k, l)] = ps;
+  }
+}
+template <bool ONCE = false>
 __device__ __forceinline__ double neg_loo_ll_f32(const double *x, int N, int Npad, bool circ, double h, double lognorm0, double cen,
                                                  double *part, double *red) {
   const int tid = threadIdx.x;
@@ -1583,7 +1640,25 @@ __device__ __forceinline__ double neg_loo_ll_f32(const double *x, int N, int Npa
   const bool behind = __builtin_amdgcn_readfirstlane((int)(i >= lastbase + 64)) != 0;  // a wave without a point (a belief of fewer points than the slot)
   const float4 *x4 = (const float4 *)xf;
   float sf = 0.f;
-  if (behind) {
+  // pair-once schedule: the waves of the full chunks (uniform); `rows` lies behind what the clearing loop below covers
+  const int W = nbp_lcv_full(N);
+  const bool once = ONCE && nbp_lcv_pairs_once(N, Npad, P);
+  float *rows = xf + 4 * G4 + 4;
+  if (once && __builtin_amdgcn_readfirstlane(i >> 6) < W) {
+    const int w = __builtin_amdgcn_readfirstlane(i >> 6), gt = nbp_lcv_tail_group(W);
+    const float xi = xf[i];
+    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+    if (circ) {
+      loo_f32_once<true>(xf, rows, W, w, i & 63, xi, K, s0, s1, s2, s3);
+      loo_f32_groups<true, false>(x4, gt, full, xi, i, K, s0, s1, s2, s3);
+      if (G4 > full) loo_f32_tail<true>(x4, full, true, xi, i, N, K, s0, s1, s2, s3);
+    } else {
+      loo_f32_once<false>(xf, rows, W, w, i & 63, xi, K, s0, s1, s2, s3);
+      loo_f32_groups<false, false>(x4, gt, full, xi, i, K, s0, s1, s2, s3);
+      if (G4 > full) loo_f32_tail<false>(x4, full, true, xi, i, N, K, s0, s1, s2, s3);
+    }
+    sf = (s0 + s1) + (s2 + s3);
+  } else if (behind) {
   } else if (redeal) {
     const int l = tid & 63, pi = lastbase + (l & ((1 << lg2) - 1)), hh = l >> lg2;
     const float xi = (pi < N) ? xf[pi] : 0.f;
@@ -1614,6 +1689,13 @@ __device__ __forceinline__ double neg_loo_ll_f32(const double *x, int N, int Npa
   double term = 0;
   if (p == 0 && i < N) {
     float s = sf;
+    if (once && i < 64 * W) {  // the travelling sums of this point, row by row (read-and-clear: LDS stays all zero)
+      for (int b = 0; b < nbp_lcv_blocks(W); b++) {
+        float *r = rows + nbp_lcv_read(W, b, i);
+        s += *r;
+        *r = 0.f;
+      }
+    }
     if (P > 1) {
       double sd = 0;
       for (int q = 0; q < P; q++) {
@@ -1637,6 +1719,7 @@ __device__ __forceinline__ double neg_loo_ll_f32(const double *x, int N, int Npa
   return fma(-0.69314718055994531 / (double)N, tsum, red[32] + lognorm0);
 }
 
+template <bool ONCE = false>  // ONCE: the single-precision evaluations of one-row workgroups visit every pair once (nbp_lcv_pairs.h)
 __device__ __forceinline__ double lcv_bandwidth_1d(const double *x, int N, int Npad, bool circ, double *part, double *red,
                                                    const double *tab, nbp_counters *ctr) {
   const int i = threadIdx.x;
@@ -1682,10 +1765,10 @@ __device__ __forceinline__ double lcv_bandwidth_1d(const double *x, int N, int N
   while (true) {
     double v, ev = 0.0;
     if (m32 && todo <= 2) {
-      v = neg_loo_ll_f32(x, N, Npad, circ, pt * scs, ln0, cen, part, red);
+      v = neg_loo_ll_f32<ONCE>(x, N, Npad, circ, pt * scs, ln0, cen, part, red);
       nev32++;
       if (!(fabs(v) < INFINITY)) { m32 = false; continue; }  // invalid (an isolated point, NaN): the same point in double precision
-      ev = lcv_f32_bound(xmax, pt * scs, N);
+      ev = lcv_f32_bound<ONCE>(xmax, pt * scs, N);
     } else {
       v = neg_loo_ll(x, N, Npad, circ, pt * scs, ln0, part, red, tab);
       nev++;

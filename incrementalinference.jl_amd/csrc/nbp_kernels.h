@@ -713,7 +713,8 @@ __global__ void nbp_deconv_kernel(NBP_DECONV_ARGS);
 static inline size_t nbp_proposal_lds_bytes(int N) { return ((size_t)3 * N + NBP_RED) * 8 + (size_t)N * 4; }
 
 // fit the bandwidth of coordinate k of a resident slot (block-uniform early exit for k >= D)
-template <int SPEC>  // 0: sequential search; 2 / 3: speculative search, that many iterations per rendezvous
+// ONCE: see lcv_bandwidth_1d (the sequential search of the four-wave throughput kernels only)
+template <int SPEC, bool ONCE = false>  // 0: sequential search; 2 / 3: speculative search, that many iterations per rendezvous
 __device__ __forceinline__ void lcv_slot_coordinate(double *s, int M, int k, int Ncap, int Npad, double *smem, nbp_counters *ctr,
                                                     nbp_spec_area *area = nullptr, int role = 0) {
   const int D = mani_dim(M), n = threadIdx.x;
@@ -739,7 +740,7 @@ __device__ __forceinline__ void lcv_slot_coordinate(double *s, int M, int k, int
     if (n == 0 && role == 0) s[3 * Ncap + k] = hs;
     return;
   }
-  double h = lcv_bandwidth_1d(X, N, Npad, is_circ(M, k), part, red, tab, ctr);
+  double h = lcv_bandwidth_1d<ONCE>(X, N, Npad, is_circ(M, k), part, red, tab, ctr);
   if (n == 0) s[3 * Ncap + k] = h;
 }
 
@@ -754,7 +755,7 @@ __device__ __forceinline__ void lcv_slot_coordinate(double *s, int M, int k, int
 __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(NBP_W_PREP)))
 nbp_bandwidth_kernel(NBP_BANDWIDTH_ARGS) {
   extern __shared__ double smem[];  // grid (jobs, 3)
-  lcv_slot_coordinate<0>(arena + S * slots[blockIdx.x], manifolds[blockIdx.x], blockIdx.y, N, Npad, smem, ctr);
+  lcv_slot_coordinate<0, true>(arena + S * slots[blockIdx.x], manifolds[blockIdx.x], blockIdx.y, N, Npad, smem, ctr);
 }
 #else
 __global__ void nbp_bandwidth_kernel(NBP_BANDWIDTH_ARGS);
@@ -1038,7 +1039,7 @@ static inline size_t nbp_kd_lds_bytes(int D, int N, int Npad, int P) {
 // kdF: the largest nfactors of the batch in its low 16 bits; bit 16 = the product launch behind this one takes the node
 // sums from the sorted coordinates itself (product_kernel_uniform<.., XS = true>): the KD builds leave them out
 #define NBP_KD_NOSTATS 0x10000
-template <int SPEC>
+template <int SPEC, bool ONCE = false>
 __device__ __forceinline__ void prep_body(const int32_t *bw_slots, const int32_t *bw_manis, int nbw, const nbp_product_desc *descs, int nprod, int kdF_,
                                           double *arena, double *ws, int N, int Npad, int64_t S, const nbp_levels &T, nbp_counters *ctr,
                                           nbp_spec_area *spec, double *smem) {
@@ -1048,7 +1049,7 @@ __device__ __forceinline__ void prep_body(const int32_t *bw_slots, const int32_t
   constexpr int KS = SPEC ? (1 << SPEC) - 1 : 1;  // workgroups per (slot, coordinate)
   if (b < 3 * nbw * KS) {  // manikde! bandwidth of (slot, coordinate)
     const int job = b / (3 * KS), k = (b % (3 * KS)) / KS, role = b % KS;
-    lcv_slot_coordinate<SPEC>(arena + S * bw_slots[job], bw_manis[job], k, N, Npad, smem, ctr, SPEC ? spec + (job * 3 + k) : nullptr, role);
+    lcv_slot_coordinate<SPEC, ONCE>(arena + S * bw_slots[job], bw_manis[job], k, N, Npad, smem, ctr, SPEC ? spec + (job * 3 + k) : nullptr, role);
     return;
   }
   const int q = b - 3 * nbw * KS, p = q / kdF, j = q % kdF;  // kdF = largest nfactors of the batch
@@ -1073,7 +1074,7 @@ __device__ __forceinline__ void prep_body(const int32_t *bw_slots, const int32_t
 __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(NBP_W_PREP)))
 nbp_prep_kernel(NBP_PREP_ARGS) {
   extern __shared__ double smem[];
-  prep_body<0>(bw_slots, bw_manis, nbw, descs, nprod, kdF, arena, ws, N, Npad, S, T, ctr, nullptr, smem);
+  prep_body<0, true>(bw_slots, bw_manis, nbw, descs, nprod, kdF, arena, ws, N, Npad, S, T, ctr, nullptr, smem);
 }
 #else
 __global__ void nbp_prep_kernel(NBP_PREP_ARGS);

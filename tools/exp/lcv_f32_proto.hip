@@ -1,6 +1,9 @@
 // Prototype of the bandwidth fit's likelihood evaluation in single precision (the "bracketing" evaluations of the golden-section
 // search): what one evaluation costs per ordered pair on gfx950 for several forms of the pair loop.  One workgroup of 256 lanes
 // per fit, N = 200 points, lane i owns point i, EV evaluations in a row at different bandwidths, chip-filling launch.
+// Second part (k_once): every unordered pair visited ONCE by a wave-wide DPP rotation (wave_ror:1, or row_ror:1 inside rows of
+// 16 lanes) against the library's ordered broadcast loop, N = 200 and 256, four 256-lane workgroups per CU: shader cycles of
+// the pair loop per wave (s_memtime) and the launch time.
 //   hipcc --offload-arch=gfx950 -O3 lcv_f32_proto.hip -o lcv_f32_proto && ./lcv_f32_proto
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -123,6 +126,181 @@ static void run(const char *name, const double *dp, float *dout, int fits, int E
   printf("%-44s %8.3f ms  %7.3f ps per ordered pair  = %7.3f ps per symmetric pair   checksum %.6e\n", name, ms, ms * 1e9 / pairs, 2 * ms * 1e9 / pairs, cs);
 }
 
+// ------------------------------------------------------------------------------------------------
+// Pair-once schedule against the ordered loop.  M: 0 = ordered broadcast loop with the self term masked in the own wave's
+// groups (the library's loop); 1 = wave_ror:1 rotation; 2 = row_ror:1 inside rows of 16 lanes, one cross-row step per 16
+// (the partner's coordinate and sum move to the next row through ds_bpermute).  NN points; the waves of the W = NN / 64 full
+// chunks run a diagonal block (t = 1 .. 32), floor((W - 1) / 2) whole blocks (t = 0 .. 63) and, for even W, half of the block
+// opposite; the partial chunk's points arrive as broadcast partners, the partial wave sums over all partners.
+#define ROR1(v) __builtin_amdgcn_mov_dpp((v), 0x13C, 0xF, 0xF, false)  // (every lane reads a lane: no old value to keep)
+#define RROR1(v) __builtin_amdgcn_mov_dpp((v), 0x121, 0xF, 0xF, false)
+__device__ __forceinline__ float ror_f(float v) { return __int_as_float(ROR1(__float_as_int(v))); }
+__device__ __forceinline__ float rror_f(float v) { return __int_as_float(RROR1(__float_as_int(v))); }
+// the rotating sum: with an old value of zero the compiler folds the rotation into the addition (v_add_f32_dpp)
+__device__ __forceinline__ float ror_s(float v) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x13C, 0xF, 0xF, false)); }
+__device__ __forceinline__ float rror_s(float v) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x121, 0xF, 0xF, false)); }
+__device__ __forceinline__ float pair_e(float xi, float y) {
+  const float d = xi - y;
+  return exp2_fast(-d * d);
+}
+// n steps of one block by wave_ror: the first step without (first = false) or with a rotation; returns the partner sums,
+// which sit first + n - 1 lanes from home
+__device__ __forceinline__ float block_wave(float xi, float y, int n, bool first, float &o0, float &o1, float &o2, float &o3) {
+  if (first) y = ror_f(y);
+  float e = pair_e(xi, y), ps = e;
+  o3 += e;
+  int s = 1;
+  for (; s + 3 < n; s += 4) {
+    y = ror_f(y); e = pair_e(xi, y); o0 += e; ps = ror_s(ps) + e;
+    y = ror_f(y); e = pair_e(xi, y); o1 += e; ps = ror_s(ps) + e;
+    y = ror_f(y); e = pair_e(xi, y); o2 += e; ps = ror_s(ps) + e;
+    y = ror_f(y); e = pair_e(xi, y); o3 += e; ps = ror_s(ps) + e;
+  }
+  for (; s < n; s++) {
+    y = ror_f(y); e = pair_e(xi, y); o0 += e; ps = ror_s(ps) + e;
+  }
+  return ps;
+}
+// the same by row_ror (a timing stand-in: the full blocks visit the right pairs, the diagonal and half blocks the right NUMBER
+// of pairs, so its checksum differs): lane l of row r meets (row r - R, lane l - t) for R = 0 .. n / 16 - 1, t = 0 .. 15 (first: from t = 1,
+// R = 0 on: n steps); moving on by a row is one ds_bpermute of the coordinate and of the sum
+__device__ __forceinline__ float block_row(float xi, float y, int n, bool first, int lane, float &o0, float &o1, float &o2, float &o3) {
+  const int up = ((((lane >> 4) - 1) & 3) * 16 + ((lane - 1) & 15)) << 2;  // from (row - 1, column - 1): the sixteenth column step and the row step in one
+  float ps = 0.f;
+  int s = first ? 1 : 0;
+  const int end = s + n;
+  if (first) y = rror_f(y);
+  while (s < end) {
+    const int m = min(end, (s & ~15) + 16);
+    for (; s < m; s++) {
+      const float e = pair_e(xi, y);
+      o0 += e;
+      ps += e;
+      if (s + 1 < m) { y = rror_f(y); ps = rror_s(ps); }
+    }
+    if (s < end) {
+      y = __int_as_float(__builtin_amdgcn_ds_bpermute(up, __float_as_int(y)));
+      ps = __int_as_float(__builtin_amdgcn_ds_bpermute(up, __float_as_int(ps)));
+    }
+  }
+  return ps;
+}
+template <int M, int NN>
+__global__ void __launch_bounds__(256) k_once(const double *pts, float *out, int EV, unsigned long long *cyc) {
+  extern __shared__ __attribute__((aligned(16))) float sm[];  // (sized by the host so that four workgroups share a CU)
+  constexpr int W = NN >> 6, G4 = (NN + 3) >> 2, KF = (W - 1) / 2, ROWS = 1 + KF + ((W & 1) ? 0 : 1);
+  float *xs = sm, *rows = sm + 4 * G4;
+  const int i = threadIdx.x, l = i & 63, w = __builtin_amdgcn_readfirstlane(i >> 6);
+  const double *x = pts + (size_t)blockIdx.x * NN;
+  for (int j = i; j < ROWS * 64 * W; j += 256) rows[j] = 0.f;
+  float acc_out = 0.f;
+  unsigned long long cy = 0;
+  for (int ev = 0; ev < EV; ev++) {
+    const double h = 0.2 + 0.01 * ev;
+    const double sc = sqrt(1.4426950408889634 / (2.0 * h * h));
+    __syncthreads();
+    for (int j = i; j < 4 * G4; j += 256) xs[j] = (j < NN) ? (float)(x[j] * sc) : 0.f;
+    __syncthreads();
+    const unsigned long long c0 = __builtin_amdgcn_s_memtime();
+    const float xi = (i < NN) ? xs[i] : 0.f;
+    const float4 *x4 = (const float4 *)xs;
+    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+    auto ordered = [&](int ga, int gb, bool mask) {
+#pragma unroll 2
+      for (int g = ga; g < gb; g++) {
+        const float4 y = x4[g];
+        float e0 = pair_e(xi, y.x), e1 = pair_e(xi, y.y), e2 = pair_e(xi, y.z), e3 = pair_e(xi, y.w);
+        const int j = 4 * g;
+        if (mask) {
+          e0 = (j == i || j >= NN) ? 0.f : e0;
+          e1 = (j + 1 == i || j + 1 >= NN) ? 0.f : e1;
+          e2 = (j + 2 == i || j + 2 >= NN) ? 0.f : e2;
+          e3 = (j + 3 == i || j + 3 >= NN) ? 0.f : e3;
+        }
+        s0 += e0; s1 += e1; s2 += e2; s3 += e3;
+      }
+    };
+    if (M == 0 || w >= W) {
+      if (i < NN) {
+        const int o0 = w * 16;
+        ordered(0, min(o0, NN >> 2), false);
+        ordered(min(o0, NN >> 2), min(o0 + 16, NN >> 2), true);
+        ordered(min(o0 + 16, NN >> 2), NN >> 2, false);
+        if (NN & 3) ordered(NN >> 2, G4, true);
+      }
+    } else {
+      auto put = [&](int r, int chunk, int off, float ps) { rows[(r * W + chunk) * 64 + ((l - off) & 63)] = ps; };
+      float ps;
+      // diagonal: t = 1 .. 31 to both ends, t = 32 to the own sum only (the lane 32 away does the same for its end)
+      if (M == 1) {
+        ps = block_wave(xi, xi, 31, true, s0, s1, s2, s3);
+        s0 += pair_e(xi, __shfl(xi, l ^ 32, 64));
+      } else {
+        ps = block_row(xi, xi, 31, true, l, s0, s1, s2, s3);
+        s0 += pair_e(xi, __shfl(xi, l ^ 32, 64));
+      }
+      put(0, w, 31, ps);
+      for (int k = 1; k <= KF; k++) {
+        int c = w + k;
+        c -= (c >= W) ? W : 0;
+        const float y = xs[64 * c + l];
+        ps = (M == 1) ? block_wave(xi, y, 64, false, s0, s1, s2, s3) : block_row(xi, y, 64, false, l, s0, s1, s2, s3);
+        put(k, c, 63, ps);
+      }
+      if ((W & 1) == 0) {
+        const bool hi = w >= W / 2;
+        const int c = hi ? w - W / 2 : w + W / 2;
+        const float y = xs[64 * c + l];
+        ps = (M == 1) ? block_wave(xi, y, 32, hi, s0, s1, s2, s3) : block_row(xi, y, 32, hi, l, s0, s1, s2, s3);
+        put(KF + 1, c, hi ? 32 : 31, ps);
+      }
+      ordered(16 * W, NN >> 2, false);
+      if (NN & 3) ordered(NN >> 2, G4, true);
+    }
+    float s = (s0 + s1) + (s2 + s3);
+    cy += __builtin_amdgcn_s_memtime() - c0;
+    __syncthreads();
+    if (M != 0 && i < 64 * W) {
+      for (int r = 0; r < ROWS; r++) {
+        s += rows[r * 64 * W + i];
+        rows[r * 64 * W + i] = 0.f;
+      }
+    }
+    acc_out += __logf(fmaxf(s, 1e-30f));
+  }
+  if (i < NN) out[(size_t)blockIdx.x * NN + i] = acc_out;
+  if (l == 0 && w < W) atomicAdd(cyc, cy);
+}
+
+template <int M, int NN>
+static void run_once(const char *name, const double *dp, float *dout, int fits, int EV, unsigned long long *dcyc) {
+  hipEvent_t a, b;
+  hipEventCreate(&a);
+  hipEventCreate(&b);
+  const size_t lds = 36 * 1024;  // 160 KB per CU: four workgroups
+  k_once<M, NN><<<fits, 256, lds>>>(dp, dout, 2, dcyc);
+  hipDeviceSynchronize();
+  hipMemset(dcyc, 0, 8);
+  hipEventRecord(a);
+  k_once<M, NN><<<fits, 256, lds>>>(dp, dout, EV, dcyc);
+  hipEventRecord(b);
+  hipEventSynchronize(b);
+  float ms;
+  hipEventElapsedTime(&ms, a, b);
+  unsigned long long cy = 0;
+  hipMemcpy(&cy, dcyc, 8, hipMemcpyDeviceToHost);
+  std::vector<float> r((size_t)fits * NN);
+  hipMemcpy(r.data(), dout, r.size() * 4, hipMemcpyDeviceToHost);
+  double cs = 0;
+  for (float v : r) cs += v;
+  constexpr int W = NN >> 6;
+  // unordered pairs a full wave's lane covers per evaluation: (NN - 1) / 2 among full chunks on average, counted as the
+  // ordered loop's NN - 1 partners halved, so that both forms divide by the same number
+  const double wave_evals = (double)fits * EV * W, upairs = 0.5 * (NN - 1);
+  printf("N %d %-34s %8.3f ms  %8.0f cycles per wave and evaluation (four waves a SIMD)  %6.2f cycles per unordered pair and wave, /4 = %5.2f per SIMD   checksum %.6e\n",
+         NN, name, ms, cy / wave_evals, cy / wave_evals / upairs, cy / wave_evals / upairs / 4, cs);
+}
+
 int main(int argc, char **argv) {
   const int fits = argc > 1 ? atoi(argv[1]) : 8192, EV = argc > 2 ? atoi(argv[2]) : 16;
   std::vector<double> p((size_t)fits * N);
@@ -142,5 +320,16 @@ int main(int argc, char **argv) {
   run<1>("V1 broadcast b128, self term masked", dp, dout, fits, EV, &r);
   run<2>("V2 packed f32, self term subtracted", dp, dout, fits, EV, &r);
   run<3>("V3 rotation (per-lane reads)", dp, dout, fits, EV, &r);
+  {  // pair-once schedule: the first `fits * 200` doubles serve as `fits * 200 / NN` clouds of NN points
+    unsigned long long *dcyc;
+    hipMalloc(&dcyc, 8);
+    const int f2 = fits * N / 256;
+    run_once<0, 200>("ordered broadcast, masked", dp, dout, f2, EV, dcyc);
+    run_once<1, 200>("pair once, wave_ror:1", dp, dout, f2, EV, dcyc);
+    run_once<2, 200>("pair once, row_ror:1 + bpermute", dp, dout, f2, EV, dcyc);
+    run_once<0, 256>("ordered broadcast, masked", dp, dout, f2, EV, dcyc);
+    run_once<1, 256>("pair once, wave_ror:1", dp, dout, f2, EV, dcyc);
+    run_once<2, 256>("pair once, row_ror:1 + bpermute", dp, dout, f2, EV, dcyc);
+  }
   return 0;
 }
