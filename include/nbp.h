@@ -381,6 +381,58 @@ nbp_status nbp_run_kld(nbp_ctx *ctx, const int32_t *slots_a, const int32_t *slot
 /* host-buffer form: stages through slots 0 and 1 */
 nbp_status nbp_kde_kld(nbp_ctx *ctx, int32_t manifold, const double *a_NxP, int32_t na, const double *bw_a_D, const double *b_NxP,
                        int32_t nb, const double *bw_b_D, double *kld_out, double *terms_out_2 /* nullable */);
+/* ---- belief overlaps ("Belief overlaps"; DEFINED by this library, unpinned: DESIGN.md 8) ---------------------------
+ * How much two resident beliefs overlap: a (n points, bandwidth h_a, manifold M_a, coordinate mask K_a) and b (m, h_b, M_b, K_b).
+ * A mask is a bit mask as in nbp_run_evaluate_marginal (bit d = coordinate d); its coordinates are taken in ascending order, and
+ * position k of a goes with position k of b.  A pair is ADMISSIBLE when the two lists have the same length D_K and, position by
+ * position, the same kind (Euclidean or circular): an SE(2) pose masked to x, y against a Euclid(2) landmark is.
+ *   s_k = h_a,k^2 + h_b,k^2,  e_ij = -1/2 sum_k delta_k(a_i, b_j)^2 / s_k  (delta wrapped to [-pi, pi) on circular positions; formed
+ *   as delta^2 times the rounded 1 / s_k, added in position order),  M = max_ij e_ij,
+ *   L_ab = ((M + log sum_i sum_j exp(e_ij - M)) - log(n m)) - sum_k 1/2 log(2 pi s_k), a term below exp(-700) dropped: the logarithm of
+ *   the integral of the product of the two marginal KDEs (exact on Euclidean coordinates; on circular ones the mass beyond +-pi is
+ *   not wrapped back), finite where every density underflows.
+ *   logc = L_ab - 1/2 (L_aa + L_bb),  c = exp(logc): 1 for equal beliefs, <= 1 on Euclidean coordinates (Cauchy-Schwarz; not
+ *   guaranteed on circular ones).  One function and one summation order behind the three L: a belief against a bit-identical copy
+ *   (or slots_a[i] == slots_b[i] with equal masks) gives logc == 0.0 exactly.  A bandwidth entry IN the mask of either belief that is
+ *   not positive and finite (or an s_k that is not): the record is NaN.  Entries outside the mask are not read.
+ * Refused before anything is launched, naming the pair -- NBP_ERR_RANGE: a slot out of range, an empty mask, a coordinate outside
+ * the manifold; NBP_ERR_ARG: an unknown manifold, an inadmissible pair.  Queued on the library stream; one copy back; synchronises. */
+typedef struct nbp_overlap_rec {
+  double logc, lab, laa, lbb;
+} nbp_overlap_rec;
+nbp_status nbp_run_overlap(nbp_ctx *ctx, const int32_t *slots_a, const int32_t *slots_b, const int32_t *manifolds_a,
+                           const int32_t *manifolds_b, const int32_t *masks_a, const int32_t *masks_b, int32_t n,
+                           nbp_overlap_rec *recs_out /* n */);
+/* host-buffer form: stages through slots 0 and 1 */
+nbp_status nbp_kde_overlap(nbp_ctx *ctx, int32_t manifold_a, const double *a_NxP, int32_t na, const double *bw_a_D, int32_t mask_a,
+                           int32_t manifold_b, const double *b_NxP, int32_t nb, const double *bw_b_D, int32_t mask_b,
+                           nbp_overlap_rec *rec_out);
+/* The search: for every row i of a list of n mutually admissible beliefs, the partners j != i ranked by logc.  Every belief has a
+ * box [lo_k, hi_k], the exact minimum and maximum of its points on each masked position.  Pair (i, j) is SKIPPED iff on some
+ * Euclidean position  gap = max(lo_i - hi_j, lo_j - hi_i) > 0  and  gap^2 > reach^2 (h_i^2 + h_j^2)  (as written, one rounding per
+ * operation); circular positions never prune.  A skipped pair has logc <= log(sqrt(n m)) - reach^2 / 2, so the options are refused
+ * (NBP_ERR_RANGE) unless  log(min_coeff) >= log(N) - reach^2 / 2 + 1, N the context's particle count: the result then equals brute
+ * force over all pairs.  Every other pair is evaluated with a = the belief of the LOWER list index: the value nbp_run_overlap gives
+ * for (a, b), bit for bit, and symmetric bit for bit.
+ * Per row: idx_out / logc_out hold the topk partners with logc >= log(min_coeff), descending, ties to the lower list index, unused
+ * entries -1 / -inf; found_out: ALL partners at or above the threshold; evaluated_out: the pairs not skipped.  A belief with an
+ * unusable bandwidth (see above) has found -1, evaluated 0, an empty row, and is nobody's partner (nor counted as evaluated).
+ * opts == NULL: the defaults below.  reach, min_coeff positive and finite, else NBP_ERR_ARG; topk outside 1 .. NBP_OVERLAP_MAXK and
+ * options that break the rule above: NBP_ERR_RANGE.  List errors as the pair form's, naming the belief; a belief that is not
+ * admissible against belief 0: NBP_ERR_ARG.  Two launches (per-belief preparation, then one workgroup per row); one copy back. */
+#define NBP_OVERLAP_MAXK 16
+#define NBP_OVERLAP_REACH 6.0
+#define NBP_OVERLAP_MIN_COEFF 1e-3
+#define NBP_OVERLAP_TOPK 8
+typedef struct nbp_overlap_opts {
+  double reach;
+  double min_coeff;
+  int32_t topk;
+  int32_t pad;
+} nbp_overlap_opts;
+nbp_status nbp_run_overlap_search(nbp_ctx *ctx, const int32_t *slots, const int32_t *manifolds, const int32_t *masks, int32_t n,
+                                  const nbp_overlap_opts *opts /* nullable */, int32_t *idx_out /* n x topk */,
+                                  double *logc_out /* n x topk */, int32_t *found_out /* n */, int32_t *evaluated_out /* n */);
 /* ---- modes of a belief ("Modes of a belief"; DEFINED by this library, unpinned: DESIGN.md 8) -----------------------
  * Mean-shift over the belief's own KDE at the bandwidth g = bw_scale * bw.  Every point x_i of the belief is a start y <- x_i;
  * one iteration is  w_j = exp(e(y, x_j)) (the exponent of nbp_run_evaluate with g in place of bw),  S = sum_j w_j,

@@ -453,6 +453,46 @@ class HipBackend:
                                          tm.ctypes.data_as(dp) if terms else None))
         return (out.value, tm) if terms else out.value
 
+    def run_overlap(self, slots_a, slots_b, manifolds_a, manifolds_b, masks_a, masks_b):
+        """the overlap of pairs of resident beliefs (nbp_run_overlap: one launch); masks = one coordinate bit mask per belief (bit d =
+        coordinate d), the pair admissible -> recs[n, 4]: logc, L_ab, L_aa, L_bb"""
+        cols = [_i32(v) for v in (slots_a, slots_b, manifolds_a, manifolds_b, masks_a, masks_b)]
+        n = cols[0][0].size
+        if any(a.size != n for a, _ in cols):
+            raise ValueError("run_overlap: six columns of one length")
+        out = np.zeros((n, 4))
+        self._check(self.lib.nbp_run_overlap(self._ctx, *(p for _, p in cols), n, out.ctypes.data_as(C.POINTER(abi.OverlapRec))))
+        return out
+
+    def kde_overlap(self, manifold_a, a, bw_a, mask_a, manifold_b, b, bw_b, mask_b):
+        """the overlap of two beliefs held on the host (nbp_kde_overlap; clobbers slots 0 and 1) -> rec[4]: logc, L_ab, L_aa, L_bb"""
+        dp = C.POINTER(C.c_double)
+        a = np.ascontiguousarray(a, dtype=np.float64).reshape(-1, abi.MANIFOLD_P[manifold_a])
+        b = np.ascontiguousarray(b, dtype=np.float64).reshape(-1, abi.MANIFOLD_P[manifold_b])
+        bw_a, bw_b = np.ascontiguousarray(bw_a, dtype=np.float64), np.ascontiguousarray(bw_b, dtype=np.float64)
+        out = np.zeros(4)
+        self._check(self.lib.nbp_kde_overlap(self._ctx, manifold_a, a.ctypes.data_as(dp), a.shape[0], bw_a.ctypes.data_as(dp), int(mask_a),
+                                             manifold_b, b.ctypes.data_as(dp), b.shape[0], bw_b.ctypes.data_as(dp), int(mask_b),
+                                             out.ctypes.data_as(C.POINTER(abi.OverlapRec))))
+        return out
+
+    def run_overlap_search(self, slots, manifolds, masks, topk=abi.OVERLAP_TOPK, min_coeff=abi.OVERLAP_MIN_COEFF, reach=abi.OVERLAP_REACH):
+        """the overlap search over a list of mutually admissible resident beliefs (nbp_run_overlap_search) ->
+        (idx[n, topk], logc[n, topk], n_found[n], n_evaluated[n]); unused entries -1 / -inf"""
+        (s, sp), (m, mp), (k, kp) = _i32(slots), _i32(manifolds), _i32(masks)
+        n = s.size
+        if m.size != n or k.size != n:
+            raise ValueError("run_overlap_search: three columns of one length")
+        topk = int(topk)
+        rows = max(topk, 0)
+        idx, logc = np.zeros((n, rows), dtype=np.int32), np.zeros((n, rows))
+        found, evaluated = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+        opts = abi.OverlapOpts(reach=float(reach), min_coeff=float(min_coeff), topk=topk, pad=0)
+        dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+        self._check(self.lib.nbp_run_overlap_search(self._ctx, sp, mp, kp, n, C.byref(opts), idx.ctypes.data_as(ip), logc.ctypes.data_as(dp),
+                                                    found.ctypes.data_as(ip), evaluated.ctypes.data_as(ip)))
+        return idx, logc, found, evaluated
+
     # ---- heatmap densities (nbp_heatmap_*; heatmap.py) -------------------------------------------------------------------------
     def heatmap_create(self, data, x, y, bw_factor=0.7):
         """nbp_heatmap_create: the field data[i, j] at (x[i], y[j]) -> a handle (heatmap_destroy it); the library checks the grid"""

@@ -16,7 +16,7 @@
 #include <rccl/rccl.h>  // types and prototypes only: the entry points are resolved with dlsym (see rccl_api)
 
 #ifndef NBP_TU
-#define NBP_TU 0  // host code: the kernels live in the nbp_k_*.hip files (-DNBP_TU=0x3FFFF: single-file build with every kernel)
+#define NBP_TU 0  // host code: the kernels live in the nbp_k_*.hip files (-DNBP_TU=0x7FFFF: single-file build with every kernel)
 #endif
 #include "nbp_kernels.h"
 #include "nbp_fused.h"
@@ -27,6 +27,7 @@
 #include "nbp_heatmap.h"
 #include "nbp_modes.h"
 #include "nbp_likelihood.h"
+#include "nbp_overlap.h"
 
 static thread_local std::string g_err;
 static nbp_status fail(nbp_status code, const std::string &msg) {
@@ -1899,6 +1900,120 @@ nbp_status nbp_kde_kld(nbp_ctx *c, int32_t manifold, const double *a, int32_t na
   NBPCHK(kde_stage(c, "kld", manifold, {{a, na, bw_a}, {b, nb, bw_b}}));
   const int32_t sa = 0, sb = 1;
   return nbp_run_kld(c, &sa, &sb, &manifold, 1, kld_out, terms_out);
+}
+
+// ---- belief overlaps (nbp_overlap.h) ---------------------------------------------------------------------------------------------
+// the kinds of a mask's coordinates in ascending order, one bit per position (1: circular), behind the length in bits 4 and up; -1:
+// an empty mask, -2: a coordinate outside the manifold
+static int overlap_kinds(int32_t manifold, int32_t mask) {
+  if (mask == 0) return -1;
+  const int D = manifold_dim_h(manifold);
+  if (mask < 0 || (mask >> D) != 0) return -2;
+  int kinds = 0, len = 0;
+  for (int d = 0; d < D; d++)
+    if (mask >> d & 1) {
+      if ((manifold == NBP_CIRCULAR && d == 0) || (manifold == NBP_SE2 && d == 2)) kinds |= 1 << len;
+      len++;
+    }
+  return kinds | len << 4;
+}
+static refusal overlap_mask_refusal(int kinds) {
+  if (kinds == -1) return refusal{NBP_ERR_RANGE, "empty mask"};
+  if (kinds == -2) return refusal{NBP_ERR_RANGE, "coordinate outside the manifold"};
+  return refusal{NBP_OK, nullptr};
+}
+
+// the overlap coefficient of pairs of beliefs resident in slots: one workgroup per pair (nbp_overlap.h), one copy back
+nbp_status nbp_run_overlap(nbp_ctx *c, const int32_t *slots_a, const int32_t *slots_b, const int32_t *manifolds_a, const int32_t *manifolds_b,
+                           const int32_t *masks_a, const int32_t *masks_b, int32_t n, nbp_overlap_rec *recs_out) {
+  if (!c || ((!slots_a || !slots_b || !manifolds_a || !manifolds_b || !masks_a || !masks_b || !recs_out) && n > 0))
+    return fail(NBP_ERR_ARG, "null argument");
+  if (n <= 0) return NBP_OK;
+  NBPCHK(batch_check(c, "overlap", {slots_a, slots_b}, manifolds_a, n, [&](int i) {
+    if (!manifold_ok(manifolds_b[i])) return refusal{NBP_ERR_ARG, "unknown manifold"};
+    const int ka = overlap_kinds(manifolds_a[i], masks_a[i]), kb = overlap_kinds(manifolds_b[i], masks_b[i]);
+    if (ka < 0) return overlap_mask_refusal(ka);
+    if (kb < 0) return overlap_mask_refusal(kb);
+    if (ka != kb) return refusal{NBP_ERR_ARG, "inadmissible pair: the masked coordinates differ in number or kind"};
+    return refusal{NBP_OK, nullptr};
+  }));
+  static_assert(sizeof(nbp_overlap_rec) == sizeof(double) * 4, "nbp_overlap_rec is packed doubles");
+  const int32_t *d[6];
+  const size_t col = 4 * (size_t)n;
+  NBPCHK(stage_columns(c, {{slots_a, col}, {slots_b, col}, {manifolds_a, col}, {manifolds_b, col}, {masks_a, col}, {masks_b, col}}, d,
+                       (size_t)n * 4));
+  NBPCHK(launch_checked(c, nbp_overlap_kernel, n, c->Npad, nbp_overlap_lds_bytes(c->N), d[0], d[1], d[2], d[3], d[4], d[5], c->arena, c->N,
+                        c->S, (nbp_overlap_rec *)c->query));
+  return query_fetch(c, recs_out, c->query, sizeof(nbp_overlap_rec) * (size_t)n);
+}
+
+// host-buffer form: stages through slots 0 and 1 (which it clobbers)
+nbp_status nbp_kde_overlap(nbp_ctx *c, int32_t manifold_a, const double *a, int32_t na, const double *bw_a, int32_t mask_a,
+                           int32_t manifold_b, const double *b, int32_t nb, const double *bw_b, int32_t mask_b, nbp_overlap_rec *rec_out) {
+  if (!c || !a || !bw_a || !b || !bw_b || !rec_out) return fail(NBP_ERR_ARG, "null argument");
+  NBPCHK(kde_check(c, "overlap", manifold_a, {{a, na, bw_a}, {b, nb, bw_b}}));
+  if (!manifold_ok(manifold_b)) return fail(NBP_ERR_ARG, "overlap: unknown manifold");
+  const int ka = overlap_kinds(manifold_a, mask_a), kb = overlap_kinds(manifold_b, mask_b);
+  for (int k : {ka, kb})
+    if (k < 0) return fail(NBP_ERR_RANGE, std::string("overlap: belief 0: ") + overlap_mask_refusal(k).what);
+  if (ka != kb) return fail(NBP_ERR_ARG, "overlap: belief 0: inadmissible pair: the masked coordinates differ in number or kind");
+  NBPCHK(nbp_belief_write(c, 0, manifold_a, a, na, bw_a, nullptr));
+  NBPCHK(nbp_belief_write(c, 1, manifold_b, b, nb, bw_b, nullptr));
+  const int32_t sa = 0, sb = 1;
+  return nbp_run_overlap(c, &sa, &sb, &manifold_a, &manifold_b, &mask_a, &mask_b, 1, rec_out);
+}
+
+// the options as given, or the defaults; refused before anything is launched
+static nbp_status overlap_opts_check(const nbp_ctx *c, const nbp_overlap_opts *opts, nbp_overlap_opts *o) {
+  *o = opts ? *opts : nbp_overlap_opts{NBP_OVERLAP_REACH, NBP_OVERLAP_MIN_COEFF, NBP_OVERLAP_TOPK, 0};
+  o->pad = 0;
+  if (!(o->reach > 0.0 && o->reach < INFINITY)) return fail(NBP_ERR_ARG, "overlap search: reach must be positive and finite");
+  if (!(o->min_coeff > 0.0 && o->min_coeff < INFINITY)) return fail(NBP_ERR_ARG, "overlap search: min_coeff must be positive and finite");
+  if (o->topk < 1 || o->topk > NBP_OVERLAP_MAXK) return fail(NBP_ERR_RANGE, "overlap search: topk outside 1 .. " + std::to_string(NBP_OVERLAP_MAXK));
+  // a skipped pair has logc <= log(N) - reach^2 / 2; one nat on top swallows every rounding
+  if (!(std::log(o->min_coeff) >= std::log((double)c->N) - 0.5 * (o->reach * o->reach) + 1.0))
+    return fail(NBP_ERR_RANGE, "overlap search: log(min_coeff) must be at least log(N) - reach^2 / 2 + 1 (a skipped pair could pass the threshold)");
+  return NBP_OK;
+}
+
+// the search over a list of beliefs resident in slots: the per-belief preparation, then one workgroup per row (nbp_overlap.h); one
+// copy back
+nbp_status nbp_run_overlap_search(nbp_ctx *c, const int32_t *slots, const int32_t *manifolds, const int32_t *masks, int32_t n,
+                                  const nbp_overlap_opts *opts, int32_t *idx_out, double *logc_out, int32_t *found_out,
+                                  int32_t *evaluated_out) {
+  if (!c || ((!slots || !manifolds || !masks || !idx_out || !logc_out || !found_out || !evaluated_out) && n > 0))
+    return fail(NBP_ERR_ARG, "null argument");
+  nbp_overlap_opts o;
+  NBPCHK(overlap_opts_check(c, opts, &o));
+  if (n <= 0) return NBP_OK;
+  int first = 0;
+  NBPCHK(batch_check(c, "overlap search", {slots}, manifolds, n, [&](int i) {
+    const int k = overlap_kinds(manifolds[i], masks[i]);
+    if (k < 0) return overlap_mask_refusal(k);
+    if (i == 0) first = k;
+    if (k != first) return refusal{NBP_ERR_ARG, "not admissible against belief 0: the masked coordinates differ in number or kind"};
+    return refusal{NBP_OK, nullptr};
+  }));
+  // the query scratch: prep[n] | logc[n topk] | idx[n topk] found[n] evaluated[n] (the last three int32: one copy back from logc on)
+  static_assert(sizeof(nbp_overlap_prep) % sizeof(double) == 0, "nbp_overlap_prep fills whole doubles of the query scratch");
+  const size_t V = (size_t)n, K = (size_t)o.topk, prep_d = V * (sizeof(nbp_overlap_prep) / sizeof(double));
+  const size_t ints = V * K + 2 * V, out_d = V * K + (ints + 1) / 2;
+  const int32_t *d[3];
+  NBPCHK(stage_columns(c, {{slots, 4 * V}, {manifolds, 4 * V}, {masks, 4 * V}}, d, prep_d + out_d));
+  nbp_overlap_prep *prep = (nbp_overlap_prep *)c->query;
+  double *dlogc = c->query + prep_d;
+  int32_t *didx = (int32_t *)(dlogc + V * K), *dfound = didx + V * K, *deval = dfound + V;
+  NBPCHK(launch_checked(c, nbp_overlap_prep_kernel, V, c->Npad, nbp_overlap_prep_lds_bytes(c->N), d[0], d[1], d[2], c->arena, c->N, c->S, prep));
+  NBPCHK(launch_checked(c, nbp_overlap_search_kernel, V, c->Npad, nbp_overlap_search_lds_bytes(c->N), d[0], d[1], d[2], n, c->arena, c->N,
+                        c->S, (const nbp_overlap_prep *)prep, o.reach * o.reach, std::log(o.min_coeff), o.topk, didx, dlogc, dfound, deval));
+  std::vector<double> back(out_d);
+  NBPCHK(query_fetch(c, back.data(), dlogc, sizeof(double) * out_d));
+  memcpy(logc_out, back.data(), sizeof(double) * V * K);
+  const int32_t *bi = (const int32_t *)(back.data() + V * K);
+  memcpy(idx_out, bi, 4 * V * K);
+  memcpy(found_out, bi + V * K, 4 * V);
+  memcpy(evaluated_out, bi + V * K + V, 4 * V);
+  return NBP_OK;
 }
 
 // ---- modes of beliefs (nbp_modes.h) ----------------------------------------------------------------------------------------------

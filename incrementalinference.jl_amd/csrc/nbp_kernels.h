@@ -22,7 +22,7 @@
 #define NBP_TU_PROPWAVE 512 // proposal kernels, one wave per proposal (chip-filling launches of simple Euclidean batches)
 #define NBP_TU_PRODLATUNI 1024 // product kernels, latency geometries (y32, l8), one manifold per instance
 #ifndef NBP_TU
-#define NBP_TU 0x3FFFF
+#define NBP_TU 0x7FFFF
 #endif
 
 // ================================================================================================

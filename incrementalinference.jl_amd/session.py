@@ -302,6 +302,48 @@ class SolveSession:
                                            lambda p, **kw: jointmodes.factorModeLikelihood(self.fg, p.label, modes, maxModes, **kw))
         return jointmodes.joint_from_tables(modes, res, skipped, maxModes)
 
+    def _overlap_labels(self, labels, what):
+        """the labels of an overlap query, all of which must have a slot in the session's context: an overlap is computed where
+        the beliefs lie, and there is no host route"""
+        if self._closed:
+            raise RuntimeError("this SolveSession is closed")
+        labels = list(self._labels if labels is None else labels)
+        if self._be is None or getattr(self._be, "run_overlap_search", None) is None:
+            raise ValueError(f"{what}: belief overlaps are computed by libnbp, and this session's backend has no such entry point")
+        missing = [v for v in labels if v not in self._labels]
+        if missing:
+            raise ValueError(f"{what}: {missing} were never part of a solve of this session")
+        return labels
+
+    def findOverlaps(self, labels=None, dims=None, number=abi.OVERLAP_TOPK, minCoeff=abi.OVERLAP_MIN_COEFF, reach=abi.OVERLAP_REACH):
+        """Which of the variables' current beliefs overlap (overlap.py) -> Overlaps, the loop-closure candidates in `.pairs()`.
+        labels: default every variable the last solve worked on; dims, number, minCoeff, reach as in `overlap.findOverlaps`.
+        Served by ONE `run_overlap_search` where the beliefs lie (`_query_resident`): no belief travels and `stats` does not move."""
+        from . import overlap
+        labels = self._overlap_labels(labels, "findOverlaps")
+        overlap.check_search_options(number, minCoeff, reach, self._be.N)
+        if not labels:
+            return overlap.findOverlaps(self.fg, [], dims, number, minCoeff, reach)
+        res = self._query_resident(labels, "run_overlap_search",
+                                   lambda here, place: (*overlap.search_columns(self.fg, here, dims, place), number, minCoeff, reach),
+                                   lambda res, i, v: res, None)
+        return overlap.Overlaps(labels, *res[labels[0]])
+
+    def overlapVariables(self, pairs, dims=None):
+        """The overlaps of pairs of variables' current beliefs (overlap.py) -> {(label_a, label_b): Overlap}, served by ONE
+        `run_overlap` where the beliefs lie (`_query_resident`)."""
+        from . import overlap
+        pairs = [tuple(p) for p in pairs]
+        labels = []
+        for p in pairs:
+            labels += [v for v in p if v not in labels]
+        labels = self._overlap_labels(labels, "overlapVariables")
+        if not pairs:
+            return {}
+        res = self._query_resident(labels, "run_overlap", lambda here, place: overlap.pair_columns(self.fg, pairs, dims, place),
+                                   lambda res, i, v: res, None)
+        return {p: overlap.overlap_from_rec(r) for p, r in zip(pairs, res[labels[0]])}
+
     # ---- one solve ---------------------------------------------------------------------------------------------------------
     def solve(self, seed=0, eliminationOrder=None, ordering="qr", return_timing=False):
         """solveTree(fg, oldtree=ses.tree, ...) in the session's context -> tree (or (tree, timing) with return_timing: the
