@@ -102,6 +102,9 @@ struct NbpDiag
   residual_evals::Int64
   lcv_evals::Int64
   lcv_evals_f32::Int64
+  proposal_launches_workgroup::Int64
+  proposal_launches_wave::Int64
+  proposal_launches_split::Int64
 end
 
 # nbp_solver_params (include/nbp_host.h): the SolverParams fields the path reads (entities/SolverParams.jl:12-75)

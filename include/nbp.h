@@ -189,6 +189,11 @@ typedef struct nbp_diag {
                             pairs): they decide comparisons whose two sides are further apart than their error bounds;
                             the bandwidth selected is that of the all-double search, bit for bit (NBP_FIT_F64=1 in the
                             environment of nbp_ctx_create: every evaluation in double precision)                        */
+  /* proposal launches by geometry, counted on the host where the launch is issued (a captured program counts at capture,
+     not at replay): the workgroup kernels, one wave per proposal, two waves per proposal */
+  int64_t proposal_launches_workgroup;
+  int64_t proposal_launches_wave;
+  int64_t proposal_launches_split;
 } nbp_diag;
 
 typedef struct nbp_ctx nbp_ctx;

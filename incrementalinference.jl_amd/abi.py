@@ -138,6 +138,9 @@ class Diag(C.Structure):
         ("residual_evals", C.c_int64),
         ("lcv_evals", C.c_int64),
         ("lcv_evals_f32", C.c_int64),
+        ("proposal_launches_workgroup", C.c_int64),
+        ("proposal_launches_wave", C.c_int64),
+        ("proposal_launches_split", C.c_int64),
     ]
 
 

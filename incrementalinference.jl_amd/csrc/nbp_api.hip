@@ -16,7 +16,7 @@
 #include <rccl/rccl.h>  // types and prototypes only: the entry points are resolved with dlsym (see rccl_api)
 
 #ifndef NBP_TU
-#define NBP_TU 0  // host code: the kernels live in the nbp_k_*.hip files (-DNBP_TU=0x7FFFF: single-file build with every kernel)
+#define NBP_TU 0  // host code: the kernels live in the nbp_k_*.hip files (-DNBP_TU=0xFFFFF: single-file build with every kernel)
 #endif
 #include "nbp_kernels.h"
 #include "nbp_fused.h"
@@ -133,6 +133,11 @@ struct nbp_ctx {
   // smallest launch of simple Euclidean proposals that runs one WAVE per proposal (launch_proposals); -1: the default of the
   // class (NBP_PROPOSAL_WAVE_MIN overrides it for every class)
   int prop_wave_min = -1;
+  // smallest launch of simple Euclid(2) proposals that runs TWO waves per proposal (below it: the workgroup kernel; from
+  // prop_wave_min on: the one-wave kernel); -1: the default (NBP_PROPOSAL_SPLIT_MIN overrides it)
+  int prop_split_min = -1;
+  // launches of launch_proposals by geometry since the last reset of nbp_diag_read: workgroup, one wave, split
+  int64_t prop_launches[3] = {0, 0, 0};
   int fused_p1_min = 2048;  // rounds with at least this many updates run one lane per particle (NBP_FUSED_P1_MIN); smaller
                             // ones two helper rows per update, so that they fill the chip with twice the lanes each
   // two-stream rounds (NBP_PIPELINE_MIN = smallest product batch; see plan_pipeline): the second stream and the fork / join
@@ -344,6 +349,7 @@ nbp_status nbp_ctx_create(int32_t device, int32_t N, int32_t n_slots, void *aren
   c->fused_on = getenv("NBP_NO_FUSED_UPDATE") == nullptr;
   if (getenv("NBP_FUSED_MIN")) c->fused_min = atoi(getenv("NBP_FUSED_MIN"));
   if (getenv("NBP_PROPOSAL_WAVE_MIN")) c->prop_wave_min = atoi(getenv("NBP_PROPOSAL_WAVE_MIN"));
+  if (getenv("NBP_PROPOSAL_SPLIT_MIN")) c->prop_split_min = atoi(getenv("NBP_PROPOSAL_SPLIT_MIN"));
   if (getenv("NBP_PIPELINE_MIN")) c->pipe_min = atoi(getenv("NBP_PIPELINE_MIN"));
   HIPCHK(hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking));
   for (int i = 0; i < 2; i++) HIPCHK(hipEventCreateWithFlags(&c->pipe_ev[i], hipEventDisableTiming));
@@ -926,6 +932,10 @@ static int proposals_uniform_class(const nbp_proposal_desc *d, int n) {
   // (a batch of priors / message priors alone runs its manifold's instance as well)
   return cls | (simple ? NBP_CLS_SIMPLE : 0);
 }
+// simple Euclid(2) batches at N = 200, us per launch (profiles/r13_proposal_split_geometry.txt): 488 proposals 162 workgroup /
+// 171 split, 550: 172 / 176, 700: 200 / 188; 3200: 528 split / 604 one wave, 4000: 656 / 630 -- the crossovers, rounded
+#define NBP_SPLIT_MIN_DEFAULT 600
+#define NBP_WAVE_MIN_LIN2_DEFAULT 3500
 static nbp_status launch_proposals(nbp_ctx *c, const nbp_launch_env &env, const nbp_proposal_desc *dev, int n, int cls = 0) {
   if (n <= 0) return NBP_OK;
   nbp_status rc = tic(c, c->ev[0]);
@@ -935,12 +945,22 @@ static nbp_status launch_proposals(nbp_ctx *c, const nbp_launch_env &env, const 
   cls &= NBP_CLS_SIMPLE - 1;
   // chip-filling launches of simple Euclidean batches: one wave per proposal, no workgroup barrier (nbp_kernels.h,
   // proposal_wave_body); rows of up to five waves (N <= 320)
-  const int wave_min = c->prop_wave_min >= 0 ? c->prop_wave_min : (cls == NBP_CLS_LIN2 ? 900 : (c->N > 256 ? 1500 : (1 << 30)));
+  const int wave_min = c->prop_wave_min >= 0 ? c->prop_wave_min : (cls == NBP_CLS_LIN2 ? NBP_WAVE_MIN_LIN2_DEFAULT : (c->N > 256 ? 1500 : (1 << 30)));
   if (simple && n >= wave_min && (cls == NBP_CLS_LIN2 || cls == NBP_CLS_LIN3) && c->N <= (cls == NBP_CLS_LIN2 ? 256 : 320)) {
     auto *wk = cls == NBP_CLS_LIN2 ? nbp_proposal_wave_kernel_lin2 : (c->N <= 256 ? nbp_proposal_wave_kernel_lin3 : nbp_proposal_wave_kernel_lin3n5);
     hipLaunchKernelGGL(wk, dim3((n + NBP_PW_WAVES - 1) / NBP_PW_WAVES), dim3(64 * NBP_PW_WAVES), nbp_proposal_wave_lds_bytes(c->N, cls == NBP_CLS_LIN2 ? 2 : 3),
                        env.stream, dev, n, c->arena, c->N, c->S, c->side, c->counters);
     HIPCHK(hipGetLastError());
+    c->prop_launches[1]++;
+    return toc(c, c->ev[0]);
+  }
+  // between the two: two waves per proposal, each owning every second chunk of 64 particles (proposal_split_body)
+  const int split_min = c->prop_split_min >= 0 ? c->prop_split_min : NBP_SPLIT_MIN_DEFAULT;
+  if (simple && cls == NBP_CLS_LIN2 && c->N <= 256 && n >= split_min) {
+    hipLaunchKernelGGL(nbp_proposal_split_kernel_lin2, dim3(n), dim3(64 * NBP_PS_W), nbp_proposal_split_lds_bytes(c->N, 2), env.stream, dev, c->arena,
+                       c->N, c->S, c->side, c->counters);
+    HIPCHK(hipGetLastError());
+    c->prop_launches[2]++;
     return toc(c, c->ev[0]);
   }
   auto *kern = cls == NBP_CLS_LIN2 ? nbp_proposal_kernel_lin2 : (cls == NBP_CLS_LIN3 ? nbp_proposal_kernel_lin3 : (cls == NBP_CLS_CIRC ? nbp_proposal_kernel_circ :
@@ -948,6 +968,7 @@ static nbp_status launch_proposals(nbp_ctx *c, const nbp_launch_env &env, const 
   hipLaunchKernelGGL(kern, dim3(n), dim3(c->Npad), nbp_proposal_lds_bytes(c->N), env.stream, dev, c->arena, c->N, c->Npad, c->S, c->side,
                      c->counters);
   HIPCHK(hipGetLastError());
+  c->prop_launches[0]++;
   return toc(c, c->ev[0]);
 }
 // room for the KD builds of nprod products in the environment's workspace; outside a round the context's workspace grows
@@ -3635,6 +3656,10 @@ nbp_status nbp_diag_read(nbp_ctx *c, nbp_diag *out, int32_t reset) {
   out->residual_evals = (int64_t)h.residual_evals;
   out->lcv_evals = (int64_t)h.lcv_evals;
   out->lcv_evals_f32 = (int64_t)h.lcv_evals_f32;
+  out->proposal_launches_workgroup = c->prop_launches[0];
+  out->proposal_launches_wave = c->prop_launches[1];
+  out->proposal_launches_split = c->prop_launches[2];
+  if (reset) c->prop_launches[0] = c->prop_launches[1] = c->prop_launches[2] = 0;
   if (reset) HIPCHK(hipMemset(c->counters, 0, offsetof(nbp_counters, flags)));  // (the flags are the context's, not counters)
   return NBP_OK;
 }

@@ -21,8 +21,9 @@
 #define NBP_TU_PREPW5 256   // bandwidth fits + KD builds at five waves per SIMD (rows of 4k + 1 waves: N = 257 .. 320)
 #define NBP_TU_PROPWAVE 512 // proposal kernels, one wave per proposal (chip-filling launches of simple Euclidean batches)
 #define NBP_TU_PRODLATUNI 1024 // product kernels, latency geometries (y32, l8), one manifold per instance
+#define NBP_TU_PROPSPLIT 524288 // proposal kernels, two waves per proposal (launches between the workgroup and the one-wave geometry)
 #ifndef NBP_TU
-#define NBP_TU 0x7FFFF
+#define NBP_TU 0xFFFFF
 #endif
 
 // ================================================================================================
@@ -655,6 +656,242 @@ NBP_PROPOSAL_WAVE(nbp_proposal_wave_kernel_lin2, NBP_EUCLID2, 4, NBP_WW_LIN2)
 NBP_PROPOSAL_WAVE(nbp_proposal_wave_kernel_lin3, NBP_EUCLID3, 4, NBP_WW_LIN3)
 NBP_PROPOSAL_WAVE(nbp_proposal_wave_kernel_lin3n5, NBP_EUCLID3, 5, NBP_WW_LIN3)
 static inline size_t nbp_proposal_wave_lds_bytes(int N, int D) { return (size_t)NBP_PW_WAVES * D * N * 8; }
+
+// ================================================================================================
+// W WAVES per proposal: the geometry between the two above, for launches of a few hundred to about two thousand simple
+// Euclidean proposals.  One wave per proposal leaves such a launch with one or two waves per SIMD, each running the NC chunk
+// searches of every inflation cycle one after the other; a workgroup of NC waves waits half its time at barriers.  Here one
+// workgroup of W waves is one proposal (grid = n): wave w owns the chunks w, w + W, w + 2W, ... (chunk c = the particles
+// 64c .. 64c + 63, particle n at lane n % 64, as in proposal_wave_body) and runs their searches one after the other, so the
+// serial length of a cycle is ceil(NC / W) searches and the waves meet only in the spread statistics.
+// Sums, bit for bit: every wave writes wave_sum() of each chunk it owns to an LDS table indexed by the CHUNK, and after a
+// barrier every lane adds the table's NC entries in chunk order -- the additions of wave_chunks_sum() and of block_sum().
+// Barriers: two __syncthreads() per inflation cycle, one behind the partial sums of the D means (table part_mu), one behind
+// those of the variance (table part_var).  The two tables are used in turn, so that between the last read of a table and its
+// next write lies the barrier of the other table, which every wave reaches only after that read: a fast wave cannot
+// overwrite a partial a slow wave has not read, and no third barrier is needed.  Every barrier is inside code whose control
+// flow depends on the descriptor alone (factor_kind, inflate_cycles), which is one per workgroup: a wave that owns no chunk
+// (N = 64 at W = 2) walks the same cycles with no live lane and reaches every barrier; the pass-through and prior branches
+// hold no barrier and the whole workgroup returns from them.
+// LDS: X[D][N] for the workgroup (a lane touches its own particles' entries only: no barrier of its own) and the two tables.
+// The measurements rotate through the wave's own NCW = ceil(NC / W) chunks.  Particle for particle the operations of
+// proposal_wave_body<FIXM, NC>.
+// ================================================================================================
+template <int FIXM, int NC, int W>
+__device__ __forceinline__ void proposal_split_body(const nbp_proposal_desc *d, double *out, double *arena, int N, int64_t S, int32_t *side,
+                                                    nbp_counters *ctr, double *X) {
+  constexpr int M = FIXM, D = FIXM, NCW = (NC + W - 1) / W;  // Euclid(D)
+  __shared__ double part_mu[D][NC], part_var[NC];
+  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), kind = d->factor_kind;
+  const int n0 = lane + 64 * w;  // the wave's first particle; its q-th is n0 + 64 W q (n < N implies a chunk below NC)
+  unsigned int n_solves = 0, n_nonconv = 0, n_nan = 0, n_evals = 0;
+  {
+    const double *src = arena + S * d->var_slot[(kind == NBP_F_PRIOR || kind == NBP_F_MSGPRIOR || kind == NBP_F_PASSTHROUGH) ? 0 : d->sfidx];
+    const int ct = slot_count(src, N);
+#pragma unroll
+    for (int q = 0; q < NCW; q++) {
+      const int n = n0 + 64 * W * q;
+      if (n < N)
+        for (int k = 0; k < D; k++) X[k * N + n] = (n < ct) ? src[k * N + n] : 0.0;
+    }
+  }
+  if (d->mhidx_out >= 0) {
+#pragma unroll
+    for (int q = 0; q < NCW; q++)
+      if (n0 + 64 * W * q < N) side[d->mhidx_out + n0 + 64 * W * q] = 1;  // every particle on the factor's one hypothesis
+  }
+  if (kind == NBP_F_PASSTHROUGH) {  // (proposal_wave_body, same branch; no barrier: the workgroup returns as a whole)
+    const double *den = arena + S * d->var_slot[1];
+    const int cd = slot_count(den, N), pm = d->partial_mask ? d->partial_mask : 7;
+#pragma unroll 1
+    for (int q = 0; q < NCW; q++) {
+      const int n = n0 + 64 * W * q;
+      if (n >= N) continue;
+      int idx = n;
+      if (!d->keep_count && cd < N) {
+        double ua, ub;
+        uniform_pair(d->seed, n, PURP_KDESEL, 0, ua, ub);
+        idx = (int)(ua * cd);
+        if (idx >= cd) idx = cd - 1;
+      }
+      double nz0 = 0, nz1 = 0, nz2 = 0, nz3 = 0;
+      if (d->keep_count == 2 && cd < N && n >= cd) {
+        double ua, ub;
+        uniform_pair(d->seed, n, PURP_OLDSEL, 0, ua, ub);
+        idx = (int)(ua * cd);
+        if (idx >= cd) idx = cd - 1;
+        normal_pair(d->seed, n, PURP_OLDNOISE, 0, nz0, nz1);
+        if (D > 2) normal_pair(d->seed, n, PURP_OLDNOISE, 1, nz2, nz3);
+      }
+      if (idx < cd)
+        for (int k = 0; k < D; k++)
+          if ((pm >> k) & 1) {
+            const double nzk = k == 0 ? nz0 : (k == 1 ? nz1 : nz2);
+            X[k * N + n] = den[k * N + idx] + den[3 * N + k] * nzk;
+          }
+      for (int k = 0; k < 3; k++) out[k * N + n] = (k < D) ? X[k * N + n] : 0.0;
+    }
+    if (w == 0 && lane < 3) {
+      const bool in = lane < D && ((pm >> lane) & 1);
+      out[3 * N + lane] = in ? den[3 * N + lane] : 0.0;
+      out[3 * N + 3 + lane] = in ? 1.0 : 0.0;
+    }
+    if (w == 0 && lane == 0) out[3 * N + 6] = (d->keep_count == 1 && cd < N) ? (double)cd : 0.0;
+    return;
+  }
+  if (kind == NBP_F_PRIOR || kind == NBP_F_MSGPRIOR) {
+    // evalPotentialSpecific(prior) with every particle on the hypothesis (no spread: no barrier in this branch)
+#pragma unroll 1
+    for (int q = 0; q < NCW; q++) {
+      const int n = n0 + 64 * W * q;
+      if (n >= N) continue;
+      double x[3] = {0, 0, 0};
+      if (kind == NBP_F_PRIOR) {
+        sample_measurement(d, n, D, x, arena, S, N);
+      } else {
+        const double *msg = arena + S * d->var_slot[1];
+        const int cm = slot_count(msg, N);
+        const uint64_t mseed = d->meas_seed ? d->meas_seed : d->seed;
+        double ua, ub, n0_, n1, n2 = 0, n3 = 0;
+        uniform_pair(mseed, n, PURP_KDESEL, 0, ua, ub);
+        int i = (int)(ua * cm);
+        if (i >= cm) i = cm - 1;
+        normal_pair(mseed, n, PURP_KDENOISE, 0, n0_, n1);
+        if (D > 2) normal_pair(mseed, n, PURP_KDENOISE, 1, n2, n3);
+        x[0] = msg[i] + msg[3 * N] * n0_;
+        if (D > 1) x[1] = msg[N + i] + msg[3 * N + 1] * n1;
+        if (D > 2) x[2] = msg[2 * N + i] + msg[3 * N + 2] * n2;
+      }
+      for (int k = 0; k < D; k++) X[k * N + n] = x[k];
+    }
+  } else {
+    // evalPotentialSpecific(relative): LinearRelative between two variables, one hypothesis group holding every particle
+    const int sf1 = d->sfidx + 1, solve_b = (sf1 == 2), vother = solve_b ? 1 : 2;
+    const double *O = arena + S * d->var_slot[vother - 1];
+    const int co = slot_count(O, N);
+    double z[NCW][D];
+#pragma unroll
+    for (int q = 0; q < NCW; q++) {
+      double zz[3] = {0, 0, 0};
+      if (n0 + 64 * W * q < N) sample_measurement(d, n0 + 64 * W * q, D, zz, arena, S, N);  // sampleFactor!, once per approxConv
+#pragma unroll
+      for (int k = 0; k < D; k++) z[q][k] = zz[k];
+    }
+    const double rN = (double)N;
+    // (inflate_cycles is the descriptor's: the same trip count, and so the same barriers, in every wave of the workgroup)
+    for (int c = 0; c < d->inflate_cycles; c++) {
+      // calcStdBasicSpread of the scratch copy: chunk partials through LDS, added in chunk order
+      double v[D][NCW], acc[NCW];
+#pragma unroll
+      for (int k = 0; k < D; k++)
+#pragma unroll
+        for (int q = 0; q < NCW; q++) {
+          const int n = n0 + 64 * W * q;
+          v[k][q] = (n < N) ? X[k * N + n] : 0.0;
+          const double s = wave_sum(v[k][q]);
+          if (lane == 0 && w + W * q < NC) part_mu[k][w + W * q] = s;
+        }
+      __syncthreads();  // the D means' partials: one barrier
+#pragma unroll
+      for (int q = 0; q < NCW; q++) acc[q] = 0.0;
+#pragma unroll
+      for (int k = 0; k < D; k++) {
+        double t = part_mu[k][0];
+#pragma unroll
+        for (int p = 1; p < NC; p++) t += part_mu[k][p];
+        const double mu = t / rN;
+#pragma unroll
+        for (int q = 0; q < NCW; q++)
+          if (n0 + 64 * W * q < N) {
+            const double dl = v[k][q] - mu;
+            acc[q] += dl * dl;
+          }
+      }
+#pragma unroll
+      for (int q = 0; q < NCW; q++) {
+        const double s = wave_sum(acc[q]);
+        if (lane == 0 && w + W * q < NC) part_var[w + W * q] = s;
+      }
+      __syncthreads();  // the variance's partials
+      double tv = part_var[0];
+#pragma unroll
+      for (int p = 1; p < NC; p++) tv += part_var[p];
+      const double sg = sqrt(tv / (double)(N - 1));
+      const double spread = d->inflation * ((1e-10 < sg) ? sg : 1.0);
+#pragma unroll 1
+      for (int q = 0; q < NCW; q++) {
+        const int n = n0 + 64 * W * q;
+        if (n < N) {
+          const int io = anyn_index(n, co, d->seed, vother);  // _getindex_anyn
+          double oth[3] = {O[io], 0, 0};
+          if (D > 1) oth[1] = O[N + io];
+          if (D > 2) oth[2] = O[2 * N + io];
+          double x[3] = {X[n], 0, 0};
+          if (D > 1) x[1] = X[N + n];
+          if (D > 2) x[2] = X[2 * N + n];
+          double zz[3] = {z[0][0], 0, 0};
+          if (D > 1) zz[1] = z[0][1];
+          if (D > 2) zz[2] = z[0][D - 1];
+          add_entropy(M, D, x, n, spread, d->seed, (1 * 8 + c) * 2, 0);
+          solve_particle_t<NBP_F_LINREL, D>(M, zz, oth, solve_b, x, n_solves, n_nonconv, n_nan, n_evals);
+          X[n] = x[0];
+          if (D > 1) X[N + n] = x[1];
+          if (D > 2) X[2 * N + n] = x[2];
+        }
+        // the wave's next chunk's measurement moves to the front (NCW rotations bring every one back to its place)
+        double z0[D];
+#pragma unroll
+        for (int k = 0; k < D; k++) z0[k] = z[0][k];
+#pragma unroll
+        for (int r = 0; r + 1 < NCW; r++)
+#pragma unroll
+          for (int k = 0; k < D; k++) z[r][k] = z[r + 1][k];
+#pragma unroll
+        for (int k = 0; k < D; k++) z[NCW - 1][k] = z0[k];
+      }
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < NCW; q++) {
+    const int n = n0 + 64 * W * q;
+    if (n < N)
+      for (int k = 0; k < D; k++) out[k * N + n] = X[k * N + n];
+  }
+  if (w == 0 && lane < 3) out[3 * N + 3 + lane] = (lane < D) ? 1.0 : 0.0;  // infoPerCoord (no partial factors in this class)
+  if (w == 0 && lane == 0) out[3 * N + 6] = 0.0;
+  {  // diagnostics: one atomic per wave
+    unsigned int cv[4] = {n_solves, n_nonconv, n_nan, n_evals};
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+      unsigned int t = cv[q];
+      for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o, 64);
+      cv[q] = t;
+    }
+    if (lane == 0 && (cv[0] | cv[3])) {
+      atomicAdd(&ctr->solves, (unsigned long long)cv[0]);
+      atomicAdd(&ctr->nonconverged, (unsigned long long)cv[1]);
+      atomicAdd(&ctr->nan_results, (unsigned long long)cv[2]);
+      atomicAdd(&ctr->residual_evals, (unsigned long long)cv[3]);
+    }
+  }
+}
+
+#define NBP_PROPOSAL_SPLIT_ARGS const nbp_proposal_desc *descs, double *arena, int N, int64_t S, int32_t *side, nbp_counters *ctr
+#if NBP_TU & NBP_TU_PROPSPLIT
+// one workgroup of W_ waves = the proposal blockIdx.x (no workgroup holds two, none is partial)
+#define NBP_PROPOSAL_SPLIT(NAME, M_, NC_, W_, WAVES)                                                                        \
+  __global__ void __launch_bounds__(64 * W_) __attribute__((amdgpu_waves_per_eu(WAVES)))                                    \
+  NAME(NBP_PROPOSAL_SPLIT_ARGS) {                                                                                           \
+    extern __shared__ double smem[];                                                                                        \
+    proposal_split_body<M_, NC_, W_>(descs + blockIdx.x, arena + S * descs[blockIdx.x].out_slot, arena, N, S, side, ctr, smem); \
+  }
+#else
+#define NBP_PROPOSAL_SPLIT(NAME, M_, NC_, W_, WAVES) __global__ void NAME(NBP_PROPOSAL_SPLIT_ARGS);
+#endif
+#define NBP_PS_W 2     // (three waves per proposal measured as well: slower from 700 proposals on, profiles/r13_proposal_split_geometry.txt)
+#define NBP_WS_LIN2 5  // 96 VGPRs, no scratch
+NBP_PROPOSAL_SPLIT(nbp_proposal_split_kernel_lin2, NBP_EUCLID2, 4, NBP_PS_W, NBP_WS_LIN2)
+static inline size_t nbp_proposal_split_lds_bytes(int N, int D) { return (size_t)D * N * 8; }
 
 // ================================================================================================
 // Deconvolution kernel: one workgroup = one approxDeconv(dfg, fct) (DeconvUtils.jl:32-160), one lane

@@ -60,7 +60,7 @@ def main():
     args, extra = ap.parse_known_args()
     t0 = time.time()
     if args.single:
-        cmd = [HIPCC] + FLAGS + ["-shared", "-DNBP_TU=0x7FFFF"] + extra + [os.path.join(CSRC, "nbp_api.hip"), os.path.join(CSRC, "nbp_host.cpp"), "-o", args.out]
+        cmd = [HIPCC] + FLAGS + ["-shared", "-DNBP_TU=0xFFFFF"] + extra + [os.path.join(CSRC, "nbp_api.hip"), os.path.join(CSRC, "nbp_host.cpp"), "-o", args.out]
         subprocess.check_call(cmd)
         print(f"built {args.out} (single translation unit) in {time.time() - t0:.0f} s")
         return
