@@ -758,6 +758,70 @@ nbp_status nbp_timing_read(nbp_ctx *ctx, double *ms, int64_t *launches);
 nbp_status nbp_timing_read_n(nbp_ctx *ctx, double *ms, int64_t *launches, int32_t n);
 nbp_status nbp_diag_read(nbp_ctx *ctx, nbp_diag *out, int32_t reset);
 
+/* ---- launch plans ------------------------------------------------------------------------
+ * What a product, fit or proposal launch would run, as the library's own planners decide it: the queries need
+ * no context and no GPU; they read the same environment switches (NBP_PRODUCT_*, NBP_LCV_*, NBP_NO_*, NBP_PROPOSAL_*, ...)
+ * in the same way as context creation does, at the time of the call.  Arrays of requests, one record each. */
+typedef struct nbp_product_plan_req {
+  int32_t N;       /* particles of the context, 8 .. NBP_MAXN                                                   */
+  int32_t n;       /* products in the launch                                                                     */
+  int32_t F, D;    /* largest density count and largest manifold dimension of the launch                        */
+  int32_t mani;    /* the manifold of a single-manifold launch, 0: mixed, -1: the widest workgroup any kernel takes */
+  int32_t geom_n;  /* 0, or the whole batch of the two-stream round this launch is a half of                     */
+} nbp_product_plan_req;
+/* refusals of a product launch (status NBP_ERR_RANGE) */
+#define NBP_PLAN_REFUSED_BIG_IN_ROUND 1 /* node statistics beyond the LDS inside a two-stream round */
+#define NBP_PLAN_REFUSED_LDS 2          /* too many densities for the LDS label table               */
+#define NBP_PLAN_REFUSED_NO_KERNEL 3    /* the kernel table has no row for the geometry             */
+typedef struct nbp_product_plan_rec {
+  int32_t status, refusal;       /* what the launch returns: NBP_OK / 0, or NBP_ERR_RANGE and which refusal; a query whose
+                                    arguments no launch can have (D of a single manifold not its dimension): NBP_ERR_ARG */
+  int32_t HL, wpb, G;            /* helper lanes per sample, waves per workgroup, workgroups per product                */
+  int32_t big, xs, circ, nch, all_levels, w1;
+  int32_t row;                   /* the row of the kernel table (-1: none) and what that row is:                        */
+  int32_t row_HL, row_mani, row_xs, row_w1;
+  int32_t launch_bound;          /* lanes the kernel of that row is compiled for                                        */
+  int32_t N, n, F, D, mani, geom_n; /* the request (nbp_last_plans: what the launch was issued with; n = 0: none yet)   */
+  int32_t pad;
+  int64_t lds, gstats;           /* dynamic LDS bytes per workgroup; doubles of the global statistics area (big)        */
+  char kernel[40];
+} nbp_product_plan_rec;
+typedef struct nbp_fit_plan_req {
+  int32_t N;
+  int32_t fits, coords;   /* bandwidth fits of the launch and their fitted coordinates (sum of the manifold dimensions)  */
+  int32_t products, kdF;  /* > 0: a prep launch beside the KD builds of that many products of up to kdF densities         */
+  int32_t geom_blocks;    /* 0, or the workgroups of the whole two-stream round this launch is a half of                  */
+} nbp_fit_plan_req;
+typedef struct nbp_fit_plan_rec {
+  int32_t status;
+  int32_t P, depth, KS, w5, threads;
+  int32_t prep;           /* 1: a prep launch, 0: a plain bandwidth launch                                               */
+  int32_t kd_nostats;     /* nbp_last_plans, prep launches: the KD builds left the node sums to an _xs product kernel     */
+  int32_t N, fits, coords, products, kdF, geom_blocks; /* the request (nbp_last_plans: N = 0: no such launch yet)        */
+  int32_t pad[2];
+  int64_t lds;
+  char kernel[40];
+} nbp_fit_plan_rec;
+typedef struct nbp_proposal_plan_req {
+  int32_t N, n;
+  int32_t manifold;       /* the manifold of a batch of one factor kind on one manifold, 0: anything else                */
+  int32_t simple;         /* every proposal a binary relative (or a prior) on its one hypothesis                         */
+} nbp_proposal_plan_req;
+typedef struct nbp_proposal_plan_rec {
+  int32_t status;
+  int32_t geometry;       /* 0: a workgroup per proposal, 1: one wave, 2: two waves                                      */
+  int32_t blocks, threads;
+  int32_t N, n, manifold, simple;
+  int64_t lds;
+  char kernel[40];
+} nbp_proposal_plan_rec;
+nbp_status nbp_plan_products(const nbp_product_plan_req *req, nbp_product_plan_rec *out, int64_t n);
+nbp_status nbp_plan_fits(const nbp_fit_plan_req *req, nbp_fit_plan_rec *out, int64_t n);
+nbp_status nbp_plan_proposals(const nbp_proposal_plan_req *req, nbp_proposal_plan_rec *out, int64_t n);
+/* The plans of the last product launch, the last prep launch and the last plain bandwidth launch of the context (any pointer
+ * may be null), stored on the host when the launch is issued -- a captured program records at capture, not at replay. */
+nbp_status nbp_last_plans(nbp_ctx *ctx, nbp_product_plan_rec *product, nbp_fit_plan_rec *prep, nbp_fit_plan_rec *fits);
+
 /* Self-test of the elementary functions the kernels and the CPU checker share (include/nbp_math.h), evaluated ON THE DEVICE:
  * fn 0: out0 = log(a); 1: (out0, out1) = (sin, cos)(a); 2: out0 = atan2(a, b); 3: out0 = wrap to [-pi, pi) of a;
  * 4: (out0, out1) = the Box-Muller pair of the uniforms (a, b).  Host buffers of n doubles (b, out1 may be null where unused).

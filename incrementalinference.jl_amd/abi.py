@@ -144,6 +144,71 @@ class Diag(C.Structure):
     ]
 
 
+class ProductPlanReq(C.Structure):
+    """nbp_product_plan_req: one product launch as nbp_plan_products takes it"""
+    _fields_ = [(k, C.c_int32) for k in ("N", "n", "F", "D", "mani", "geom_n")]
+
+
+PLAN_REFUSED_BIG_IN_ROUND, PLAN_REFUSED_LDS, PLAN_REFUSED_NO_KERNEL = 1, 2, 3
+
+
+class _PlanRec(C.Structure):
+    def as_dict(self):
+        return {k: (getattr(self, k).decode() if k == "kernel" else getattr(self, k)) for k, _ in self._fields_ if not k.startswith("pad")}
+
+
+class ProductPlanRec(_PlanRec):
+    """nbp_product_plan_rec: what a product launch runs (nbp_plan_products, nbp_last_plans)"""
+    _fields_ = [(k, C.c_int32) for k in ("status", "refusal", "HL", "wpb", "G", "big", "xs", "circ", "nch", "all_levels", "w1", "row", "row_HL",
+                                         "row_mani", "row_xs", "row_w1", "launch_bound", "N", "n", "F", "D", "mani", "geom_n", "pad")] + \
+               [("lds", C.c_int64), ("gstats", C.c_int64), ("kernel", C.c_char * 40)]
+
+
+class FitPlanReq(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("N", "fits", "coords", "products", "kdF", "geom_blocks")]
+
+
+class FitPlanRec(_PlanRec):
+    _fields_ = [(k, C.c_int32) for k in ("status", "P", "depth", "KS", "w5", "threads", "prep", "kd_nostats", "N", "fits", "coords", "products",
+                                         "kdF", "geom_blocks")] + [("pad", C.c_int32 * 2), ("lds", C.c_int64), ("kernel", C.c_char * 40)]
+
+
+class ProposalPlanReq(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("N", "n", "manifold", "simple")]
+
+
+class ProposalPlanRec(_PlanRec):
+    _fields_ = [(k, C.c_int32) for k in ("status", "geometry", "blocks", "threads", "N", "n", "manifold", "simple")] + \
+               [("lds", C.c_int64), ("kernel", C.c_char * 40)]
+
+
+def _plan(fn_name, Req, Rec, reqs):
+    """the batched plan queries: a list of tuples in the field order of `Req` -> a ctypes array of `Rec` (no context, no GPU)"""
+    lib = load_library()
+    n = len(reqs)
+    arr = (Req * n)(*[Req(*r) for r in reqs])
+    out = (Rec * n)()
+    rc = getattr(lib, fn_name)(arr, out, n)
+    if rc != 0:
+        raise ValueError(f"{fn_name}: status {rc}: {lib.nbp_last_error().decode()}")
+    return out
+
+
+def plan_products(reqs):
+    """reqs: (N, n, F, D, mani, geom_n) each -> ProductPlanRec array"""
+    return _plan("nbp_plan_products", ProductPlanReq, ProductPlanRec, reqs)
+
+
+def plan_fits(reqs):
+    """reqs: (N, fits, coords, products, kdF, geom_blocks) each -> FitPlanRec array"""
+    return _plan("nbp_plan_fits", FitPlanReq, FitPlanRec, reqs)
+
+
+def plan_proposals(reqs):
+    """reqs: (N, n, manifold, simple) each -> ProposalPlanRec array"""
+    return _plan("nbp_plan_proposals", ProposalPlanReq, ProposalPlanRec, reqs)
+
+
 def slot_stride(N):
     return 3 * N + 8
 
@@ -162,6 +227,7 @@ EXPORTS = [
     "nbp_program_create", "nbp_program_add_stage", "nbp_program_set_option", "nbp_program_finalize", "nbp_program_run",
     "nbp_program_reseed", "nbp_program_num_seeds", "nbp_program_set_seeds", "nbp_program_seed_order", "nbp_ctx_attach", "nbp_ctx_attached", "nbp_program_num_stages", "nbp_program_num_fused", "nbp_program_num_two_stream", "nbp_program_destroy",
     "nbp_timing_enable", "nbp_timing_read", "nbp_timing_read_n", "nbp_diag_read",
+    "nbp_plan_products", "nbp_plan_fits", "nbp_plan_proposals", "nbp_last_plans",
     "nbp_comm_unique_id", "nbp_comm_create", "nbp_comm_destroy", "nbp_comm_info", "nbp_exchange", "nbp_math_eval",
 ]
 
@@ -277,6 +343,10 @@ def load_library(path=None):
     lib.nbp_program_num_fused.argtypes = [vp, C.POINTER(i32)]
     lib.nbp_program_num_two_stream.argtypes = [vp, C.POINTER(i32)]
     lib.nbp_diag_read.argtypes = [vp, C.POINTER(Diag), i32]
+    lib.nbp_plan_products.argtypes = [C.POINTER(ProductPlanReq), C.POINTER(ProductPlanRec), i64]
+    lib.nbp_plan_fits.argtypes = [C.POINTER(FitPlanReq), C.POINTER(FitPlanRec), i64]
+    lib.nbp_plan_proposals.argtypes = [C.POINTER(ProposalPlanReq), C.POINTER(ProposalPlanRec), i64]
+    lib.nbp_last_plans.argtypes = [vp, C.POINTER(ProductPlanRec), C.POINTER(FitPlanRec), C.POINTER(FitPlanRec)]
     for name in EXPORTS:
         fn = getattr(lib, name)
         if fn.restype is C.c_int:

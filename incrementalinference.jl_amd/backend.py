@@ -662,6 +662,13 @@ class HipBackend:
         self._check(self.lib.nbp_diag_read(self._ctx, C.byref(d), int(reset)))
         return {k: getattr(d, k) for k, _ in abi.Diag._fields_}
 
+    def last_plans(self):
+        """{"product", "prep", "fits"}: what the last product / prep / plain bandwidth launch of this context ran, as dicts of the
+        fields of nbp_product_plan_rec / nbp_fit_plan_rec (recorded on the host when the launch is issued)"""
+        p, q, f = abi.ProductPlanRec(), abi.FitPlanRec(), abi.FitPlanRec()
+        self._check(self.lib.nbp_last_plans(self._ctx, C.byref(p), C.byref(q), C.byref(f)))
+        return {"product": p.as_dict(), "prep": q.as_dict(), "fits": f.as_dict()}
+
     def arena_ptr(self):
         return self.lib.nbp_arena_ptr(self._ctx)
 

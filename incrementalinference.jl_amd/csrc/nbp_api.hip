@@ -156,6 +156,9 @@ struct nbp_ctx {
   // kernels (for A/B runs and tests)
   int prod_hl2_min = 192, prod_nch = 0, prod_all_levels_hl = 8;
   bool prod_xs = true, prod_lat_uni = true;
+  // what the last product / prep / plain bandwidth launch ran (nbp_last_plans): stored on the host where the launch is issued
+  nbp_product_plan_rec last_product{};
+  nbp_fit_plan_rec last_prep{}, last_fit{};
   // timing: 0 proposal, 1 prep, 2 product, 3 plain bandwidth, 4 fused update kernel
   bool timing = false;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev[5];
@@ -166,24 +169,27 @@ struct nbp_ctx {
 // The product kernels: helper lanes per sample, the manifold of a single-manifold instance (0: any mix), node sums from the
 // sorted coordinates (`xs`), launch bound for at most one workgroup per CU (`w1`).  product_plan picks its kernel here.
 typedef void (*nbp_product_fn)(const nbp_product_desc *, double *, const double *, int, double *, int, int64_t, int32_t *, nbp_levels);
-struct nbp_product_kernel_row { nbp_product_fn fn; int HL, mani; bool xs, w1; };
+struct nbp_product_kernel_row { nbp_product_fn fn; int HL, mani; bool xs, w1; const char *name; int lb; };
+// (name and launch bound of a row: the kernel's own, NBP_PRODUCT_LATENCY / NBP_PRODUCT_UNIFORM / NBP_PRODUCT_LATENCY_UNIFORM in nbp_kernels.h)
+#define NBP_ROW(NAME, HL_, MANI_, XS_, W1_, LB_) {NAME, HL_, MANI_, XS_, W1_, #NAME, LB_}
 static const nbp_product_kernel_row NBP_PRODUCT_KERNELS[] = {
-    {nbp_product_kernel_y32, 32, 0, false, false},           {nbp_product_kernel_y32_w1, 32, 0, false, true},
-    {nbp_product_kernel_l8, 8, 0, false, false},             {nbp_product_kernel_l8_w1, 8, 0, false, true},
-    {nbp_product_kernel_t2, 2, 0, false, false},
-    {nbp_product_kernel_y32_e1, 32, NBP_EUCLID1, false, false}, {nbp_product_kernel_y32_e2, 32, NBP_EUCLID2, false, false},
-    {nbp_product_kernel_y32_e3, 32, NBP_EUCLID3, false, false}, {nbp_product_kernel_y32_ci, 32, NBP_CIRCULAR, false, false},
-    {nbp_product_kernel_y32_se, 32, NBP_SE2, false, false},
-    {nbp_product_kernel_l8_e1, 8, NBP_EUCLID1, false, false},   {nbp_product_kernel_l8_e2, 8, NBP_EUCLID2, false, false},
-    {nbp_product_kernel_l8_e3, 8, NBP_EUCLID3, false, false},   {nbp_product_kernel_l8_ci, 8, NBP_CIRCULAR, false, false},
-    {nbp_product_kernel_l8_se, 8, NBP_SE2, false, false},
-    {nbp_product_kernel_t2_e1, 2, NBP_EUCLID1, false, false},   {nbp_product_kernel_t2_e2, 2, NBP_EUCLID2, false, false},
-    {nbp_product_kernel_t2_e3, 2, NBP_EUCLID3, false, false},   {nbp_product_kernel_t2_ci, 2, NBP_CIRCULAR, false, false},
-    {nbp_product_kernel_t2_se, 2, NBP_SE2, false, false},
-    {nbp_product_kernel_t2_e1_xs, 2, NBP_EUCLID1, true, false}, {nbp_product_kernel_t2_e2_xs, 2, NBP_EUCLID2, true, false},
-    {nbp_product_kernel_t2_e3_xs, 2, NBP_EUCLID3, true, false}, {nbp_product_kernel_t2_ci_xs, 2, NBP_CIRCULAR, true, false},
-    {nbp_product_kernel_t2_se_xs, 2, NBP_SE2, true, false},
+    NBP_ROW(nbp_product_kernel_y32, 32, 0, false, false, 512),           NBP_ROW(nbp_product_kernel_y32_w1, 32, 0, false, true, 256),
+    NBP_ROW(nbp_product_kernel_l8, 8, 0, false, false, 512),             NBP_ROW(nbp_product_kernel_l8_w1, 8, 0, false, true, 256),
+    NBP_ROW(nbp_product_kernel_t2, 2, 0, false, false, 512),
+    NBP_ROW(nbp_product_kernel_y32_e1, 32, NBP_EUCLID1, false, false, 512), NBP_ROW(nbp_product_kernel_y32_e2, 32, NBP_EUCLID2, false, false, 512),
+    NBP_ROW(nbp_product_kernel_y32_e3, 32, NBP_EUCLID3, false, false, 512), NBP_ROW(nbp_product_kernel_y32_ci, 32, NBP_CIRCULAR, false, false, 512),
+    NBP_ROW(nbp_product_kernel_y32_se, 32, NBP_SE2, false, false, 512),
+    NBP_ROW(nbp_product_kernel_l8_e1, 8, NBP_EUCLID1, false, false, 512),   NBP_ROW(nbp_product_kernel_l8_e2, 8, NBP_EUCLID2, false, false, 512),
+    NBP_ROW(nbp_product_kernel_l8_e3, 8, NBP_EUCLID3, false, false, 512),   NBP_ROW(nbp_product_kernel_l8_ci, 8, NBP_CIRCULAR, false, false, 512),
+    NBP_ROW(nbp_product_kernel_l8_se, 8, NBP_SE2, false, false, 512),
+    NBP_ROW(nbp_product_kernel_t2_e1, 2, NBP_EUCLID1, false, false, NBP_PROD_LB(NBP_EUCLID1)),   NBP_ROW(nbp_product_kernel_t2_e2, 2, NBP_EUCLID2, false, false, NBP_PROD_LB(NBP_EUCLID2)),
+    NBP_ROW(nbp_product_kernel_t2_e3, 2, NBP_EUCLID3, false, false, NBP_PROD_LB(NBP_EUCLID3)),   NBP_ROW(nbp_product_kernel_t2_ci, 2, NBP_CIRCULAR, false, false, NBP_PROD_LB(NBP_CIRCULAR)),
+    NBP_ROW(nbp_product_kernel_t2_se, 2, NBP_SE2, false, false, NBP_PROD_LB(NBP_SE2)),
+    NBP_ROW(nbp_product_kernel_t2_e1_xs, 2, NBP_EUCLID1, true, false, NBP_PROD_LB(NBP_EUCLID1)), NBP_ROW(nbp_product_kernel_t2_e2_xs, 2, NBP_EUCLID2, true, false, NBP_PROD_LB(NBP_EUCLID2)),
+    NBP_ROW(nbp_product_kernel_t2_e3_xs, 2, NBP_EUCLID3, true, false, NBP_PROD_LB(NBP_EUCLID3)), NBP_ROW(nbp_product_kernel_t2_ci_xs, 2, NBP_CIRCULAR, true, false, NBP_PROD_LB(NBP_CIRCULAR)),
+    NBP_ROW(nbp_product_kernel_t2_se_xs, 2, NBP_SE2, true, false, NBP_PROD_LB(NBP_SE2)),
 };
+#undef NBP_ROW
 
 static int manifold_dim_h(int m) { return m == NBP_SE2 ? 3 : (m == NBP_CIRCULAR ? 1 : m); }
 static int manifold_P_h(int m) { return m == NBP_SE2 ? 6 : manifold_dim_h(m); }
@@ -233,9 +239,9 @@ int64_t nbp_slot_stride_doubles(int32_t N) { return 3 * (int64_t)N + 8; }
 int64_t nbp_arena_bytes(int32_t N, int32_t n_slots) { return nbp_slot_stride_doubles(N) * 8 * (int64_t)n_slots; }
 const char *nbp_last_error(void) { return g_err.c_str(); }
 
-// data-independent level tables of the balanced KD-tree over N leaves
-static nbp_status build_levels(nbp_ctx *c) {
-  const int N = c->N;
+// data-independent level tables of the balanced KD-tree over N leaves, on the host: T.N, T.L, T.cnt and T.off, and the arrays
+// build_levels uploads
+static nbp_status levels_host(int N, nbp_levels &T, std::vector<int32_t> &ints, std::vector<double> &dbls) {
   std::vector<std::vector<int>> lo(1), hi(1), child;
   lo[0] = {0};
   hi[0] = {N};
@@ -264,32 +270,37 @@ static nbp_status build_levels(nbp_ctx *c) {
     if (l >= NBP_MAXLEVELS - 1) return fail(NBP_ERR_RANGE, "tree too deep");
   }
   const int L = l;
-  std::vector<int32_t> ints;
-  std::vector<double> dbls;
   int total = 0;
-  for (int i = 0; i <= L; i++) { c->T.cnt[i] = (int)lo[i].size(); c->T.off[i] = total; total += c->T.cnt[i]; }
+  for (int i = 0; i <= L; i++) { T.cnt[i] = (int)lo[i].size(); T.off[i] = total; total += T.cnt[i]; }
   if ((size_t)total > nbp_kd_nodes_cap(N)) return fail(NBP_ERR_RANGE, "level tables exceed the node-sum workspace");
   std::vector<int32_t> nlo(total), nhi(total), nch(total, 0), pos((size_t)(L + 1) * N);
   dbls.resize(2 * (size_t)total);
   for (int i = 0; i <= L; i++)
-    for (int k = 0; k < c->T.cnt[i]; k++) {
-      nlo[c->T.off[i] + k] = lo[i][k];
-      nhi[c->T.off[i] + k] = hi[i][k];
-      if (i < L) nch[c->T.off[i] + k] = child[i][k];
-      dbls[c->T.off[i] + k] = std::log((double)(hi[i][k] - lo[i][k]) / (double)N);
-      dbls[total + c->T.off[i] + k] = (double)(hi[i][k] - lo[i][k]) / (double)N;
+    for (int k = 0; k < T.cnt[i]; k++) {
+      nlo[T.off[i] + k] = lo[i][k];
+      nhi[T.off[i] + k] = hi[i][k];
+      if (i < L) nch[T.off[i] + k] = child[i][k];
+      dbls[T.off[i] + k] = std::log((double)(hi[i][k] - lo[i][k]) / (double)N);
+      dbls[total + T.off[i] + k] = (double)(hi[i][k] - lo[i][k]) / (double)N;
       for (int p = lo[i][k]; p < hi[i][k]; p++) pos[(size_t)i * N + p] = k;
     }
   ints.insert(ints.end(), nlo.begin(), nlo.end());
   ints.insert(ints.end(), nhi.begin(), nhi.end());
   ints.insert(ints.end(), nch.begin(), nch.end());
   ints.insert(ints.end(), pos.begin(), pos.end());
+  T.N = N;
+  T.L = L;
+  return NBP_OK;
+}
+static nbp_status build_levels(nbp_ctx *c) {
+  std::vector<int32_t> ints;
+  std::vector<double> dbls;
+  NBPCHK(levels_host(c->N, c->T, ints, dbls));
+  const int total = c->T.off[c->T.L] + c->T.cnt[c->T.L];
   HIPCHK(hipMalloc(&c->lv_ints, ints.size() * 4));
   HIPCHK(hipMalloc(&c->lv_dbls, dbls.size() * 8));
   HIPCHK(hipMemcpy(c->lv_ints, ints.data(), ints.size() * 4, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(c->lv_dbls, dbls.data(), dbls.size() * 8, hipMemcpyHostToDevice));
-  c->T.N = N;
-  c->T.L = L;
   c->T.node_lo = c->lv_ints;
   c->T.node_hi = c->lv_ints + total;
   c->T.node_child = c->lv_ints + 2 * total;
@@ -297,6 +308,36 @@ static nbp_status build_levels(nbp_ctx *c) {
   c->T.node_logw = c->lv_dbls;
   c->T.node_w = c->lv_dbls + total;
   return NBP_OK;
+}
+
+// Everything the launch planners (proposal_plan, fit_plan, product_plan) read of a context besides the level table: the sizes
+// that follow from N and the switches of the environment.  nbp_ctx_create and the plan queries (nbp_plan_products, ...) both
+// fill a context here, so that a query sees what a context created at that moment would.
+static void ctx_plan_fields(nbp_ctx *c, int N) {
+  c->N = N;
+  c->S = nbp_slot_stride_doubles(N);
+  c->Npad = ((N + 63) / 64) * 64;
+  c->P = 1024 / c->Npad;
+  if (c->P > 4) c->P = 4;
+  if (c->P < 1) c->P = 1;
+  c->threads = c->P * c->Npad;
+  c->spec_on = getenv("NBP_NO_SPECULATIVE_FITS") == nullptr;
+  c->spec_depth3 = !(getenv("NBP_SPEC_DEPTH3") && atoi(getenv("NBP_SPEC_DEPTH3")) == 0);
+  c->fused_on = getenv("NBP_NO_FUSED_UPDATE") == nullptr;
+  if (getenv("NBP_FUSED_MIN")) c->fused_min = atoi(getenv("NBP_FUSED_MIN"));
+  if (getenv("NBP_PROPOSAL_WAVE_MIN")) c->prop_wave_min = atoi(getenv("NBP_PROPOSAL_WAVE_MIN"));
+  if (getenv("NBP_PROPOSAL_SPLIT_MIN")) c->prop_split_min = atoi(getenv("NBP_PROPOSAL_SPLIT_MIN"));
+  if (getenv("NBP_PIPELINE_MIN")) c->pipe_min = atoi(getenv("NBP_PIPELINE_MIN"));
+  if (getenv("NBP_FUSED_P1_MIN")) c->fused_p1_min = atoi(getenv("NBP_FUSED_P1_MIN"));
+  if (getenv("NBP_PRODUCT_HL2_MIN")) c->prod_hl2_min = atoi(getenv("NBP_PRODUCT_HL2_MIN"));
+  if (getenv("NBP_PRODUCT_NCH")) c->prod_nch = atoi(getenv("NBP_PRODUCT_NCH"));
+  if (getenv("NBP_PRODUCT_ALL_LEVELS_HL")) c->prod_all_levels_hl = atoi(getenv("NBP_PRODUCT_ALL_LEVELS_HL"));
+  c->prod_xs = getenv("NBP_NO_XS_PRODUCTS") == nullptr;
+  c->prod_lat_uni = getenv("NBP_NO_UNIFORM_LATENCY_PRODUCTS") == nullptr;
+  if (getenv("NBP_LCV_P2_MIN")) c->lcv_p2_min = atoi(getenv("NBP_LCV_P2_MIN"));
+  if (getenv("NBP_LCV_P1_MIN")) c->lcv_p1_min = atoi(getenv("NBP_LCV_P1_MIN"));
+  c->fit_w5 = getenv("NBP_NO_W5_FITS") == nullptr;
+  c->debug_occupancy = getenv("NBP_DEBUG_OCCUPANCY") != nullptr;
 }
 
 nbp_status nbp_ctx_create(int32_t device, int32_t N, int32_t n_slots, void *arena, int64_t arena_bytes,
@@ -316,14 +357,8 @@ nbp_status nbp_ctx_create(int32_t device, int32_t N, int32_t n_slots, void *aren
     ~guard_t() { if (c) nbp_ctx_destroy(c); }
   } guard{c};
   c->device = device;
-  c->N = N;
   c->n_slots = n_slots;
-  c->S = nbp_slot_stride_doubles(N);
-  c->Npad = ((N + 63) / 64) * 64;
-  c->P = 1024 / c->Npad;
-  if (c->P > 4) c->P = 4;
-  if (c->P < 1) c->P = 1;
-  c->threads = c->P * c->Npad;
+  ctx_plan_fields(c, N);
   c->side_ints = side_ints > 0 ? side_ints : 1;
   if (arena) {
     if (arena_bytes < nbp_arena_bytes(N, n_slots)) return fail(NBP_ERR_ARG, "arena too small");
@@ -344,25 +379,8 @@ nbp_status nbp_ctx_create(int32_t device, int32_t N, int32_t n_slots, void *aren
   }
   HIPCHK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
   HIPCHK(hipMalloc(&c->spec, sizeof(nbp_spec_area) * 3 * NBP_SPEC_MAXJOBS));
-  c->spec_on = getenv("NBP_NO_SPECULATIVE_FITS") == nullptr;
-  c->spec_depth3 = !(getenv("NBP_SPEC_DEPTH3") && atoi(getenv("NBP_SPEC_DEPTH3")) == 0);
-  c->fused_on = getenv("NBP_NO_FUSED_UPDATE") == nullptr;
-  if (getenv("NBP_FUSED_MIN")) c->fused_min = atoi(getenv("NBP_FUSED_MIN"));
-  if (getenv("NBP_PROPOSAL_WAVE_MIN")) c->prop_wave_min = atoi(getenv("NBP_PROPOSAL_WAVE_MIN"));
-  if (getenv("NBP_PROPOSAL_SPLIT_MIN")) c->prop_split_min = atoi(getenv("NBP_PROPOSAL_SPLIT_MIN"));
-  if (getenv("NBP_PIPELINE_MIN")) c->pipe_min = atoi(getenv("NBP_PIPELINE_MIN"));
   HIPCHK(hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking));
   for (int i = 0; i < 2; i++) HIPCHK(hipEventCreateWithFlags(&c->pipe_ev[i], hipEventDisableTiming));
-  if (getenv("NBP_FUSED_P1_MIN")) c->fused_p1_min = atoi(getenv("NBP_FUSED_P1_MIN"));
-  if (getenv("NBP_PRODUCT_HL2_MIN")) c->prod_hl2_min = atoi(getenv("NBP_PRODUCT_HL2_MIN"));
-  if (getenv("NBP_PRODUCT_NCH")) c->prod_nch = atoi(getenv("NBP_PRODUCT_NCH"));
-  if (getenv("NBP_PRODUCT_ALL_LEVELS_HL")) c->prod_all_levels_hl = atoi(getenv("NBP_PRODUCT_ALL_LEVELS_HL"));
-  c->prod_xs = getenv("NBP_NO_XS_PRODUCTS") == nullptr;
-  c->prod_lat_uni = getenv("NBP_NO_UNIFORM_LATENCY_PRODUCTS") == nullptr;
-  if (getenv("NBP_LCV_P2_MIN")) c->lcv_p2_min = atoi(getenv("NBP_LCV_P2_MIN"));
-  if (getenv("NBP_LCV_P1_MIN")) c->lcv_p1_min = atoi(getenv("NBP_LCV_P1_MIN"));
-  c->fit_w5 = getenv("NBP_NO_W5_FITS") == nullptr;
-  c->debug_occupancy = getenv("NBP_DEBUG_OCCUPANCY") != nullptr;
   nbp_status rc = build_levels(c);
   if (rc != NBP_OK) return rc;
   // allow the full 160 KiB LDS for the product kernels
@@ -936,39 +954,65 @@ static int proposals_uniform_class(const nbp_proposal_desc *d, int n) {
 // 171 split, 550: 172 / 176, 700: 200 / 188; 3200: 528 split / 604 one wave, 4000: 656 / 630 -- the crossovers, rounded
 #define NBP_SPLIT_MIN_DEFAULT 600
 #define NBP_WAVE_MIN_LIN2_DEFAULT 3500
-static nbp_status launch_proposals(nbp_ctx *c, const nbp_launch_env &env, const nbp_proposal_desc *dev, int n, int cls = 0) {
-  if (n <= 0) return NBP_OK;
-  nbp_status rc = tic(c, c->ev[0]);
-  if (rc) return rc;
-  (void)hipGetLastError();  // clear stale, unrelated errors
+// What a proposal launch runs, decided in one place (launch_proposals; nbp_plan_proposals): the geometry (0: a workgroup per
+// proposal, 1: one wave, 2: two waves), the grid, the workgroup, the LDS and the kernel's name.  `cls` as
+// proposals_uniform_class gives it.
+struct nbp_proposal_plan {
+  int geometry = 0, blocks = 0, threads = 0;
+  size_t lds = 0;
+  const char *name = "";
+};
+static nbp_proposal_plan proposal_plan(const nbp_ctx *c, int n, int cls) {
+  nbp_proposal_plan q;
   const bool simple = (cls & NBP_CLS_SIMPLE) != 0;
   cls &= NBP_CLS_SIMPLE - 1;
   // chip-filling launches of simple Euclidean batches: one wave per proposal, no workgroup barrier (nbp_kernels.h,
   // proposal_wave_body); rows of up to five waves (N <= 320)
   const int wave_min = c->prop_wave_min >= 0 ? c->prop_wave_min : (cls == NBP_CLS_LIN2 ? NBP_WAVE_MIN_LIN2_DEFAULT : (c->N > 256 ? 1500 : (1 << 30)));
   if (simple && n >= wave_min && (cls == NBP_CLS_LIN2 || cls == NBP_CLS_LIN3) && c->N <= (cls == NBP_CLS_LIN2 ? 256 : 320)) {
-    auto *wk = cls == NBP_CLS_LIN2 ? nbp_proposal_wave_kernel_lin2 : (c->N <= 256 ? nbp_proposal_wave_kernel_lin3 : nbp_proposal_wave_kernel_lin3n5);
-    hipLaunchKernelGGL(wk, dim3((n + NBP_PW_WAVES - 1) / NBP_PW_WAVES), dim3(64 * NBP_PW_WAVES), nbp_proposal_wave_lds_bytes(c->N, cls == NBP_CLS_LIN2 ? 2 : 3),
-                       env.stream, dev, n, c->arena, c->N, c->S, c->side, c->counters);
-    HIPCHK(hipGetLastError());
-    c->prop_launches[1]++;
-    return toc(c, c->ev[0]);
+    q.geometry = 1;
+    q.blocks = (n + NBP_PW_WAVES - 1) / NBP_PW_WAVES;
+    q.threads = 64 * NBP_PW_WAVES;
+    q.lds = nbp_proposal_wave_lds_bytes(c->N, cls == NBP_CLS_LIN2 ? 2 : 3);
+    q.name = cls == NBP_CLS_LIN2 ? "nbp_proposal_wave_kernel_lin2" : (c->N <= 256 ? "nbp_proposal_wave_kernel_lin3" : "nbp_proposal_wave_kernel_lin3n5");
+    return q;
   }
   // between the two: two waves per proposal, each owning every second chunk of 64 particles (proposal_split_body)
   const int split_min = c->prop_split_min >= 0 ? c->prop_split_min : NBP_SPLIT_MIN_DEFAULT;
   if (simple && cls == NBP_CLS_LIN2 && c->N <= 256 && n >= split_min) {
-    hipLaunchKernelGGL(nbp_proposal_split_kernel_lin2, dim3(n), dim3(64 * NBP_PS_W), nbp_proposal_split_lds_bytes(c->N, 2), env.stream, dev, c->arena,
-                       c->N, c->S, c->side, c->counters);
-    HIPCHK(hipGetLastError());
-    c->prop_launches[2]++;
-    return toc(c, c->ev[0]);
+    q.geometry = 2;
+    q.blocks = n;
+    q.threads = 64 * NBP_PS_W;
+    q.lds = nbp_proposal_split_lds_bytes(c->N, 2);
+    q.name = "nbp_proposal_split_kernel_lin2";
+    return q;
   }
-  auto *kern = cls == NBP_CLS_LIN2 ? nbp_proposal_kernel_lin2 : (cls == NBP_CLS_LIN3 ? nbp_proposal_kernel_lin3 : (cls == NBP_CLS_CIRC ? nbp_proposal_kernel_circ :
-               (cls == NBP_CLS_SE2 ? nbp_proposal_kernel_se2 : nbp_proposal_kernel)));
-  hipLaunchKernelGGL(kern, dim3(n), dim3(c->Npad), nbp_proposal_lds_bytes(c->N), env.stream, dev, c->arena, c->N, c->Npad, c->S, c->side,
-                     c->counters);
+  q.blocks = n;
+  q.threads = c->Npad;
+  q.lds = nbp_proposal_lds_bytes(c->N);
+  q.name = cls == NBP_CLS_LIN2 ? "nbp_proposal_kernel_lin2" : (cls == NBP_CLS_LIN3 ? "nbp_proposal_kernel_lin3" : (cls == NBP_CLS_CIRC ? "nbp_proposal_kernel_circ" :
+           (cls == NBP_CLS_SE2 ? "nbp_proposal_kernel_se2" : "nbp_proposal_kernel")));
+  return q;
+}
+static nbp_status launch_proposals(nbp_ctx *c, const nbp_launch_env &env, const nbp_proposal_desc *dev, int n, int cls = 0) {
+  if (n <= 0) return NBP_OK;
+  nbp_status rc = tic(c, c->ev[0]);
+  if (rc) return rc;
+  (void)hipGetLastError();  // clear stale, unrelated errors
+  const nbp_proposal_plan q = proposal_plan(c, n, cls);
+  cls &= NBP_CLS_SIMPLE - 1;
+  if (q.geometry == 1) {
+    auto *wk = cls == NBP_CLS_LIN2 ? nbp_proposal_wave_kernel_lin2 : (c->N <= 256 ? nbp_proposal_wave_kernel_lin3 : nbp_proposal_wave_kernel_lin3n5);
+    hipLaunchKernelGGL(wk, dim3(q.blocks), dim3(q.threads), q.lds, env.stream, dev, n, c->arena, c->N, c->S, c->side, c->counters);
+  } else if (q.geometry == 2) {
+    hipLaunchKernelGGL(nbp_proposal_split_kernel_lin2, dim3(q.blocks), dim3(q.threads), q.lds, env.stream, dev, c->arena, c->N, c->S, c->side, c->counters);
+  } else {
+    auto *kern = cls == NBP_CLS_LIN2 ? nbp_proposal_kernel_lin2 : (cls == NBP_CLS_LIN3 ? nbp_proposal_kernel_lin3 : (cls == NBP_CLS_CIRC ? nbp_proposal_kernel_circ :
+                 (cls == NBP_CLS_SE2 ? nbp_proposal_kernel_se2 : nbp_proposal_kernel)));
+    hipLaunchKernelGGL(kern, dim3(q.blocks), dim3(q.threads), q.lds, env.stream, dev, c->arena, c->N, c->Npad, c->S, c->side, c->counters);
+  }
   HIPCHK(hipGetLastError());
-  c->prop_launches[0]++;
+  c->prop_launches[q.geometry]++;
   return toc(c, c->ev[0]);
 }
 // room for the KD builds of nprod products in the environment's workspace; outside a round the context's workspace grows
@@ -1078,6 +1122,16 @@ static nbp_fit_plan fit_plan(const nbp_ctx *c, const nbp_launch_env &env, int nb
   if (nkd > 0) f.lds = std::max(f.lds, nbp_kd_lds_bytes(3, c->N, c->Npad, f.P));
   return f;
 }
+// a fit plan as nbp_plan_fits / nbp_last_plans report it (`prep`: the launch is launch_prep's)
+static nbp_fit_plan_rec fit_plan_rec(const nbp_ctx *c, const nbp_launch_env &env, int nbw, int coords, int nprod, int kdF, bool prep, const nbp_fit_plan &f) {
+  nbp_fit_plan_rec r{};
+  r.status = NBP_OK;
+  r.P = f.P; r.depth = f.depth; r.KS = f.KS; r.w5 = f.w5; r.threads = f.threads; r.prep = prep;
+  r.N = c->N; r.fits = nbw; r.coords = coords; r.products = nprod; r.kdF = kdF; r.geom_blocks = env.geom_blocks;
+  r.lds = (int64_t)f.lds;
+  snprintf(r.kernel, sizeof(r.kernel), "%s%s", prep ? "nbp_prep_kernel" : "nbp_bandwidth_kernel", f.depth == 3 ? "_spec<3>" : (f.depth == 2 ? "_spec<2>" : (f.w5 ? "_w5" : "")));
+  return r;
+}
 
 // ---- product launches ----
 // Geometry: HL helper lanes per sample (64/HL samples per wave), workgroups of `wpb` waves, grid.y = G workgroups per product.
@@ -1115,9 +1169,10 @@ static const size_t NBP_PRODUCT_ALL_LEVELS_LDS = 76 * 1024;
 static const long NBP_PRODUCT_W1_BLOCKS = 256;
 
 // `mani`: the manifold of a single-manifold batch (0: mixed; < 0: size for the widest workgroup any kernel takes)
-static void product_geometry(const nbp_ctx *c, const nbp_launch_env &env, int n, int *HL, int *wpb, int *G, int mani) {
+// `lanes`: 0, or the helper lanes per sample to take whatever the batch size says
+static void product_geometry(const nbp_ctx *c, const nbp_launch_env &env, int n, int *HL, int *wpb, int *G, int mani, int lanes = 0) {
   if (env.geom_n) n = env.geom_n;  // one half of a two-stream round: the geometry of the whole batch
-  *HL = n >= c->prod_hl2_min ? 2 : (n >= 16 ? 8 : 32);
+  *HL = lanes ? lanes : (n >= c->prod_hl2_min ? 2 : (n >= 16 ? 8 : 32));
   const int SW = 64 / *HL, waves = (c->N + SW - 1) / SW, cap = (*HL >= 8) ? NBP_PRODUCT_LAT_WAVES : 8;
   int g = (waves + cap - 1) / cap;
   *wpb = (waves + g - 1) / g;
@@ -1157,6 +1212,7 @@ struct nbp_product_plan {
   bool w1 = false;              // a `_w1` kernel
   size_t lds = 0, gstats = 0;   // dynamic LDS bytes per workgroup; doubles of the global statistics area (big only)
   nbp_product_fn fn = nullptr;  // from NBP_PRODUCT_KERNELS (nullptr: the table has none for this plan)
+  int row = -1;                 // its row there
 };
 // `maxFD` encodes the largest (F, D) of the batch as F*4 + D; `mani` as for product_geometry
 static nbp_product_plan product_plan(const nbp_ctx *c, const nbp_launch_env &env, int n, int maxFD, int mani) {
@@ -1166,7 +1222,10 @@ static nbp_product_plan product_plan(const nbp_ctx *c, const nbp_launch_env &env
   // big: the statistics do not fit with the chunk sums the throughput geometries keep in LDS (two chunks per lane at least)
   p.big = nbp_product_lds_bytes(F, D, c->N, p.wpb * 64 / p.HL, false, p.HL <= 4 ? (size_t)2 * 2 * p.wpb * 64 : 0,
                                 product_lays_circ(p.HL, mani)) > NBP_PRODUCT_LDS_CAP;
-  if (p.big && p.HL != 8) product_geometry(c, env, 16, &p.HL, &p.wpb, &p.G, 0);  // many densities: small sample groups keep the label table in LDS
+  // many densities: small sample groups keep the label table in LDS, and only the generic kernels of EIGHT helper lanes have the
+  // scratch path.  (Asked for by lanes, not by a batch size of 16: under NBP_PRODUCT_HL2_MIN <= 16 that size is a throughput
+  //  batch, the plan stayed at two helper lanes and a kernel without the scratch path ran past its LDS -- DESIGN.md 8.)
+  if (p.big && p.HL != 8) product_geometry(c, env, 16, &p.HL, &p.wpb, &p.G, 0, 8);
   const int TB = p.wpb * 64, SPB = TB / p.HL;
   p.circ = product_lays_circ(p.HL, mani);
   // The launch takes the node sums from the sorted coordinates itself (4 KB instead of 33 KB of KD workspace per density
@@ -1211,8 +1270,36 @@ static nbp_product_plan product_plan(const nbp_ctx *c, const nbp_launch_env &env
   const int km = (mani > 0 && (p.HL <= 4 || (c->prod_lat_uni && !p.big))) ? mani : 0;
   p.w1 = km == 0 && p.HL >= 8 && TB <= 256 && (long)n * p.G <= NBP_PRODUCT_W1_BLOCKS && !env.geom_n;
   for (const nbp_product_kernel_row &k : NBP_PRODUCT_KERNELS)
-    if (k.HL == p.HL && k.mani == km && k.xs == p.xs && k.w1 == p.w1) p.fn = k.fn;
+    if (k.HL == p.HL && k.mani == km && k.xs == p.xs && k.w1 == p.w1) { p.fn = k.fn; p.row = (int)(&k - NBP_PRODUCT_KERNELS); }
   return p;
+}
+// what launch_products refuses of a plan (0: nothing; NBP_PLAN_REFUSED_* of nbp.h), and why
+// (the halves of a two-stream round take the geometry of the whole batch, whose throughput kernels have no scratch path, and
+//  share one scratch area: nbp_program_finalize pipelines no round whose products are big -- refused here should it ever)
+static int product_plan_refusal(const nbp_product_plan &p, const nbp_launch_env &env, const char **why) {
+  const char *w = nullptr;
+  int r = 0;
+  if (p.big && env.geom_n) { r = NBP_PLAN_REFUSED_BIG_IN_ROUND; w = "product: node statistics beyond the LDS inside a two-stream round"; }
+  else if (p.lds > 160 * 1024) { r = NBP_PLAN_REFUSED_LDS; w = "product: too many densities for the LDS label table"; }
+  else if (!p.fn) { r = NBP_PLAN_REFUSED_NO_KERNEL; w = "product: no kernel for the launch's geometry"; }
+  if (why) *why = w;
+  return r;
+}
+// a product plan as nbp_plan_products / nbp_last_plans report it
+static nbp_product_plan_rec product_plan_rec(const nbp_ctx *c, const nbp_launch_env &env, int n, int maxFD, int mani, const nbp_product_plan &p) {
+  nbp_product_plan_rec r{};
+  r.refusal = product_plan_refusal(p, env, nullptr);
+  r.status = r.refusal ? NBP_ERR_RANGE : NBP_OK;
+  r.HL = p.HL; r.wpb = p.wpb; r.G = p.G; r.big = p.big; r.xs = p.xs; r.circ = p.circ; r.nch = p.nch; r.all_levels = p.all_levels; r.w1 = p.w1;
+  r.row = p.row;
+  if (p.row >= 0) {
+    const nbp_product_kernel_row &k = NBP_PRODUCT_KERNELS[p.row];
+    r.row_HL = k.HL; r.row_mani = k.mani; r.row_xs = k.xs; r.row_w1 = k.w1; r.launch_bound = k.lb;
+    snprintf(r.kernel, sizeof(r.kernel), "%s", k.name);
+  }
+  r.N = c->N; r.n = n; r.F = maxFD / 4; r.D = maxFD % 4; r.mani = mani; r.geom_n = env.geom_n;
+  r.lds = (int64_t)p.lds; r.gstats = (int64_t)p.gstats;
+  return r;
 }
 
 // the rendezvous areas of the next launch of speculative fits, blanked on the launch's stream
@@ -1232,6 +1319,8 @@ static nbp_status launch_prep(nbp_ctx *c, nbp_launch_env &env, const nbp_fits_de
   const nbp_fit_plan f = fit_plan(c, env, bw.n, bw.coords, n, F);
   (void)hipGetLastError();
   const int kdF = F | (product_plan(c, env, n, maxFD, mani).xs ? NBP_KD_NOSTATS : 0);
+  c->last_prep = fit_plan_rec(c, env, bw.n, bw.coords, n, F, true, f);
+  c->last_prep.kd_nostats = (kdF & NBP_KD_NOSTATS) != 0;
   const dim3 grid(3 * bw.n * f.KS + n * F);
   if (f.depth) {
     blank_spec_areas(c, env, bw.n);
@@ -1264,11 +1353,9 @@ static int products_uniform_manifold(const nbp_product_desc *d, int n) {
 static nbp_status launch_products(nbp_ctx *c, const nbp_launch_env &env, const nbp_product_desc *dev, int n, int maxFD, int mani = 0) {
   if (n <= 0) return NBP_OK;
   const nbp_product_plan p = product_plan(c, env, n, maxFD, mani);
-  // (the halves of a two-stream round take the geometry of the whole batch, whose throughput kernels have no scratch path, and
-  //  share one scratch area: nbp_program_finalize pipelines no round whose products are big -- refused here should it ever)
-  if (p.big && env.geom_n) return fail(NBP_ERR_RANGE, "product: node statistics beyond the LDS inside a two-stream round");
-  if (p.lds > 160 * 1024) return fail(NBP_ERR_RANGE, "product: too many densities for the LDS label table");
-  if (!p.fn) return fail(NBP_ERR_RANGE, "product: no kernel for the launch's geometry");
+  c->last_product = product_plan_rec(c, env, n, maxFD, mani, p);
+  const char *why = nullptr;
+  if (product_plan_refusal(p, env, &why)) return fail(NBP_ERR_RANGE, why);
   nbp_status rc = NBP_OK;
   if (p.big) {
     rc = ensure_gstats(c, p.gstats);
@@ -1304,6 +1391,7 @@ static nbp_status launch_bandwidth(nbp_ctx *c, const nbp_launch_env &env, const 
   if (rc) return rc;
   (void)hipGetLastError();
   const nbp_fit_plan f = fit_plan(c, env, bw.n, bw.coords);
+  c->last_fit = fit_plan_rec(c, env, bw.n, bw.coords, 0, 0, false, f);
   if (f.depth) {
     blank_spec_areas(c, env, bw.n);
     hipLaunchKernelGGL(f.depth == 3 ? nbp_bandwidth_kernel_spec<3> : nbp_bandwidth_kernel_spec<2>, dim3(bw.n, 3, f.KS), dim3(f.threads), f.lds, env.stream,
@@ -3645,6 +3733,89 @@ nbp_status nbp_timing_read_n(nbp_ctx *c, double *ms, int64_t *launches, int32_t 
   }
   return NBP_OK;
 }
+// ---- launch plans (nbp.h): the planners themselves, on a context that holds only what they read -----------------------
+// (ctx_plan_fields + the level table of N; no device, no stream: nothing here touches the GPU)
+static nbp_status plan_ctx(nbp_ctx &c, int N) {
+  if (N < 8 || N > NBP_MAXN) return fail(NBP_ERR_RANGE, "N must be in [8, 512]");
+  std::vector<int32_t> ints;
+  std::vector<double> dbls;
+  ctx_plan_fields(&c, N);
+  return levels_host(N, c.T, ints, dbls);
+}
+nbp_status nbp_plan_products(const nbp_product_plan_req *req, nbp_product_plan_rec *out, int64_t n) {
+  if ((!req || !out) && n > 0) return fail(NBP_ERR_ARG, "null argument");
+  nbp_ctx c;
+  for (int64_t i = 0; i < n; i++) {
+    const nbp_product_plan_req &q = req[i];
+    if (c.N != q.N) {  // (requests sorted by N build the level table once per N)
+      c = nbp_ctx();
+      NBPCHK(plan_ctx(c, q.N));
+    }
+    if (q.n < 1 || q.F < 1 || q.F > NBP_MAXF || q.D < 1 || q.D > 3 || q.mani < -1 || q.mani > NBP_SE2 || q.geom_n < 0)
+      return fail(NBP_ERR_ARG, "plan query: request " + std::to_string(i) + ": out of range");
+    nbp_launch_env env;
+    env.geom_n = q.geom_n;
+    if (q.mani > 0 && manifold_dim_h(q.mani) != q.D) {  // products_maxfd: D is the batch's largest dimension -- its manifold's
+      out[i] = nbp_product_plan_rec{};
+      out[i].status = NBP_ERR_ARG;
+      out[i].row = -1;
+      out[i].N = q.N; out[i].n = q.n; out[i].F = q.F; out[i].D = q.D; out[i].mani = q.mani; out[i].geom_n = q.geom_n;
+      continue;
+    }
+    out[i] = product_plan_rec(&c, env, q.n, q.F * 4 + q.D, q.mani, product_plan(&c, env, q.n, q.F * 4 + q.D, q.mani));
+  }
+  return NBP_OK;
+}
+nbp_status nbp_plan_fits(const nbp_fit_plan_req *req, nbp_fit_plan_rec *out, int64_t n) {
+  if ((!req || !out) && n > 0) return fail(NBP_ERR_ARG, "null argument");
+  nbp_ctx c;
+  for (int64_t i = 0; i < n; i++) {
+    const nbp_fit_plan_req &q = req[i];
+    if (c.N != q.N) {
+      c = nbp_ctx();
+      NBPCHK(plan_ctx(c, q.N));
+    }
+    if (q.fits < 0 || q.coords < 0 || q.products < 0 || q.kdF < 0 || q.geom_blocks < 0 || (q.fits == 0 && q.products == 0))
+      return fail(NBP_ERR_ARG, "plan query: request " + std::to_string(i) + ": out of range");
+    nbp_launch_env env;
+    env.geom_blocks = q.geom_blocks;
+    env.geom_n = q.geom_blocks ? std::max(q.products, 1) : 0;  // (a round sets both; the fit plan reads geom_n as a flag)
+    const bool prep = q.products > 0;
+    out[i] = fit_plan_rec(&c, env, q.fits, q.coords, q.products, q.kdF, prep, fit_plan(&c, env, q.fits, q.coords, q.products, q.kdF));
+  }
+  return NBP_OK;
+}
+nbp_status nbp_plan_proposals(const nbp_proposal_plan_req *req, nbp_proposal_plan_rec *out, int64_t n) {
+  if ((!req || !out) && n > 0) return fail(NBP_ERR_ARG, "null argument");
+  nbp_ctx c;
+  for (int64_t i = 0; i < n; i++) {
+    const nbp_proposal_plan_req &q = req[i];
+    if (c.N != q.N) {
+      c = nbp_ctx();
+      NBPCHK(plan_ctx(c, q.N));
+    }
+    if (q.n < 1 || q.manifold < 0 || q.manifold > NBP_SE2) return fail(NBP_ERR_ARG, "plan query: request " + std::to_string(i) + ": out of range");
+    const int M = q.manifold;  // (the classes of proposals_uniform_class; Euclid(1) has none)
+    const int cls = M == NBP_EUCLID2 ? NBP_CLS_LIN2 : (M == NBP_EUCLID3 ? NBP_CLS_LIN3 : (M == NBP_CIRCULAR ? NBP_CLS_CIRC : (M == NBP_SE2 ? NBP_CLS_SE2 : 0)));
+    const nbp_proposal_plan p = proposal_plan(&c, q.n, cls | ((cls && q.simple) ? NBP_CLS_SIMPLE : 0));
+    nbp_proposal_plan_rec r{};
+    r.status = NBP_OK;
+    r.geometry = p.geometry; r.blocks = p.blocks; r.threads = p.threads;
+    r.N = q.N; r.n = q.n; r.manifold = q.manifold; r.simple = q.simple;
+    r.lds = (int64_t)p.lds;
+    snprintf(r.kernel, sizeof(r.kernel), "%s", p.name);
+    out[i] = r;
+  }
+  return NBP_OK;
+}
+nbp_status nbp_last_plans(nbp_ctx *c, nbp_product_plan_rec *product, nbp_fit_plan_rec *prep, nbp_fit_plan_rec *fits) {
+  if (!c) return fail(NBP_ERR_ARG, "ctx is null");
+  if (product) *product = c->last_product;
+  if (prep) *prep = c->last_prep;
+  if (fits) *fits = c->last_fit;
+  return NBP_OK;
+}
+
 nbp_status nbp_diag_read(nbp_ctx *c, nbp_diag *out, int32_t reset) {
   if (!c || !out) return fail(NBP_ERR_ARG, "null argument");
   nbp_counters h;

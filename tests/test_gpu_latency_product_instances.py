@@ -2,7 +2,10 @@
 whose multi-density products share one manifold, have only full inputs and keep their node statistics in LDS runs a
 single-manifold instance (nbp_product_kernel_{y32,l8}_{e1,e2,e3,ci,se}); partial, mixed and big launches run the generic
 kernels.  Both run the same product_body, so the points and the labels must be the oracle's and the generic kernel's, bit for
-bit.  The generic leg runs in a child process with NBP_NO_UNIFORM_LATENCY_PRODUCTS set (the library reads it once)."""
+bit.  The generic leg runs in a child process with NBP_NO_UNIFORM_LATENCY_PRODUCTS set (the library reads it once).
+
+Which kernel a launch ran is read from the plan it recorded (HipBackend.last_plans) and asserted for both legs: a case that a
+moved threshold sends to another kernel fails instead of passing on it."""
 import os
 import subprocess
 import sys
@@ -36,8 +39,9 @@ def cases():
     return out
 
 
-def run(make, N, specs, keep=None):
-    """-> ({product: points}, {product: labels}) of the products in `keep` (all by default)"""
+def run(make, N, specs, keep=None, plans=None):
+    """-> ({product: points}, {product: labels}) of the products in `keep` (all by default); `plans` (a dict) receives what the
+    launches of the batch recorded (HipBackend.last_plans)"""
     manis = sorted({m for m, _, _ in specs})
     base = {m: k * (NSRC + 1) for k, m in enumerate(manis)}  # NSRC sources of each manifold + one slot of old points
     out0 = len(manis) * (NSRC + 1)
@@ -54,11 +58,27 @@ def run(make, N, specs, keep=None):
                  for i, (m, F, parts) in enumerate(specs)]
         idx = list(range(len(specs))) if keep is None else keep
         be.run_products([descs[i] for i in idx])  # each product depends on its own descriptor only
+        if plans is not None:
+            plans.update(be.last_plans())
         pts = {i: be.slot_read(out0 + i, specs[i][0])[0] for i in idx}
         labs = {i: np.array(be.side_read(i * N * Fmax, N * specs[i][1])) for i in idx}
         return pts, labs
     finally:
         be.close()
+
+
+GENERIC_PLAN = ("HL", "row_mani", "w1", "big", "n", "G")  # what the generic leg hands back of its recorded plans
+
+
+def expected_plan(key, N, specs):
+    """what the docstring says the launch of a case runs: (helper lanes, kernel of the single-manifold leg, `_w1` of the generic leg)"""
+    n = len(specs)
+    HL = 32 if n < 16 else 8
+    geom = "y32" if HL == 32 else "l8"
+    uniform = key.split("_")[0] in MANIS
+    G = -(-(-(-N // (64 // HL))) // 4)  # workgroups of four waves per product
+    w1 = n * G <= 256  # at most one workgroup per CU: the generic kernels take their `_w1` form
+    return HL, f"nbp_product_kernel_{geom}_{key.split('_')[0]}" if uniform else f"nbp_product_kernel_{geom}" + ("_w1" if w1 else ""), w1
 
 
 def hip(N, n_slots, side_ints):
@@ -69,7 +89,9 @@ def _generic_leg(path):
     """(child process, NBP_NO_UNIFORM_LATENCY_PRODUCTS set) every case on the generic kernels -> one .npz"""
     arrs = {}
     for key, (N, specs) in cases().items():
-        pts, labs = run(hip, N, specs)
+        ran = {}
+        pts, labs = run(hip, N, specs, plans=ran)
+        arrs[f"{key}/plan"] = np.array([ran["product"][k] for k in GENERIC_PLAN])
         for i in pts:
             arrs[f"{key}/p{i}"] = pts[i]
             arrs[f"{key}/l{i}"] = labs[i]
@@ -91,7 +113,16 @@ def generic(tmp_path_factory):
 @pytest.mark.parametrize("key", list(cases()))
 def test_latency_products_equal_oracle_and_generic_kernel(key, generic, oracle_backend):
     N, specs = cases()[key]
-    pts, labs = run(hip, N, specs)
+    ran = {}
+    pts, labs = run(hip, N, specs, plans=ran)
+    HL, kernel, w1 = expected_plan(key, N, specs)
+    plan, gplan = ran["product"], dict(zip(GENERIC_PLAN, generic[f"{key}/plan"]))
+    assert (plan["status"], plan["HL"], plan["kernel"], plan["big"], plan["n"]) == (0, HL, kernel, 0, len(specs)), plan
+    assert (gplan["HL"], gplan["row_mani"], gplan["w1"], gplan["big"], gplan["n"]) == (HL, 0, int(w1), 0, len(specs)), gplan
+    if key.endswith("_N200_n36_F2"):   # (SHAPES: at most 256 workgroups, the generic kernels in their `_w1` form ...
+        assert gplan["w1"] == 1 and gplan["n"] * gplan["G"] == 252
+    if key.endswith("_N300_n60_F3"):   #  ... and more)
+        assert gplan["w1"] == 0 and gplan["n"] * gplan["G"] == 600
     keep = sorted({0, len(specs) // 2, len(specs) - 1} | {i for i in range(len(specs)) if specs[i][2] is not None or specs[i][0] != specs[0][0]})[:6]
     opts, olabs = run(lambda n, s, si: oracle_backend(n, s, si), N, specs, keep=keep)
     for i in range(len(specs)):

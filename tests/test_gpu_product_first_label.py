@@ -13,14 +13,18 @@ for every kernel that runs `product_body`:
     `_xs` single-manifold instances for full inputs, the generic t2 kernel for partial ones), the same 500 with
     NBP_NO_XS_PRODUCTS (the single-manifold instances that read the node sums of the KD workspace), and 200 products at N = 512,
     where three and four densities of a manifold of dimension >= 2 do not fit the LDS (`big`: node statistics in global
-    memory, generic l8 kernel; two densities never exceed the LDS at N <= 512 and run the wide t2 instances there);
+    memory, generic l8 kernel; two densities never exceed the LDS at N <= 512 and run the wide t2 instances there; three partial
+    densities on Euclid(2) fit as well, in the generic t2 kernel);
   * the fused update kernel under NBP_FUSED_MIN, in both of its forms (two helper rows per update, and one lane per particle
     under NBP_FUSED_P1_MIN).  It takes Euclid(2) rounds without label output only (`fused_plan`), so points and bandwidths
     are what is compared there.
 
 The harness is the one of test_gpu_latency_product_instances.py (`run`: sources, descriptors, label areas, a fixed subset of
 the batch on the oracle) and of test_gpu_fused_update.py (`_round`); `niter` goes into their descriptors on the way to the
-backend.  Exact equality throughout, no case skipped, the set of cases fixed."""
+backend.  Exact equality throughout, no case skipped, the set of cases fixed.
+
+Every case asserts the plan its launch recorded (HipBackend.last_plans) against what its geometry stands for -- `_assert_geometry` --
+so that a moved threshold fails the case instead of moving it to another kernel."""
 import numpy as np
 import pytest
 
@@ -68,6 +72,32 @@ def _specs(name, F, n, partial):
     return [(man, F, _masks(D, F, i) if partial else None) for i in range(n)]
 
 
+def _assert_geometry(geom, name, partial, F, plan):
+    """the recorded plan of the launch is the one GEOMS[geom] is there for (the docstring above)"""
+    N, n, _ = GEOMS[geom]
+    D = abi.MANIFOLD_DIM[MANIS[name]]
+    assert (plan["status"], plan["N"], plan["n"], plan["F"], plan["geom_n"]) == (0, N, n, F, 0), plan
+    generic = plan["row_mani"] == 0
+    assert generic == (partial or bool(plan["big"])) and plan["mani"] == (0 if partial else MANIS[name]), plan  # partial and big: generic kernels
+    if geom in ("y32", "l8"):
+        assert plan["HL"] == (32 if geom == "y32" else 8) and not plan["big"] and not plan["xs"], plan
+        assert plan["kernel"].startswith(f"nbp_product_kernel_{geom}" + ("" if partial else f"_{name}")), plan
+    elif geom in ("t2", "t2_noxs"):
+        assert plan["HL"] == 2 and not plan["big"], plan
+        assert plan["xs"] == (geom == "t2" and not partial), plan  # an `_xs` row for full inputs, the KD workspace's node sums otherwise
+        assert plan["kernel"] == "nbp_product_kernel_t2" + ("" if partial else f"_{name}" + ("_xs" if geom == "t2" else "")), plan
+    else:  # n512: three and four densities of a manifold of dimension >= 2 do not fit the LDS ...
+        # ... but for three PARTIAL densities on Euclid(2): the generic t2 kernel runs them in two workgroups of eight waves, whose
+        # label table and chunk sums are half those of the one wide workgroup of the full batch, and the statistics fit (147 KB)
+        assert plan["big"] == int(F >= 3 and D >= 2 and not (partial and name == "e2" and F == 3)), plan
+        if plan["big"]:
+            assert plan["HL"] == 8 and plan["kernel"] == "nbp_product_kernel_l8" and plan["gstats"] > 0, plan
+        else:
+            assert plan["HL"] == 2, plan
+            if not partial and name in ("e1", "e2", "e3"):
+                assert (plan["wpb"], plan["G"]) == (16, 1), plan  # the wide t2 instances: one workgroup of sixteen waves
+
+
 def _cases():
     out = []
     for geom in GEOMS:
@@ -88,7 +118,9 @@ def test_points_and_labels_equal_the_oracle(geom, name, inputs, F, niter, oracle
         monkeypatch.setenv(k, v)  # (read when the context is created)
     specs = _specs(name, F, n, inputs == "partial")
     keep = sorted({0, 1, 2, n // 2, n - 1} & set(range(n)))  # every mask pattern, the middle and the end of the batch
-    pts, labs = run(lambda *a: _WithNiter(hip(*a), niter), N, specs)
+    ran = {}
+    pts, labs = run(lambda *a: _WithNiter(hip(*a), niter), N, specs, plans=ran)
+    _assert_geometry(geom, name, inputs == "partial", F, ran["product"])
     opts, olabs = run(lambda *a: _WithNiter(oracle_backend(*a), niter), N, specs, keep=keep)
     for i in range(n):
         assert np.isfinite(pts[i]).all(), f"product {i}"
