@@ -438,6 +438,62 @@ typedef struct nbp_overlap_opts {
 nbp_status nbp_run_overlap_search(nbp_ctx *ctx, const int32_t *slots, const int32_t *manifolds, const int32_t *masks, int32_t n,
                                   const nbp_overlap_opts *opts /* nullable */, int32_t *idx_out /* n x topk */,
                                   double *logc_out /* n x topk */, int32_t *found_out /* n */, int32_t *evaluated_out /* n */);
+/* ---- credible regions ("Credible regions"; DEFINED by this library, unpinned: DESIGN.md 8) ---------------------------
+ * How much of a resident belief lies where: the levels of its highest-density regions (HDR), the credibility of reference points and
+ * the quantiles of its coordinates.  The belief has c points x_i (the count the slot holds), bandwidth h and manifold M; K is a
+ * non-empty coordinate mask as in nbp_run_evaluate_marginal (bit d = coordinate d).  Only the bandwidth entries in K are read.
+ *   l_i = M_i + log(sum_{j != i} exp(e_ij - M_i)) - log((c - 1) prod_{d in K} sqrt(2 pi) h_d), e_ij the exponent of
+ *     nbp_run_evaluate_marginal on K, M_i = max_{j != i} e_ij: the LEAVE-ONE-OUT log density of each own point, j ascending in one
+ *     lane, two passes.  Exclusion is by index: a duplicate of x_i stays in.  Finite where every term underflows.
+ *   order = the particle indices by ascending (l_i, i): ties break by index.
+ *   log_level[a], for the mass m_a in (0, 1]: k = ceil(m_a (double)c) clamped to 1 .. c; the k-th largest l_i, l at position c - k of
+ *     the ascending order.  The region is {x : log p_K(x) >= log_level}; its contour on a marginal grid of the same coordinates lies at
+ *     exp(log_level).  n_inside[a] = #{i : l_i >= log_level[a]} (>= k, more only through ties).  log_min / log_max: the least and
+ *     the greatest l_i.
+ *   a query q: logdens = the log density of the whole KDE at q on K (all c points, normalised by c: l_p(q) of nbp_run_kld with the
+ *     mask); n_above = #{i : l_i > logdens}; mass = (double)n_above / (double)c, the mass of the smallest region that still contains
+ *     q (0 at the densest place, 1 in the far tail); q lies inside the m_a-region iff logdens >= log_level[a].  Entries of a query
+ *     outside K are not read.
+ *   quant[d][p], for every coordinate d of the manifold whatever K and the probability prob[p] in [0, 1]: v_i = x_id (a circular
+ *     coordinate: x_id - mean[d] wrapped to [-pi, pi)), sorted; t = (double)(c - 1) prob, lo = floor(t), hi = min(lo + 1, c - 1),
+ *     Q = v_lo + (t - lo) (v_hi - v_lo) (Julia's and numpy's default, type 7), one rounding per operation; a circular coordinate
+ *     delivers mean[d] + Q wrapped.  mean = the mean nbp_run_ppe delivers, bit for bit.  The bandwidth plays no part.
+ *   c == 1: levels, l_i, log_min / log_max and masses are NaN, n_inside 0, n_above -1, order = {0}; a query's logdens stands; every
+ *     quantile is the point.  A bandwidth entry in K that is not positive and finite: levels, l_i and query results are NaN, n_inside
+ *     0, n_above -1, order -1; the quantiles are delivered all the same.
+ * Unused entries of a record are zero.  Refused with NBP_ERR_RANGE, naming the belief, before anything is launched: a slot out of
+ * range, an empty mask or one that leaves the manifold, n_mass or n_prob outside 0 .. NBP_CRED_MAX, a mass outside (0, 1] or a
+ * probability outside [0, 1] (non-finite ones too), a non-finite query entry, a q_first that does not ascend from 0.  An unknown
+ * manifold and null pointers (with n > 0): NBP_ERR_ARG; n <= 0: NBP_OK.  q_first == NULL: no queries (queries and qrec_out are not
+ * read).  One workgroup per belief in ONE launch; queued on the library stream; one copy each way; synchronises. */
+#define NBP_CRED_MAX 8
+typedef struct nbp_credible_opts {
+  int32_t n_mass, n_prob;
+  double mass[NBP_CRED_MAX], prob[NBP_CRED_MAX];
+} nbp_credible_opts;
+typedef struct nbp_credible_rec {
+  double log_level[NBP_CRED_MAX];
+  double quant[NBP_MAXD][NBP_CRED_MAX];
+  double mean[NBP_MAXD];
+  double log_min, log_max;
+  int32_t n_inside[NBP_CRED_MAX];
+  int32_t count, pad;
+} nbp_credible_rec;
+typedef struct nbp_credibility_rec {
+  double logdens, mass;
+  int32_t n_above, pad;
+} nbp_credibility_rec;
+nbp_status nbp_run_credible(nbp_ctx *ctx, const int32_t *slots, const int32_t *manifolds, const int32_t *masks, int32_t n,
+                            const nbp_credible_opts *opts, const int32_t *q_first /* n+1, nullable: no queries */,
+                            const double *queries /* q_first[n] x NBP_MAXD */, nbp_credible_rec *rec_out /* n */,
+                            double *logdens_out /* n x N, nullable; NaN beyond the count */,
+                            int32_t *order_out /* n x N, nullable; -1 beyond the count */,
+                            nbp_credibility_rec *qrec_out /* q_first[n] */);
+/* host-buffer form, like nbp_kde_meancov: stages through slot 0 (N = the context's particle count in the output shapes) */
+nbp_status nbp_kde_credible(nbp_ctx *ctx, int32_t manifold, const double *pts_NxP, int32_t n_pts, const double *bw_D, int32_t mask,
+                            const nbp_credible_opts *opts, const double *queries /* nq x NBP_MAXD */, int32_t nq,
+                            nbp_credible_rec *rec_out, double *logdens_out /* N, nullable */, int32_t *order_out /* N, nullable */,
+                            nbp_credibility_rec *qrec_out /* nq */);
 /* ---- modes of a belief ("Modes of a belief"; DEFINED by this library, unpinned: DESIGN.md 8) -----------------------
  * Mean-shift over the belief's own KDE at the bandwidth g = bw_scale * bw.  Every point x_i of the belief is a start y <- x_i;
  * one iteration is  w_j = exp(e(y, x_j)) (the exponent of nbp_run_evaluate with g in place of bw),  S = sum_j w_j,

@@ -493,6 +493,66 @@ class HipBackend:
                                                     found.ctypes.data_as(ip), evaluated.ctypes.data_as(ip)))
         return idx, logc, found, evaluated
 
+    # ---- credible regions (nbp_run_credible; credible.py) ----------------------------------------------------------------------
+    CRED_REC = np.dtype([("log_level", np.float64, (abi.CRED_MAX,)), ("quant", np.float64, (abi.MAXD, abi.CRED_MAX)),
+                         ("mean", np.float64, (abi.MAXD,)), ("log_min", np.float64), ("log_max", np.float64),
+                         ("n_inside", np.int32, (abi.CRED_MAX,)), ("count", np.int32), ("pad", np.int32)])
+    CREDIBILITY_REC = np.dtype([("logdens", np.float64), ("mass", np.float64), ("n_above", np.int32), ("pad", np.int32)])
+
+    @staticmethod
+    def _credible_opts(mass, probs):
+        mass, probs = np.asarray(mass, dtype=np.float64).reshape(-1), np.asarray(probs, dtype=np.float64).reshape(-1)
+        o = abi.CredibleOpts(n_mass=mass.size, n_prob=probs.size)  # (more than CRED_MAX entries: the library refuses the count)
+        o.mass[:min(mass.size, abi.CRED_MAX)] = mass[:abi.CRED_MAX].tolist()
+        o.prob[:min(probs.size, abi.CRED_MAX)] = probs[:abi.CRED_MAX].tolist()
+        return o
+
+    def run_credible(self, slots, manifolds, masks, mass=(), probs=(), queries=None, logdens=True, order=True):
+        """credible regions of resident beliefs (nbp_run_credible: one launch); masks = one coordinate bit mask per belief (bit d =
+        coordinate d); mass / probs: up to 8 each; queries: None, or one array (q_i x D or x 3, tangent coordinates; may be empty)
+        per belief -> (recs[n], logdens[n, N] or None, order[n, N] or None, qrecs[Q] or None, first[n + 1] or None): recs / qrecs
+        structured arrays with the fields of nbp_credible_rec / nbp_credibility_rec, the queries of belief i in
+        qrecs[first[i]:first[i + 1]]; rows of logdens / order beyond a belief's count hold NaN / -1"""
+        assert self.CRED_REC.itemsize == C.sizeof(abi.CredibleRec) and self.CREDIBILITY_REC.itemsize == C.sizeof(abi.CredibilityRec)
+        (s, sp), (m, mp), (k, kp) = _i32(slots), _i32(manifolds), _i32(masks)
+        n = s.size
+        if m.size != n or k.size != n:
+            raise ValueError("run_credible: three columns of one length")
+        dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+        recs = np.zeros(n, dtype=self.CRED_REC)
+        ld = np.zeros((n, self.N)) if logdens else None
+        od = np.zeros((n, self.N), dtype=np.int32) if order else None
+        Q = first = qrecs = None
+        if queries is not None:
+            Q, first = _pack_queries(m, queries)
+            qrecs = np.zeros(int(first[-1]), dtype=self.CREDIBILITY_REC)
+        opts = self._credible_opts(mass, probs)
+        self._check(self.lib.nbp_run_credible(
+            self._ctx, sp, mp, kp, n, C.byref(opts), first.ctypes.data_as(ip) if first is not None else None,
+            Q.ctypes.data_as(dp) if Q is not None else None, recs.ctypes.data_as(C.POINTER(abi.CredibleRec)),
+            ld.ctypes.data_as(dp) if logdens else None, od.ctypes.data_as(ip) if order else None,
+            qrecs.ctypes.data_as(C.POINTER(abi.CredibilityRec)) if qrecs is not None else None))
+        return recs, ld, od, qrecs, first
+
+    def kde_credible(self, manifold, pts, bw, mask, mass=(), probs=(), queries=None, logdens=True, order=True):
+        """credible regions of a belief held on the host (nbp_kde_credible; clobbers slot 0); queries: None or q x D (or x 3) tangent
+        coordinates -> (rec, logdens[c] or None, order[c] or None, qrecs[q] or None)"""
+        dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+        pts = np.ascontiguousarray(pts, dtype=np.float64).reshape(-1, abi.MANIFOLD_P[manifold])
+        bw = np.ascontiguousarray(bw, dtype=np.float64)
+        c = pts.shape[0]
+        rec = np.zeros(1, dtype=self.CRED_REC)
+        ld = np.zeros(self.N) if logdens else None
+        od = np.zeros(self.N, dtype=np.int32) if order else None
+        Q, first = _pack_queries([manifold], [queries if queries is not None else np.zeros((0, abi.MAXD))])
+        qrecs = np.zeros(int(first[1]), dtype=self.CREDIBILITY_REC)
+        opts = self._credible_opts(mass, probs)
+        self._check(self.lib.nbp_kde_credible(
+            self._ctx, manifold, pts.ctypes.data_as(dp), c, bw.ctypes.data_as(dp), int(mask), C.byref(opts), Q.ctypes.data_as(dp),
+            int(first[1]), rec.ctypes.data_as(C.POINTER(abi.CredibleRec)), ld.ctypes.data_as(dp) if logdens else None,
+            od.ctypes.data_as(ip) if order else None, qrecs.ctypes.data_as(C.POINTER(abi.CredibilityRec))))
+        return rec[0], (ld[:c] if logdens else None), (od[:c] if order else None), (qrecs if queries is not None else None)
+
     # ---- heatmap densities (nbp_heatmap_*; heatmap.py) -------------------------------------------------------------------------
     def heatmap_create(self, data, x, y, bw_factor=0.7):
         """nbp_heatmap_create: the field data[i, j] at (x[i], y[j]) -> a handle (heatmap_destroy it); the library checks the grid"""

@@ -158,6 +158,19 @@ class Belief:
         from .modes import belief_modes
         return belief_modes(self.manifold, self.pts, self.bw, bwScale, tol, maxIter, merge, backend)
 
+    def credible(self, mass=(0.5, 0.9, 0.95), probs=(0.025, 0.25, 0.5, 0.75, 0.975), dims=None, backend=None):
+        """belief.credible(): the levels of the belief's highest-density regions at `mass` and the quantiles of its coordinates at
+        `probs` (credible.py) -> CredibleRegion; dims: the 1-BASED coordinates the density is taken on (None: all); computed by
+        libnbp (nbp_kde_credible, through slot 0; backend None: HipBackend)"""
+        from .credible import belief_credible
+        return belief_credible(self.manifold, self.pts, self.bw, mass, probs, dims, backend)
+
+    def credibility(self, pts, dims=None, backend=None):
+        """belief.credibility(pts): the mass of the smallest highest-density region that still contains each reference point
+        (tangent coordinates: one point, or q x D) -> Credibility(mass, logdens, n_above); `dims` and `backend` as in `credible`"""
+        from .credible import belief_credibility
+        return belief_credibility(self.manifold, self.pts, self.bw, pts, dims, backend)
+
 
 def getBelief(fg, label):
     """getBelief(dfg, label): the variable's current belief, callable at query points"""

@@ -28,6 +28,7 @@
 #include "nbp_modes.h"
 #include "nbp_likelihood.h"
 #include "nbp_overlap.h"
+#include "nbp_credible.h"
 
 static thread_local std::string g_err;
 static nbp_status fail(nbp_status code, const std::string &msg) {
@@ -2123,6 +2124,87 @@ nbp_status nbp_run_overlap_search(nbp_ctx *c, const int32_t *slots, const int32_
   memcpy(found_out, bi + V * K, 4 * V);
   memcpy(evaluated_out, bi + V * K + V, 4 * V);
   return NBP_OK;
+}
+
+// ---- credible regions (nbp_credible.h) -------------------------------------------------------------------------------------------
+// the options of a credible-region batch; refused before anything is launched, naming the entry
+static nbp_status credible_opts_check(const nbp_credible_opts *o) {
+  const std::string lim = std::to_string(NBP_CRED_MAX);
+  if (o->n_mass < 0 || o->n_mass > NBP_CRED_MAX) return fail(NBP_ERR_RANGE, "credible: n_mass outside 0 .. " + lim);
+  if (o->n_prob < 0 || o->n_prob > NBP_CRED_MAX) return fail(NBP_ERR_RANGE, "credible: n_prob outside 0 .. " + lim);
+  for (int a = 0; a < o->n_mass; a++)  // (a NaN fails both comparisons)
+    if (!(o->mass[a] > 0.0 && o->mass[a] <= 1.0)) return fail(NBP_ERR_RANGE, "credible: mass " + std::to_string(a) + " outside (0, 1]");
+  for (int p = 0; p < o->n_prob; p++)
+    if (!(o->prob[p] >= 0.0 && o->prob[p] <= 1.0)) return fail(NBP_ERR_RANGE, "credible: probability " + std::to_string(p) + " outside [0, 1]");
+  return NBP_OK;
+}
+
+// HDR levels, credibility of reference points and coordinate quantiles of beliefs resident in slots: one workgroup per belief
+// (nbp_credible.h).  Columns, options and queries go up in one staging copy; records, query records and the optional per-particle
+// outputs come back in one copy.
+nbp_status nbp_run_credible(nbp_ctx *c, const int32_t *slots, const int32_t *manifolds, const int32_t *masks, int32_t n,
+                            const nbp_credible_opts *opts, const int32_t *q_first, const double *queries, nbp_credible_rec *rec_out,
+                            double *logdens_out, int32_t *order_out, nbp_credibility_rec *qrec_out) {
+  if (!c || ((!slots || !manifolds || !masks || !opts || !rec_out) && n > 0)) return fail(NBP_ERR_ARG, "null argument");
+  if (n <= 0) return NBP_OK;
+  NBPCHK(credible_opts_check(opts));
+  if (q_first && q_first[0] != 0) return fail(NBP_ERR_RANGE, "credible: belief 0: q_first must ascend from 0");
+  NBPCHK(batch_check(c, "credible", {slots}, manifolds, n, [&](int i) {
+    if (masks[i] == 0) return refusal{NBP_ERR_RANGE, "empty mask"};
+    if (masks[i] < 0 || (masks[i] >> manifold_dim_h(manifolds[i])) != 0) return refusal{NBP_ERR_RANGE, "coordinate outside the manifold"};
+    if (!q_first) return refusal{NBP_OK, nullptr};
+    if (q_first[i + 1] < q_first[i]) return refusal{NBP_ERR_RANGE, "q_first must ascend from 0"};
+    if (q_first[i + 1] > q_first[i] && (!queries || !qrec_out)) return refusal{NBP_ERR_ARG, "null argument"};
+    for (int32_t q = q_first[i]; q < q_first[i + 1]; q++)
+      for (int d = 0; d < NBP_MAXD; d++)
+        if ((masks[i] >> d & 1) && !std::isfinite(queries[(size_t)q * NBP_MAXD + d]))
+          return refusal{NBP_ERR_RANGE, "a query entry is not finite"};
+    return refusal{NBP_OK, nullptr};
+  }));
+  static_assert(sizeof(nbp_credible_rec) % sizeof(double) == 0 && sizeof(nbp_credibility_rec) % sizeof(double) == 0,
+                "the credible records fill whole doubles of the query scratch");
+  static_assert(sizeof(nbp_credible_opts) % sizeof(double) == 0, "nbp_credible_opts fills whole doubles of the staging copy");
+  const size_t V = (size_t)n, Q = q_first ? (size_t)q_first[n] : 0, N = (size_t)c->N;
+  // the query scratch: rec[n] | qrec[Q] | logdens[n N] | order[n N] (int32); the last two only where the caller asks for them
+  const size_t rec_d = V * (sizeof(nbp_credible_rec) / sizeof(double)), qrec_d = Q * (sizeof(nbp_credibility_rec) / sizeof(double));
+  const size_t ld_d = logdens_out ? V * N : 0, ord_d = order_out ? (V * N + 1) / 2 : 0, all_d = rec_d + qrec_d + ld_d + ord_d;
+  const int32_t *d[6];
+  NBPCHK(stage_columns(c, {{slots, 4 * V}, {manifolds, 4 * V}, {masks, 4 * V}, {opts, sizeof(nbp_credible_opts)},
+                           {q_first, q_first ? 4 * (V + 1) : 0}, {queries, sizeof(double) * NBP_MAXD * Q}}, d, all_d));
+  nbp_credible_rec *drec = (nbp_credible_rec *)c->query;
+  nbp_credibility_rec *dqrec = (nbp_credibility_rec *)(c->query + rec_d);
+  double *dld = c->query + rec_d + qrec_d;
+  int32_t *dord = (int32_t *)(dld + ld_d);
+  NBPCHK(launch_checked(c, nbp_credible_kernel, V, c->Npad, nbp_credible_lds_bytes(c->N), d[0], d[1], d[2], (const nbp_credible_opts *)d[3],
+                        q_first ? d[4] : (const int32_t *)nullptr, (const double *)d[5], c->arena, c->N, c->S, drec,
+                        logdens_out ? dld : (double *)nullptr, order_out ? dord : (int32_t *)nullptr, dqrec));
+  std::vector<double> back(all_d);
+  NBPCHK(query_fetch(c, back.data(), c->query, sizeof(double) * all_d));
+  memcpy(rec_out, back.data(), sizeof(double) * rec_d);
+  if (Q) memcpy(qrec_out, back.data() + rec_d, sizeof(double) * qrec_d);
+  if (logdens_out) memcpy(logdens_out, back.data() + rec_d + qrec_d, sizeof(double) * V * N);
+  if (order_out) memcpy(order_out, back.data() + rec_d + qrec_d + ld_d, 4 * V * N);
+  return NBP_OK;
+}
+
+// host-buffer form: stages through slot 0 (which it clobbers), like nbp_kde_meancov; everything is checked before slot 0 is touched
+nbp_status nbp_kde_credible(nbp_ctx *c, int32_t manifold, const double *pts, int32_t n_pts, const double *bw, int32_t mask,
+                            const nbp_credible_opts *opts, const double *queries, int32_t nq, nbp_credible_rec *rec_out,
+                            double *logdens_out, int32_t *order_out, nbp_credibility_rec *qrec_out) {
+  if (!c || !pts || !bw || !opts || !rec_out || ((!queries || !qrec_out) && nq > 0)) return fail(NBP_ERR_ARG, "null argument");
+  NBPCHK(kde_check(c, "credible", manifold, {{pts, n_pts, bw}}));
+  if (nq < 0) return fail(NBP_ERR_ARG, "credible: nq < 0");
+  NBPCHK(credible_opts_check(opts));
+  if (mask == 0) return fail(NBP_ERR_RANGE, "credible: belief 0: empty mask");
+  if (mask < 0 || (mask >> manifold_dim_h(manifold)) != 0) return fail(NBP_ERR_RANGE, "credible: belief 0: coordinate outside the manifold");
+  for (int32_t q = 0; q < nq; q++)
+    for (int d = 0; d < NBP_MAXD; d++)
+      if ((mask >> d & 1) && !std::isfinite(queries[(size_t)q * NBP_MAXD + d]))
+        return fail(NBP_ERR_RANGE, "credible: belief 0: a query entry is not finite");
+  // (a bandwidth entry outside the mask is not read by the kernel, but the slot write wants a full vector: the caller's is passed on)
+  NBPCHK(kde_write(c, manifold, {{pts, n_pts, bw}}));
+  const int32_t slot = 0, q_first[2] = {0, nq};
+  return nbp_run_credible(c, &slot, &manifold, &mask, 1, opts, q_first, queries, rec_out, logdens_out, order_out, qrec_out);
 }
 
 // ---- modes of beliefs (nbp_modes.h) ----------------------------------------------------------------------------------------------

@@ -24,6 +24,7 @@
 #include "nbp_kde.h"
 
 #define NBP_TU_STATS 8192  // the belief-statistics kernels (nbp_k_stats.hip)
+#define NBP_TU_CREDIBLE 128  // the credible-region kernel (nbp_k_credible.hip, nbp_credible.h): defined here, it shares stats_deviation
 
 // one record per belief; entries beyond the manifold's dimension are zero
 struct nbp_meancov_rec {
@@ -39,13 +40,16 @@ struct nbp_kld_rec {
 #define NBP_KLD_ARGS                                                                                                   \
   const int32_t *slots_a, const int32_t *slots_b, const int32_t *manifolds, const double *arena, int N, int64_t S,     \
       nbp_kld_rec *out
-#if NBP_TU & NBP_TU_STATS
+#if NBP_TU & (NBP_TU_STATS | NBP_TU_CREDIBLE)
 // the deviation of a coordinate from the mean: the world frame, circular coordinates wrapped.  (Pinning SE(2) to Manifolds.jl's
 // coordinates at the mean would change this function alone.)
 __device__ __forceinline__ double stats_deviation(double x, double mu, bool circ) {
   const double d = x - mu;
   return circ ? wrap_pi(d) : d;
 }
+#endif
+
+#if NBP_TU & NBP_TU_STATS
 
 // One workgroup per belief, 64 ceil(N / 64) lanes (the shape of nbp_ppe_kernel: the mean's bits depend on it).  LDS: X[3][N] | red.
 // Lane i owns point i; six block_sums at most.  The manifold is a runtime value.  No atomics.

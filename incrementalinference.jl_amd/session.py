@@ -302,18 +302,22 @@ class SolveSession:
                                            lambda p, **kw: jointmodes.factorModeLikelihood(self.fg, p.label, modes, maxModes, **kw))
         return jointmodes.joint_from_tables(modes, res, skipped, maxModes)
 
-    def _overlap_labels(self, labels, what):
-        """the labels of an overlap query, all of which must have a slot in the session's context: an overlap is computed where
-        the beliefs lie, and there is no host route"""
+    def _device_labels(self, labels, what, method, name):
+        """the labels of a query that has no host route: all of them must have a slot in the session's context, since the query
+        is computed where the beliefs lie"""
         if self._closed:
             raise RuntimeError("this SolveSession is closed")
         labels = list(self._labels if labels is None else labels)
-        if self._be is None or getattr(self._be, "run_overlap_search", None) is None:
-            raise ValueError(f"{what}: belief overlaps are computed by libnbp, and this session's backend has no such entry point")
+        if self._be is None or getattr(self._be, method, None) is None:
+            raise ValueError(f"{what}: {name} are computed by libnbp, and this session's backend has no such entry point")
         missing = [v for v in labels if v not in self._labels]
         if missing:
             raise ValueError(f"{what}: {missing} were never part of a solve of this session")
         return labels
+
+    def _overlap_labels(self, labels, what):
+        """the labels of an overlap query (`_device_labels`: there is no host route)"""
+        return self._device_labels(labels, what, "run_overlap_search", "belief overlaps")
 
     def findOverlaps(self, labels=None, dims=None, number=abi.OVERLAP_TOPK, minCoeff=abi.OVERLAP_MIN_COEFF, reach=abi.OVERLAP_REACH):
         """Which of the variables' current beliefs overlap (overlap.py) -> Overlaps, the loop-closure candidates in `.pairs()`.
@@ -343,6 +347,37 @@ class SolveSession:
         res = self._query_resident(labels, "run_overlap", lambda here, place: overlap.pair_columns(self.fg, pairs, dims, place),
                                    lambda res, i, v: res, None)
         return {p: overlap.overlap_from_rec(r) for p, r in zip(pairs, res[labels[0]])}
+
+    def credibleRegions(self, labels=None, mass=(0.5, 0.9, 0.95), probs=(0.025, 0.25, 0.5, 0.75, 0.975), dims=None):
+        """The credible regions of the variables' current beliefs (credible.py) -> {label: CredibleRegion}.  labels: default every
+        variable the last solve worked on; mass, probs, dims as in `credible.credibleRegionAll`.  Served by ONE `run_credible`
+        where the beliefs lie (`_query_resident`): no belief travels and `stats` does not move.  There is no host route."""
+        from . import credible
+        labels = self._device_labels(labels, "credibleRegions", "run_credible", "credible regions")
+        mass, probs = credible._options(mass, probs)
+        if not labels:
+            return {}
+        var = self.fg.getVariable
+        return self._query_resident(labels, "run_credible",
+                                    lambda here, place: (*credible.region_columns(self.fg, here, dims, place), mass, probs),
+                                    lambda res, i, v: credible.region_from_records(var(v).varType.manifold, mass, probs, res[0][i],
+                                                                                   res[1][i], res[2][i]), None)
+
+    def credibility(self, points, dims=None):
+        """The credibility of reference points under the variables' current beliefs (credible.py): points = {label: point or
+        points} -> {label: Credibility(mass, logdens, n_above)}; `credible.coverage` of the result is the calibration table.
+        Served by ONE `run_credible` where the beliefs lie (`_query_resident`)."""
+        from . import credible
+        labels = self._device_labels(list(points), "credibility", "run_credible", "credible regions")
+        if not labels:
+            return {}
+        var = self.fg.getVariable
+        packed = {v: credible.query_points(var(v).varType.manifold, dims, points[v]) for v in labels}
+        return self._query_resident(labels, "run_credible",
+                                    lambda here, place: (*credible.region_columns(self.fg, here, dims, place), (), (),
+                                                         [packed[v][0] for v in here], False, False),
+                                    lambda res, i, v: credible.credibility_from_records(res[3][res[4][i]:res[4][i + 1]], packed[v][1]),
+                                    None)
 
     # ---- one solve ---------------------------------------------------------------------------------------------------------
     def solve(self, seed=0, eliminationOrder=None, ordering="qr", return_timing=False):
