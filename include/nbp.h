@@ -541,6 +541,60 @@ nbp_status nbp_kde_modes(nbp_ctx *ctx, int32_t manifold, const double *pts_NxP, 
                          const nbp_modes_opts *opts /* nullable */, nbp_mode_rec *recs_out /* NBP_MODES_MAX */, int32_t *n_modes_out,
                          int32_t *labels_out /* n_pts, nullable */, int32_t *iters_out /* n_pts, nullable */,
                          int32_t *n_unconverged_out /* nullable */);
+/* ---- mixture summaries ("Mixture summaries"; DEFINED by this library, unpinned: DESIGN.md 8) -------------------------
+ * A resident belief as a Gaussian mixture of K <= NBP_MIX_MAX components (w_k, mu_k, Sigma_k): the form a belief can go back into a
+ * graph in (NBP_F_PRIOR with components) or leave the library in.  Tangent coordinates at the identity (SE(2): x, y, theta in the
+ * world frame); c the count the slot holds, D the dimension, delta(x, mu) = x - mu wrapped to [-pi, pi) on circular coordinates,
+ * H = diag(h_d^2) the belief's own bandwidth.  The belief's KDE is itself a mixture of c Gaussians N(x_i, H); it is reduced by
+ * hierarchical EM on the kernel centres, each kernel's width entering in expectation.
+ *   start   one label row per belief (labels[row[i]], int32, -1 .. NBP_MIX_MAX - 1): particle i starts in the component its label
+ *     names with r_ik = 1, a particle labelled -1 starts in none.  A component is live when a particle below the count carries its
+ *     label; mu_k starts at init_mean[i][k] (the modes of nbp_run_modes and their ranks are what the Python layer passes).
+ *   M-step  live components in ascending k: n_k = sum_i r_ik; a live component with n_k < 0.5 is dropped for good (weight 0, no
+ *     part in later steps, counted in n_dropped); w_k = n_k / sum_{l live} n_l;
+ *     mu_k <- wrap(mu_k + sum_i r_ik delta(x_i, mu_k) / n_k) (on a Euclidean coordinate the weighted mean in one step);
+ *     Sigma_k = sum_i r_ik delta_i delta_i^T / n_k + H, delta_i about the new mean.  Sigma_k >= H: never singular, no floor.
+ *   E-step  l_ik = log w_k + log N(delta(x_i, mu_k); 0, Sigma_k) - tr(Sigma_k^-1 H) / 2 (the Cholesky factor in closed form);
+ *     lse_i = logsumexp_k l_ik in two passes (the maximum, then the sum), k ascending in one lane; r_ik = exp(l_ik - lse_i);
+ *     J = (1 / c) sum_i lse_i, finite where every density underflows.  A proper EM: on Euclidean manifolds J never decreases.
+ *   stop    after the E-step of iteration t >= 2 when J_t - J_(t-1) <= tol (converged = 1), or after max_iter iterations.  tol = 0
+ *     runs max_iter iterations (converged = 0).
+ *   result  live components ranked by weight descending, ties by the lower starting index: weight, mean, cov (NBP_MAXD x NBP_MAXD,
+ *     row-major, zero beyond D, both triangles the same double), count = the particles whose greatest r is this component's (ties
+ *     to the lower starting index); n_comp, iters, converged, n_dropped, objective = J.  Entries from n_comp on are zero.
+ *     labels_out: each particle's component by its final rank, -1 beyond the count.
+ *   a bandwidth entry that is not positive and finite, or a row with no label >= 0 below the count: n_comp = 0, iters = 0, every
+ *     double of the record NaN, labels_out -1.  c = 1: one component, the point itself, Sigma = H.
+ * Sums over the particles: a butterfly inside each wave, then the waves in order (the additions of nbp_run_meancov).  A belief's
+ * result depends on the belief, its labels, its starting means and the options alone, not on the beliefs that share the launch.
+ * opts == NULL: the defaults below.  NBP_ERR_ARG: tol negative or not finite, max_iter < 1, a label outside -1 .. NBP_MIX_MAX - 1
+ * in a row an item names (all N entries of such a row are looked at; a row no item names is not read), a negative row, an unknown
+ * manifold, null pointers (with n > 0); NBP_ERR_RANGE: a slot out of range.  Refused before anything is launched.  n <= 0: NBP_OK.
+ * One workgroup per belief in ONE launch; queued on the library stream; one copy each way; synchronises. */
+#define NBP_MIX_MAX 8
+#define NBP_MIX_TOL 1e-8
+#define NBP_MIX_MAX_ITER 500
+typedef struct nbp_mixture_opts {
+  double tol;
+  int32_t max_iter, pad;
+} nbp_mixture_opts;
+typedef struct nbp_mixture_rec {
+  double weight[NBP_MIX_MAX];
+  double mean[NBP_MIX_MAX][NBP_MAXD];
+  double cov[NBP_MIX_MAX][NBP_MAXD * NBP_MAXD];
+  double objective;
+  int32_t count[NBP_MIX_MAX];
+  int32_t n_comp, iters, converged, n_dropped;
+} nbp_mixture_rec;
+nbp_status nbp_run_mixture(nbp_ctx *ctx, const int32_t *slots, const int32_t *manifolds, int32_t n,
+                           const int32_t *labels /* n_rows x N */, const int32_t *row /* n: the label row of belief i */,
+                           const double *init_mean /* n x NBP_MIX_MAX x NBP_MAXD */, const nbp_mixture_opts *opts /* nullable */,
+                           nbp_mixture_rec *recs_out /* n */, int32_t *labels_out /* n x N, nullable */);
+/* host-buffer form, like nbp_kde_modes: stages through slot 0; labels / labels_out hold n_pts entries (a belief of more than N
+ * points keeps its first N: the entries of labels_out beyond them are -1) */
+nbp_status nbp_kde_mixture(nbp_ctx *ctx, int32_t manifold, const double *pts_NxP, int32_t n_pts, const double *bw_D,
+                           const int32_t *labels /* n_pts */, const double *init_mean /* NBP_MIX_MAX x NBP_MAXD */,
+                           const nbp_mixture_opts *opts /* nullable */, nbp_mixture_rec *rec_out, int32_t *labels_out /* n_pts, nullable */);
 /* ---- factor likelihoods ("Factor likelihoods"; DEFINED by this library, unpinned: DESIGN.md 8) ----------------------
  * The likelihood of a factor's measurement model under the current beliefs of its variables: which association of a multihypo
  * factor won, which Mixture component explains the data, which factor disagrees with the solution.  One ITEM is (measurement

@@ -97,6 +97,21 @@ class ModeRec(C.Structure):
 MODES_MAX = 32
 MODES_BW_SCALE, MODES_TOL, MODES_MAX_ITER, MODES_MERGE = 2.0, 1e-6, 500, 1e-2
 
+MIX_MAX = 8  # NBP_MIX_MAX: components per nbp_run_mixture
+MIX_TOL, MIX_MAX_ITER = 1e-8, 500
+
+
+class MixtureOpts(C.Structure):
+    """nbp_mixture_opts: the stopping rule of the mixture fit (the defaults: NBP_MIX_* of include/nbp.h)"""
+    _fields_ = [("tol", C.c_double), ("max_iter", C.c_int32), ("pad", C.c_int32)]
+
+
+class MixtureRec(C.Structure):
+    """nbp_mixture_rec: one belief of nbp_run_mixture, the components by weight descending; entries from n_comp on are zero"""
+    _fields_ = [("weight", C.c_double * MIX_MAX), ("mean", (C.c_double * MAXD) * MIX_MAX), ("cov", (C.c_double * (MAXD * MAXD)) * MIX_MAX),
+                ("objective", C.c_double), ("count", C.c_int32 * MIX_MAX), ("n_comp", C.c_int32), ("iters", C.c_int32),
+                ("converged", C.c_int32), ("n_dropped", C.c_int32)]
+
 
 class LikelihoodDesc(C.Structure):
     """nbp_likelihood_desc: one item of nbp_run_factor_likelihood -- a measurement model and the slots of its one or two roles"""
@@ -243,7 +258,7 @@ EXPORTS = [
     "nbp_ctx_reserve_resident", "nbp_ctx_resident", "nbp_belief_write_batch_async", "nbp_belief_read_batch_begin", "nbp_belief_read_batch_end",
     "nbp_run_copies_async", "nbp_program_retire",
     "nbp_slot_write", "nbp_slot_read", "nbp_belief_write", "nbp_belief_read", "nbp_belief_write_batch", "nbp_belief_read_batch", "nbp_run_resample", "nbp_side_write", "nbp_side_read",
-    "nbp_run_proposals", "nbp_run_bandwidth", "nbp_run_ppe", "nbp_kde_ppe", "nbp_run_evaluate", "nbp_kde_evaluate", "nbp_run_marginal_grid", "nbp_kde_marginal_grid", "nbp_run_evaluate_marginal", "nbp_run_mmd", "nbp_kde_mmd", "nbp_run_meancov", "nbp_kde_meancov", "nbp_run_kld", "nbp_kde_kld", "nbp_run_overlap", "nbp_kde_overlap", "nbp_run_overlap_search", "nbp_run_credible", "nbp_kde_credible", "nbp_run_modes", "nbp_kde_modes", "nbp_run_factor_likelihood", "nbp_factor_likelihood", "nbp_run_factor_mode_likelihood", "nbp_factor_mode_likelihood", "nbp_heatmap_create", "nbp_heatmap_build", "nbp_heatmap_draw", "nbp_heatmap_info", "nbp_heatmap_destroy", "nbp_heatmap_scan_eval", "nbp_heatmap_search_eval", "nbp_run_products", "nbp_run_copies", "nbp_run_deconv", "nbp_kde_bandwidth", "nbp_conv", "nbp_manifold_product",
+    "nbp_run_proposals", "nbp_run_bandwidth", "nbp_run_ppe", "nbp_kde_ppe", "nbp_run_evaluate", "nbp_kde_evaluate", "nbp_run_marginal_grid", "nbp_kde_marginal_grid", "nbp_run_evaluate_marginal", "nbp_run_mmd", "nbp_kde_mmd", "nbp_run_meancov", "nbp_kde_meancov", "nbp_run_kld", "nbp_kde_kld", "nbp_run_overlap", "nbp_kde_overlap", "nbp_run_overlap_search", "nbp_run_credible", "nbp_kde_credible", "nbp_run_modes", "nbp_kde_modes", "nbp_run_mixture", "nbp_kde_mixture", "nbp_run_factor_likelihood", "nbp_factor_likelihood", "nbp_run_factor_mode_likelihood", "nbp_factor_mode_likelihood", "nbp_heatmap_create", "nbp_heatmap_build", "nbp_heatmap_draw", "nbp_heatmap_info", "nbp_heatmap_destroy", "nbp_heatmap_scan_eval", "nbp_heatmap_search_eval", "nbp_run_products", "nbp_run_copies", "nbp_run_deconv", "nbp_kde_bandwidth", "nbp_conv", "nbp_manifold_product",
     "nbp_program_create", "nbp_program_add_stage", "nbp_program_set_option", "nbp_program_finalize", "nbp_program_run",
     "nbp_program_reseed", "nbp_program_num_seeds", "nbp_program_set_seeds", "nbp_program_seed_order", "nbp_ctx_attach", "nbp_ctx_attached", "nbp_program_num_stages", "nbp_program_num_fused", "nbp_program_num_two_stream", "nbp_program_destroy",
     "nbp_timing_enable", "nbp_timing_read", "nbp_timing_read_n", "nbp_diag_read",
@@ -326,6 +341,8 @@ def load_library(path=None):
                                      C.POINTER(CredibilityRec)]
     lib.nbp_run_modes.argtypes = [vp, ip, ip, i32, C.POINTER(ModesOpts), C.POINTER(ModeRec), ip, ip, ip, ip]
     lib.nbp_kde_modes.argtypes = [vp, i32, dp, i32, dp, C.POINTER(ModesOpts), C.POINTER(ModeRec), ip, ip, ip, ip]
+    lib.nbp_run_mixture.argtypes = [vp, ip, ip, i32, ip, ip, dp, C.POINTER(MixtureOpts), C.POINTER(MixtureRec), ip]
+    lib.nbp_kde_mixture.argtypes = [vp, i32, dp, i32, dp, ip, dp, C.POINTER(MixtureOpts), C.POINTER(MixtureRec), ip]
     lib.nbp_run_factor_likelihood.argtypes = [vp, C.POINTER(LikelihoodDesc), i32, dp, dp]
     lib.nbp_factor_likelihood.argtypes = [vp, C.POINTER(LikelihoodDesc), dp, i32, dp, i32, dp, dp]
     lib.nbp_run_factor_mode_likelihood.argtypes = [vp, C.POINTER(LikelihoodDesc), ip, ip, i32, ip, i32, dp, ip]

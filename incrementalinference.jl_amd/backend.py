@@ -374,6 +374,52 @@ class HipBackend:
                                            its.ctypes.data_as(ip), C.byref(unc)))
         return recs, nm.value, lab[:c], its[:c], unc.value
 
+    # ---- mixture summaries (nbp_run_mixture; mixture.py) -----------------------------------------------------------------------
+    MIX_REC = np.dtype([("weight", np.float64, (abi.MIX_MAX,)), ("mean", np.float64, (abi.MIX_MAX, abi.MAXD)),
+                        ("cov", np.float64, (abi.MIX_MAX, abi.MAXD, abi.MAXD)), ("objective", np.float64),
+                        ("count", np.int32, (abi.MIX_MAX,)), ("n_comp", np.int32), ("iters", np.int32), ("converged", np.int32),
+                        ("n_dropped", np.int32)])
+
+    def run_mixture(self, slots, manifolds, labels, init_mean, tol=abi.MIX_TOL, max_iter=abi.MIX_MAX_ITER, rows=None):
+        """Gaussian-mixture summaries of resident beliefs (nbp_run_mixture: the whole EM of every belief in one launch).  labels:
+        int32 rows of N starting labels (-1 .. 7), row rows[i] for belief i (default: row i); init_mean: n x 8 x 3 starting means
+        -> (recs[n], labels[n, N]): recs a structured array with the fields of nbp_mixture_rec, the components by weight
+        descending; rows of labels beyond a belief's count hold -1"""
+        assert self.MIX_REC.itemsize == C.sizeof(abi.MixtureRec)
+        (s, sp), (m, mp) = _i32(slots), _i32(manifolds)
+        n = s.size
+        lab, lp = _i32(labels)
+        lab = lab.reshape(-1, self.N)
+        r, rp = _i32(np.arange(n) if rows is None else rows)
+        mu = np.ascontiguousarray(init_mean, dtype=np.float64)
+        if m.size != n or r.size != n or mu.shape != (n, abi.MIX_MAX, abi.MAXD) or (n and int(r.max()) >= lab.shape[0]):
+            raise ValueError("run_mixture: one slot, manifold, label row and 8 x 3 starting means per belief")
+        recs = np.zeros(n, dtype=self.MIX_REC)
+        out = np.zeros((n, self.N), dtype=np.int32)
+        ip = C.POINTER(C.c_int32)
+        opts = abi.MixtureOpts(tol=float(tol), max_iter=int(max_iter))
+        self._check(self.lib.nbp_run_mixture(self._ctx, sp, mp, n, lp, rp, mu.ctypes.data_as(C.POINTER(C.c_double)), C.byref(opts),
+                                             recs.ctypes.data_as(C.POINTER(abi.MixtureRec)), out.ctypes.data_as(ip)))
+        return recs, out
+
+    def kde_mixture(self, manifold, pts, bw, labels, init_mean, tol=abi.MIX_TOL, max_iter=abi.MIX_MAX_ITER):
+        """the mixture summary of a belief held on the host (nbp_kde_mixture; clobbers slot 0); labels: c starting labels; init_mean:
+        8 x 3 -> (rec, labels[c])"""
+        dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+        pts = np.ascontiguousarray(pts, dtype=np.float64).reshape(-1, abi.MANIFOLD_P[manifold])
+        bw = np.ascontiguousarray(bw, dtype=np.float64)
+        c = pts.shape[0]
+        lab, lp = _i32(labels)
+        mu = np.ascontiguousarray(init_mean, dtype=np.float64)
+        if lab.size != c or mu.shape != (abi.MIX_MAX, abi.MAXD):
+            raise ValueError("kde_mixture: one label per point and 8 x 3 starting means")
+        rec = np.zeros(1, dtype=self.MIX_REC)
+        out = np.zeros(max(c, 1), dtype=np.int32)
+        opts = abi.MixtureOpts(tol=float(tol), max_iter=int(max_iter))
+        self._check(self.lib.nbp_kde_mixture(self._ctx, manifold, pts.ctypes.data_as(dp), c, bw.ctypes.data_as(dp), lp, mu.ctypes.data_as(dp),
+                                             C.byref(opts), rec.ctypes.data_as(C.POINTER(abi.MixtureRec)), out.ctypes.data_as(ip)))
+        return rec[0], out[:c]
+
     def run_factor_likelihood(self, descs):
         """the likelihood of factors under resident beliefs (nbp_run_factor_likelihood: every item in one launch); descs: a
         sequence (or ctypes array) of abi.LikelihoodDesc -> (loglik[n], comp_loglik[n, 4]); entries of comp_loglik beyond an item's

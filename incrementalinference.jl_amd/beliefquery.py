@@ -165,6 +165,13 @@ class Belief:
         from .credible import belief_credible
         return belief_credible(self.manifold, self.pts, self.bw, mass, probs, dims, backend)
 
+    def mixture(self, maxComponents=abi.MIX_MAX, bwScale=abi.MODES_BW_SCALE, tol=abi.MIX_TOL, maxIter=abi.MIX_MAX_ITER, backend=None):
+        """belief.mixture(): the belief as a Gaussian mixture of at most `maxComponents` components (mixture.py) -> BeliefMixture,
+        whose `asPrior(varType)` goes back into a graph; computed by libnbp on a HIP `backend` (nbp_kde_modes and nbp_kde_mixture,
+        through slot 0), by numpy otherwise"""
+        from .mixture import belief_mixture
+        return belief_mixture(self.manifold, self.pts, self.bw, maxComponents, bwScale, tol, maxIter, backend)
+
     def credibility(self, pts, dims=None, backend=None):
         """belief.credibility(pts): the mass of the smallest highest-density region that still contains each reference point
         (tangent coordinates: one point, or q x D) -> Credibility(mass, logdens, n_above); `dims` and `backend` as in `credible`"""

@@ -16,7 +16,7 @@
 #include <rccl/rccl.h>  // types and prototypes only: the entry points are resolved with dlsym (see rccl_api)
 
 #ifndef NBP_TU
-#define NBP_TU 0  // host code: the kernels live in the nbp_k_*.hip files (-DNBP_TU=0xFFFFF: single-file build with every kernel)
+#define NBP_TU 0  // host code: the kernels live in the nbp_k_*.hip files (-DNBP_TU=0x1FFFFF: single-file build with every kernel)
 #endif
 #include "nbp_kernels.h"
 #include "nbp_fused.h"
@@ -29,6 +29,7 @@
 #include "nbp_likelihood.h"
 #include "nbp_overlap.h"
 #include "nbp_credible.h"
+#include "nbp_mixture.h"
 
 static thread_local std::string g_err;
 static nbp_status fail(nbp_status code, const std::string &msg) {
@@ -2266,6 +2267,75 @@ nbp_status nbp_kde_modes(nbp_ctx *c, int32_t manifold, const double *pts, int32_
     if (labels_out) labels_out[i] = i < c->N ? lab[i] : -1;
     if (iters_out) iters_out[i] = i < c->N ? its[i] : 0;
   }
+  return NBP_OK;
+}
+
+// ---- mixture summaries of beliefs (nbp_mixture.h) ----------------------------------------------------------------------------------
+// the options as given, or the defaults; refused before anything is launched
+static nbp_status mixture_opts_check(const nbp_mixture_opts *opts, nbp_mixture_opts *o) {
+  *o = opts ? *opts : nbp_mixture_opts{NBP_MIX_TOL, NBP_MIX_MAX_ITER, 0};
+  o->pad = 0;
+  if (!(o->tol >= 0.0 && o->tol < INFINITY)) return fail(NBP_ERR_ARG, "mixture: tol must be finite and not negative");
+  if (o->max_iter < 1) return fail(NBP_ERR_ARG, "mixture: max_iter must be at least 1");
+  return NBP_OK;
+}
+static nbp_status mixture_labels_check(const int32_t *lab, size_t cnt, int belief) {
+  for (size_t k = 0; k < cnt; k++)
+    if (lab[k] < -1 || lab[k] >= NBP_MIX_MAX)
+      return fail(NBP_ERR_ARG, "mixture: belief " + std::to_string(belief) + ": label " + std::to_string(k) + " outside -1 .. NBP_MIX_MAX - 1");
+  return NBP_OK;
+}
+
+// Gaussian-mixture summaries of beliefs resident in slots: one workgroup per belief runs the whole EM (nbp_mixture.h).  The label
+// rows the items name are gathered on the host (a row no item names is not read), so the columns, the rows and the starting means
+// go up in one staging copy; the records and the optional labels come back in one copy.
+nbp_status nbp_run_mixture(nbp_ctx *c, const int32_t *slots, const int32_t *manifolds, int32_t n, const int32_t *labels, const int32_t *row,
+                           const double *init_mean, const nbp_mixture_opts *opts, nbp_mixture_rec *recs_out, int32_t *labels_out) {
+  if (!c || ((!slots || !manifolds || !labels || !row || !init_mean || !recs_out) && n > 0)) return fail(NBP_ERR_ARG, "null argument");
+  if (n <= 0) return NBP_OK;
+  nbp_mixture_opts o;
+  NBPCHK(mixture_opts_check(opts, &o));
+  NBPCHK(batch_check(c, "mixture", {slots}, manifolds, n, [&](int i) {
+    return row[i] < 0 ? refusal{NBP_ERR_ARG, "a negative label row"} : refusal{NBP_OK, nullptr};
+  }));
+  const size_t V = (size_t)n, N = (size_t)c->N;
+  std::vector<int32_t> rows(V * N);
+  for (size_t i = 0; i < V; i++) {
+    NBPCHK(mixture_labels_check(labels + (size_t)row[i] * N, N, (int)i));
+    memcpy(rows.data() + i * N, labels + (size_t)row[i] * N, 4 * N);
+  }
+  static_assert(sizeof(nbp_mixture_rec) % sizeof(double) == 0, "nbp_mixture_rec fills whole doubles of the query scratch");
+  const size_t rec_d = V * (sizeof(nbp_mixture_rec) / sizeof(double)), lab_d = labels_out ? (V * N + 1) / 2 : 0;
+  const int32_t *d[4];
+  NBPCHK(stage_columns(c, {{slots, 4 * V}, {manifolds, 4 * V}, {rows.data(), 4 * V * N}, {init_mean, sizeof(double) * NBP_MIX_MAX * NBP_MAXD * V}},
+                       d, rec_d + lab_d));
+  int32_t *dlab = (int32_t *)(c->query + rec_d);
+  NBPCHK(launch_checked(c, nbp_mixture_kernel, V, c->Npad, nbp_mixture_lds_bytes(c->N), d[0], d[1], d[2], (const double *)d[3], c->arena, c->N,
+                        c->S, o, (nbp_mixture_rec *)c->query, labels_out ? dlab : (int32_t *)nullptr));
+  std::vector<double> back(rec_d + lab_d);
+  NBPCHK(query_fetch(c, back.data(), c->query, sizeof(double) * back.size()));
+  memcpy(recs_out, back.data(), sizeof(double) * rec_d);
+  if (labels_out) memcpy(labels_out, back.data() + rec_d, 4 * V * N);
+  return NBP_OK;
+}
+
+// host-buffer form: stages through slot 0 (which it clobbers), like nbp_kde_modes; everything is checked before slot 0 is touched.
+// The label row is padded with -1.
+nbp_status nbp_kde_mixture(nbp_ctx *c, int32_t manifold, const double *pts, int32_t n_pts, const double *bw, const int32_t *labels,
+                           const double *init_mean, const nbp_mixture_opts *opts, nbp_mixture_rec *rec_out, int32_t *labels_out) {
+  if (!c || !pts || !bw || !labels || !init_mean || !rec_out) return fail(NBP_ERR_ARG, "null argument");
+  nbp_mixture_opts o;
+  NBPCHK(mixture_opts_check(opts, &o));
+  NBPCHK(kde_check(c, "mixture", manifold, {{pts, n_pts, bw}}));
+  const int N = c->N, kept = n_pts < N ? n_pts : N;
+  NBPCHK(mixture_labels_check(labels, (size_t)kept, 0));
+  NBPCHK(kde_write(c, manifold, {{pts, n_pts, bw}}));
+  std::vector<int32_t> lab((size_t)N, -1), out(labels_out ? (size_t)N : 0);
+  memcpy(lab.data(), labels, 4 * (size_t)kept);
+  const int32_t slot = 0, row = 0;
+  NBPCHK(nbp_run_mixture(c, &slot, &manifold, 1, lab.data(), &row, init_mean, &o, rec_out, labels_out ? out.data() : nullptr));
+  if (labels_out)
+    for (int i = 0; i < n_pts; i++) labels_out[i] = i < N ? out[i] : -1;
   return NBP_OK;
 }
 

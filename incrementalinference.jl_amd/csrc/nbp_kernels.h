@@ -23,7 +23,7 @@
 #define NBP_TU_PRODLATUNI 1024 // product kernels, latency geometries (y32, l8), one manifold per instance
 #define NBP_TU_PROPSPLIT 524288 // proposal kernels, two waves per proposal (launches between the workgroup and the one-wave geometry)
 #ifndef NBP_TU
-#define NBP_TU 0xFFFFF
+#define NBP_TU 0x1FFFFF
 #endif
 
 // ================================================================================================

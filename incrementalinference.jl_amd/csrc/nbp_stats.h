@@ -25,6 +25,7 @@
 
 #define NBP_TU_STATS 8192  // the belief-statistics kernels (nbp_k_stats.hip)
 #define NBP_TU_CREDIBLE 128  // the credible-region kernel (nbp_k_credible.hip, nbp_credible.h): defined here, it shares stats_deviation
+#define NBP_TU_MIXTURE 1048576  // the mixture-summary kernel (nbp_k_mixture.hip, nbp_mixture.h): likewise
 
 // one record per belief; entries beyond the manifold's dimension are zero
 struct nbp_meancov_rec {
@@ -40,7 +41,7 @@ struct nbp_kld_rec {
 #define NBP_KLD_ARGS                                                                                                   \
   const int32_t *slots_a, const int32_t *slots_b, const int32_t *manifolds, const double *arena, int N, int64_t S,     \
       nbp_kld_rec *out
-#if NBP_TU & (NBP_TU_STATS | NBP_TU_CREDIBLE)
+#if NBP_TU & (NBP_TU_STATS | NBP_TU_CREDIBLE | NBP_TU_MIXTURE)
 // the deviation of a coordinate from the mean: the world frame, circular coordinates wrapped.  (Pinning SE(2) to Manifolds.jl's
 // coordinates at the mean would change this function alone.)
 __device__ __forceinline__ double stats_deviation(double x, double mu, bool circ) {

@@ -164,7 +164,7 @@ class SolveSession:
         self.stats["last"]["readbacks"] += len(wanted)
 
     # ---- statistics of the resident beliefs ------------------------------------------------------------------------------
-    def _query_resident(self, labels, method, args, pick, host):
+    def _query_resident(self, labels, method, args, pick, host, call=None):
         """One query of the variables' current beliefs -> {label: result} in the order of `labels` (default: every variable the
         last solve worked on).  On a backend that has `method`, the beliefs the residency table holds as current are read where
         they lie, in ONE call `method(*args(here, place))` -- here: the labels that have a slot, place: label -> slot -- and
@@ -172,7 +172,7 @@ class SolveSession:
         is not resident (edited on the host since, or invalidated) goes up first by the session's upload path and is counted as
         an upload.  `host(label, **kw)` is the same query on the host copy: for every label where there is no context or the
         backend lacks `method`, and with backend=self.backend for a variable that has no slot in the session's context (never
-        part of a solve)."""
+        part of a solve).  call: a query of several launches, `call(backend, *args(here, place))` in place of the one method."""
         if self._closed:
             raise RuntimeError("this SolveSession is closed")
         labels = list(self._labels if labels is None else labels)
@@ -185,7 +185,7 @@ class SolveSession:
         if here:
             try:
                 self._upload(self.fg, [(v, place[v]) for v in here], len(self._labels))
-                res = getattr(be, method)(*args(here, place))
+                res = call(be, *args(here, place)) if call is not None else getattr(be, method)(*args(here, place))
             except BaseException:
                 self._table.clear()  # the device state is unknown: the host copy wins
                 raise
@@ -378,6 +378,21 @@ class SolveSession:
                                                          [packed[v][0] for v in here], False, False),
                                     lambda res, i, v: credible.credibility_from_records(res[3][res[4][i]:res[4][i + 1]], packed[v][1]),
                                     None)
+
+    def fitBeliefMixtures(self, labels=None, maxComponents=abi.MIX_MAX, bwScale=abi.MODES_BW_SCALE, tol=abi.MIX_TOL, maxIter=abi.MIX_MAX_ITER):
+        """The variables' current beliefs as Gaussian mixtures (mixture.py) -> {label: BeliefMixture}.  labels: default every
+        variable the last solve worked on; maxComponents, bwScale, tol, maxIter as in `mixture.fitBeliefMixture`.  Served by ONE
+        `run_modes` and ONE `run_mixture` where libnbp holds the beliefs (`_query_resident`): no belief travels and `stats` does
+        not move; on the host copy, `mixture.fitBeliefMixture`."""
+        from . import mixture
+        K, mode_kw, kw = mixture._options(maxComponents, bwScale, tol, maxIter)
+        var = self.fg.getVariable
+
+        def run(here, place):
+            return ([place[v] for v in here], [var(v).varType.manifold for v in here], [len(var(v).val) for v in here], K, mode_kw, kw)
+        return self._query_resident(labels, "run_mixture", run, lambda res, i, v: res[i],
+                                    lambda v, **k: mixture.fitBeliefMixture(self.fg, v, maxComponents, bwScale, tol, maxIter, **k),
+                                    call=lambda be, *a: mixture.resident_mixtures(be, *a))
 
     # ---- one solve ---------------------------------------------------------------------------------------------------------
     def solve(self, seed=0, eliminationOrder=None, ordering="qr", return_timing=False):
