@@ -19,10 +19,35 @@ class NbpError(RuntimeError):
     (reference: CliqStateMachineUtils.jl:184-246, test/testCSMMonitor.jl:51)."""
 
 
+_IP, _DP = C.POINTER(C.c_int32), C.POINTER(C.c_double)
+
+
 def _i32(seq):
     """a sequence as a contiguous int32 array and the pointer to it that libnbp takes (the pointer holds a reference to the array)"""
     a = np.ascontiguousarray(seq, dtype=np.int32)
-    return a, a.ctypes.data_as(C.POINTER(C.c_int32))
+    return a, a.ctypes.data_as(_IP)
+
+
+def _f64(a, shape=None):
+    """the float64 twin of _i32: a contiguous array (reshaped to `shape`) and the pointer to it"""
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    a = a if shape is None else a.reshape(shape)
+    return a, a.ctypes.data_as(_DP)
+
+
+def _ptr(a, to=None):
+    """the pointer libnbp takes to an output array -- float64 or int32, or structured with records of the ctypes type `to`; None for
+    None: an optional output nobody asked for"""
+    if a is None:
+        return None
+    return a.ctypes.data_as(C.POINTER(to) if to else _IP if a.dtype == np.int32 else _DP)
+
+
+def _host_belief(manifold, pts, bw=None):
+    """a belief held on the host as the nbp_kde_* entries take it -> (the pointer to its points c x P, c, the pointer to its bandwidth or
+    None); the pointers hold references to the arrays made here"""
+    pts, pp = _f64(pts, (-1, abi.MANIFOLD_P[manifold]))
+    return pp, pts.shape[0], None if bw is None else _f64(bw)[1]
 
 
 def _pack_queries(manifolds, queries, all_columns=False):
@@ -181,8 +206,7 @@ class HipBackend:
         (s, sp), (_, mp) = _i32(slots), _i32(manifolds)
         n = s.size
         mean, mx, idx = np.zeros((n, abi.MAXD)), np.zeros((n, abi.MAXD)), np.zeros(n, dtype=np.int32)
-        ip, dp = C.POINTER(C.c_int32), C.POINTER(C.c_double)
-        self._check(self.lib.nbp_run_ppe(self._ctx, sp, mp, n, mean.ctypes.data_as(dp), mx.ctypes.data_as(dp), idx.ctypes.data_as(ip)))
+        self._check(self.lib.nbp_run_ppe(self._ctx, sp, mp, n, _ptr(mean), _ptr(mx), _ptr(idx)))
         return mean, mx, idx
 
     def run_resample(self, slots, manifolds, seed=0):
@@ -200,13 +224,10 @@ class HipBackend:
 
     def kde_ppe(self, manifold, pts, bw):
         """calcPPE of a belief held on the host (nbp_kde_ppe; clobbers slot 0) -> (mean[D], max[D], max_index)"""
-        dp = C.POINTER(C.c_double)
-        pts = np.ascontiguousarray(pts, dtype=np.float64).reshape(-1, abi.MANIFOLD_P[manifold])
-        bw = np.ascontiguousarray(bw, dtype=np.float64)
+        pp, c, bp = _host_belief(manifold, pts, bw)
         D = abi.MANIFOLD_DIM[manifold]
         mean, mx, idx = np.zeros(D), np.zeros(D), C.c_int32(0)
-        self._check(self.lib.nbp_kde_ppe(self._ctx, manifold, pts.ctypes.data_as(dp), pts.shape[0], bw.ctypes.data_as(dp),
-                                         mean.ctypes.data_as(dp), mx.ctypes.data_as(dp), C.byref(idx)))
+        self._check(self.lib.nbp_kde_ppe(self._ctx, manifold, pp, c, bp, _ptr(mean), _ptr(mx), C.byref(idx)))
         return mean, mx, idx.value
 
     def _run_evaluate(self, slots, manifolds, masks, queries):
@@ -215,8 +236,7 @@ class HipBackend:
         n = s.size
         Q, first = _pack_queries(m, queries)
         out = np.zeros(int(first[-1]))
-        ip, dp = C.POINTER(C.c_int32), C.POINTER(C.c_double)
-        tail = (n, first.ctypes.data_as(ip), Q.ctypes.data_as(dp), out.ctypes.data_as(dp))
+        tail = (n, _ptr(first), _ptr(Q), _ptr(out))
         if masks is None:
             self._check(self.lib.nbp_run_evaluate(self._ctx, sp, mp, *tail))
         else:
@@ -230,13 +250,10 @@ class HipBackend:
 
     def kde_evaluate(self, manifold, pts, bw, queries):
         """densities of a belief held on the host at query points in tangent coordinates (nbp_kde_evaluate; clobbers slot 0)"""
-        dp = C.POINTER(C.c_double)
-        pts = np.ascontiguousarray(pts, dtype=np.float64).reshape(-1, abi.MANIFOLD_P[manifold])
-        bw = np.ascontiguousarray(bw, dtype=np.float64)
+        pp, c, bp = _host_belief(manifold, pts, bw)
         Q, first = _pack_queries([manifold], [queries], all_columns=True)
         out = np.zeros(int(first[1]))
-        self._check(self.lib.nbp_kde_evaluate(self._ctx, manifold, pts.ctypes.data_as(dp), pts.shape[0], bw.ctypes.data_as(dp),
-                                              Q.ctypes.data_as(dp), int(first[1]), out.ctypes.data_as(dp)))
+        self._check(self.lib.nbp_kde_evaluate(self._ctx, manifold, pp, c, bp, _ptr(Q), int(first[1]), _ptr(out)))
         return out
 
     @staticmethod
@@ -272,23 +289,18 @@ class HipBackend:
             first[i + 1] = first[i] + max(int(np.prod(sh)), 0)
         first = first.astype(np.int32)
         out, ext = np.zeros(int(first[-1])), np.zeros((nd, 4))
-        ip, dp = C.POINTER(C.c_int32), C.POINTER(C.c_double)
-        self._check(self.lib.nbp_run_marginal_grid(self._ctx, arr, nd, first.ctypes.data_as(ip), out.ctypes.data_as(dp),
-                                                   ext.ctypes.data_as(dp)))
+        self._check(self.lib.nbp_run_marginal_grid(self._ctx, arr, nd, _ptr(first), _ptr(out), _ptr(ext)))
         res = [out[first[i]:first[i + 1]].reshape(sh) for i, sh in enumerate(shapes)]
         return (res, ext) if return_extent else res
 
     def kde_marginal_grid(self, manifold, pts, bw, dims, n, extent=None, margin=4.0):
         """the marginal grid of a belief held on the host (nbp_kde_marginal_grid; clobbers slot 0) -> (grid, (lo0, step0, lo1,
         step1)); dims 0-based"""
-        dp = C.POINTER(C.c_double)
-        pts = np.ascontiguousarray(pts, dtype=np.float64).reshape(-1, abi.MANIFOLD_P[manifold])
-        bw = np.ascontiguousarray(bw, dtype=np.float64)
+        pp, c, bp = _host_belief(manifold, pts, bw)
         g = self._grid_desc(0, manifold, dims, n, extent, margin)
         shape = (g.n[0],) if g.dims[1] == -1 else (g.n[0], g.n[1])
         out, ext = np.zeros(max(int(np.prod(shape)), 0)), np.zeros(4)
-        self._check(self.lib.nbp_kde_marginal_grid(self._ctx, manifold, pts.ctypes.data_as(dp), pts.shape[0], bw.ctypes.data_as(dp),
-                                                   C.byref(g), out.ctypes.data_as(dp), ext.ctypes.data_as(dp)))
+        self._check(self.lib.nbp_kde_marginal_grid(self._ctx, manifold, pp, c, bp, C.byref(g), _ptr(out), _ptr(ext)))
         return out.reshape(shape), ext
 
     def run_evaluate_marginal(self, slots, manifolds, masks, queries):
@@ -300,17 +312,14 @@ class HipBackend:
         """mmd of pairs of resident beliefs (nbp_run_mmd) -> values[n], from one launch"""
         (a, ap), (_, bp), (_, mp) = _i32(slots_a), _i32(slots_b), _i32(manifolds)
         out = np.zeros(a.size)
-        self._check(self.lib.nbp_run_mmd(self._ctx, ap, bp, mp, a.size, float(sigma), out.ctypes.data_as(C.POINTER(C.c_double))))
+        self._check(self.lib.nbp_run_mmd(self._ctx, ap, bp, mp, a.size, float(sigma), _ptr(out)))
         return out
 
     def kde_mmd(self, manifold, a, b, sigma=0.001):
         """mmd of two beliefs held on the host (nbp_kde_mmd; clobbers slots 0 and 1)"""
-        dp = C.POINTER(C.c_double)
-        a = np.ascontiguousarray(a, dtype=np.float64).reshape(-1, abi.MANIFOLD_P[manifold])
-        b = np.ascontiguousarray(b, dtype=np.float64).reshape(-1, abi.MANIFOLD_P[manifold])
+        (ap, na, _), (bp, nb, _) = _host_belief(manifold, a), _host_belief(manifold, b)
         out = C.c_double(0.0)
-        self._check(self.lib.nbp_kde_mmd(self._ctx, manifold, a.ctypes.data_as(dp), a.shape[0], b.ctypes.data_as(dp), b.shape[0],
-                                         float(sigma), C.byref(out)))
+        self._check(self.lib.nbp_kde_mmd(self._ctx, manifold, ap, na, bp, nb, float(sigma), C.byref(out)))
         return out.value
 
     def run_meancov(self, slots, manifolds):
@@ -319,18 +328,15 @@ class HipBackend:
         (s, sp), (_, mp) = _i32(slots), _i32(manifolds)
         n = s.size
         mean, cov = np.zeros((n, abi.MAXD)), np.zeros((n, abi.MAXD, abi.MAXD))
-        dp = C.POINTER(C.c_double)
-        self._check(self.lib.nbp_run_meancov(self._ctx, sp, mp, n, mean.ctypes.data_as(dp), cov.ctypes.data_as(dp)))
+        self._check(self.lib.nbp_run_meancov(self._ctx, sp, mp, n, _ptr(mean), _ptr(cov)))
         return mean, cov
 
     def kde_meancov(self, manifold, pts):
         """calcMeanCovar of a belief held on the host (nbp_kde_meancov; clobbers slot 0) -> (mean[D], cov[D, D])"""
-        dp = C.POINTER(C.c_double)
-        pts = np.ascontiguousarray(pts, dtype=np.float64).reshape(-1, abi.MANIFOLD_P[manifold])
+        pp, c, _ = _host_belief(manifold, pts)
         D = abi.MANIFOLD_DIM[manifold]
         mean, cov = np.zeros(D), np.zeros((D, D))
-        self._check(self.lib.nbp_kde_meancov(self._ctx, manifold, pts.ctypes.data_as(dp), pts.shape[0], mean.ctypes.data_as(dp),
-                                             cov.ctypes.data_as(dp)))
+        self._check(self.lib.nbp_kde_meancov(self._ctx, manifold, pp, c, _ptr(mean), _ptr(cov)))
         return mean, cov
 
     _MODE_REC = np.dtype([("location", np.float64, (abi.MAXD,)), ("density", np.float64), ("count", np.int32), ("leader", np.int32)])
@@ -351,27 +357,21 @@ class HipBackend:
         recs = np.zeros((n, abi.MODES_MAX), dtype=self._MODE_REC)
         nm, unc = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
         lab, its = np.zeros((n, self.N), dtype=np.int32), np.zeros((n, self.N), dtype=np.int32)
-        ip = C.POINTER(C.c_int32)
         opts = self._modes_opts(bw_scale, tol, max_iter, merge)
-        self._check(self.lib.nbp_run_modes(self._ctx, sp, mp, n, C.byref(opts), recs.ctypes.data_as(C.POINTER(abi.ModeRec)),
-                                           nm.ctypes.data_as(ip), lab.ctypes.data_as(ip), its.ctypes.data_as(ip), unc.ctypes.data_as(ip)))
+        self._check(self.lib.nbp_run_modes(self._ctx, sp, mp, n, C.byref(opts), _ptr(recs, abi.ModeRec), _ptr(nm), _ptr(lab), _ptr(its), _ptr(unc)))
         return recs, nm, lab, its, unc
 
     def kde_modes(self, manifold, pts, bw, bw_scale=abi.MODES_BW_SCALE, tol=abi.MODES_TOL, max_iter=abi.MODES_MAX_ITER,
                   merge=abi.MODES_MERGE):
         """the modes of a belief held on the host (nbp_kde_modes; clobbers slot 0) -> (recs[32], n_modes, labels[c], iters[c],
         n_unconverged)"""
-        dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
-        pts = np.ascontiguousarray(pts, dtype=np.float64).reshape(-1, abi.MANIFOLD_P[manifold])
-        bw = np.ascontiguousarray(bw, dtype=np.float64)
-        c = pts.shape[0]
+        pp, c, bp = _host_belief(manifold, pts, bw)
         recs = np.zeros(abi.MODES_MAX, dtype=self._MODE_REC)
         nm, unc = C.c_int32(0), C.c_int32(0)
         lab, its = np.zeros(max(c, 1), dtype=np.int32), np.zeros(max(c, 1), dtype=np.int32)
         opts = self._modes_opts(bw_scale, tol, max_iter, merge)
-        self._check(self.lib.nbp_kde_modes(self._ctx, manifold, pts.ctypes.data_as(dp), c, bw.ctypes.data_as(dp), C.byref(opts),
-                                           recs.ctypes.data_as(C.POINTER(abi.ModeRec)), C.byref(nm), lab.ctypes.data_as(ip),
-                                           its.ctypes.data_as(ip), C.byref(unc)))
+        self._check(self.lib.nbp_kde_modes(self._ctx, manifold, pp, c, bp, C.byref(opts), _ptr(recs, abi.ModeRec), C.byref(nm), _ptr(lab),
+                                           _ptr(its), C.byref(unc)))
         return recs, nm.value, lab[:c], its[:c], unc.value
 
     # ---- mixture summaries (nbp_run_mixture; mixture.py) -----------------------------------------------------------------------
@@ -391,33 +391,27 @@ class HipBackend:
         lab, lp = _i32(labels)
         lab = lab.reshape(-1, self.N)
         r, rp = _i32(np.arange(n) if rows is None else rows)
-        mu = np.ascontiguousarray(init_mean, dtype=np.float64)
+        mu, mup = _f64(init_mean)
         if m.size != n or r.size != n or mu.shape != (n, abi.MIX_MAX, abi.MAXD) or (n and int(r.max()) >= lab.shape[0]):
             raise ValueError("run_mixture: one slot, manifold, label row and 8 x 3 starting means per belief")
         recs = np.zeros(n, dtype=self.MIX_REC)
         out = np.zeros((n, self.N), dtype=np.int32)
-        ip = C.POINTER(C.c_int32)
         opts = abi.MixtureOpts(tol=float(tol), max_iter=int(max_iter))
-        self._check(self.lib.nbp_run_mixture(self._ctx, sp, mp, n, lp, rp, mu.ctypes.data_as(C.POINTER(C.c_double)), C.byref(opts),
-                                             recs.ctypes.data_as(C.POINTER(abi.MixtureRec)), out.ctypes.data_as(ip)))
+        self._check(self.lib.nbp_run_mixture(self._ctx, sp, mp, n, lp, rp, mup, C.byref(opts), _ptr(recs, abi.MixtureRec), _ptr(out)))
         return recs, out
 
     def kde_mixture(self, manifold, pts, bw, labels, init_mean, tol=abi.MIX_TOL, max_iter=abi.MIX_MAX_ITER):
         """the mixture summary of a belief held on the host (nbp_kde_mixture; clobbers slot 0); labels: c starting labels; init_mean:
         8 x 3 -> (rec, labels[c])"""
-        dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
-        pts = np.ascontiguousarray(pts, dtype=np.float64).reshape(-1, abi.MANIFOLD_P[manifold])
-        bw = np.ascontiguousarray(bw, dtype=np.float64)
-        c = pts.shape[0]
+        pp, c, bp = _host_belief(manifold, pts, bw)
         lab, lp = _i32(labels)
-        mu = np.ascontiguousarray(init_mean, dtype=np.float64)
+        mu, mup = _f64(init_mean)
         if lab.size != c or mu.shape != (abi.MIX_MAX, abi.MAXD):
             raise ValueError("kde_mixture: one label per point and 8 x 3 starting means")
         rec = np.zeros(1, dtype=self.MIX_REC)
         out = np.zeros(max(c, 1), dtype=np.int32)
         opts = abi.MixtureOpts(tol=float(tol), max_iter=int(max_iter))
-        self._check(self.lib.nbp_kde_mixture(self._ctx, manifold, pts.ctypes.data_as(dp), c, bw.ctypes.data_as(dp), lp, mu.ctypes.data_as(dp),
-                                             C.byref(opts), rec.ctypes.data_as(C.POINTER(abi.MixtureRec)), out.ctypes.data_as(ip)))
+        self._check(self.lib.nbp_kde_mixture(self._ctx, manifold, pp, c, bp, lp, mup, C.byref(opts), _ptr(rec, abi.MixtureRec), _ptr(out)))
         return rec[0], out[:c]
 
     def run_factor_likelihood(self, descs):
@@ -425,22 +419,17 @@ class HipBackend:
         sequence (or ctypes array) of abi.LikelihoodDesc -> (loglik[n], comp_loglik[n, 4]); entries of comp_loglik beyond an item's
         ncomp are NaN"""
         arr, n = _as_array(descs, abi.LikelihoodDesc)
-        dp = C.POINTER(C.c_double)
         ll, cl = np.zeros(n), np.zeros((n, abi.MAXC))
-        self._check(self.lib.nbp_run_factor_likelihood(self._ctx, arr, n, ll.ctypes.data_as(dp), cl.ctypes.data_as(dp)))
+        self._check(self.lib.nbp_run_factor_likelihood(self._ctx, arr, n, _ptr(ll), _ptr(cl)))
         return ll, cl
 
     def factor_likelihood(self, desc, a, b=None):
         """the likelihood of one factor under beliefs held on the host (nbp_factor_likelihood; clobbers slots 0 and 1); a, b: host
         points (n x P) of the two roles, b None for a unary factor -> (loglik, comp_loglik[4])"""
-        dp = C.POINTER(C.c_double)
-        P = abi.MANIFOLD_P[desc.manifold]
-        a = np.ascontiguousarray(a, dtype=np.float64).reshape(-1, P)
-        b = None if b is None else np.ascontiguousarray(b, dtype=np.float64).reshape(-1, P)
+        ap, na, _ = _host_belief(desc.manifold, a)
+        bp, nb, _ = (None, 0, None) if b is None else _host_belief(desc.manifold, b)
         ll, cl = C.c_double(0.0), np.zeros(abi.MAXC)
-        self._check(self.lib.nbp_factor_likelihood(self._ctx, C.byref(desc), a.ctypes.data_as(dp), a.shape[0],
-                                                   b.ctypes.data_as(dp) if b is not None else None, b.shape[0] if b is not None else 0,
-                                                   C.byref(ll), cl.ctypes.data_as(dp)))
+        self._check(self.lib.nbp_factor_likelihood(self._ctx, C.byref(desc), ap, na, bp, nb, C.byref(ll), _ptr(cl)))
         return ll.value, cl
 
     def run_factor_mode_likelihood(self, descs, row_a, row_b, labels):
@@ -453,29 +442,22 @@ class HipBackend:
         if ra.size != n or rb.size != n:
             raise ValueError("run_factor_mode_likelihood: one row index per item and role")
         lab = np.ascontiguousarray(labels, dtype=np.int32).reshape(-1, self.N)
-        dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
         tab, cnt = np.zeros((n, abi.MAXK, abi.MAXK)), np.zeros((n, 2, abi.MAXK), dtype=np.int32)
-        self._check(self.lib.nbp_run_factor_mode_likelihood(self._ctx, arr, rap, rbp, n, lab.ctypes.data_as(ip), lab.shape[0],
-                                                            tab.ctypes.data_as(dp), cnt.ctypes.data_as(ip)))
+        self._check(self.lib.nbp_run_factor_mode_likelihood(self._ctx, arr, rap, rbp, n, _ptr(lab), lab.shape[0], _ptr(tab), _ptr(cnt)))
         return tab, cnt
 
     def factor_mode_likelihood(self, desc, a, labels_a=None, b=None, labels_b=None):
         """the mode-by-mode likelihood of one factor under beliefs held on the host (nbp_factor_mode_likelihood; clobbers slots 0
         and 1); a, b: host points (n x P) of the two roles, b None for a unary factor; labels_*: one group per point, None: every
         point in group 0 -> (table[8, 8], counts[2, 8])"""
-        dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
-        P = abi.MANIFOLD_P[desc.manifold]
-        a = np.ascontiguousarray(a, dtype=np.float64).reshape(-1, P)
-        b = None if b is None else np.ascontiguousarray(b, dtype=np.float64).reshape(-1, P)
+        ap, na, _ = _host_belief(desc.manifold, a)
+        bp, nb, _ = (None, 0, None) if b is None else _host_belief(desc.manifold, b)
         la = None if labels_a is None else np.ascontiguousarray(labels_a, dtype=np.int32).reshape(-1)
         lb = None if labels_b is None or b is None else np.ascontiguousarray(labels_b, dtype=np.int32).reshape(-1)
-        if (la is not None and la.size != a.shape[0]) or (lb is not None and lb.size != b.shape[0]):
+        if (la is not None and la.size != na) or (lb is not None and lb.size != nb):
             raise ValueError("factor_mode_likelihood: one label per point")
         tab, cnt = np.zeros((abi.MAXK, abi.MAXK)), np.zeros((2, abi.MAXK), dtype=np.int32)
-        self._check(self.lib.nbp_factor_mode_likelihood(
-            self._ctx, C.byref(desc), a.ctypes.data_as(dp), a.shape[0], la.ctypes.data_as(ip) if la is not None else None,
-            b.ctypes.data_as(dp) if b is not None else None, b.shape[0] if b is not None else 0,
-            lb.ctypes.data_as(ip) if lb is not None else None, tab.ctypes.data_as(dp), cnt.ctypes.data_as(ip)))
+        self._check(self.lib.nbp_factor_mode_likelihood(self._ctx, C.byref(desc), ap, na, _ptr(la), bp, nb, _ptr(lb), _ptr(tab), _ptr(cnt)))
         return tab, cnt
 
     def run_kld(self, slots_a, slots_b, manifolds, terms=False):
@@ -483,20 +465,14 @@ class HipBackend:
         terms = (Eaa, Eab), values = Eaa - Eab, entropy(a) = -Eaa"""
         (a, ap), (_, bp), (_, mp) = _i32(slots_a), _i32(slots_b), _i32(manifolds)
         out, tm = np.zeros(a.size), np.zeros((a.size, 2))
-        dp = C.POINTER(C.c_double)
-        self._check(self.lib.nbp_run_kld(self._ctx, ap, bp, mp, a.size, out.ctypes.data_as(dp), tm.ctypes.data_as(dp) if terms else None))
+        self._check(self.lib.nbp_run_kld(self._ctx, ap, bp, mp, a.size, _ptr(out), _ptr(tm if terms else None)))
         return (out, tm) if terms else out
 
     def kde_kld(self, manifold, a, bw_a, b, bw_b, terms=False):
         """kld of two beliefs held on the host (nbp_kde_kld; clobbers slots 0 and 1) -> value, or (value, (Eaa, Eab))"""
-        dp = C.POINTER(C.c_double)
-        a = np.ascontiguousarray(a, dtype=np.float64).reshape(-1, abi.MANIFOLD_P[manifold])
-        b = np.ascontiguousarray(b, dtype=np.float64).reshape(-1, abi.MANIFOLD_P[manifold])
-        bw_a, bw_b = np.ascontiguousarray(bw_a, dtype=np.float64), np.ascontiguousarray(bw_b, dtype=np.float64)
+        (ap, na, ha), (bp, nb, hb) = _host_belief(manifold, a, bw_a), _host_belief(manifold, b, bw_b)
         out, tm = C.c_double(0.0), np.zeros(2)
-        self._check(self.lib.nbp_kde_kld(self._ctx, manifold, a.ctypes.data_as(dp), a.shape[0], bw_a.ctypes.data_as(dp),
-                                         b.ctypes.data_as(dp), b.shape[0], bw_b.ctypes.data_as(dp), C.byref(out),
-                                         tm.ctypes.data_as(dp) if terms else None))
+        self._check(self.lib.nbp_kde_kld(self._ctx, manifold, ap, na, ha, bp, nb, hb, C.byref(out), _ptr(tm if terms else None)))
         return (out.value, tm) if terms else out.value
 
     def run_overlap(self, slots_a, slots_b, manifolds_a, manifolds_b, masks_a, masks_b):
@@ -507,19 +483,15 @@ class HipBackend:
         if any(a.size != n for a, _ in cols):
             raise ValueError("run_overlap: six columns of one length")
         out = np.zeros((n, 4))
-        self._check(self.lib.nbp_run_overlap(self._ctx, *(p for _, p in cols), n, out.ctypes.data_as(C.POINTER(abi.OverlapRec))))
+        self._check(self.lib.nbp_run_overlap(self._ctx, *(p for _, p in cols), n, _ptr(out, abi.OverlapRec)))
         return out
 
     def kde_overlap(self, manifold_a, a, bw_a, mask_a, manifold_b, b, bw_b, mask_b):
         """the overlap of two beliefs held on the host (nbp_kde_overlap; clobbers slots 0 and 1) -> rec[4]: logc, L_ab, L_aa, L_bb"""
-        dp = C.POINTER(C.c_double)
-        a = np.ascontiguousarray(a, dtype=np.float64).reshape(-1, abi.MANIFOLD_P[manifold_a])
-        b = np.ascontiguousarray(b, dtype=np.float64).reshape(-1, abi.MANIFOLD_P[manifold_b])
-        bw_a, bw_b = np.ascontiguousarray(bw_a, dtype=np.float64), np.ascontiguousarray(bw_b, dtype=np.float64)
+        (ap, na, ha), (bp, nb, hb) = _host_belief(manifold_a, a, bw_a), _host_belief(manifold_b, b, bw_b)
         out = np.zeros(4)
-        self._check(self.lib.nbp_kde_overlap(self._ctx, manifold_a, a.ctypes.data_as(dp), a.shape[0], bw_a.ctypes.data_as(dp), int(mask_a),
-                                             manifold_b, b.ctypes.data_as(dp), b.shape[0], bw_b.ctypes.data_as(dp), int(mask_b),
-                                             out.ctypes.data_as(C.POINTER(abi.OverlapRec))))
+        self._check(self.lib.nbp_kde_overlap(self._ctx, manifold_a, ap, na, ha, int(mask_a), manifold_b, bp, nb, hb, int(mask_b),
+                                             _ptr(out, abi.OverlapRec)))
         return out
 
     def run_overlap_search(self, slots, manifolds, masks, topk=abi.OVERLAP_TOPK, min_coeff=abi.OVERLAP_MIN_COEFF, reach=abi.OVERLAP_REACH):
@@ -534,9 +506,7 @@ class HipBackend:
         idx, logc = np.zeros((n, rows), dtype=np.int32), np.zeros((n, rows))
         found, evaluated = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
         opts = abi.OverlapOpts(reach=float(reach), min_coeff=float(min_coeff), topk=topk, pad=0)
-        dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
-        self._check(self.lib.nbp_run_overlap_search(self._ctx, sp, mp, kp, n, C.byref(opts), idx.ctypes.data_as(ip), logc.ctypes.data_as(dp),
-                                                    found.ctypes.data_as(ip), evaluated.ctypes.data_as(ip)))
+        self._check(self.lib.nbp_run_overlap_search(self._ctx, sp, mp, kp, n, C.byref(opts), _ptr(idx), _ptr(logc), _ptr(found), _ptr(evaluated)))
         return idx, logc, found, evaluated
 
     # ---- credible regions (nbp_run_credible; credible.py) ----------------------------------------------------------------------
@@ -564,7 +534,6 @@ class HipBackend:
         n = s.size
         if m.size != n or k.size != n:
             raise ValueError("run_credible: three columns of one length")
-        dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
         recs = np.zeros(n, dtype=self.CRED_REC)
         ld = np.zeros((n, self.N)) if logdens else None
         od = np.zeros((n, self.N), dtype=np.int32) if order else None
@@ -573,30 +542,22 @@ class HipBackend:
             Q, first = _pack_queries(m, queries)
             qrecs = np.zeros(int(first[-1]), dtype=self.CREDIBILITY_REC)
         opts = self._credible_opts(mass, probs)
-        self._check(self.lib.nbp_run_credible(
-            self._ctx, sp, mp, kp, n, C.byref(opts), first.ctypes.data_as(ip) if first is not None else None,
-            Q.ctypes.data_as(dp) if Q is not None else None, recs.ctypes.data_as(C.POINTER(abi.CredibleRec)),
-            ld.ctypes.data_as(dp) if logdens else None, od.ctypes.data_as(ip) if order else None,
-            qrecs.ctypes.data_as(C.POINTER(abi.CredibilityRec)) if qrecs is not None else None))
+        self._check(self.lib.nbp_run_credible(self._ctx, sp, mp, kp, n, C.byref(opts), _ptr(first), _ptr(Q), _ptr(recs, abi.CredibleRec), _ptr(ld),
+                                              _ptr(od), _ptr(qrecs, abi.CredibilityRec)))
         return recs, ld, od, qrecs, first
 
     def kde_credible(self, manifold, pts, bw, mask, mass=(), probs=(), queries=None, logdens=True, order=True):
         """credible regions of a belief held on the host (nbp_kde_credible; clobbers slot 0); queries: None or q x D (or x 3) tangent
         coordinates -> (rec, logdens[c] or None, order[c] or None, qrecs[q] or None)"""
-        dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
-        pts = np.ascontiguousarray(pts, dtype=np.float64).reshape(-1, abi.MANIFOLD_P[manifold])
-        bw = np.ascontiguousarray(bw, dtype=np.float64)
-        c = pts.shape[0]
+        pp, c, bp = _host_belief(manifold, pts, bw)
         rec = np.zeros(1, dtype=self.CRED_REC)
         ld = np.zeros(self.N) if logdens else None
         od = np.zeros(self.N, dtype=np.int32) if order else None
         Q, first = _pack_queries([manifold], [queries if queries is not None else np.zeros((0, abi.MAXD))])
         qrecs = np.zeros(int(first[1]), dtype=self.CREDIBILITY_REC)
         opts = self._credible_opts(mass, probs)
-        self._check(self.lib.nbp_kde_credible(
-            self._ctx, manifold, pts.ctypes.data_as(dp), c, bw.ctypes.data_as(dp), int(mask), C.byref(opts), Q.ctypes.data_as(dp),
-            int(first[1]), rec.ctypes.data_as(C.POINTER(abi.CredibleRec)), ld.ctypes.data_as(dp) if logdens else None,
-            od.ctypes.data_as(ip) if order else None, qrecs.ctypes.data_as(C.POINTER(abi.CredibilityRec))))
+        self._check(self.lib.nbp_kde_credible(self._ctx, manifold, pp, c, bp, int(mask), C.byref(opts), _ptr(Q), int(first[1]),
+                                              _ptr(rec, abi.CredibleRec), _ptr(ld), _ptr(od), _ptr(qrecs, abi.CredibilityRec)))
         return rec[0], (ld[:c] if logdens else None), (od[:c] if order else None), (qrecs if queries is not None else None)
 
     # ---- heatmap densities (nbp_heatmap_*; heatmap.py) -------------------------------------------------------------------------

@@ -26,6 +26,7 @@ On a HIP backend both are one kernel launch for any number of resident beliefs (
 csrc/nbp_query.h).  `density_numpy` and `mmd_numpy` restate the definitions on the host and serve wherever no such backend is at
 hand (the CPU oracle has no such entry point)."""
 import math
+from contextlib import closing, contextmanager, nullcontext
 
 import numpy as np
 
@@ -111,17 +112,47 @@ def mmd_numpy(manifold, A, B, sigma=0.001):
     return saa / (n * n) + sbb / (m * m) - 2 * sab / (n * m)
 
 
-def _hip(backend, N, n_slots, method):
-    """(backend, whether it is ours to close) when `backend` names one that has `method`, else (None, False)"""
-    if backend is None:
-        return None, False
+@contextmanager
+def _backend(backend, N, n_slots, method, required=None):
+    """with _backend(...) as be: the backend a query runs on -- `backend` (class, factory or instance) where it has `method`, else
+    None: the numpy route.  One made here is closed on the way out, however the block ends.  required: the family has no host route
+    -- None means HipBackend, and a backend without `method` is a ValueError that opens with this text"""
     from .solver import _make_backend
-    be, own = _make_backend(backend, max(int(N), 8), n_slots)
-    if getattr(be, method, None) is None:
-        if own:
-            be.close()
-        return None, False
-    return be, own
+    be, own = (None, False) if backend is None and not required else _make_backend(backend, max(int(N), 8), n_slots)
+    with closing(be) if own else nullcontext():
+        if getattr(be, method, None) is not None:
+            yield be
+        elif required:
+            raise ValueError(f"{required}: the backend has no {method}")
+        else:
+            yield None
+
+
+def _bw(manifold, bw):
+    """a bandwidth of D entries: what a slot takes (entries a short bandwidth lacks are 0: unusable where the mask needs them)"""
+    D = abi.MANIFOLD_DIM[manifold]
+    out = np.zeros(D)
+    bw = np.asarray([] if bw is None else bw, dtype=np.float64).reshape(-1)[:D]
+    out[:len(bw)] = bw
+    return out
+
+
+def _bw_ones(manifold, bw):
+    """for the queries a bandwidth plays no part in: the slot of a belief that has none carries ones"""
+    return bw if bw is not None else np.ones(abi.MANIFOLD_DIM[manifold])
+
+
+@contextmanager
+def _staged(fg, labels, backend, method, bw=lambda manifold, bw: bw, required=None):
+    """with _staged(...) as (be, place): `_backend`, with the beliefs of the variables `labels` written to slots 0 .. L-1 by ONE
+    beliefs_write where there is a backend; place: label -> slot.  bw(manifold, v.bw): the bandwidth a slot is given (default: as
+    stored; `_bw_ones`; `_bw`)"""
+    vs = [fg.getVariable(v) for v in labels]
+    mans = [_manifold(v.varType) for v in vs]
+    with _backend(backend, max([len(v.val) for v in vs] + [1]), max(len(vs), 1), method, required) as be:
+        if be is not None and vs:
+            be.beliefs_write(list(range(len(vs))), mans, [(v.val, bw(m, v.bw), None) for v, m in zip(vs, mans)])
+        yield be, {v: i for i, v in enumerate(labels)}
 
 
 class Belief:
@@ -137,14 +168,10 @@ class Belief:
         `backend`: a HIP backend (class, factory or instance: nbp_kde_evaluate, through slot 0); anything without that entry
         point, or None: numpy."""
         Q = ppe_coords(self.manifold, np.asarray(pts, dtype=np.float64).reshape(-1, abi.MANIFOLD_P[self.manifold]))
-        be, own = _hip(backend, len(self.pts), 1, "kde_evaluate")
-        try:
+        with _backend(backend, len(self.pts), 1, "kde_evaluate") as be:
             if be is not None:
                 return be.kde_evaluate(self.manifold, self.pts, self.bw, Q)
             return density_numpy(self.manifold, ppe_coords(self.manifold, self.pts), self.bw, Q)
-        finally:
-            if own:
-                be.close()
 
     def marginal(self, dims):
         """belief.marginal(dims): the marginal density on the 1-BASED coordinates `dims` (marginal.py) -- callable at host points,
@@ -196,14 +223,10 @@ def mmd(p1, p2, varType, bw=(0.001,), backend=None):
     a = np.asarray(_points(p1), dtype=np.float64).reshape(-1, abi.MANIFOLD_P[man])
     b = np.asarray(_points(p2), dtype=np.float64).reshape(-1, abi.MANIFOLD_P[man])
     sigma = float(bw[0])
-    be, own = _hip(backend, max(len(a), len(b)), 2, "kde_mmd")
-    try:
+    with _backend(backend, max(len(a), len(b)), 2, "kde_mmd") as be:
         if be is not None:
             return be.kde_mmd(man, a, b, sigma)
         return mmd_numpy(man, ppe_coords(man, a), ppe_coords(man, b), sigma)
-    finally:
-        if own:
-            be.close()
 
 
 def isapproxBeliefs(p1, p2, varType, atol=1e-6, backend=None):
@@ -222,12 +245,8 @@ def mmdVariables(fgA, fgB, labels=None, bw=(0.001,), backend=None):
     sigma = float(bw[0])
     if L == 0:
         return labels, np.zeros(0)
-    be, own = _hip(backend, max(len(v.val) for v in va + vb), 2 * L, "run_mmd")
-    try:
+    with _backend(backend, max(len(v.val) for v in va + vb), 2 * L, "run_mmd") as be:
         if be is not None:
             be.beliefs_write(list(range(2 * L)), mans + mans, [(v.val, v.bw, None) for v in va + vb])
             return labels, be.run_mmd(list(range(L)), list(range(L, 2 * L)), mans, sigma)
         return labels, np.array([mmd_numpy(m, ppe_coords(m, a.val), ppe_coords(m, b.val), sigma) for m, a, b in zip(mans, va, vb)])
-    finally:
-        if own:
-            be.close()

@@ -31,7 +31,7 @@ import math
 import numpy as np
 
 from . import abi
-from .beliefquery import Belief, _hip, _manifold, _wrap
+from .beliefquery import Belief, _backend, _bw_ones, _manifold, _staged, _wrap
 from .ppe import _circular, _natural, mean_geodesic_walk, ppe_coords
 
 _LOG_SQRT_2PI_ARG = math.sqrt(2.0 * math.pi)
@@ -111,14 +111,10 @@ def calcMeanCovar(fg, label, backend=None):
     instance: computed on the device, nbp_kde_meancov through slot 0); anything without that entry point, or None: numpy."""
     v = fg.getVariable(label)
     man = v.varType.manifold
-    be, own = _hip(backend, len(v.val), 1, "kde_meancov")
-    try:
+    with _backend(backend, len(v.val), 1, "kde_meancov") as be:
         if be is not None:
             return be.kde_meancov(man, v.val)
         return meancov_numpy(man, v.val)
-    finally:
-        if own:
-            be.close()
 
 
 def calcMeanCovarAll(fg, labels=None, backend=None):
@@ -129,18 +125,12 @@ def calcMeanCovarAll(fg, labels=None, backend=None):
     if not vs:
         return {}
     mans = [v.varType.manifold for v in vs]
-    be, own = _hip(backend, max(len(v.val) for v in vs), len(vs), "run_meancov")
-    try:
+    with _staged(fg, labels, backend, "run_meancov", _bw_ones) as (be, _):
         if be is None:
             return {l: meancov_numpy(m, v.val) for l, m, v in zip(labels, mans, vs)}
-        be.beliefs_write(list(range(len(vs))), mans, [(v.val, v.bw if v.bw is not None else np.ones(abi.MANIFOLD_DIM[m]), None)
-                                                      for v, m in zip(vs, mans)])
         mean, cov = be.run_meancov(list(range(len(vs))), mans)
         dims = [abi.MANIFOLD_DIM[m] for m in mans]
         return {l: (mean[i, :D].copy(), cov[i, :D, :D].copy()) for i, (l, D) in enumerate(zip(labels, dims))}
-    finally:
-        if own:
-            be.close()
 
 
 def _points_bw(p, what):
@@ -159,16 +149,12 @@ def _kld_terms(p1, p2, varType, backend, what):
     D = abi.MANIFOLD_DIM[man]
     if len(bw_a) < D or len(bw_b) < D:
         raise ValueError(f"{what}: a bandwidth of {D} entries is needed")
-    be, own = _hip(backend, max(len(a), len(b)), 2, "kde_kld")
-    try:
+    with _backend(backend, max(len(a), len(b)), 2, "kde_kld") as be:
         if be is not None:
             val, tm = be.kde_kld(man, a, bw_a[:D], b, bw_b[:D], terms=True)
             return val, float(tm[0]), float(tm[1])
         eaa, eab = kld_terms_numpy(man, ppe_coords(man, a), bw_a, ppe_coords(man, b), bw_b)
         return eaa - eab, eaa, eab
-    finally:
-        if own:
-            be.close()
 
 
 def kld(p1, p2, varType, backend=None):

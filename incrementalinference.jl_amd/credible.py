@@ -41,8 +41,8 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import abi
-from .beliefquery import _manifold, _wrap
-from .overlap import _bw, _device, _write_all, dims_mask
+from .beliefquery import _backend, _bw, _manifold, _staged, _wrap
+from .overlap import dims_mask
 from .ppe import _circular, _natural, mean_geodesic_walk, ppe_coords
 
 _SQRT_2PI = 2.5066282746310002  # NBP_SQRT_2PI of csrc/nbp_kde.h
@@ -272,6 +272,9 @@ def query_points(manifold, dims, pts):
     return out, single
 
 
+_NO_HOST_ROUTE = "belief overlaps are computed by libnbp"  # (the wording these refusals have always had; beliefquery._backend)
+
+
 def region_columns(fg, labels, dims, place):
     """(slots, manifolds, masks) of run_credible for variable labels; place: label -> slot"""
     mans = [_manifold(fg.getVariable(v).varType) for v in labels]
@@ -287,13 +290,8 @@ def credibleRegionAll(fg, labels=None, mass=MASS, probs=PROBS, dims=None, backen
     if not labels:
         return {}
     cols = region_columns(fg, labels, dims, {v: i for i, v in enumerate(labels)})
-    be, own = _device(backend, max(len(fg.getVariable(v).val) for v in labels), len(labels), "run_credible")
-    try:
-        _write_all(be, fg, labels)
+    with _staged(fg, labels, backend, "run_credible", _bw, _NO_HOST_ROUTE) as (be, _):
         recs, ld, od, _, _ = be.run_credible(*cols, mass, probs)
-    finally:
-        if own:
-            be.close()
     return {v: region_from_records(m, mass, probs, recs[i], ld[i], od[i]) for i, (v, m) in enumerate(zip(labels, cols[1]))}
 
 
@@ -312,35 +310,22 @@ def credibility(fg, points, dims=None, backend=None):
         return {}
     cols = region_columns(fg, labels, dims, {v: i for i, v in enumerate(labels)})
     packed = [query_points(m, dims, points[v]) for v, m in zip(labels, cols[1])]
-    be, own = _device(backend, max(len(fg.getVariable(v).val) for v in labels), len(labels), "run_credible")
-    try:
-        _write_all(be, fg, labels)
+    with _staged(fg, labels, backend, "run_credible", _bw, _NO_HOST_ROUTE) as (be, _):
         _, _, _, qrecs, first = be.run_credible(*cols, (), (), [q for q, _ in packed], logdens=False, order=False)
-    finally:
-        if own:
-            be.close()
     return {v: credibility_from_records(qrecs[first[i]:first[i + 1]], packed[i][1]) for i, v in enumerate(labels)}
 
 
 def belief_credible(manifold, pts, bw, mass=MASS, probs=PROBS, dims=None, backend=None):
     """`Belief.credible`: the credible regions of a belief held on the host (nbp_kde_credible, through slot 0)"""
     mass, probs = _options(mass, probs)
-    be, own = _device(backend, len(pts), 1, "kde_credible")
-    try:
+    with _backend(backend, len(pts), 1, "kde_credible", _NO_HOST_ROUTE) as be:
         rec, ld, od, _ = be.kde_credible(manifold, pts, _bw(manifold, bw), dims_mask(manifold, dims), mass, probs)
-    finally:
-        if own:
-            be.close()
     return region_from_records(manifold, mass, probs, rec, ld, od)
 
 
 def belief_credibility(manifold, pts, bw, points, dims=None, backend=None):
     """`Belief.credibility`: the credibility of reference points under a belief held on the host (nbp_kde_credible)"""
     Q, single = query_points(manifold, dims, points)
-    be, own = _device(backend, len(pts), 1, "kde_credible")
-    try:
+    with _backend(backend, len(pts), 1, "kde_credible", _NO_HOST_ROUTE) as be:
         _, _, _, qrecs = be.kde_credible(manifold, pts, _bw(manifold, bw), dims_mask(manifold, dims), (), (), Q, logdens=False, order=False)
-    finally:
-        if own:
-            be.close()
     return credibility_from_records(qrecs, single)

@@ -16,7 +16,7 @@
 #include <rccl/rccl.h>  // types and prototypes only: the entry points are resolved with dlsym (see rccl_api)
 
 #ifndef NBP_TU
-#define NBP_TU 0  // host code: the kernels live in the nbp_k_*.hip files (-DNBP_TU=0x1FFFFF: single-file build with every kernel)
+#define NBP_TU 0  // host code: the kernels live in the nbp_k_*.hip files (-DNBP_TU=NBP_TU_ALL: single-file build with every kernel)
 #endif
 #include "nbp_kernels.h"
 #include "nbp_fused.h"
@@ -196,6 +196,7 @@ static const nbp_product_kernel_row NBP_PRODUCT_KERNELS[] = {
 static int manifold_dim_h(int m) { return m == NBP_SE2 ? 3 : (m == NBP_CIRCULAR ? 1 : m); }
 static int manifold_P_h(int m) { return m == NBP_SE2 ? 6 : manifold_dim_h(m); }
 static bool manifold_ok(int m) { return m >= NBP_EUCLID1 && m <= NBP_SE2; }
+static bool manifold_circ_h(int m, int d) { return (m == NBP_CIRCULAR && d == 0) || (m == NBP_SE2 && d == 2); }  // (is_circ of the device)
 static double wrap_h(double a) { return nbpm_wrap_pi(a); }  // (include/nbp_math.h)
 
 // ---- helpers of the batches over resident beliefs (used far below; the templates need C++ linkage, so they stand here) ----------
@@ -209,6 +210,12 @@ struct refusal {
   const char *what;  // nullptr: none
 };
 static refusal no_refusal(int) { return {NBP_OK, nullptr}; }
+// a coordinate bit mask (bit d = coordinate d) names at least one coordinate and none beyond the manifold's
+static refusal mask_refusal(int manifold, int32_t mask) {
+  if (mask == 0) return {NBP_ERR_RANGE, "empty mask"};
+  if (mask < 0 || (mask >> manifold_dim_h(manifold)) != 0) return {NBP_ERR_RANGE, "coordinate outside the manifold"};
+  return {NBP_OK, nullptr};
+}
 
 template <class K, class... A>
 static nbp_status launch_checked(nbp_ctx *c, K kernel, size_t blocks, int lanes, size_t lds, A... args) {
@@ -1664,7 +1671,9 @@ nbp_status nbp_run_copies_async(nbp_ctx *c, const nbp_copy_desc *descs, int32_t 
 // ---- batches over resident beliefs -------------------------------------------------------------------------------------------
 // Every nbp_run_* below is one sequence: the device selected and the columns checked (batch_check), the columns staged in
 // one copy and the result scratch reserved (stage_columns), one launch (launch_checked), the results copied back and the stream
-// waited for (query_fetch).  The nbp_kde_* forms put their host buffers into slot 0 (and 1) first (kde_check, kde_write).
+// waited for (query_fetch, scratch_layout::fetch).  The nbp_kde_* forms put their host buffers into slot 0 (and 1) first (kde_check,
+// kde_write), and EVERY REFUSAL OF SUCH A FORM COMES BEFORE SLOT 0 IS TOUCHED: what the batch form refuses in an element is one function
+// (grid_desc_check, credible_check, overlap_check, likelihood_check), which the host-buffer form calls on its own element before kde_write.
 // the scratch of the belief queries holds at least `doubles` (called with the stream idle: stage_upload has waited)
 static nbp_status query_reserve(nbp_ctx *c, size_t doubles) {
   if (doubles <= c->query_cap) return NBP_OK;
@@ -1703,6 +1712,34 @@ static nbp_status query_fetch(nbp_ctx *c, void *dst, const void *src, size_t byt
   return NBP_OK;
 }
 
+// The query scratch of one entry: parts in order, each `count` elements of `elem` bytes starting on a whole double, `to` where it goes
+// on the host (nullptr: nowhere).  total() is what stage_columns reserves; at(c, k) is part k on the device, asked for AFTER
+// stage_columns (which may move c->query); fetch() is the one copy back, from the first to the last part wanted, and the wait for it.
+struct scratch_layout {
+  struct part {
+    size_t elem, count;
+    void *to;
+  };
+  std::vector<part> parts;
+  std::vector<size_t> off;  // in doubles; one more than parts: the total
+  scratch_layout(std::initializer_list<part> ps) : parts(ps), off(1, 0) {
+    for (const part &p : parts) off.push_back(off.back() + (p.elem * p.count + 7) / 8);
+  }
+  size_t total() const { return off.back(); }
+  double *at(const nbp_ctx *c, size_t k) const { return c->query + off[k]; }
+  nbp_status fetch(nbp_ctx *c) const {
+    size_t first = parts.size(), last = 0;
+    for (size_t k = 0; k < parts.size(); k++)
+      if (parts[k].to) first = std::min(first, k), last = k;
+    if (first == last) return query_fetch(c, parts[first].to, c->query + off[first], parts[first].elem * parts[first].count);  // no detour
+    std::vector<double> back(off[last + 1] - off[first]);
+    NBPCHK(query_fetch(c, back.data(), c->query + off[first], sizeof(double) * back.size()));
+    for (size_t k = first; k <= last; k++)
+      if (parts[k].to) memcpy(parts[k].to, back.data() + (off[k] - off[first]), parts[k].elem * parts[k].count);
+    return NBP_OK;
+  }
+};
+
 // Host-buffer forms: the beliefs go through slot 0 (and slot 1), which they clobber.  bw == nullptr: the bandwidth plays no part
 // in the query, the slot carries ones.
 struct host_belief {
@@ -1720,9 +1757,8 @@ static nbp_status kde_check(const nbp_ctx *c, const char *who, int32_t manifold,
 static nbp_status kde_write(nbp_ctx *c, int32_t manifold, std::initializer_list<host_belief> bels) {
   const double ones[NBP_MAXD] = {1.0, 1.0, 1.0};
   int32_t slot = 0;
-  for (const host_belief &b : bels) {
-    NBPCHK(nbp_belief_write(c, slot++, manifold, b.pts, b.n, b.bw ? b.bw : ones, nullptr));
-  }
+  for (const host_belief &b : bels)
+    if (b.pts) NBPCHK(nbp_belief_write(c, slot++, manifold, b.pts, b.n, b.bw ? b.bw : ones, nullptr));  // (no points: a role a unary factor lacks)
   return NBP_OK;
 }
 static nbp_status kde_stage(nbp_ctx *c, const char *who, int32_t manifold, std::initializer_list<host_belief> bels) {
@@ -1749,11 +1785,12 @@ nbp_status nbp_run_ppe(nbp_ctx *c, const int32_t *slots, const int32_t *manifold
   if (n <= 0) return NBP_OK;
   NBPCHK(batch_check(c, "ppe", {slots}, manifolds, n, no_refusal));
   static_assert(sizeof(nbp_ppe_rec) % sizeof(double) == 0, "nbp_ppe_rec fills whole doubles of the query scratch");
-  const int32_t *d[2];
-  NBPCHK(stage_columns(c, {{slots, 4 * (size_t)n}, {manifolds, 4 * (size_t)n}}, d, (size_t)n * (sizeof(nbp_ppe_rec) / sizeof(double))));
-  NBPCHK(launch_checked(c, nbp_ppe_kernel, n, c->Npad, nbp_ppe_lds_bytes(c->N), d[0], d[1], c->arena, c->N, c->S, (nbp_ppe_rec *)c->query));
   std::vector<nbp_ppe_rec> rec((size_t)n);
-  NBPCHK(query_fetch(c, rec.data(), c->query, sizeof(nbp_ppe_rec) * (size_t)n));
+  const scratch_layout q{{sizeof(nbp_ppe_rec), (size_t)n, rec.data()}};
+  const int32_t *d[2];
+  NBPCHK(stage_columns(c, {{slots, 4 * (size_t)n}, {manifolds, 4 * (size_t)n}}, d, q.total()));
+  NBPCHK(launch_checked(c, nbp_ppe_kernel, n, c->Npad, nbp_ppe_lds_bytes(c->N), d[0], d[1], c->arena, c->N, c->S, (nbp_ppe_rec *)q.at(c, 0)));
+  NBPCHK(q.fetch(c));
   for (int i = 0; i < n; i++) {
     for (int k = 0; k < NBP_MAXD; k++) {
       mean_out[(size_t)i * NBP_MAXD + k] = rec[i].mean[k];
@@ -1842,8 +1879,7 @@ static nbp_status grid_desc_check(const nbp_ctx *c, const nbp_grid_desc &g, int 
     if (g.dims[a] < 0 || g.dims[a] >= D) return fail(NBP_ERR_RANGE, who + "coordinate outside the manifold");
     if (a == 1 && g.dims[1] == g.dims[0]) return fail(NBP_ERR_RANGE, who + "repeated coordinate");
     if (g.n[a] < 1 || g.n[a] > NBP_GRID_MAX) return fail(NBP_ERR_RANGE, who + "n outside 1 .. " + std::to_string(NBP_GRID_MAX));
-    const bool circ = (g.manifold == NBP_CIRCULAR && g.dims[a] == 0) || (g.manifold == NBP_SE2 && g.dims[a] == 2);
-    if (autoext && !circ && g.n[a] < 2) return fail(NBP_ERR_RANGE, who + "automatic extent of a Euclidean axis needs n >= 2");
+    if (autoext && !manifold_circ_h(g.manifold, g.dims[a]) && g.n[a] < 2) return fail(NBP_ERR_RANGE, who + "automatic extent of a Euclidean axis needs n >= 2");
     if (!autoext && !(std::isfinite(g.lo[a]) && std::isfinite(g.step[a]))) return fail(NBP_ERR_RANGE, who + "lo / step not finite");
     pts *= g.n[a];
   }
@@ -1914,10 +1950,7 @@ nbp_status nbp_run_evaluate_marginal(nbp_ctx *c, const int32_t *slots, const int
   if (n <= 0) return NBP_OK;
   if (q_first[0] != 0) return fail(NBP_ERR_ARG, "evaluate marginal: q_first[0] must be 0");
   NBPCHK(batch_check(c, "evaluate marginal", {slots}, manifolds, n, [&](int i) {
-    if (q_first[i + 1] < q_first[i]) return refusal{NBP_ERR_ARG, "q_first must not decrease"};
-    if (masks[i] == 0) return refusal{NBP_ERR_RANGE, "empty mask"};
-    if (masks[i] < 0 || (masks[i] >> manifold_dim_h(manifolds[i])) != 0) return refusal{NBP_ERR_RANGE, "coordinate outside the manifold"};
-    return refusal{NBP_OK, nullptr};
+    return q_first[i + 1] < q_first[i] ? refusal{NBP_ERR_ARG, "q_first must not decrease"} : mask_refusal(manifolds[i], masks[i]);
   }));
   return run_point_density(c, slots, manifolds, masks, n, q_first, queries, dens_out);
 }
@@ -1952,12 +1985,13 @@ nbp_status nbp_run_meancov(nbp_ctx *c, const int32_t *slots, const int32_t *mani
   if (n <= 0) return NBP_OK;
   NBPCHK(batch_check(c, "meancov", {slots}, manifolds, n, no_refusal));
   static_assert(sizeof(nbp_meancov_rec) == sizeof(double) * (NBP_MAXD + NBP_MAXD * NBP_MAXD), "nbp_meancov_rec is packed doubles");
-  const int32_t *d[2];
-  NBPCHK(stage_columns(c, {{slots, 4 * (size_t)n}, {manifolds, 4 * (size_t)n}}, d, (size_t)n * (sizeof(nbp_meancov_rec) / sizeof(double))));
-  NBPCHK(launch_checked(c, nbp_meancov_kernel, n, c->Npad, nbp_meancov_lds_bytes(c->N), d[0], d[1], c->arena, c->N, c->S,
-                      (nbp_meancov_rec *)c->query));
   std::vector<nbp_meancov_rec> rec((size_t)n);
-  NBPCHK(query_fetch(c, rec.data(), c->query, sizeof(nbp_meancov_rec) * (size_t)n));
+  const scratch_layout q{{sizeof(nbp_meancov_rec), (size_t)n, rec.data()}};
+  const int32_t *d[2];
+  NBPCHK(stage_columns(c, {{slots, 4 * (size_t)n}, {manifolds, 4 * (size_t)n}}, d, q.total()));
+  NBPCHK(launch_checked(c, nbp_meancov_kernel, n, c->Npad, nbp_meancov_lds_bytes(c->N), d[0], d[1], c->arena, c->N, c->S,
+                        (nbp_meancov_rec *)q.at(c, 0)));
+  NBPCHK(q.fetch(c));
   for (int i = 0; i < n; i++) {
     memcpy(mean_out + (size_t)i * NBP_MAXD, rec[i].mean, sizeof(rec[i].mean));
     memcpy(cov_out + (size_t)i * NBP_MAXD * NBP_MAXD, rec[i].cov, sizeof(rec[i].cov));
@@ -1988,12 +2022,12 @@ nbp_status nbp_run_kld(nbp_ctx *c, const int32_t *slots_a, const int32_t *slots_
   if (n <= 0) return NBP_OK;
   NBPCHK(batch_check(c, "kld", {slots_a, slots_b}, manifolds, n, no_refusal));
   static_assert(sizeof(nbp_kld_rec) == sizeof(double) * 3, "nbp_kld_rec is packed doubles");
-  const int32_t *d[3];
-  NBPCHK(stage_columns(c, {{slots_a, 4 * (size_t)n}, {slots_b, 4 * (size_t)n}, {manifolds, 4 * (size_t)n}}, d, (size_t)n * 3));
-  NBPCHK(launch_checked(c, nbp_kld_kernel, n, c->Npad, nbp_kld_lds_bytes(c->N), d[0], d[1], d[2], c->arena, c->N, c->S,
-                      (nbp_kld_rec *)c->query));
   std::vector<nbp_kld_rec> rec((size_t)n);
-  NBPCHK(query_fetch(c, rec.data(), c->query, sizeof(nbp_kld_rec) * (size_t)n));
+  const scratch_layout q{{sizeof(nbp_kld_rec), (size_t)n, rec.data()}};
+  const int32_t *d[3];
+  NBPCHK(stage_columns(c, {{slots_a, 4 * (size_t)n}, {slots_b, 4 * (size_t)n}, {manifolds, 4 * (size_t)n}}, d, q.total()));
+  NBPCHK(launch_checked(c, nbp_kld_kernel, n, c->Npad, nbp_kld_lds_bytes(c->N), d[0], d[1], d[2], c->arena, c->N, c->S, (nbp_kld_rec *)q.at(c, 0)));
+  NBPCHK(q.fetch(c));
   for (int i = 0; i < n; i++) {
     kld_out[i] = rec[i].kld;
     if (terms_out) {
@@ -2014,24 +2048,27 @@ nbp_status nbp_kde_kld(nbp_ctx *c, int32_t manifold, const double *a, int32_t na
 }
 
 // ---- belief overlaps (nbp_overlap.h) ---------------------------------------------------------------------------------------------
-// the kinds of a mask's coordinates in ascending order, one bit per position (1: circular), behind the length in bits 4 and up; -1:
-// an empty mask, -2: a coordinate outside the manifold
+// the kinds of a mask's coordinates (mask_refusal has let it pass) in ascending order: one bit each (1: circular), behind the length << 4
 static int overlap_kinds(int32_t manifold, int32_t mask) {
-  if (mask == 0) return -1;
-  const int D = manifold_dim_h(manifold);
-  if (mask < 0 || (mask >> D) != 0) return -2;
   int kinds = 0, len = 0;
-  for (int d = 0; d < D; d++)
+  for (int d = 0; d < manifold_dim_h(manifold); d++)
     if (mask >> d & 1) {
-      if ((manifold == NBP_CIRCULAR && d == 0) || (manifold == NBP_SE2 && d == 2)) kinds |= 1 << len;
+      if (manifold_circ_h(manifold, d)) kinds |= 1 << len;
       len++;
     }
   return kinds | len << 4;
 }
-static refusal overlap_mask_refusal(int kinds) {
-  if (kinds == -1) return refusal{NBP_ERR_RANGE, "empty mask"};
-  if (kinds == -2) return refusal{NBP_ERR_RANGE, "coordinate outside the manifold"};
-  return refusal{NBP_OK, nullptr};
+// what both forms of the pair entry refuse, pair by pair
+static nbp_status overlap_check(nbp_ctx *c, const int32_t *slots_a, const int32_t *slots_b, const int32_t *manifolds_a,
+                                const int32_t *manifolds_b, const int32_t *masks_a, const int32_t *masks_b, int32_t n) {
+  return batch_check(c, "overlap", {slots_a, slots_b}, manifolds_a, n, [&](int i) {
+    if (!manifold_ok(manifolds_b[i])) return refusal{NBP_ERR_ARG, "unknown manifold"};
+    for (const refusal &r : {mask_refusal(manifolds_a[i], masks_a[i]), mask_refusal(manifolds_b[i], masks_b[i])})
+      if (r.what) return r;
+    if (overlap_kinds(manifolds_a[i], masks_a[i]) != overlap_kinds(manifolds_b[i], masks_b[i]))
+      return refusal{NBP_ERR_ARG, "inadmissible pair: the masked coordinates differ in number or kind"};
+    return refusal{NBP_OK, nullptr};
+  });
 }
 
 // the overlap coefficient of pairs of beliefs resident in slots: one workgroup per pair (nbp_overlap.h), one copy back
@@ -2040,14 +2077,7 @@ nbp_status nbp_run_overlap(nbp_ctx *c, const int32_t *slots_a, const int32_t *sl
   if (!c || ((!slots_a || !slots_b || !manifolds_a || !manifolds_b || !masks_a || !masks_b || !recs_out) && n > 0))
     return fail(NBP_ERR_ARG, "null argument");
   if (n <= 0) return NBP_OK;
-  NBPCHK(batch_check(c, "overlap", {slots_a, slots_b}, manifolds_a, n, [&](int i) {
-    if (!manifold_ok(manifolds_b[i])) return refusal{NBP_ERR_ARG, "unknown manifold"};
-    const int ka = overlap_kinds(manifolds_a[i], masks_a[i]), kb = overlap_kinds(manifolds_b[i], masks_b[i]);
-    if (ka < 0) return overlap_mask_refusal(ka);
-    if (kb < 0) return overlap_mask_refusal(kb);
-    if (ka != kb) return refusal{NBP_ERR_ARG, "inadmissible pair: the masked coordinates differ in number or kind"};
-    return refusal{NBP_OK, nullptr};
-  }));
+  NBPCHK(overlap_check(c, slots_a, slots_b, manifolds_a, manifolds_b, masks_a, masks_b, n));
   static_assert(sizeof(nbp_overlap_rec) == sizeof(double) * 4, "nbp_overlap_rec is packed doubles");
   const int32_t *d[6];
   const size_t col = 4 * (size_t)n;
@@ -2063,14 +2093,11 @@ nbp_status nbp_kde_overlap(nbp_ctx *c, int32_t manifold_a, const double *a, int3
                            int32_t manifold_b, const double *b, int32_t nb, const double *bw_b, int32_t mask_b, nbp_overlap_rec *rec_out) {
   if (!c || !a || !bw_a || !b || !bw_b || !rec_out) return fail(NBP_ERR_ARG, "null argument");
   NBPCHK(kde_check(c, "overlap", manifold_a, {{a, na, bw_a}, {b, nb, bw_b}}));
-  if (!manifold_ok(manifold_b)) return fail(NBP_ERR_ARG, "overlap: unknown manifold");
-  const int ka = overlap_kinds(manifold_a, mask_a), kb = overlap_kinds(manifold_b, mask_b);
-  for (int k : {ka, kb})
-    if (k < 0) return fail(NBP_ERR_RANGE, std::string("overlap: belief 0: ") + overlap_mask_refusal(k).what);
-  if (ka != kb) return fail(NBP_ERR_ARG, "overlap: belief 0: inadmissible pair: the masked coordinates differ in number or kind");
+  if (!manifold_ok(manifold_b)) return fail(NBP_ERR_ARG, "overlap: unknown manifold");  // (kde_check's wording, for the second belief)
+  const int32_t sa = 0, sb = 1;
+  NBPCHK(overlap_check(c, &sa, &sb, &manifold_a, &manifold_b, &mask_a, &mask_b, 1));
   NBPCHK(nbp_belief_write(c, 0, manifold_a, a, na, bw_a, nullptr));
   NBPCHK(nbp_belief_write(c, 1, manifold_b, b, nb, bw_b, nullptr));
-  const int32_t sa = 0, sb = 1;
   return nbp_run_overlap(c, &sa, &sb, &manifold_a, &manifold_b, &mask_a, &mask_b, 1, rec_out);
 }
 
@@ -2099,32 +2126,25 @@ nbp_status nbp_run_overlap_search(nbp_ctx *c, const int32_t *slots, const int32_
   if (n <= 0) return NBP_OK;
   int first = 0;
   NBPCHK(batch_check(c, "overlap search", {slots}, manifolds, n, [&](int i) {
+    const refusal r = mask_refusal(manifolds[i], masks[i]);
+    if (r.what) return r;
     const int k = overlap_kinds(manifolds[i], masks[i]);
-    if (k < 0) return overlap_mask_refusal(k);
     if (i == 0) first = k;
-    if (k != first) return refusal{NBP_ERR_ARG, "not admissible against belief 0: the masked coordinates differ in number or kind"};
-    return refusal{NBP_OK, nullptr};
+    return k != first ? refusal{NBP_ERR_ARG, "not admissible against belief 0: the masked coordinates differ in number or kind"} : r;
   }));
-  // the query scratch: prep[n] | logc[n topk] | idx[n topk] found[n] evaluated[n] (the last three int32: one copy back from logc on)
+  // the query scratch: prep[n] | logc[n topk] | idx[n topk] | found[n] | evaluated[n] (the last three int32): one copy back from logc on
   static_assert(sizeof(nbp_overlap_prep) % sizeof(double) == 0, "nbp_overlap_prep fills whole doubles of the query scratch");
-  const size_t V = (size_t)n, K = (size_t)o.topk, prep_d = V * (sizeof(nbp_overlap_prep) / sizeof(double));
-  const size_t ints = V * K + 2 * V, out_d = V * K + (ints + 1) / 2;
+  const size_t V = (size_t)n, K = (size_t)o.topk;
+  const scratch_layout q{{sizeof(nbp_overlap_prep), V, nullptr}, {sizeof(double), V * K, logc_out}, {4, V * K, idx_out}, {4, V, found_out},
+                         {4, V, evaluated_out}};
   const int32_t *d[3];
-  NBPCHK(stage_columns(c, {{slots, 4 * V}, {manifolds, 4 * V}, {masks, 4 * V}}, d, prep_d + out_d));
-  nbp_overlap_prep *prep = (nbp_overlap_prep *)c->query;
-  double *dlogc = c->query + prep_d;
-  int32_t *didx = (int32_t *)(dlogc + V * K), *dfound = didx + V * K, *deval = dfound + V;
-  NBPCHK(launch_checked(c, nbp_overlap_prep_kernel, V, c->Npad, nbp_overlap_prep_lds_bytes(c->N), d[0], d[1], d[2], c->arena, c->N, c->S, prep));
+  NBPCHK(stage_columns(c, {{slots, 4 * V}, {manifolds, 4 * V}, {masks, 4 * V}}, d, q.total()));
+  NBPCHK(launch_checked(c, nbp_overlap_prep_kernel, V, c->Npad, nbp_overlap_prep_lds_bytes(c->N), d[0], d[1], d[2], c->arena, c->N, c->S,
+                        (nbp_overlap_prep *)q.at(c, 0)));
   NBPCHK(launch_checked(c, nbp_overlap_search_kernel, V, c->Npad, nbp_overlap_search_lds_bytes(c->N), d[0], d[1], d[2], n, c->arena, c->N,
-                        c->S, (const nbp_overlap_prep *)prep, o.reach * o.reach, std::log(o.min_coeff), o.topk, didx, dlogc, dfound, deval));
-  std::vector<double> back(out_d);
-  NBPCHK(query_fetch(c, back.data(), dlogc, sizeof(double) * out_d));
-  memcpy(logc_out, back.data(), sizeof(double) * V * K);
-  const int32_t *bi = (const int32_t *)(back.data() + V * K);
-  memcpy(idx_out, bi, 4 * V * K);
-  memcpy(found_out, bi + V * K, 4 * V);
-  memcpy(evaluated_out, bi + V * K + V, 4 * V);
-  return NBP_OK;
+                        c->S, (const nbp_overlap_prep *)q.at(c, 0), o.reach * o.reach, std::log(o.min_coeff), o.topk, (int32_t *)q.at(c, 2),
+                        q.at(c, 1), (int32_t *)q.at(c, 3), (int32_t *)q.at(c, 4)));
+  return q.fetch(c);
 }
 
 // ---- credible regions (nbp_credible.h) -------------------------------------------------------------------------------------------
@@ -2140,6 +2160,25 @@ static nbp_status credible_opts_check(const nbp_credible_opts *o) {
   return NBP_OK;
 }
 
+// what both forms of the credible entry refuse: the options, then belief by belief the mask and the queries
+static nbp_status credible_check(nbp_ctx *c, const int32_t *slots, const int32_t *manifolds, const int32_t *masks, int32_t n,
+                                 const nbp_credible_opts *opts, const int32_t *q_first, const double *queries,
+                                 const nbp_credibility_rec *qrec_out) {
+  NBPCHK(credible_opts_check(opts));
+  if (q_first && q_first[0] != 0) return fail(NBP_ERR_RANGE, "credible: belief 0: q_first must ascend from 0");
+  return batch_check(c, "credible", {slots}, manifolds, n, [&](int i) {
+    const refusal r = mask_refusal(manifolds[i], masks[i]);
+    if (r.what || !q_first) return r;
+    if (q_first[i + 1] < q_first[i]) return refusal{NBP_ERR_RANGE, "q_first must ascend from 0"};
+    if (q_first[i + 1] > q_first[i] && (!queries || !qrec_out)) return refusal{NBP_ERR_ARG, "null argument"};
+    for (int32_t q = q_first[i]; q < q_first[i + 1]; q++)
+      for (int d = 0; d < NBP_MAXD; d++)
+        if ((masks[i] >> d & 1) && !std::isfinite(queries[(size_t)q * NBP_MAXD + d]))
+          return refusal{NBP_ERR_RANGE, "a query entry is not finite"};
+    return refusal{NBP_OK, nullptr};
+  });
+}
+
 // HDR levels, credibility of reference points and coordinate quantiles of beliefs resident in slots: one workgroup per belief
 // (nbp_credible.h).  Columns, options and queries go up in one staging copy; records, query records and the optional per-particle
 // outputs come back in one copy.
@@ -2148,44 +2187,22 @@ nbp_status nbp_run_credible(nbp_ctx *c, const int32_t *slots, const int32_t *man
                             double *logdens_out, int32_t *order_out, nbp_credibility_rec *qrec_out) {
   if (!c || ((!slots || !manifolds || !masks || !opts || !rec_out) && n > 0)) return fail(NBP_ERR_ARG, "null argument");
   if (n <= 0) return NBP_OK;
-  NBPCHK(credible_opts_check(opts));
-  if (q_first && q_first[0] != 0) return fail(NBP_ERR_RANGE, "credible: belief 0: q_first must ascend from 0");
-  NBPCHK(batch_check(c, "credible", {slots}, manifolds, n, [&](int i) {
-    if (masks[i] == 0) return refusal{NBP_ERR_RANGE, "empty mask"};
-    if (masks[i] < 0 || (masks[i] >> manifold_dim_h(manifolds[i])) != 0) return refusal{NBP_ERR_RANGE, "coordinate outside the manifold"};
-    if (!q_first) return refusal{NBP_OK, nullptr};
-    if (q_first[i + 1] < q_first[i]) return refusal{NBP_ERR_RANGE, "q_first must ascend from 0"};
-    if (q_first[i + 1] > q_first[i] && (!queries || !qrec_out)) return refusal{NBP_ERR_ARG, "null argument"};
-    for (int32_t q = q_first[i]; q < q_first[i + 1]; q++)
-      for (int d = 0; d < NBP_MAXD; d++)
-        if ((masks[i] >> d & 1) && !std::isfinite(queries[(size_t)q * NBP_MAXD + d]))
-          return refusal{NBP_ERR_RANGE, "a query entry is not finite"};
-    return refusal{NBP_OK, nullptr};
-  }));
+  NBPCHK(credible_check(c, slots, manifolds, masks, n, opts, q_first, queries, qrec_out));
   static_assert(sizeof(nbp_credible_rec) % sizeof(double) == 0 && sizeof(nbp_credibility_rec) % sizeof(double) == 0,
                 "the credible records fill whole doubles of the query scratch");
   static_assert(sizeof(nbp_credible_opts) % sizeof(double) == 0, "nbp_credible_opts fills whole doubles of the staging copy");
   const size_t V = (size_t)n, Q = q_first ? (size_t)q_first[n] : 0, N = (size_t)c->N;
   // the query scratch: rec[n] | qrec[Q] | logdens[n N] | order[n N] (int32); the last two only where the caller asks for them
-  const size_t rec_d = V * (sizeof(nbp_credible_rec) / sizeof(double)), qrec_d = Q * (sizeof(nbp_credibility_rec) / sizeof(double));
-  const size_t ld_d = logdens_out ? V * N : 0, ord_d = order_out ? (V * N + 1) / 2 : 0, all_d = rec_d + qrec_d + ld_d + ord_d;
+  const scratch_layout q{{sizeof(nbp_credible_rec), V, rec_out}, {sizeof(nbp_credibility_rec), Q, qrec_out},
+                         {sizeof(double), logdens_out ? V * N : 0, logdens_out}, {4, order_out ? V * N : 0, order_out}};
   const int32_t *d[6];
   NBPCHK(stage_columns(c, {{slots, 4 * V}, {manifolds, 4 * V}, {masks, 4 * V}, {opts, sizeof(nbp_credible_opts)},
-                           {q_first, q_first ? 4 * (V + 1) : 0}, {queries, sizeof(double) * NBP_MAXD * Q}}, d, all_d));
-  nbp_credible_rec *drec = (nbp_credible_rec *)c->query;
-  nbp_credibility_rec *dqrec = (nbp_credibility_rec *)(c->query + rec_d);
-  double *dld = c->query + rec_d + qrec_d;
-  int32_t *dord = (int32_t *)(dld + ld_d);
+                           {q_first, q_first ? 4 * (V + 1) : 0}, {queries, sizeof(double) * NBP_MAXD * Q}}, d, q.total()));
   NBPCHK(launch_checked(c, nbp_credible_kernel, V, c->Npad, nbp_credible_lds_bytes(c->N), d[0], d[1], d[2], (const nbp_credible_opts *)d[3],
-                        q_first ? d[4] : (const int32_t *)nullptr, (const double *)d[5], c->arena, c->N, c->S, drec,
-                        logdens_out ? dld : (double *)nullptr, order_out ? dord : (int32_t *)nullptr, dqrec));
-  std::vector<double> back(all_d);
-  NBPCHK(query_fetch(c, back.data(), c->query, sizeof(double) * all_d));
-  memcpy(rec_out, back.data(), sizeof(double) * rec_d);
-  if (Q) memcpy(qrec_out, back.data() + rec_d, sizeof(double) * qrec_d);
-  if (logdens_out) memcpy(logdens_out, back.data() + rec_d + qrec_d, sizeof(double) * V * N);
-  if (order_out) memcpy(order_out, back.data() + rec_d + qrec_d + ld_d, 4 * V * N);
-  return NBP_OK;
+                        q_first ? d[4] : (const int32_t *)nullptr, (const double *)d[5], c->arena, c->N, c->S, (nbp_credible_rec *)q.at(c, 0),
+                        logdens_out ? q.at(c, 2) : (double *)nullptr, order_out ? (int32_t *)q.at(c, 3) : (int32_t *)nullptr,
+                        (nbp_credibility_rec *)q.at(c, 1)));
+  return q.fetch(c);
 }
 
 // host-buffer form: stages through slot 0 (which it clobbers), like nbp_kde_meancov; everything is checked before slot 0 is touched
@@ -2195,16 +2212,10 @@ nbp_status nbp_kde_credible(nbp_ctx *c, int32_t manifold, const double *pts, int
   if (!c || !pts || !bw || !opts || !rec_out || ((!queries || !qrec_out) && nq > 0)) return fail(NBP_ERR_ARG, "null argument");
   NBPCHK(kde_check(c, "credible", manifold, {{pts, n_pts, bw}}));
   if (nq < 0) return fail(NBP_ERR_ARG, "credible: nq < 0");
-  NBPCHK(credible_opts_check(opts));
-  if (mask == 0) return fail(NBP_ERR_RANGE, "credible: belief 0: empty mask");
-  if (mask < 0 || (mask >> manifold_dim_h(manifold)) != 0) return fail(NBP_ERR_RANGE, "credible: belief 0: coordinate outside the manifold");
-  for (int32_t q = 0; q < nq; q++)
-    for (int d = 0; d < NBP_MAXD; d++)
-      if ((mask >> d & 1) && !std::isfinite(queries[(size_t)q * NBP_MAXD + d]))
-        return fail(NBP_ERR_RANGE, "credible: belief 0: a query entry is not finite");
+  const int32_t slot = 0, q_first[2] = {0, nq};
+  NBPCHK(credible_check(c, &slot, &manifold, &mask, 1, opts, q_first, queries, qrec_out));
   // (a bandwidth entry outside the mask is not read by the kernel, but the slot write wants a full vector: the caller's is passed on)
   NBPCHK(kde_write(c, manifold, {{pts, n_pts, bw}}));
-  const int32_t slot = 0, q_first[2] = {0, nq};
   return nbp_run_credible(c, &slot, &manifold, &mask, 1, opts, q_first, queries, rec_out, logdens_out, order_out, qrec_out);
 }
 
@@ -2231,23 +2242,18 @@ nbp_status nbp_run_modes(nbp_ctx *c, const int32_t *slots, const int32_t *manifo
   NBPCHK(modes_opts_check(opts, &o));
   NBPCHK(batch_check(c, "modes", {slots}, manifolds, n, no_refusal));
   static_assert(sizeof(nbp_mode_rec) % sizeof(double) == 0, "nbp_mode_rec fills whole doubles of the query scratch");
-  const size_t hdr_d = (size_t)n, rec_d = (size_t)n * NBP_MODES_MAX * (sizeof(nbp_mode_rec) / sizeof(double));
-  const size_t row_d = ((size_t)n * (size_t)c->N + 1) / 2;
+  const size_t V = (size_t)n, rows = V * (size_t)c->N;
+  std::vector<int32_t> hh(2 * V);
+  const scratch_layout q{{4, 2 * V, hh.data()}, {sizeof(nbp_mode_rec), V * NBP_MODES_MAX, recs_out}, {4, rows, labels_out}, {4, rows, iters_out}};
   const int32_t *d[2];
-  NBPCHK(stage_columns(c, {{slots, 4 * (size_t)n}, {manifolds, 4 * (size_t)n}}, d, hdr_d + rec_d + 2 * row_d));
-  int32_t *dh = (int32_t *)c->query, *dl = (int32_t *)(c->query + hdr_d + rec_d), *di = (int32_t *)(c->query + hdr_d + rec_d + row_d);
+  NBPCHK(stage_columns(c, {{slots, 4 * V}, {manifolds, 4 * V}}, d, q.total()));
   NBPCHK(launch_checked(c, nbp_modes_kernel, n, c->Npad, nbp_modes_lds_bytes(c->N), d[0], d[1], c->arena, c->N, c->S, o,
-                        (nbp_mode_rec *)(c->query + hdr_d), dh, dl, di));
-  std::vector<double> back(hdr_d + rec_d + (iters_out ? 2 * row_d : (labels_out ? row_d : 0)));
-  NBPCHK(query_fetch(c, back.data(), c->query, sizeof(double) * back.size()));
-  const int32_t *hh = (const int32_t *)back.data();
+                        (nbp_mode_rec *)q.at(c, 1), (int32_t *)q.at(c, 0), (int32_t *)q.at(c, 2), (int32_t *)q.at(c, 3)));
+  NBPCHK(q.fetch(c));
   for (int i = 0; i < n; i++) {
     n_modes_out[i] = hh[2 * i];
     if (n_unconverged_out) n_unconverged_out[i] = hh[2 * i + 1];
   }
-  memcpy(recs_out, back.data() + hdr_d, sizeof(double) * rec_d);
-  if (labels_out) memcpy(labels_out, back.data() + hdr_d + rec_d, sizeof(int32_t) * (size_t)n * (size_t)c->N);
-  if (iters_out) memcpy(iters_out, back.data() + hdr_d + rec_d + row_d, sizeof(int32_t) * (size_t)n * (size_t)c->N);
   return NBP_OK;
 }
 
@@ -2305,18 +2311,13 @@ nbp_status nbp_run_mixture(nbp_ctx *c, const int32_t *slots, const int32_t *mani
     memcpy(rows.data() + i * N, labels + (size_t)row[i] * N, 4 * N);
   }
   static_assert(sizeof(nbp_mixture_rec) % sizeof(double) == 0, "nbp_mixture_rec fills whole doubles of the query scratch");
-  const size_t rec_d = V * (sizeof(nbp_mixture_rec) / sizeof(double)), lab_d = labels_out ? (V * N + 1) / 2 : 0;
+  const scratch_layout q{{sizeof(nbp_mixture_rec), V, recs_out}, {4, labels_out ? V * N : 0, labels_out}};
   const int32_t *d[4];
   NBPCHK(stage_columns(c, {{slots, 4 * V}, {manifolds, 4 * V}, {rows.data(), 4 * V * N}, {init_mean, sizeof(double) * NBP_MIX_MAX * NBP_MAXD * V}},
-                       d, rec_d + lab_d));
-  int32_t *dlab = (int32_t *)(c->query + rec_d);
+                       d, q.total()));
   NBPCHK(launch_checked(c, nbp_mixture_kernel, V, c->Npad, nbp_mixture_lds_bytes(c->N), d[0], d[1], d[2], (const double *)d[3], c->arena, c->N,
-                        c->S, o, (nbp_mixture_rec *)c->query, labels_out ? dlab : (int32_t *)nullptr));
-  std::vector<double> back(rec_d + lab_d);
-  NBPCHK(query_fetch(c, back.data(), c->query, sizeof(double) * back.size()));
-  memcpy(recs_out, back.data(), sizeof(double) * rec_d);
-  if (labels_out) memcpy(labels_out, back.data() + rec_d, 4 * V * N);
-  return NBP_OK;
+                        c->S, o, (nbp_mixture_rec *)q.at(c, 0), labels_out ? (int32_t *)q.at(c, 1) : (int32_t *)nullptr));
+  return q.fetch(c);
 }
 
 // host-buffer form: stages through slot 0 (which it clobbers), like nbp_kde_modes; everything is checked before slot 0 is touched.
@@ -2409,12 +2410,13 @@ nbp_status nbp_run_factor_likelihood(nbp_ctx *c, const nbp_likelihood_desc *desc
   NBPCHK(likelihood_check(c, descs, n));
   static_assert(sizeof(nbp_likelihood_rec) == sizeof(double) * (1 + NBP_MAXC), "nbp_likelihood_rec is packed doubles");
   static_assert(sizeof(nbp_likelihood_desc) % 8 == 0, "nbp_likelihood_desc keeps its doubles aligned in an array");
-  const int32_t *d[1];
-  NBPCHK(stage_columns(c, {{descs, sizeof(nbp_likelihood_desc) * (size_t)n}}, d, (size_t)n * (1 + NBP_MAXC)));
-  NBPCHK(launch_checked(c, nbp_likelihood_kernel, n, c->Npad, nbp_likelihood_lds_bytes(c->N), (const nbp_likelihood_desc *)d[0], c->arena,
-                        c->N, c->S, (nbp_likelihood_rec *)c->query));
   std::vector<nbp_likelihood_rec> rec((size_t)n);
-  NBPCHK(query_fetch(c, rec.data(), c->query, sizeof(nbp_likelihood_rec) * (size_t)n));
+  const scratch_layout q{{sizeof(nbp_likelihood_rec), (size_t)n, rec.data()}};
+  const int32_t *d[1];
+  NBPCHK(stage_columns(c, {{descs, sizeof(nbp_likelihood_desc) * (size_t)n}}, d, q.total()));
+  NBPCHK(launch_checked(c, nbp_likelihood_kernel, n, c->Npad, nbp_likelihood_lds_bytes(c->N), (const nbp_likelihood_desc *)d[0], c->arena,
+                        c->N, c->S, (nbp_likelihood_rec *)q.at(c, 0)));
+  NBPCHK(q.fetch(c));
   for (int i = 0; i < n; i++) {
     loglik_out[i] = rec[i].loglik;
     if (comp_loglik_out)
@@ -2423,26 +2425,33 @@ nbp_status nbp_run_factor_likelihood(nbp_ctx *c, const nbp_likelihood_desc *desc
   return NBP_OK;
 }
 
+// the opening of both host-buffer forms: *p = the descriptor aimed at slot 0 (and 1: *unary false), checked as its batch form checks it
+static nbp_status likelihood_host_desc(nbp_ctx *c, const char *who, const nbp_likelihood_desc *desc, const double *a, int32_t na,
+                                       const double *b, int32_t nb, const void *out, nbp_likelihood_desc *p, bool *unary) {
+  if (!c || !desc || !a || !out || (desc->kind != NBP_F_PRIOR && !b)) return fail(NBP_ERR_ARG, "null argument");
+  *p = *desc;
+  *unary = p->kind == NBP_F_PRIOR;
+  p->slot_a = 0;
+  p->slot_b = *unary ? -1 : 1;
+  if (!*unary && c->n_slots < 2) return fail(NBP_ERR_RANGE, std::string(who) + ": the context needs two slots");
+  NBPCHK(likelihood_check(c, p, 1));
+  if (na < 0 || (!*unary && nb < 0)) return fail(NBP_ERR_ARG, std::string(who) + ": a negative count");
+  return NBP_OK;
+}
+
 // host-buffer form: stages through slots 0 and 1 (which it clobbers), like nbp_kde_kld; the descriptor's own slots are not read
 nbp_status nbp_factor_likelihood(nbp_ctx *c, const nbp_likelihood_desc *desc, const double *a, int32_t na, const double *b, int32_t nb,
                                  double *loglik_out, double *comp_loglik_out) {
-  if (!c || !desc || !a || !loglik_out) return fail(NBP_ERR_ARG, "null argument");
-  nbp_likelihood_desc p = *desc;
-  const bool unary = p.kind == NBP_F_PRIOR;
-  if (!unary && !b) return fail(NBP_ERR_ARG, "null argument");
-  p.slot_a = 0;
-  p.slot_b = unary ? -1 : 1;
-  if (!unary && c->n_slots < 2) return fail(NBP_ERR_RANGE, "factor_likelihood: the context needs two slots");
-  NBPCHK(likelihood_check(c, &p, 1));
-  if (na < 0 || (!unary && nb < 0)) return fail(NBP_ERR_ARG, "factor_likelihood: a negative count");
+  nbp_likelihood_desc p;
+  bool unary;
+  NBPCHK(likelihood_host_desc(c, "factor_likelihood", desc, a, na, b, nb, loglik_out, &p, &unary));
   if (na == 0 || (!unary && nb == 0)) {  // a belief without points: NaN, nothing launched
     *loglik_out = NAN;
     if (comp_loglik_out)
       for (int k = 0; k < NBP_MAXC; k++) comp_loglik_out[k] = NAN;
     return NBP_OK;
   }
-  if (unary) NBPCHK(kde_write(c, p.manifold, {{a, na, nullptr}}));
-  else NBPCHK(kde_write(c, p.manifold, {{a, na, nullptr}, {b, nb, nullptr}}));
+  NBPCHK(kde_write(c, p.manifold, {{a, na, nullptr}, {unary ? nullptr : b, nb, nullptr}}));
   return nbp_run_factor_likelihood(c, &p, 1, loglik_out, comp_loglik_out);
 }
 
@@ -2469,31 +2478,21 @@ nbp_status nbp_run_factor_mode_likelihood(nbp_ctx *c, const nbp_likelihood_desc 
           return fail(NBP_ERR_ARG, "factor_mode_likelihood: label row " + std::to_string(r) + ": entry " + std::to_string(k) + " outside -1 .. NBP_MAXK - 1");
     }
   }
-  const size_t tab_d = (size_t)n * NBP_MAXK * NBP_MAXK, cnt_d = (size_t)n * NBP_MAXK;  // (2 x NBP_MAXK int32 = NBP_MAXK doubles per item)
+  const scratch_layout q{{sizeof(double), (size_t)n * NBP_MAXK * NBP_MAXK, table_out}, {4, (size_t)n * 2 * NBP_MAXK, counts_out}};
   const int32_t *d[4];
   NBPCHK(stage_columns(c, {{descs, sizeof(nbp_likelihood_desc) * (size_t)n}, {row_a, 4 * (size_t)n}, {row_b, 4 * (size_t)n},
-                           {labels, 4 * (size_t)n_rows * N}}, d, tab_d + cnt_d));
+                           {labels, 4 * (size_t)n_rows * N}}, d, q.total()));
   NBPCHK(launch_checked(c, nbp_mode_likelihood_kernel, n, c->Npad, nbp_mode_likelihood_lds_bytes(c->N), (const nbp_likelihood_desc *)d[0], d[1],
-                        d[2], d[3], c->arena, c->N, c->S, c->query, (int32_t *)(c->query + tab_d)));
-  std::vector<double> back(tab_d + (counts_out ? cnt_d : 0));
-  NBPCHK(query_fetch(c, back.data(), c->query, sizeof(double) * back.size()));
-  memcpy(table_out, back.data(), sizeof(double) * tab_d);
-  if (counts_out) memcpy(counts_out, back.data() + tab_d, sizeof(double) * cnt_d);
-  return NBP_OK;
+                        d[2], d[3], c->arena, c->N, c->S, q.at(c, 0), (int32_t *)q.at(c, 1)));
+  return q.fetch(c);
 }
 
 // host-buffer form: stages through slots 0 and 1 (which it clobbers), like nbp_factor_likelihood; the label rows are padded with -1
 nbp_status nbp_factor_mode_likelihood(nbp_ctx *c, const nbp_likelihood_desc *desc, const double *a, int32_t na, const int32_t *labels_a,
                                       const double *b, int32_t nb, const int32_t *labels_b, double *table_out, int32_t *counts_out) {
-  if (!c || !desc || !a || !table_out) return fail(NBP_ERR_ARG, "null argument");
-  nbp_likelihood_desc p = *desc;
-  const bool unary = p.kind == NBP_F_PRIOR;
-  if (!unary && !b) return fail(NBP_ERR_ARG, "null argument");
-  p.slot_a = 0;
-  p.slot_b = unary ? -1 : 1;
-  if (!unary && c->n_slots < 2) return fail(NBP_ERR_RANGE, "factor_mode_likelihood: the context needs two slots");
-  NBPCHK(likelihood_check(c, &p, 1));
-  if (na < 0 || (!unary && nb < 0)) return fail(NBP_ERR_ARG, "factor_mode_likelihood: a negative count");
+  nbp_likelihood_desc p;
+  bool unary;
+  NBPCHK(likelihood_host_desc(c, "factor_mode_likelihood", desc, a, na, b, nb, table_out, &p, &unary));
   const int N = c->N;
   std::vector<int32_t> rows;
   int32_t ra = -1, rb = -1, n_rows = 0;
@@ -2513,8 +2512,7 @@ nbp_status nbp_factor_mode_likelihood(nbp_ctx *c, const nbp_likelihood_desc *des
       for (int k = 0; k < 2 * NBP_MAXK; k++) counts_out[k] = 0;
     return NBP_OK;
   }
-  if (unary) NBPCHK(kde_write(c, p.manifold, {{a, na, nullptr}}));
-  else NBPCHK(kde_write(c, p.manifold, {{a, na, nullptr}, {b, nb, nullptr}}));
+  NBPCHK(kde_write(c, p.manifold, {{a, na, nullptr}, {unary ? nullptr : b, nb, nullptr}}));
   return nbp_run_factor_mode_likelihood(c, &p, &ra, &rb, 1, rows.data(), n_rows, table_out, counts_out);
 }
 

@@ -14,7 +14,7 @@
 #pragma once
 #include "nbp_kernels.h"
 #include "nbp_kde.h"
-#include "nbp_stats.h"  // stats_deviation; NBP_TU_CREDIBLE
+#include "nbp_stats.h"  // stats_deviation
 
 // the sort's length: the next power of two >= N, at least one wave (N <= 512: at most 512)
 __host__ __device__ static inline int nbp_credible_P(int N) {

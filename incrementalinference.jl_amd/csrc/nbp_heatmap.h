@@ -29,9 +29,8 @@
 //   over the tiles b with cdf at the tile's last element as the probe, then within the tile found: the first element with
 //   t < cdf wherever cdf is monotone; the last element where rounding leaves none.  Nothing is normalised: no division.
 #pragma once
-#include "nbp_device.h"
+#include "nbp_kernels.h"
 
-#define NBP_TU_HEATMAP 32768  // the heatmap kernels (nbp_k_heatmap.hip)
 #define PURP_HMCELL 16        // ua -> the cell of pre-sample m (k = 0)
 #define PURP_HMNOISE 17       // kernel noise: k = 0 of a pre-sample (seed), k = 1 of a jittered draw (seed2)
 #define PURP_HMPICK 18        // ua -> the pre-sample that draw k takes (k = 0)

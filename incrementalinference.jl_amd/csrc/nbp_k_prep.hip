@@ -1,3 +1,3 @@
 // bandwidth fits + KD builds, sequential golden-section search
-#define NBP_TU 2
+#define NBP_TU NBP_TU_PREP
 #include "nbp_kernels.h"

@@ -1,3 +1,3 @@
 // product kernels, latency geometries, any mix of manifolds (y32, l8)
-#define NBP_TU 8
+#define NBP_TU NBP_TU_PRODLAT
 #include "nbp_kernels.h"

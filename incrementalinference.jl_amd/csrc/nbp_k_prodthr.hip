@@ -1,3 +1,3 @@
 // product kernels, throughput geometry, any mix of manifolds (t2)
-#define NBP_TU 16
+#define NBP_TU NBP_TU_PRODTHR
 #include "nbp_kernels.h"

@@ -1,3 +1,3 @@
 // proposal kernels, two waves per proposal (see nbp_kernels.h, "Translation units")
-#define NBP_TU 524288
+#define NBP_TU NBP_TU_PROPSPLIT
 #include "nbp_kernels.h"

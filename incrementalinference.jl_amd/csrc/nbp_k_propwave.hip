@@ -1,3 +1,3 @@
 // proposal kernels, one wave per proposal (see nbp_kernels.h, "Translation units")
-#define NBP_TU 512
+#define NBP_TU NBP_TU_PROPWAVE
 #include "nbp_kernels.h"

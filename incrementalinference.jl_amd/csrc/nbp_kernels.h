@@ -10,20 +10,35 @@
 
 // Translation units: libnbp is built from several .hip files in parallel (tools/build_lib.py), each defining one group of
 // kernels (NBP_TU = the groups this file defines; everything else is declared only, so that the host code in nbp_api.hip
-// can launch it).  A file that does not set NBP_TU defines every kernel (single-file build).
+// can launch it).  A file that does not set NBP_TU defines every kernel (single-file build).  EVERY group is in this list, in the
+// order of its bit; a new one goes at the end, and NBP_TU_ALL names it.
 #define NBP_TU_PROPOSAL 1   // proposal / deconv kernels + the small copy / reseed / resample kernels
 #define NBP_TU_PREP 2       // bandwidth fits + KD builds, sequential search
 #define NBP_TU_PREPSPEC 4   // the same with the speculative search
 #define NBP_TU_PRODLAT 8    // product kernels, latency geometries, any mix of manifolds (y32, l8)
 #define NBP_TU_PRODTHR 16   // product kernels, throughput geometry, any mix of manifolds (t2)
 #define NBP_TU_PRODUNI 32   // product kernels, throughput geometry, one manifold per instance (t2)
-#define NBP_TU_FUSED 64     // the fused variable-update kernels
+#define NBP_TU_FUSED 64     // the fused variable-update kernels (nbp_fused.h)
+#define NBP_TU_CREDIBLE 128 // the credible-region kernel (nbp_credible.h)
 #define NBP_TU_PREPW5 256   // bandwidth fits + KD builds at five waves per SIMD (rows of 4k + 1 waves: N = 257 .. 320)
 #define NBP_TU_PROPWAVE 512 // proposal kernels, one wave per proposal (chip-filling launches of simple Euclidean batches)
 #define NBP_TU_PRODLATUNI 1024 // product kernels, latency geometries (y32, l8), one manifold per instance
-#define NBP_TU_PROPSPLIT 524288 // proposal kernels, two waves per proposal (launches between the workgroup and the one-wave geometry)
+#define NBP_TU_PPE 2048        // the point-estimate kernel (nbp_ppe.h)
+#define NBP_TU_QUERY 4096      // the query kernels (nbp_query.h)
+#define NBP_TU_STATS 8192      // the belief-statistics kernels (nbp_stats.h)
+#define NBP_TU_MARGINAL 16384  // the marginal kernels (nbp_marginal.h)
+#define NBP_TU_HEATMAP 32768   // the heatmap kernels (nbp_heatmap.h)
+#define NBP_TU_MODES 65536     // the mode-finding kernel (nbp_modes.h)
+#define NBP_TU_LIKELIHOOD 131072 // the factor-likelihood kernels (nbp_likelihood.h)
+#define NBP_TU_OVERLAP 262144    // the overlap kernels (nbp_overlap.h)
+#define NBP_TU_PROPSPLIT 524288  // proposal kernels, two waves per proposal (launches between the workgroup and the one-wave geometry)
+#define NBP_TU_MIXTURE 1048576   // the mixture-summary kernel (nbp_mixture.h)
+#define NBP_TU_ALL (2 * NBP_TU_MIXTURE - 1)  // every bit up to the last of the list
 #ifndef NBP_TU
-#define NBP_TU 0x1FFFFF
+#define NBP_TU NBP_TU_ALL
+#endif
+#if NBP_TU & ~NBP_TU_ALL
+#error "NBP_TU names a group that NBP_TU_ALL leaves out: the single-file build would drop its kernels"
 #endif
 
 // ================================================================================================

@@ -16,7 +16,6 @@
 #pragma once
 #include "nbp_kernels.h"
 
-#define NBP_TU_LIKELIHOOD 131072  // the factor-likelihood kernel (nbp_k_likelihood.hip)
 
 #define NBP_LIK_HALF_LOG_2PI 0.91893853320467274178  // log(2 pi) / 2
 

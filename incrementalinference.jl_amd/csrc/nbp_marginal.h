@@ -19,7 +19,7 @@
 // (DESIGN.md 8).
 #pragma once
 #include "nbp_kde.h"
-#include "nbp_query.h"  // eval_body; NBP_TU_MARGINAL
+#include "nbp_query.h"  // eval_body
 
 #define NBP_GRID_TILE 32    // 2-D: grid points per axis of one tile
 #define NBP_GRID_RB 4       // 2-D: a lane owns RB x RB points of the tile (8 x 8 lanes: one wave per tile)

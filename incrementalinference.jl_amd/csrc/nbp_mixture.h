@@ -23,7 +23,7 @@
 #pragma once
 #include "nbp_kernels.h"
 #include "nbp_kde.h"
-#include "nbp_stats.h"  // stats_deviation; NBP_TU_MIXTURE
+#include "nbp_stats.h"  // stats_deviation
 
 #define NBP_MIX_LOG_2PI 1.8378770664093453  // log(2 pi)
 #define NBP_MIX_SUMS (NBP_MIX_MAX * 6)      // the most sums one reduction carries: six scatter entries per component

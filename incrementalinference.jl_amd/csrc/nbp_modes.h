@@ -18,7 +18,6 @@
 #include "nbp_kernels.h"
 #include "nbp_kde.h"
 
-#define NBP_TU_MODES 65536  // the mode-finding kernel (nbp_k_modes.hip)
 
 // the sums of one mean-shift step at y over the rows of X[3][N] in LDS (every lane of a wave reads the same address: broadcast)
 __device__ __forceinline__ void modes_sums(double y0, double y1, double y2, const double *X, int N, int c, bool k1, bool k2, bool c0,

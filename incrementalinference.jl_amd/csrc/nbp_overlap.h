@@ -17,7 +17,6 @@
 #include "nbp_kernels.h"
 #include "nbp_kde.h"
 
-#define NBP_TU_OVERLAP 262144  // the overlap kernels (nbp_k_overlap.hip)
 
 // what nbp_overlap_prep_kernel leaves per listed belief for the search: the box of its points on every masked position, the
 // masked bandwidth, L_aa, and whether the bandwidth is usable

@@ -10,7 +10,6 @@
 #include "nbp_kernels.h"
 #include "nbp_kde.h"
 
-#define NBP_TU_PPE 2048  // the point-estimate kernel (nbp_k_ppe.hip)
 
 // one record per belief; entries beyond the manifold's dimension are zero
 struct nbp_ppe_rec {

@@ -19,8 +19,6 @@
 #include "nbp_kernels.h"
 #include "nbp_kde.h"
 
-#define NBP_TU_QUERY 4096  // the query kernels (nbp_k_query.hip)
-#define NBP_TU_MARGINAL 16384  // the marginal kernels (nbp_k_marginal.hip, nbp_marginal.h): defined here, they share eval_body
 
 #define NBP_QUERY_TILE 256  // queries of one belief per workgroup of nbp_eval_kernel: one lane each
 // Weight of the squared heading difference in the mmd's squared distance on SE(2).  Manifolds.jl's Frobenius metric on the

@@ -23,9 +23,6 @@
 #include "nbp_kernels.h"
 #include "nbp_kde.h"
 
-#define NBP_TU_STATS 8192  // the belief-statistics kernels (nbp_k_stats.hip)
-#define NBP_TU_CREDIBLE 128  // the credible-region kernel (nbp_k_credible.hip, nbp_credible.h): defined here, it shares stats_deviation
-#define NBP_TU_MIXTURE 1048576  // the mixture-summary kernel (nbp_k_mixture.hip, nbp_mixture.h): likewise
 
 // one record per belief; entries beyond the manifold's dimension are zero
 struct nbp_meancov_rec {

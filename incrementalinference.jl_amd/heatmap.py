@@ -29,6 +29,7 @@ reference marks it "NOT ACTIVE YET")."""
 import numpy as np
 
 from . import abi
+from .beliefquery import _backend
 
 PURP_HMCELL, PURP_HMNOISE, PURP_HMPICK = 16, 17, 18  # csrc/nbp_heatmap.h (the next free purposes after PURP_PINDEX = 15)
 NBP_TAG = 0x4E4250
@@ -190,9 +191,9 @@ def heatmap_density_numpy(data, x, y, bw_factor=0.7, M=10000, n=None, seed=0, se
 
 
 # ---- the classes ------------------------------------------------------------------------------------------------------------------
-def _backend(backend, n):
-    from .solver import _make_backend
-    return _make_backend(backend, min(max(int(n), 8), abi.MAXN), 1)
+def _device(backend, n, method):
+    """the HIP backend a heatmap density is built or evaluated on (None: HipBackend), holding n points (at most MAXN)"""
+    return _backend(backend, min(int(n), abi.MAXN), 1, method, required="heatmap densities are computed by libnbp")
 
 
 class HeatmapGridDensity:
@@ -209,28 +210,20 @@ class HeatmapGridDensity:
         _, self.points, self.bw = self._draw(n, self.seed, 0)
 
     def _draw(self, n, seed, jitter):
-        be, own = _backend(self._backend, n)
-        try:
+        with _device(self._backend, n, "heatmap_create") as be:
             hm = be.heatmap_create(self.data, self.domain[0], self.domain[1], self.bw_factor)
             try:
                 be.heatmap_build(hm, self.N, self.seed, outputs=False)
                 return be.heatmap_draw(hm, n, seed, jitter=jitter)
             finally:
                 be.heatmap_destroy(hm)
-        finally:
-            if own:
-                be.close()
 
     def __call__(self, pts, backend=None):
         """hgd(pts): the density of (points, bw) at pts (q x 2), through kde_evaluate -- a context holds at most N points of a
         belief, so the points go in runs of N and the runs' densities are averaged by their share of the points"""
-        be, own = _backend(self._backend if backend is None else backend, len(self.points))
-        try:
+        with _device(self._backend if backend is None else backend, len(self.points), "kde_evaluate") as be:
             Q, n = np.asarray(pts, dtype=np.float64).reshape(-1, 2), len(self.points)
             return sum(be.kde_evaluate(abi.EUCLID2, self.points[a:a + be.N], self.bw, Q) * (min(be.N, n - a) / n) for a in range(0, n, be.N))
-        finally:
-            if own:
-                be.close()
 
     def sample(self, n, seed=0):
         """AMP.sample(hgd, n): n draws of pre-sample + h * randn (rebuilds the pre-samples of the construction: same seed, same M)"""

@@ -32,7 +32,7 @@ import numpy as np
 
 from . import abi, likelihood
 from . import modes as _modes
-from .beliefquery import _hip
+from .beliefquery import _staged
 from .likelihood import _UNARY, _coords, block_sum_numpy, check_desc, pair_terms, shifted_exp
 from .ppe import _natural
 
@@ -201,8 +201,7 @@ def _tables_of(fg, plans, modes, maxModes, backend, mode_kw):
     backend the beliefs are written once; one run_modes launch (where modes are to be found) and one table launch follow."""
     names = _plan_variables(plans)
     vs = [fg.getVariable(v) for v in names]
-    be, own = _hip(backend, max([len(v.val) for v in vs] + [1]), max(len(vs), 1), "run_factor_mode_likelihood")
-    try:
+    with _staged(fg, names, backend, "run_factor_mode_likelihood") as (be, place):
         modes = dict(modes) if modes is not None else {}
         missing = [v for v in names if v not in modes]
         if be is None:
@@ -211,17 +210,11 @@ def _tables_of(fg, plans, modes, maxModes, backend, mode_kw):
                 modes[v] = _modes.modes_numpy(var.varType.manifold, var.val, var.bw, **mode_kw)
             return modes, _numpy_plans(fg, plans, modes, maxModes)
         mans = [v.varType.manifold for v in vs]
-        if vs:
-            be.beliefs_write(list(range(len(vs))), mans, [(v.val, v.bw, None) for v in vs])
-        place = {v: i for i, v in enumerate(names)}
         if missing:
             res = be.run_modes([place[v] for v in missing], [mans[place[v]] for v in missing], **mode_kw)
             for i, v in enumerate(missing):
                 modes[v] = _modes.modes_from_records(mans[place[v]], *(r[i] for r in res), len(vs[place[v]].val))
         return modes, run_mode_plans(be, plans, place, modes, maxModes)
-    finally:
-        if own:
-            be.close()
 
 
 def factorModeLikelihoodAll(fg, labels=None, modes=None, maxModes=MAXK, backend=None, skip_unsupported=True):

@@ -35,7 +35,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import abi
-from .beliefquery import _hip
+from .beliefquery import _staged
 from .ppe import _natural, ppe_coords
 
 _HALF_LOG_2PI = 0.91893853320467274178  # NBP_LIK_HALF_LOG_2PI of csrc/nbp_likelihood.h
@@ -431,9 +431,7 @@ def factorLikelihoodAll(fg, labels=None, backend=None, skip_unsupported=True):
     for p in plans:
         for a, b in p.roles:
             names += [v for v in (a, b) if v is not None and v not in names]
-    vs = [fg.getVariable(v) for v in names]
-    be, own = _hip(backend, max([len(v.val) for v in vs] + [1]), max(len(vs), 1), "run_factor_likelihood")
-    try:
+    with _staged(fg, names, backend, "run_factor_likelihood") as (be, place):
         if be is None:
             res = {}
             for p in plans:
@@ -441,13 +439,8 @@ def factorLikelihoodAll(fg, labels=None, backend=None, skip_unsupported=True):
                        for d, (a, b) in zip(p.descs, p.roles)]
                 res[p.label] = assemble(p, [g[0] for g in got], [g[1] for g in got])
         else:
-            if vs:
-                be.beliefs_write(list(range(len(vs))), [v.varType.manifold for v in vs], [(v.val, v.bw, None) for v in vs])
-            res = run_plans(be, plans, {v: i for i, v in enumerate(names)})
+            res = run_plans(be, plans, place)
         return FactorLikelihoods(((p.label, res[p.label]) for p in plans), skipped=skipped)
-    finally:
-        if own:
-            be.close()
 
 
 def factorLikelihood(fg, fct, backend=None):

@@ -32,7 +32,7 @@ import math
 import numpy as np
 
 from . import abi
-from .beliefquery import Belief, _hip, _manifold, _wrap
+from .beliefquery import Belief, _backend, _manifold, _wrap
 from .ppe import _circular, ppe_coords
 
 GRID_MAX = abi.GRID_MAX
@@ -191,15 +191,11 @@ class Marginal:
         HIP backend (class, factory or instance: the belief goes to slot 0, nbp_run_evaluate_marginal); else numpy."""
         b = self.belief
         Q = ppe_coords(b.manifold, np.asarray(pts, dtype=np.float64).reshape(-1, abi.MANIFOLD_P[b.manifold]))
-        be, own = _hip(backend, len(b.pts), 1, "run_evaluate_marginal")
-        try:
+        with _backend(backend, len(b.pts), 1, "run_evaluate_marginal") as be:
             if be is not None:
                 be.belief_write(0, b.manifold, b.pts, b.bw)
                 return be.run_evaluate_marginal([0], [b.manifold], [_mask(self._dims0)], [Q])[0]
             return marginal_density_numpy(b.manifold, ppe_coords(b.manifold, b.pts), b.bw, self._dims0, Q)
-        finally:
-            if own:
-                be.close()
 
     def grid(self, n, extent=None, margin=4.0, backend=None):
         """p_K on a regular grid of n points per axis (a scalar n: the same on every axis) -> (grid, axes): grid of shape (n0,) or
@@ -210,17 +206,13 @@ class Marginal:
             raise ValueError("a grid has one or two coordinates")
         n = [int(v) for v in np.atleast_1d(n)]
         n = n * k if len(n) == 1 else n
-        be, own = _hip(backend, len(b.pts), 1, "kde_marginal_grid")
-        try:
+        with _backend(backend, len(b.pts), 1, "kde_marginal_grid") as be:
             if be is not None:
                 g, ext = be.kde_marginal_grid(b.manifold, b.pts, b.bw, self._dims0, n, extent, margin)
             else:
                 lo, step = (None, None) if extent is None else _extent_args(extent, k)
                 g, ext = marginal_grid_numpy(b.manifold, ppe_coords(b.manifold, b.pts), b.bw, self._dims0, n, lo, step, margin)
             return g, grid_axes(ext, n)
-        finally:
-            if own:
-                be.close()
 
 
 def marginalGrid(fg, label, dims=None, n=64, extent=None, margin=4.0, backend=None):

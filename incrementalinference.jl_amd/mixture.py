@@ -36,7 +36,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import abi
-from .beliefquery import _hip
+from .beliefquery import _backend, _staged
 from .likelihood import _wrap
 from .modes import BeliefModes, _options as _mode_options, modes_from_records, modes_numpy
 from .ppe import _circular, _natural, ppe_coords
@@ -343,17 +343,13 @@ def belief_mixture(manifold, pts, bw, maxComponents=abi.MIX_MAX, bwScale=abi.MOD
     nbp_kde_mixture, through slot 0); anything without that entry point, or None: numpy."""
     K, mode_kw, kw = _options(maxComponents, bwScale, tol, maxIter)
     pts = np.asarray(pts, dtype=np.float64).reshape(-1, abi.MANIFOLD_P[manifold])
-    be, own = _hip(backend, len(pts), 1, "kde_mixture")
-    try:
+    with _backend(backend, len(pts), 1, "kde_mixture") as be:
         if be is None:
             return mixture_host(manifold, pts, bw, K, mode_kw, kw)
         bm = modes_from_records(manifold, *be.kde_modes(manifold, pts, bw, **mode_kw), len(pts))
         lab, mu = starting_from_modes(bm, K)
         rec, out = be.kde_mixture(manifold, pts, bw, lab, mu, **kw)
         return mixture_from_record(manifold, rec, out, len(pts), bm)
-    finally:
-        if own:
-            be.close()
 
 
 def fitBeliefMixture(fg, label, maxComponents=abi.MIX_MAX, bwScale=abi.MODES_BW_SCALE, tol=abi.MIX_TOL, maxIter=abi.MIX_MAX_ITER,
@@ -388,13 +384,7 @@ def fitBeliefMixtureAll(fg, labels=None, maxComponents=abi.MIX_MAX, bwScale=abi.
     if not vs:
         return {}
     mans = [v.varType.manifold for v in vs]
-    be, own = _hip(backend, max(len(v.val) for v in vs), len(vs), "run_mixture")
-    try:
+    with _staged(fg, labels, backend, "run_mixture") as (be, _):
         if be is None:
             return {l: mixture_host(m, v.val, v.bw, K, mode_kw, kw) for l, m, v in zip(labels, mans, vs)}
-        slots = list(range(len(vs)))
-        be.beliefs_write(slots, mans, [(v.val, v.bw, None) for v in vs])
-        return dict(zip(labels, resident_mixtures(be, slots, mans, [len(v.val) for v in vs], K, mode_kw, kw)))
-    finally:
-        if own:
-            be.close()
+        return dict(zip(labels, resident_mixtures(be, list(range(len(vs))), mans, [len(v.val) for v in vs], K, mode_kw, kw)))

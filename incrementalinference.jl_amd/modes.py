@@ -31,7 +31,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import abi
-from .beliefquery import _hip, _wrap
+from .beliefquery import _backend, _staged, _wrap
 from .ppe import _circular, _natural, ppe_coords
 
 MODES_MAX = abi.MODES_MAX
@@ -183,14 +183,10 @@ def belief_modes(manifold, pts, bw, bwScale=abi.MODES_BW_SCALE, tol=abi.MODES_TO
     0); anything without that entry point, or None: numpy."""
     kw = _options(bwScale, tol, maxIter, merge)
     pts = np.asarray(pts, dtype=np.float64).reshape(-1, abi.MANIFOLD_P[manifold])
-    be, own = _hip(backend, len(pts), 1, "kde_modes")
-    try:
+    with _backend(backend, len(pts), 1, "kde_modes") as be:
         if be is not None:
             return modes_from_records(manifold, *be.kde_modes(manifold, pts, bw, **kw), len(pts))
         return modes_numpy(manifold, pts, bw, **kw)
-    finally:
-        if own:
-            be.close()
 
 
 def getBeliefModes(fg, label, bwScale=abi.MODES_BW_SCALE, tol=abi.MODES_TOL, maxIter=abi.MODES_MAX_ITER, merge=abi.MODES_MERGE, backend=None):
@@ -209,13 +205,8 @@ def getBeliefModesAll(fg, labels=None, bwScale=abi.MODES_BW_SCALE, tol=abi.MODES
     if not vs:
         return {}
     mans = [v.varType.manifold for v in vs]
-    be, own = _hip(backend, max(len(v.val) for v in vs), len(vs), "run_modes")
-    try:
+    with _staged(fg, labels, backend, "run_modes") as (be, _):
         if be is None:
             return {l: modes_numpy(m, v.val, v.bw, **kw) for l, m, v in zip(labels, mans, vs)}
-        be.beliefs_write(list(range(len(vs))), mans, [(v.val, v.bw, None) for v in vs])
         res = be.run_modes(list(range(len(vs))), mans, **kw)
         return {l: modes_from_records(m, *(r[i] for r in res), len(v.val)) for i, (l, m, v) in enumerate(zip(labels, mans, vs))}
-    finally:
-        if own:
-            be.close()

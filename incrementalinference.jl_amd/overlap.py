@@ -36,7 +36,7 @@ from collections import namedtuple
 import numpy as np
 
 from . import abi
-from .beliefquery import Belief, _hip, _manifold
+from .beliefquery import Belief, _backend, _bw, _manifold, _staged
 from .likelihood import _coords, _wrap, block_sum_numpy, shifted_exp
 from .marginal import marginal_density_numpy
 from .ppe import _natural, getPPE, ppe_coords
@@ -266,18 +266,13 @@ def findBeliefsNear(fg, loc, dims=None, number=3, regexFilter=None, backend=None
     Q = np.zeros((1, abi.MAXD))
     for d, x in zip(dims, loc):
         Q[0, d - 1] = x
-    be, own = _hip(backend, max(len(v.val) for v in vs), len(vs), "run_evaluate_marginal")
-    try:
+    with _staged(fg, labels, backend, "run_evaluate_marginal") as (be, _):
         if be is not None:
-            be.beliefs_write(list(range(len(vs))), mans, [(v.val, v.bw, None) for v in vs])
             got = be.run_evaluate_marginal(list(range(len(vs))), mans, [dims_mask(m, dims) for m in mans], [Q] * len(vs))
             dens = np.array([g[0] for g in got])
         else:
             dens = np.array([marginal_density_numpy(m, ppe_coords(m, v.val), v.bw, [d - 1 for d in dims], Q[:, :abi.MANIFOLD_DIM[m]])[0]
                              for m, v in zip(mans, vs)])
-    finally:
-        if own:
-            be.close()
     prm = sorted(range(len(labels)), key=lambda i: (-dens[i] if np.isfinite(dens[i]) else np.inf, i))[:number]
     return [labels[i] for i in prm], dens[prm]
 
@@ -285,15 +280,7 @@ def findBeliefsNear(fg, loc, dims=None, number=3, regexFilter=None, backend=None
 # ------------------------------------------------------------------------------------------------
 # overlaps on the device
 # ------------------------------------------------------------------------------------------------
-def _device(backend, N, n_slots, method):
-    """the HIP backend the overlaps run on (None: HipBackend): there is no host route"""
-    if backend is None:
-        from .backend import HipBackend
-        backend = HipBackend
-    be, own = _hip(backend, N, n_slots, method)
-    if be is None:
-        raise ValueError(f"belief overlaps are computed by libnbp: the backend has no {method}")
-    return be, own
+_NO_HOST_ROUTE = "belief overlaps are computed by libnbp"  # (`required` of beliefquery._backend: None means HipBackend)
 
 
 def overlap_from_rec(rec):
@@ -322,21 +309,8 @@ def beliefOverlap(p1, p2, varType, dims=None, backend=None):
         raise ValueError("beliefOverlap: inadmissible pair: the compared coordinates differ in number or kind")
     a = np.asarray(a, dtype=np.float64).reshape(-1, abi.MANIFOLD_P[ma])
     b = np.asarray(b, dtype=np.float64).reshape(-1, abi.MANIFOLD_P[mb])
-    be, own = _device(backend, max(len(a), len(b)), 2, "kde_overlap")
-    try:
+    with _backend(backend, max(len(a), len(b)), 2, "kde_overlap", _NO_HOST_ROUTE) as be:
         return overlap_from_rec(be.kde_overlap(ma, a, _bw(ma, bw_a), ka, mb, b, _bw(mb, bw_b), kb))
-    finally:
-        if own:
-            be.close()
-
-
-def _bw(manifold, bw):
-    """a bandwidth of D entries: what a slot takes (entries a short bandwidth lacks are 0: unusable where the mask needs them)"""
-    D = abi.MANIFOLD_DIM[manifold]
-    out = np.zeros(D)
-    bw = np.asarray([] if bw is None else bw, dtype=np.float64).reshape(-1)[:D]
-    out[:len(bw)] = bw
-    return out
 
 
 def pair_columns(fg, pairs, dims, place):
@@ -353,13 +327,6 @@ def pair_columns(fg, pairs, dims, place):
     return cols
 
 
-def _write_all(be, fg, labels):
-    vs = [fg.getVariable(v) for v in labels]
-    mans = [_manifold(v.varType) for v in vs]
-    be.beliefs_write(list(range(len(vs))), mans, [(v.val, _bw(m, v.bw), None) for v, m in zip(vs, mans)])
-    return mans
-
-
 def overlapVariables(fg, pairs, dims=None, backend=None):
     """The overlaps of pairs of variables' current beliefs -> {(label_a, label_b): Overlap}.  dims: the 1-BASED coordinates compared
     (default: all; then the two variables of a pair share a manifold's kinds).  The beliefs go to slots once and ONE run_overlap
@@ -371,13 +338,8 @@ def overlapVariables(fg, pairs, dims=None, backend=None):
     for p in pairs:
         labels += [v for v in p if v not in labels]
     cols = pair_columns(fg, pairs, dims, {v: i for i, v in enumerate(labels)})
-    be, own = _device(backend, max(len(fg.getVariable(v).val) for v in labels), len(labels), "run_overlap")
-    try:
-        _write_all(be, fg, labels)
+    with _staged(fg, labels, backend, "run_overlap", _bw, _NO_HOST_ROUTE) as (be, _):
         recs = be.run_overlap(*cols)
-    finally:
-        if own:
-            be.close()
     return {p: overlap_from_rec(r) for p, r in zip(pairs, recs)}
 
 
@@ -430,12 +392,6 @@ def findOverlaps(fg, labels=None, dims=None, number=TOPK, minCoeff=MIN_COEFF, re
     if not labels:
         return Overlaps([], np.zeros((0, number), dtype=np.int32), np.zeros((0, number)), [], [])
     cols = search_columns(fg, labels, dims, {v: i for i, v in enumerate(labels)})
-    N = max(len(fg.getVariable(v).val) for v in labels)
-    be, own = _device(backend, N, len(labels), "run_overlap_search")
-    try:
+    with _staged(fg, labels, backend, "run_overlap_search", _bw, _NO_HOST_ROUTE) as (be, _):
         check_search_options(number, minCoeff, reach, be.N)
-        _write_all(be, fg, labels)
         return Overlaps(labels, *be.run_overlap_search(*cols, number, minCoeff, reach))
-    finally:
-        if own:
-            be.close()

@@ -101,18 +101,9 @@ def calcPPE(fg, label, backend=None):
     instance: the estimate is computed on the device, nbp_kde_ppe); anything without a PPE entry point, or None: numpy."""
     v = fg.getVariable(label)
     man = v.varType.manifold
-    be, own = None, False
-    if backend is not None:
-        from .solver import _make_backend
-        be, own = _make_backend(backend, len(v.val), 1)
-    try:
-        if getattr(be, "kde_ppe", None) is not None:
-            mean, mx, idx = be.kde_ppe(man, v.val, v.bw)
-        else:
-            mean, mx, idx = ppe_numpy(man, v.val, v.bw)
-    finally:
-        if own:
-            be.close()
+    from .beliefquery import _backend  # (beliefquery imports this module)
+    with _backend(backend, len(v.val), 1, "kde_ppe") as be:
+        mean, mx, idx = be.kde_ppe(man, v.val, v.bw) if be is not None else ppe_numpy(man, v.val, v.bw)
     return MeanMaxPPE(mean.copy(), mx, mean, int(idx))
 
 

@@ -158,3 +158,108 @@ def test_reference_assertion_three_door_sighting_density(oracle_backend):
     print(f"X0 at the doors: {dens}")
     for d in dens:
         assert 0.1 < d, dens
+
+
+# ---- which backend a graph-level query uses, what it writes to it, and who closes it ---------------------------------------------
+class _Recorder:
+    """a stand-in backend that records what the graph-level functions do to it; `has`: the run_* methods it offers; `fail`: they raise"""
+    made = []
+
+    def __init__(self, N, n_slots, side_ints=0, has=("run_meancov", "run_modes", "run_mmd"), fail=False):
+        self.N, self.n_slots, self.writes, self.closed, self.fail = N, n_slots, [], 0, fail
+        for m in has:
+            setattr(self, m, getattr(self, "_" + m))
+        _Recorder.made.append(self)
+
+    def slot_write(self, *a):
+        raise AssertionError("the graph-level queries write beliefs in one batch")
+
+    def beliefs_write(self, slots, manifolds, beliefs):
+        assert len(slots) == len(manifolds) == len(beliefs)
+        self.writes.append(list(slots))
+
+    def close(self):
+        self.closed += 1
+
+    def _ran(self):
+        if self.fail:
+            raise RuntimeError("the launch failed")
+
+    def _run_meancov(self, slots, manifolds):
+        self._ran()
+        return np.zeros((len(slots), abi.MAXD)), np.zeros((len(slots), abi.MAXD, abi.MAXD))
+
+    def _run_modes(self, slots, manifolds, **kw):
+        self._ran()
+        n = len(slots)
+        z = np.zeros(n, dtype=np.int32)
+        return (np.zeros((n, abi.MODES_MAX), dtype=iif.HipBackend._MODE_REC), z, np.zeros((n, self.N), dtype=np.int32),
+                np.zeros((n, self.N), dtype=np.int32), z)
+
+    def _run_mmd(self, slots_a, slots_b, manifolds, sigma):
+        self._ran()
+        return np.zeros(len(slots_a))
+
+
+def _three_variables(seed):
+    fg = iif.initfg(iif.SolverParams(N=20))
+    rng = np.random.default_rng(seed)
+    for i in range(3):
+        iif.addVariable(fg, f"x{i}", iif.ContinuousScalar)
+        v = fg.getVariable(f"x{i}")
+        v.val, v.bw = rng.normal(i, 0.3, size=(20, 1)), np.array([0.2])
+    return fg
+
+
+_QUERIES = {
+    "calcMeanCovarAll": (lambda fg, be: iif.calcMeanCovarAll(fg, backend=be), [0, 1, 2]),
+    "getBeliefModesAll": (lambda fg, be: iif.getBeliefModesAll(fg, backend=be), [0, 1, 2]),
+    "mmdVariables": (lambda fg, be: iif.mmdVariables(fg, _three_variables(2), backend=be), [0, 1, 2, 3, 4, 5]),
+}
+
+
+def _same(a, b):
+    if isinstance(a, dict):
+        return a.keys() == b.keys() and all(_same(a[k], b[k]) for k in a)
+    if isinstance(a, (tuple, list)):
+        return len(a) == len(b) and all(_same(x, y) for x, y in zip(a, b))
+    if isinstance(a, np.ndarray):
+        return np.array_equal(a, b)
+    return _same(vars(a), vars(b)) if hasattr(a, "__dict__") else a == b
+
+
+@pytest.mark.parametrize("name", sorted(_QUERIES))
+def test_graph_queries_make_write_and_close_their_backend_once(name):
+    query, slots = _QUERIES[name]
+    fg = _three_variables(1)
+    # a backend passed as a class (or factory): made once, one batch write of slots 0 .. L-1, closed exactly once -- also when the run raises
+    for fail in (False, True):
+        _Recorder.made = []
+        make = lambda N, n_slots, side_ints=0: _Recorder(N, n_slots, side_ints, fail=fail)  # noqa: E731
+        if fail:
+            with pytest.raises(RuntimeError, match="the launch failed"):
+                query(fg, make)
+        else:
+            query(fg, make)
+        (be,) = _Recorder.made
+        assert be.writes == [slots] and be.closed == 1 and be.n_slots == len(slots), (fail, be.writes, be.closed)
+    _Recorder.made = []
+    query(fg, _Recorder)
+    assert len(_Recorder.made) == 1 and _Recorder.made[0].writes == [slots] and _Recorder.made[0].closed == 1
+    # a backend passed as an instance is never closed
+    for fail in (False, True):
+        be = _Recorder(20, 6, fail=fail)
+        if fail:
+            with pytest.raises(RuntimeError, match="the launch failed"):
+                query(fg, be)
+        else:
+            query(fg, be)
+        assert be.writes == [slots] and be.closed == 0
+    # a backend without the method: the numpy result, nothing written; closed if it was made for the call
+    want = query(fg, None)
+    _Recorder.made = []
+    got = query(fg, lambda N, n_slots, side_ints=0: _Recorder(N, n_slots, side_ints, has=()))
+    (be,) = _Recorder.made
+    assert _same(got, want) and be.writes == [] and be.closed == 1
+    be = _Recorder(20, 6, has=())
+    assert _same(query(fg, be), want) and be.writes == [] and be.closed == 0

@@ -304,6 +304,36 @@ def test_refusals(hip_backend):
         be.close()
 
 
+def test_every_refusal_of_the_kde_form_comes_before_slot_0_is_touched(hip_backend):
+    be = hip_backend(64, 2)
+    try:
+        E2, rng = abi.EUCLID2, np.random.default_rng(88)
+        kept = [(np.ascontiguousarray(pc.cloud("gaussian", E2, 64, rng)), np.array([0.3, 0.2 + 0.1 * s])) for s in (0, 1)]
+        for s, (p, h) in enumerate(kept):
+            be.belief_write(s, E2, p, h)
+        before = [be.belief_read(s, E2) for s in (0, 1)]
+        other, bw, q = np.ones((64, 2)), [0.5, 0.5], np.zeros((2, 2))
+
+        def refused(code, text, mask, mass=(0.5,), queries=None):
+            with pytest.raises(iif.NbpError) as e:
+                be.kde_credible(E2, other, bw, mask, mass, (0.5,), queries)
+            assert str(e.value) == f"libnbp status {code}: {text}", e.value
+        refused(-4, "credible: belief 0: empty mask", 0)
+        refused(-4, "credible: belief 0: coordinate outside the manifold", 4)
+        refused(-4, "credible: belief 0: coordinate outside the manifold", -1)
+        for bad in (np.nan, np.inf):
+            refused(-4, "credible: belief 0: a query entry is not finite", 2, queries=np.array([[0.0, 0.0], [0.0, bad]]))
+        refused(-4, "credible: n_mass outside 0 .. 8", 3, mass=(0.5,) * 9)
+        refused(-4, "credible: mass 0 outside (0, 1]", 3, mass=(0.0,))
+        for s, (p, h) in enumerate(kept):
+            after = be.belief_read(s, E2)
+            assert after[0].tobytes() == p.tobytes() and after[1].tobytes() == h.tobytes(), s
+            assert all(a.tobytes() == b.tobytes() for a, b in zip(after, before[s])), s
+        assert be.kde_credible(E2, other, bw, 1, (0.5,), (0.5,), np.array([[0.0, np.nan]]))[0]["count"] == 64  # outside the mask: not read
+    finally:
+        be.close()
+
+
 # ---- the mirror ------------------------------------------------------------------------------------------------------------------
 def _chain(graph):
     fg = iif.initfg(iif.SolverParams(N=100))

@@ -3,6 +3,7 @@ ABI, the mirror and a solve session.  The pair form is held to the numpy restate
 out per case on the host: 16 max(|float64 - long double| of the restatement, 4 ulp(max(1, |l|))).  The search is held to the pair form
 on the device, exactly: every pair of every scene is evaluated by run_overlap and ranked on the host."""
 import copy
+import ctypes as C
 import math
 
 import numpy as np
@@ -289,6 +290,40 @@ def test_refusals_name_the_index_and_leave_the_context_usable(hip_backend):
         search(r"status -1.*min_coeff", min_coeff=0.0)
         idx, val, found, evaluated = be.run_overlap_search([0, 3, 1], [E2, E2, SE2], [3, 3, 3], topk=16)
         assert idx.shape == (3, 16) and np.all(found >= 0) and be.run_overlap(*good).tobytes() == ok.tobytes()
+    finally:
+        be.close()
+
+
+def test_every_refusal_of_the_kde_form_comes_before_slots_0_and_1_are_touched(hip_backend):
+    be = hip_backend(64, 2)
+    try:
+        E2, CI, rng = abi.EUCLID2, abi.CIRCULAR, np.random.default_rng(801)
+        kept = [(np.ascontiguousarray(pc.cloud("gaussian", E2, 64, rng)), np.array([0.3, 0.2 + 0.1 * s])) for s in (0, 1)]
+        for s, (p, h) in enumerate(kept):
+            be.belief_write(s, E2, p, h)
+        before = [be.belief_read(s, E2) for s in (0, 1)]
+        a, h2, c1, h1 = np.ones((64, 2)), np.array([0.5, 0.5]), np.ones((64, 1)), np.array([0.5])
+
+        def refused(code, text, call):
+            with pytest.raises(iif.NbpError) as e:
+                call()
+            assert str(e.value) == f"libnbp status {code}: {text}", e.value
+        for ka, kb in ((0, 3), (3, 0)):
+            refused(-4, "overlap: belief 0: empty mask", lambda: be.kde_overlap(E2, a, h2, ka, E2, a, h2, kb))
+        for ka, kb in ((4, 3), (3, 4), (-1, 3), (3, -1)):
+            refused(-4, "overlap: belief 0: coordinate outside the manifold", lambda: be.kde_overlap(E2, a, h2, ka, E2, a, h2, kb))
+        refused(-1, "overlap: belief 0: inadmissible pair: the masked coordinates differ in number or kind",
+                lambda: be.kde_overlap(CI, c1, h1, 1, E2, a, h2, 1))
+        refused(-1, "overlap: belief 0: inadmissible pair: the masked coordinates differ in number or kind",
+                lambda: be.kde_overlap(E2, a, h2, 3, E2, a, h2, 1))
+        dp, rec = C.POINTER(C.c_double), abi.OverlapRec()  # (the wrapper cannot shape the points of a manifold it does not know)
+        refused(-1, "overlap: unknown manifold", lambda: be._check(be.lib.nbp_kde_overlap(
+            be._ctx, E2, a.ctypes.data_as(dp), 64, h2.ctypes.data_as(dp), 3, 9, a.ctypes.data_as(dp), 64, h2.ctypes.data_as(dp), 3, C.byref(rec))))
+        for s, (p, h) in enumerate(kept):
+            after = be.belief_read(s, E2)
+            assert after[0].tobytes() == p.tobytes() and after[1].tobytes() == h.tobytes(), s
+            assert all(x.tobytes() == y.tobytes() for x, y in zip(after, before[s])), s
+        assert np.isfinite(be.kde_overlap(E2, a, h2, 1, E2, a, h2, 2)).all()  # the context stays usable
     finally:
         be.close()
 

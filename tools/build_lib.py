@@ -22,8 +22,8 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-val
 # -ffp-contract=off: ONE ROUNDING PER WRITTEN OPERATION in every kernel -- the arithmetic of the CPU checker (gcc -ffp-contract=off)
 # and of Julia; the multiply-adds that are wanted are explicit fma() calls (round 6: DESIGN.md section 5; +1..2 % per solve,
 # profiles/r06_contract_off_cost.txt)
-HEADERS = [os.path.join(CSRC, h) for h in ("nbp_kernels.h", "nbp_device.h", "nbp_lcv_table.h", "nbp_lcv_pairs.h", "nbp_fused.h", "nbp_kde.h", "nbp_ppe.h", "nbp_query.h", "nbp_stats.h", "nbp_marginal.h", "nbp_heatmap.h", "nbp_modes.h", "nbp_likelihood.h", "nbp_overlap.h", "nbp_credible.h", "nbp_mixture.h")] + \
-          [os.path.join(ROOT, "include", h) for h in ("nbp.h", "nbp_host.h", "nbp_math.h")]
+# every header there is: a translation unit is stale when any header it can include is newer (hdr_m narrows the list)
+HEADERS = sorted(os.path.join(d, h) for d in (CSRC, os.path.join(ROOT, "include")) for h in os.listdir(d) if h.endswith(".h"))
 
 
 def sources():
@@ -60,7 +60,7 @@ def main():
     args, extra = ap.parse_known_args()
     t0 = time.time()
     if args.single:
-        cmd = [HIPCC] + FLAGS + ["-shared", "-DNBP_TU=0x1FFFFF"] + extra + [os.path.join(CSRC, "nbp_api.hip"), os.path.join(CSRC, "nbp_host.cpp"), "-o", args.out]
+        cmd = [HIPCC] + FLAGS + ["-shared", "-DNBP_TU=NBP_TU_ALL"] + extra + [os.path.join(CSRC, "nbp_api.hip"), os.path.join(CSRC, "nbp_host.cpp"), "-o", args.out]
         subprocess.check_call(cmd)
         print(f"built {args.out} (single translation unit) in {time.time() - t0:.0f} s")
         return
@@ -68,7 +68,7 @@ def main():
     tag = ("_" + re.sub(r"\W", "", "".join(extra))) if extra else ""
     # what a translation unit includes: the kernel groups everything but the host header, nbp_host.cpp only the two ABI headers
     def hdr_m(src):
-        hs = [h for h in HEADERS if os.path.exists(h)]
+        hs = HEADERS
         if src.endswith("nbp_host.cpp"):
             hs = [h for h in hs if os.path.basename(h) in ("nbp.h", "nbp_host.h")]  # (no device code: nbp_math.h is not included)
         elif os.path.basename(src).startswith("nbp_k_"):
