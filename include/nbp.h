@@ -438,6 +438,51 @@ typedef struct nbp_overlap_opts {
 nbp_status nbp_run_overlap_search(nbp_ctx *ctx, const int32_t *slots, const int32_t *manifolds, const int32_t *masks, int32_t n,
                                   const nbp_overlap_opts *opts /* nullable */, int32_t *idx_out /* n x topk */,
                                   double *logc_out /* n x topk */, int32_t *found_out /* n */, int32_t *evaluated_out /* n */);
+/* ---- scene densities ("Scene densities"; DEFINED by this library, unpinned: DESIGN.md 8) ------------------------------
+ * Every belief of a list on ONE regular grid: the picture of a whole solution.  Belief v: slots[v], manifolds[v], the one or two
+ * 0-based coordinates dims[2 v], dims[2 v + 1] (-1: a 1-D scene), weight weights[v] (weights == NULL: all 1).  ADMISSIBLE: every
+ * belief names as many coordinates as belief 0 and, axis by axis, the same kind (Euclidean or circular) -- an SE(2) pose on (x, y)
+ * beside a Euclid(2) landmark is.  A belief is USABLE when its bandwidth entries on its coordinates are positive and finite; an
+ * unusable one adds nothing and has skipped_out[v] = 1.
+ *   box    per axis a, d = dims_v[a], h = bw_v[d], mn / mx the exact minimum / maximum of the belief's points on d:
+ *          cull_lo = mn - reach h, cull_hi = mx + reach h, ext_lo = mn - margin h, ext_hi = mx + margin h (one rounding per operation)
+ *   grid   point k of axis a = lo[a] + (double)k step[a]; row-major, axis 0 slowest; a 1-D scene has n[1] = 1.  flags &
+ *          NBP_SCENE_AUTO_EXTENT: lo and step are not read; a Euclidean axis has lo = min ext_lo and hi = max ext_hi over the usable
+ *          beliefs, step = (hi - lo) / (n - 1) (no usable belief: lo = step = 0); a circular axis lo = -pi, step = 2 pi / n.
+ *   reach  belief v is IN REACH of a grid point when cull_lo <= g <= cull_hi on every Euclidean axis; circular axes never cull;
+ *          reach = +inf: every belief is in reach of every point.
+ *   value  S[k0][k1] = sum_v w_v (P_v / norm_v) over the usable beliefs in reach of the point, in list order, P_v and norm_v the sum
+ *          and the normalisation of the marginal grid above: one belief with weight 1 and reach = +inf gives that grid bit for bit.
+ *          A point no belief reaches is exactly 0.0.  A value depends on the list, the weights and its grid point alone.
+ *   owner  (owner_out != NULL) the list index of the largest term w_v (P_v / norm_v) > 0 among the beliefs in reach of the point,
+ *          ties to the lower index; -1 where there is none.
+ *   bound  a belief out of reach of a point has every particle further than reach h from it on some axis: each term left out is
+ *          below  w_v exp(-reach^2 / 2) / prod_a (sqrt(2 pi) h_a).
+ * extent_out_4: lo0, step0, lo1, step1 as used (1-D: lo1 = step1 = 0).  tile_beliefs_out: the (tile, belief) pairs the tiles worked
+ * on, out of tiles x V.  V = 0 is NBP_OK and leaves a grid of zeros (owners -1).  Refused before anything is launched or written,
+ * naming the belief -- NBP_ERR_RANGE: a slot or coordinate outside the context or manifold, a repeated coordinate, n outside 1 ..
+ * NBP_SCENE_MAX or n0 n1 > 2^22 (or n[1] != 1 in a 1-D scene), n < 2 on a Euclidean axis with the automatic extent, a non-finite lo, a
+ * step that is not finite and positive (explicit extent); NBP_ERR_ARG: an unknown manifold or flag, a belief inadmissible against
+ * belief 0, a weight that is negative or not finite, a margin that is not finite, a reach that is NaN or not positive, V < 0, a NULL
+ * required pointer.  Queued on the library stream (per-belief preparation, the extent where automatic, one wave per tile); the grid
+ * and the owners are copied straight into out / owner_out, the other outputs in one more copy; synchronises.  There is no host-buffer form: a scene has many beliefs, write them with nbp_belief_write_batch. */
+#define NBP_SCENE_AUTO_EXTENT 1
+#define NBP_SCENE_MAX 4096
+#define NBP_SCENE_REACH 6.0
+#define NBP_SCENE_MARGIN 4.0
+typedef struct nbp_scene_desc {
+  int32_t n[2];
+  int32_t flags;
+  int32_t pad;
+  double lo[2];
+  double step[2];
+  double margin;
+  double reach;
+} nbp_scene_desc;
+nbp_status nbp_run_scene_grid(nbp_ctx *ctx, const int32_t *slots, const int32_t *manifolds, const int32_t *dims /* V x 2 */,
+                              const double *weights /* V, nullable */, int32_t V, const nbp_scene_desc *desc,
+                              double *out /* n0 * n1 */, int32_t *owner_out /* nullable */, int32_t *skipped_out /* V, nullable */,
+                              double *extent_out_4 /* nullable */, int64_t *tile_beliefs_out /* nullable */);
 /* ---- credible regions ("Credible regions"; DEFINED by this library, unpinned: DESIGN.md 8) ---------------------------
  * How much of a resident belief lies where: the levels of its highest-density regions (HDR), the credibility of reference points and
  * the quantiles of its coordinates.  The belief has c points x_i (the count the slot holds), bandwidth h and manifold M; K is a

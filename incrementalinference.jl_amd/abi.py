@@ -134,6 +134,15 @@ class OverlapOpts(C.Structure):
 
 OVERLAP_MAXK, OVERLAP_REACH, OVERLAP_MIN_COEFF, OVERLAP_TOPK = 16, 6.0, 1e-3, 8
 
+
+class SceneDesc(C.Structure):
+    """nbp_scene_desc: the one grid of nbp_run_scene_grid (flags & SCENE_AUTO_EXTENT: lo and step are not read)"""
+    _fields_ = [("n", C.c_int32 * 2), ("flags", C.c_int32), ("pad", C.c_int32), ("lo", C.c_double * 2), ("step", C.c_double * 2),
+                ("margin", C.c_double), ("reach", C.c_double)]
+
+
+SCENE_AUTO_EXTENT, SCENE_MAX, SCENE_REACH, SCENE_MARGIN, SCENE_MAX_POINTS = 1, 4096, 6.0, 4.0, 1 << 22
+
 CRED_MAX = 8  # NBP_CRED_MAX: masses and probabilities per nbp_run_credible
 
 
@@ -258,7 +267,7 @@ EXPORTS = [
     "nbp_ctx_reserve_resident", "nbp_ctx_resident", "nbp_belief_write_batch_async", "nbp_belief_read_batch_begin", "nbp_belief_read_batch_end",
     "nbp_run_copies_async", "nbp_program_retire",
     "nbp_slot_write", "nbp_slot_read", "nbp_belief_write", "nbp_belief_read", "nbp_belief_write_batch", "nbp_belief_read_batch", "nbp_run_resample", "nbp_side_write", "nbp_side_read",
-    "nbp_run_proposals", "nbp_run_bandwidth", "nbp_run_ppe", "nbp_kde_ppe", "nbp_run_evaluate", "nbp_kde_evaluate", "nbp_run_marginal_grid", "nbp_kde_marginal_grid", "nbp_run_evaluate_marginal", "nbp_run_mmd", "nbp_kde_mmd", "nbp_run_meancov", "nbp_kde_meancov", "nbp_run_kld", "nbp_kde_kld", "nbp_run_overlap", "nbp_kde_overlap", "nbp_run_overlap_search", "nbp_run_credible", "nbp_kde_credible", "nbp_run_modes", "nbp_kde_modes", "nbp_run_mixture", "nbp_kde_mixture", "nbp_run_factor_likelihood", "nbp_factor_likelihood", "nbp_run_factor_mode_likelihood", "nbp_factor_mode_likelihood", "nbp_heatmap_create", "nbp_heatmap_build", "nbp_heatmap_draw", "nbp_heatmap_info", "nbp_heatmap_destroy", "nbp_heatmap_scan_eval", "nbp_heatmap_search_eval", "nbp_run_products", "nbp_run_copies", "nbp_run_deconv", "nbp_kde_bandwidth", "nbp_conv", "nbp_manifold_product",
+    "nbp_run_proposals", "nbp_run_bandwidth", "nbp_run_ppe", "nbp_kde_ppe", "nbp_run_evaluate", "nbp_kde_evaluate", "nbp_run_marginal_grid", "nbp_kde_marginal_grid", "nbp_run_evaluate_marginal", "nbp_run_mmd", "nbp_kde_mmd", "nbp_run_meancov", "nbp_kde_meancov", "nbp_run_kld", "nbp_kde_kld", "nbp_run_overlap", "nbp_kde_overlap", "nbp_run_overlap_search", "nbp_run_scene_grid", "nbp_run_credible", "nbp_kde_credible", "nbp_run_modes", "nbp_kde_modes", "nbp_run_mixture", "nbp_kde_mixture", "nbp_run_factor_likelihood", "nbp_factor_likelihood", "nbp_run_factor_mode_likelihood", "nbp_factor_mode_likelihood", "nbp_heatmap_create", "nbp_heatmap_build", "nbp_heatmap_draw", "nbp_heatmap_info", "nbp_heatmap_destroy", "nbp_heatmap_scan_eval", "nbp_heatmap_search_eval", "nbp_run_products", "nbp_run_copies", "nbp_run_deconv", "nbp_kde_bandwidth", "nbp_conv", "nbp_manifold_product",
     "nbp_program_create", "nbp_program_add_stage", "nbp_program_set_option", "nbp_program_finalize", "nbp_program_run",
     "nbp_program_reseed", "nbp_program_num_seeds", "nbp_program_set_seeds", "nbp_program_seed_order", "nbp_ctx_attach", "nbp_ctx_attached", "nbp_program_num_stages", "nbp_program_num_fused", "nbp_program_num_two_stream", "nbp_program_destroy",
     "nbp_timing_enable", "nbp_timing_read", "nbp_timing_read_n", "nbp_diag_read",
@@ -335,6 +344,7 @@ def load_library(path=None):
     lib.nbp_run_overlap.argtypes = [vp, ip, ip, ip, ip, ip, ip, i32, C.POINTER(OverlapRec)]
     lib.nbp_kde_overlap.argtypes = [vp, i32, dp, i32, dp, i32, i32, dp, i32, dp, i32, C.POINTER(OverlapRec)]
     lib.nbp_run_overlap_search.argtypes = [vp, ip, ip, ip, i32, C.POINTER(OverlapOpts), ip, dp, ip, ip]
+    lib.nbp_run_scene_grid.argtypes = [vp, ip, ip, ip, dp, i32, C.POINTER(SceneDesc), dp, ip, ip, dp, C.POINTER(i64)]
     lib.nbp_run_credible.argtypes = [vp, ip, ip, ip, i32, C.POINTER(CredibleOpts), ip, dp, C.POINTER(CredibleRec), dp, ip,
                                      C.POINTER(CredibilityRec)]
     lib.nbp_kde_credible.argtypes = [vp, i32, dp, i32, dp, i32, C.POINTER(CredibleOpts), dp, i32, C.POINTER(CredibleRec), dp, ip,

@@ -509,6 +509,46 @@ class HipBackend:
         self._check(self.lib.nbp_run_overlap_search(self._ctx, sp, mp, kp, n, C.byref(opts), _ptr(idx), _ptr(logc), _ptr(found), _ptr(evaluated)))
         return idx, logc, found, evaluated
 
+    def run_scene_grid(self, slots, manifolds, dims, n, extent=None, margin=abi.SCENE_MARGIN, reach=abi.SCENE_REACH, weights=None,
+                       owner=False):
+        """every belief of a list of mutually admissible resident beliefs on ONE grid (nbp_run_scene_grid; scene.py): dims = the one
+        or two 0-BASED coordinates of every belief (one list for all, or one per belief), n = the points per axis, extent = (lo0,
+        step0[, lo1, step1]) or None for the automatic one with `margin`, weights = one per belief or None ->
+        (grid (n0,) or (n0, n1), extent[4] as used, owner grid or None, skipped[V], tile_beliefs)"""
+        (s, sp), (m, mp) = _i32(slots), _i32(manifolds)
+        V = s.size
+        dd = np.asarray(dims, dtype=np.int64)
+        if dd.ndim < 2:
+            dd = np.tile(dd.reshape(1, -1), (V, 1))
+        axes = dd.shape[1]
+        if m.size != V or dd.shape[0] != V or axes not in (1, 2):
+            raise ValueError("run_scene_grid: one manifold per slot and one or two coordinates per belief")
+        col = np.full((V, 2), -1, dtype=np.int32)
+        col[:, :axes] = dd
+        n = [int(v) for v in np.atleast_1d(n)]
+        n = n * axes if len(n) == 1 else n
+        if len(n) != axes:
+            raise ValueError("run_scene_grid: one size per axis")
+        g = abi.SceneDesc(margin=float(margin), reach=float(reach))
+        g.n[0], g.n[1] = n[0], n[1] if axes == 2 else 1
+        if extent is None:
+            g.flags = abi.SCENE_AUTO_EXTENT
+        else:
+            e = np.asarray(extent, dtype=np.float64).reshape(-1)
+            if e.size != 2 * axes:
+                raise ValueError("an extent is (lo, step) per axis")
+            for a in range(axes):
+                g.lo[a], g.step[a] = e[2 * a], e[2 * a + 1]
+        pts = max(g.n[0], 0) * max(g.n[1], 0)
+        w = None if weights is None else _f64(weights, (V,))
+        out, ext = np.zeros(pts), np.zeros(4)
+        own = np.full(pts, -1, dtype=np.int32) if owner else None
+        skipped, tb = np.zeros(V, dtype=np.int32), C.c_int64(0)
+        self._check(self.lib.nbp_run_scene_grid(self._ctx, sp, mp, _ptr(col), w[1] if w else None, V, C.byref(g), _ptr(out), _ptr(own),
+                                                _ptr(skipped), _ptr(ext), C.byref(tb)))
+        shape = (g.n[0],) if axes == 1 else (g.n[0], g.n[1])
+        return out.reshape(shape), ext, (own.reshape(shape) if owner else None), skipped, tb.value
+
     # ---- credible regions (nbp_run_credible; credible.py) ----------------------------------------------------------------------
     CRED_REC = np.dtype([("log_level", np.float64, (abi.CRED_MAX,)), ("quant", np.float64, (abi.MAXD, abi.CRED_MAX)),
                          ("mean", np.float64, (abi.MAXD,)), ("log_min", np.float64), ("log_max", np.float64),

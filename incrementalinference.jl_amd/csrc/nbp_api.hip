@@ -30,6 +30,7 @@
 #include "nbp_overlap.h"
 #include "nbp_credible.h"
 #include "nbp_mixture.h"
+#include "nbp_scene.h"
 
 static thread_local std::string g_err;
 static nbp_status fail(nbp_status code, const std::string &msg) {
@@ -1738,6 +1739,26 @@ struct scratch_layout {
       if (parts[k].to) memcpy(parts[k].to, back.data() + (off[k] - off[first]), parts[k].elem * parts[k].count);
     return NBP_OK;
   }
+  // fetch() for a layout whose parts from `big` on are large (grids): those go straight into the caller's buffers -- a staging vector
+  // of their size costs more than the kernel (profiles/marginal_grid_kernel.txt, profiles/scene_grid.txt) -- and the small parts
+  // before them come back in one copy; one wait for all of it
+  nbp_status fetch_split(nbp_ctx *c, size_t big) const {
+    for (size_t k = big; k < parts.size(); k++)
+      if (parts[k].to && parts[k].count)
+        HIPCHK(hipMemcpyAsync(parts[k].to, c->query + off[k], parts[k].elem * parts[k].count, hipMemcpyDeviceToHost, c->stream));
+    size_t first = big, last = 0;
+    for (size_t k = 0; k < big; k++)
+      if (parts[k].to && parts[k].count) first = std::min(first, k), last = k;
+    if (first == big) {
+      HIPCHK(hipStreamSynchronize(c->stream));
+      return NBP_OK;
+    }
+    std::vector<double> back(off[last + 1] - off[first]);
+    NBPCHK(query_fetch(c, back.data(), c->query + off[first], sizeof(double) * back.size()));
+    for (size_t k = first; k <= last; k++)
+      if (parts[k].to) memcpy(parts[k].to, back.data() + (off[k] - off[first]), parts[k].elem * parts[k].count);
+    return NBP_OK;
+  }
 };
 
 // Host-buffer forms: the beliefs go through slot 0 (and slot 1), which they clobber.  bw == nullptr: the bandwidth plays no part
@@ -2145,6 +2166,92 @@ nbp_status nbp_run_overlap_search(nbp_ctx *c, const int32_t *slots, const int32_
                         c->S, (const nbp_overlap_prep *)q.at(c, 0), o.reach * o.reach, std::log(o.min_coeff), o.topk, (int32_t *)q.at(c, 2),
                         q.at(c, 1), (int32_t *)q.at(c, 3), (int32_t *)q.at(c, 4)));
   return q.fetch(c);
+}
+
+// ---- scene densities (nbp_scene.h) -------------------------------------------------------------------------------------------------
+// what the scene entry refuses in its descriptor, whatever the list holds
+static nbp_status scene_desc_check(const nbp_scene_desc &g) {
+  const std::string who = "scene grid: ";
+  if (g.flags & ~NBP_SCENE_AUTO_EXTENT) return fail(NBP_ERR_ARG, who + "unknown flag");
+  if (!std::isfinite(g.margin)) return fail(NBP_ERR_ARG, who + "margin not finite");
+  if (!(g.reach > 0.0)) return fail(NBP_ERR_ARG, who + "reach must be positive (+inf: no culling)");
+  for (int a = 0; a < 2; a++)
+    if (g.n[a] < 1 || g.n[a] > NBP_SCENE_MAX) return fail(NBP_ERR_RANGE, who + "n outside 1 .. " + std::to_string(NBP_SCENE_MAX));
+  if ((int64_t)g.n[0] * g.n[1] > ((int64_t)1 << 22)) return fail(NBP_ERR_RANGE, who + "more than 2^22 grid points");
+  return NBP_OK;
+}
+
+// Every belief of a list of resident beliefs on one grid: the per-belief preparation, the extent where it is automatic, one wave per
+// tile (nbp_scene.h).  The columns (and an explicit extent) go up in one staging copy; the number of tiles depends on n alone, so
+// nothing comes back between the launches; the grid (and the owners) are copied straight into the caller's buffers, whatever else
+// was asked for in one more copy (scratch_layout::fetch_split).
+nbp_status nbp_run_scene_grid(nbp_ctx *c, const int32_t *slots, const int32_t *manifolds, const int32_t *dims, const double *weights,
+                              int32_t V, const nbp_scene_desc *desc, double *out, int32_t *owner_out, int32_t *skipped_out,
+                              double *extent_out, int64_t *tile_beliefs_out) {
+  if (!c || !desc || !out || V < 0 || ((!slots || !manifolds || !dims) && V > 0)) return fail(NBP_ERR_ARG, "scene grid: null argument or V < 0");
+  const nbp_scene_desc g = *desc;
+  NBPCHK(scene_desc_check(g));
+  const bool autoext = g.flags & NBP_SCENE_AUTO_EXTENT;
+  const size_t pts = (size_t)g.n[0] * (size_t)g.n[1];
+  const int axes = V > 0 && dims[1] == -1 ? 1 : 2;  // (belief 0 sets the shape of the scene)
+  int circ = 0;
+  NBPCHK(batch_check(c, "scene grid", {slots}, manifolds, V, [&](int i) {
+    const int D = manifold_dim_h(manifolds[i]), d0 = dims[2 * i], d1 = dims[2 * i + 1];
+    if (d0 < 0 || d0 >= D || d1 < -1 || d1 >= D) return refusal{NBP_ERR_RANGE, "coordinate outside the manifold"};
+    if (d1 == d0) return refusal{NBP_ERR_RANGE, "repeated coordinate"};
+    int kinds = manifold_circ_h(manifolds[i], d0) ? 1 : 0;
+    if (d1 >= 0 && manifold_circ_h(manifolds[i], d1)) kinds |= 2;
+    if (i == 0) circ = kinds;
+    if ((d1 == -1 ? 1 : 2) != axes || kinds != circ)
+      return refusal{NBP_ERR_ARG, "not admissible against belief 0: the coordinates differ in number or kind"};
+    if (weights && !(weights[i] >= 0.0 && std::isfinite(weights[i]))) return refusal{NBP_ERR_ARG, "weight negative or not finite"};
+    return refusal{NBP_OK, nullptr};
+  }));
+  if (V > 0 && axes == 1 && g.n[1] != 1) return fail(NBP_ERR_RANGE, "scene grid: a 1-D scene has n[1] = 1");
+  for (int a = 0; a < axes; a++) {
+    if (autoext && V > 0 && !(circ >> a & 1) && g.n[a] < 2) return fail(NBP_ERR_RANGE, "scene grid: automatic extent of a Euclidean axis needs n >= 2");
+    if (!autoext && !std::isfinite(g.lo[a])) return fail(NBP_ERR_RANGE, "scene grid: lo not finite");
+    if (!autoext && !(g.step[a] > 0.0 && std::isfinite(g.step[a]))) return fail(NBP_ERR_RANGE, "scene grid: step must be finite and positive");
+  }
+  double ext[4] = {0.0, 0.0, 0.0, 0.0};
+  if (!autoext)
+    for (int a = 0; a < axes; a++) ext[2 * a] = g.lo[a], ext[2 * a + 1] = g.step[a];
+  if (V == 0) {  // nothing to add: a grid of zeros, nobody's
+    std::fill(out, out + pts, 0.0);
+    if (owner_out) std::fill(owner_out, owner_out + pts, -1);
+    if (extent_out) memcpy(extent_out, ext, sizeof(ext));
+    if (tile_beliefs_out) *tile_beliefs_out = 0;
+    return NBP_OK;
+  }
+  const bool two = axes == 2;
+  const size_t tiles = two ? (size_t)((g.n[0] + NBP_GRID_TILE - 1) / NBP_GRID_TILE) * (size_t)((g.n[1] + NBP_GRID_TILE - 1) / NBP_GRID_TILE)
+                           : (size_t)((g.n[0] + NBP_GRID_TILE1 - 1) / NBP_GRID_TILE1);
+  std::vector<int32_t> counts(tile_beliefs_out ? tiles : 0);
+  // the query scratch: records | skipped | extent | tile counts | grid | owners; the small parts come back in one copy
+  static_assert(sizeof(nbp_scene_rec) % sizeof(double) == 0, "nbp_scene_rec fills whole doubles of the query scratch");
+  const size_t n = (size_t)V;
+  const scratch_layout q{{sizeof(nbp_scene_rec), n, nullptr}, {4, n, skipped_out}, {sizeof(double), 4, autoext ? extent_out : nullptr},
+                         {4, tiles, tile_beliefs_out ? counts.data() : nullptr}, {sizeof(double), pts, out}, {4, owner_out ? pts : 0, owner_out}};
+  const int32_t *d[5];
+  NBPCHK(stage_columns(c, {{slots, 4 * n}, {manifolds, 4 * n}, {dims, 8 * n}, {weights, weights ? 8 * n : 0}, {ext, sizeof(ext)}}, d, q.total()));
+  nbp_scene_rec *recs = (nbp_scene_rec *)q.at(c, 0);
+  const double *dw = weights ? (const double *)d[3] : nullptr, *dext = autoext ? q.at(c, 2) : (const double *)d[4];
+  NBPCHK(launch_checked(c, nbp_scene_prep_kernel, n, c->Npad, 0, d[0], d[1], d[2], (const double *)c->arena, c->N, c->S, g.margin, g.reach, recs,
+                        (int32_t *)q.at(c, 1)));
+  if (autoext)
+    NBPCHK(launch_checked(c, nbp_scene_extent_kernel, 1, NBP_GRID_LANES, 0, (const nbp_scene_rec *)recs, (int)V, (int)two, circ, (int)g.n[0],
+                          (int)g.n[1], q.at(c, 2)));
+  NBPCHK(launch_checked(c, owner_out ? nbp_scene_grid_owner_kernel : nbp_scene_grid_kernel, tiles, NBP_GRID_LANES, 0, (const nbp_scene_rec *)recs,
+                        d[0], d[2], dw, (int)V, (const double *)c->arena, c->N, c->S, (int)two, circ, (int)g.n[0], (int)g.n[1], dext, q.at(c, 4),
+                        (int32_t *)q.at(c, 5), (int32_t *)q.at(c, 3)));
+  NBPCHK(q.fetch_split(c, 4));  // (the grid and the owners straight into the caller's buffers)
+  if (extent_out && !autoext) memcpy(extent_out, ext, sizeof(ext));
+  if (tile_beliefs_out) {
+    int64_t sum = 0;
+    for (int32_t k : counts) sum += k;
+    *tile_beliefs_out = sum;
+  }
+  return NBP_OK;
 }
 
 // ---- credible regions (nbp_credible.h) -------------------------------------------------------------------------------------------

@@ -36,6 +36,15 @@
 #define NBP_EVAL_MARGINAL_ARGS                                                                                         \
   const int32_t *tiles, const int32_t *slots, const int32_t *manifolds, const int32_t *masks, const double *arena,     \
       int N, int64_t S, const double *queries, double *dens
+#if NBP_TU & (NBP_TU_MARGINAL | NBP_TU_SCENE)
+// one entry of a per-axis table (the scene kernels of nbp_scene.h call it too: the same bits)
+__device__ __forceinline__ double grid_axis_term(double g, double x, bool circ, double r, const double *tab) {
+  double d = g - x;
+  if (circ) d = wrap_pi(d);
+  d *= r;
+  return exp_nonpos(-0.5 * (d * d), tab);
+}
+#endif
 #if NBP_TU & NBP_TU_MARGINAL
 // the automatic extent of one axis from the exact minimum and maximum of its coordinate
 __device__ __forceinline__ void grid_auto_axis(bool circ, double mn, double mx, double h, double margin, int n, double *lo,
@@ -48,12 +57,6 @@ __device__ __forceinline__ void grid_auto_axis(bool circ, double mn, double mx, 
     *lo = l;
     *step = (u - l) / (double)(n - 1);
   }
-}
-__device__ __forceinline__ double grid_axis_term(double g, double x, bool circ, double r, const double *tab) {
-  double d = g - x;
-  if (circ) d = wrap_pi(d);
-  d *= r;
-  return exp_nonpos(-0.5 * (d * d), tab);
 }
 
 // One workgroup (one wave) per tile.  LDS: exp table | X[2][CHUNK] | E[2][CHUNK][TILE].  2-D: over chunks of particles in

@@ -9,6 +9,8 @@ What travels is what changed: new variables and host edits go up, the beliefs a 
 hot path is host traffic that no longer happens."""
 import time
 
+import numpy as np
+
 from . import abi, bayestree
 from .ppe import MeanMaxPPE
 from .solver import (TreeProgram, _initialised_subgraph, _make_backend, _refuse_joint_recycling, _runs_on_libnbp,
@@ -393,6 +395,35 @@ class SolveSession:
         return self._query_resident(labels, "run_mixture", run, lambda res, i, v: res[i],
                                     lambda v, **k: mixture.fitBeliefMixture(self.fg, v, maxComponents, bwScale, tol, maxIter, **k),
                                     call=lambda be, *a: mixture.resident_mixtures(be, *a))
+
+    def sceneGrid(self, labels=None, dims=(1, 2), n=512, extent=None, margin=abi.SCENE_MARGIN, reach=abi.SCENE_REACH, weights=None,
+                  owner=False):
+        """The variables' current beliefs on ONE grid (scene.py) -> Scene.  labels: a list, a regular expression, or None for every
+        variable the last solve worked on whose manifold has the coordinates; the other arguments as in `scene.sceneGrid`.  Served
+        by ONE `run_scene_grid` where the beliefs lie (`_query_resident`): no belief travels and `stats` does not move.  Without a
+        context, on a backend without that entry point, or with a variable that has no slot in the session's context:
+        `scene.sceneGrid` on the host copy (with backend=self.backend where there is a context)."""
+        from . import scene
+        if self._closed:
+            raise RuntimeError("this SolveSession is closed")
+        if labels is None and self._labels:
+            per = dims if isinstance(dims, dict) else None
+            need = (lambda v: max(np.atleast_1d(per[v]))) if per is not None else (lambda v: max(np.atleast_1d(dims)))
+            labels = [v for v in sorted(self._labels, key=scene._natural)  # (natural order: `scene.sceneGrid`'s, so the same sums)
+                      if (per is None or v in per) and self.fg.getVariable(v).varType.dim >= need(v)]
+        labels, dims_of = scene.scene_labels(self.fg, labels, dims)
+        args = (dims_of, n, extent, margin, reach, weights, owner)
+        if self._be is None or getattr(self._be, "run_scene_grid", None) is None:
+            return scene.sceneGrid(self.fg, labels, *args)
+        if not labels or any(v not in self._labels for v in labels):
+            return scene.sceneGrid(self.fg, labels, *args, backend=self.backend)
+
+        def run(here, place):
+            slots, mans, dd, w = scene.scene_columns(self.fg, here, dims_of, weights, place)
+            nn = scene._sizes(n, len(dd[0]))
+            return slots, mans, dd, nn, None if extent is None else np.asarray(extent, dtype=np.float64).reshape(-1), margin, reach, w, owner
+        res = self._query_resident(labels, "run_scene_grid", run, lambda res, i, v: res, None)[labels[0]]
+        return scene.scene_from_result(labels, n, res[:4], res[4])
 
     # ---- one solve ---------------------------------------------------------------------------------------------------------
     def solve(self, seed=0, eliminationOrder=None, ordering="qr", return_timing=False):
