@@ -105,6 +105,9 @@ struct NbpDiag
   proposal_launches_workgroup::Int64
   proposal_launches_wave::Int64
   proposal_launches_split::Int64
+  lane_side_launches::Int64
+  lane_waits::Int64
+  lane_side_updates::Int64
 end
 
 # nbp_solver_params (include/nbp_host.h): the SolverParams fields the path reads (entities/SolverParams.jl:12-75)

@@ -194,6 +194,11 @@ typedef struct nbp_diag {
   int64_t proposal_launches_workgroup;
   int64_t proposal_launches_wave;
   int64_t proposal_launches_split;
+  /* program lanes (nbp_program_set_lanes), counted on the host the same way: launches issued on lane 1, waits of one lane
+     for the other, variable updates (product descriptors) that ran on lane 1 */
+  int64_t lane_side_launches;
+  int64_t lane_waits;
+  int64_t lane_side_updates;
 } nbp_diag;
 
 typedef struct nbp_ctx nbp_ctx;
@@ -879,6 +884,20 @@ nbp_status nbp_program_num_fused(nbp_program *prog, int32_t *out);
 /* rounds of a finalized program whose two halves run on two streams, one launch apart (environment NBP_PIPELINE_MIN =
  * smallest product batch that is split; same particles and bandwidths as the single-stream order, bit for bit) */
 nbp_status nbp_program_num_two_stream(nbp_program *prog, int32_t *out);
+/* Lanes.  A hint for one stage, given before nbp_program_finalize: descriptor i may run on lane lane_of_descriptor[i] (0: the
+ * library stream, 1: a second stream), beside whatever the other lane runs meanwhile -- for the updates of cliques whose
+ * schedules are longer than their siblings', which would otherwise ride in chip-filling stages and finish alone (the native
+ * host marks them: nbp_tree_schedule).  The stage list, the seed order and every result stay what they are without the
+ * hint: what a lane waits for is derived from the slots, so a wrong hint costs time only.  Environment NBP_NO_LANES=1 (read
+ * at nbp_ctx_create): hints are ignored. */
+nbp_status nbp_program_set_lanes(nbp_program *prog, int32_t stage, const int32_t *lane_of_descriptor, int32_t n);
+/* The plan of a finalized program, one record per part in list order (per stage its lane-0 descriptors, then its lane-1
+ * descriptors): n_out = the number of parts (0: the program runs without lanes); at most cap records are written.
+ * wait = the part of the other lane that must have finished before this one starts, -1: none. */
+typedef struct nbp_lane_part_rec {
+  int32_t stage, lane, first_desc, n, wait, signals;
+} nbp_lane_part_rec;
+nbp_status nbp_program_lane_plan(nbp_program *prog, nbp_lane_part_rec *out, int32_t cap, int32_t *n_out);
 nbp_status nbp_program_destroy(nbp_program *prog);
 /* destroy without waiting: the program is dropped once everything queued on the library stream so far has run */
 nbp_status nbp_program_retire(nbp_program *prog);

@@ -338,6 +338,10 @@ nbp_status nbp_clique_seam_times(double *seconds_out6, int32_t mode);
 /* test access: the descriptors of stage s of the last compile (kind = NBP_STAGE_*; bytes copied <= cap) */
 int32_t nbp_tree_num_stages(const nbp_tree *t);
 nbp_status nbp_tree_stage(const nbp_tree *t, int32_t s, int32_t *kind, int32_t *n, void *descs_out, int64_t cap_bytes);
+/* the lane hint of stage s, one entry per descriptor (nbp_program_set_lanes; all 0 where the schedule marked nothing):
+ * nbp_tree_schedule gives lane 1 to every round of a clique whose schedule covers a time step of at most
+ * NBP_LANE_NARROW_MAX updates (environment, default 32) and a wider one, and to the points-only copies that feed it */
+nbp_status nbp_tree_stage_lanes(const nbp_tree *t, int32_t s, int32_t *lanes_out, int32_t cap);
 
 #ifdef __cplusplus
 }

@@ -791,7 +791,7 @@ _STAGE_CTYPE = {abi.STAGE_PROPOSALS: abi.ProposalDesc, abi.STAGE_PRODUCTS: abi.P
 class HipProgram:
     """A device-resident schedule: list of (kind, descriptor-array) stages uploaded once."""
 
-    def __init__(self, backend, stages, lazy_bandwidth=False, fused_updates=True):
+    def __init__(self, backend, stages, lazy_bandwidth=False, fused_updates=True, lanes=None):
         self.backend, lib = backend, backend.lib
         self._p = C.c_void_p()
         backend._check(lib.nbp_program_create(backend._ctx, C.byref(self._p)))
@@ -803,8 +803,19 @@ class HipProgram:
         for kind, descs in stages:
             arr, n = _as_array(descs, _STAGE_CTYPE[kind])
             backend._check(lib.nbp_program_add_stage(self._p, kind, C.cast(arr, C.c_void_p), n))
+        for s, hint in (lanes or {}).items():  # {stage: [lane per descriptor]} (nbp_program_set_lanes); the Python host passes none
+            arr = (C.c_int32 * max(len(hint), 1))(*[int(x) for x in hint])
+            backend._check(lib.nbp_program_set_lanes(self._p, s, arr, len(hint)))
         backend._check(lib.nbp_program_finalize(self._p))
         self.n_stages = len(stages)
+
+    def lane_plan(self):
+        """the parts of a program with lanes, in list order: dicts of the fields of nbp_lane_part_rec ([]: no lanes)"""
+        n = C.c_int32(0)
+        self.backend._check(self.backend.lib.nbp_program_lane_plan(self._p, None, 0, C.byref(n)))
+        recs = (abi.LanePartRec * max(n.value, 1))()
+        self.backend._check(self.backend.lib.nbp_program_lane_plan(self._p, recs, n.value, C.byref(n)))
+        return [{k: getattr(r, k) for k, _ in abi.LanePartRec._fields_} for r in recs[:n.value]]
 
     def num_fused(self):
         """rounds (PROPOSALS + PRODUCTS stage pairs) that run as one launch of the fused update kernel"""

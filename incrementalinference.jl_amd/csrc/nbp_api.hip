@@ -31,6 +31,7 @@
 #include "nbp_credible.h"
 #include "nbp_mixture.h"
 #include "nbp_scene.h"
+#include "../../include/nbp_lanes.h"
 
 static thread_local std::string g_err;
 static nbp_status fail(nbp_status code, const std::string &msg) {
@@ -148,6 +149,17 @@ struct nbp_ctx {
   hipStream_t stream2 = nullptr;
   hipEvent_t pipe_ev[2] = {nullptr, nullptr};
   int pipe_min = 1 << 30;
+  // program lanes (plan_lanes / run_lanes): lane 1 runs on stream2 with a rendezvous area (the second half of `spec`), a
+  // statistics area and a share of the KD workspace of its own; the events of the cross-lane waits, per recording lane, plus
+  // the fork and the join of a range.  NBP_NO_LANES=1: hints are ignored (the launch sequence of a program without them)
+  bool no_lanes = false;
+  hipEvent_t lane_ev[2][4] = {{nullptr, nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr, nullptr}};
+  hipEvent_t lane_fork = nullptr, lane_join = nullptr;
+  double *gstats1 = nullptr;
+  size_t gstats1_doubles = 0;
+  // since the last reset of nbp_diag_read, counted where the launch is issued: launches on lane 1, cross-lane waits, updates
+  // (product descriptors) that ran on lane 1
+  int64_t lane_side_launches = 0, lane_waits = 0, lane_side_updates = 0;
   // fit launches (fit_plan): NBP_LCV_P2_MIN / NBP_LCV_P1_MIN = workgroups of a launch above which a fit runs on two / one helper
   // rows; NBP_NO_W5_FITS: never the five-wave instances; NBP_DEBUG_OCCUPANCY: print what the runtime says a CU holds of a
   // plain bandwidth launch
@@ -338,6 +350,7 @@ static void ctx_plan_fields(nbp_ctx *c, int N) {
   if (getenv("NBP_PROPOSAL_WAVE_MIN")) c->prop_wave_min = atoi(getenv("NBP_PROPOSAL_WAVE_MIN"));
   if (getenv("NBP_PROPOSAL_SPLIT_MIN")) c->prop_split_min = atoi(getenv("NBP_PROPOSAL_SPLIT_MIN"));
   if (getenv("NBP_PIPELINE_MIN")) c->pipe_min = atoi(getenv("NBP_PIPELINE_MIN"));
+  c->no_lanes = getenv("NBP_NO_LANES") && atoi(getenv("NBP_NO_LANES")) != 0;
   if (getenv("NBP_FUSED_P1_MIN")) c->fused_p1_min = atoi(getenv("NBP_FUSED_P1_MIN"));
   if (getenv("NBP_PRODUCT_HL2_MIN")) c->prod_hl2_min = atoi(getenv("NBP_PRODUCT_HL2_MIN"));
   if (getenv("NBP_PRODUCT_NCH")) c->prod_nch = atoi(getenv("NBP_PRODUCT_NCH"));
@@ -388,9 +401,12 @@ nbp_status nbp_ctx_create(int32_t device, int32_t N, int32_t n_slots, void *aren
     HIPCHK(hipMemcpy(&c->counters->flags, &fl, sizeof(fl), hipMemcpyHostToDevice));
   }
   HIPCHK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-  HIPCHK(hipMalloc(&c->spec, sizeof(nbp_spec_area) * 3 * NBP_SPEC_MAXJOBS));
+  HIPCHK(hipMalloc(&c->spec, sizeof(nbp_spec_area) * 3 * NBP_SPEC_MAXJOBS * 2));  // (the second half: lane 1 of a program)
   HIPCHK(hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking));
   for (int i = 0; i < 2; i++) HIPCHK(hipEventCreateWithFlags(&c->pipe_ev[i], hipEventDisableTiming));
+  for (int i = 0; i < 8; i++) HIPCHK(hipEventCreateWithFlags(&c->lane_ev[i / 4][i % 4], hipEventDisableTiming));
+  HIPCHK(hipEventCreateWithFlags(&c->lane_fork, hipEventDisableTiming));
+  HIPCHK(hipEventCreateWithFlags(&c->lane_join, hipEventDisableTiming));
   nbp_status rc = build_levels(c);
   if (rc != NBP_OK) return rc;
   // allow the full 160 KiB LDS for the product kernels
@@ -463,6 +479,10 @@ nbp_status nbp_ctx_destroy(nbp_ctx *c) {
   if (c->spec) hipFree(c->spec);
   if (c->stream2) hipStreamDestroy(c->stream2);
   for (int i = 0; i < 2; i++) if (c->pipe_ev[i]) hipEventDestroy(c->pipe_ev[i]);
+  for (int i = 0; i < 8; i++) if (c->lane_ev[i / 4][i % 4]) hipEventDestroy(c->lane_ev[i / 4][i % 4]);
+  if (c->lane_fork) hipEventDestroy(c->lane_fork);
+  if (c->lane_join) hipEventDestroy(c->lane_join);
+  if (c->gstats1) hipFree(c->gstats1);
   if (c->stream) hipStreamDestroy(c->stream);
   delete c;
   return NBP_OK;
@@ -931,8 +951,13 @@ struct nbp_launch_env {
   double *ws = nullptr;
   size_t ws_doubles = 0;
   int geom_n = 0, geom_blocks = 0;
+  // a lane of a program (run_lanes): 0 = none; 1, 2 = lane 0, lane 1.  Its share of the workspace is fixed (sized at
+  // nbp_program_finalize: the other lane's launches are in flight beside it); lane 1 has the second rendezvous area and the
+  // second statistics area
+  int lane = 0;
 };
-static nbp_launch_env ctx_env(const nbp_ctx *c) { return {c->stream, c->ws, c->ws_doubles, 0, 0}; }
+static nbp_launch_env ctx_env(const nbp_ctx *c) { return {c->stream, c->ws, c->ws_doubles, 0, 0, 0}; }
+static nbp_spec_area *env_spec(const nbp_ctx *c, const nbp_launch_env &env) { return c->spec + (env.lane == 2 ? 3 * NBP_SPEC_MAXJOBS : 0); }
 
 // 0, or the class of a batch whose relative factors are all full (non-partial) factors of one kind on one manifold, with
 // everything else in it (priors, message priors, pass-through densities) on that manifold as well: LinearRelative on
@@ -1033,6 +1058,7 @@ static nbp_status ensure_ws(nbp_ctx *c, nbp_launch_env &env, int nprod, int kdF)
   // a half of a two-stream round may hold an INTERIOR pointer of the workspace (the second half's share): never freed or
   // re-allocated here -- the round is sized at finalize, a shortfall now is a planning error, not a reason to grow
   if (env.geom_n) return fail(NBP_ERR_RANGE, "KD workspace too small inside a two-stream round (sized at nbp_program_finalize)");
+  if (env.lane) return fail(NBP_ERR_RANGE, "KD workspace too small for a lane of a program (sized at nbp_program_finalize)");
   HIPCHK(hipStreamSynchronize(c->stream));
   if (c->ws) HIPCHK(hipFree(c->ws));
   c->ws = nullptr;
@@ -1315,7 +1341,7 @@ static nbp_product_plan_rec product_plan_rec(const nbp_ctx *c, const nbp_launch_
 // the rendezvous areas of the next launch of speculative fits, blanked on the launch's stream
 static void blank_spec_areas(nbp_ctx *c, const nbp_launch_env &env, int jobs) {
   const int words = (int)(sizeof(nbp_spec_area) / 8) * 3 * jobs;
-  hipLaunchKernelGGL(nbp_spec_blank_kernel, dim3((words + 255) / 256), dim3(256), 0, env.stream, (unsigned long long *)c->spec, words);
+  hipLaunchKernelGGL(nbp_spec_blank_kernel, dim3((words + 255) / 256), dim3(256), 0, env.stream, (unsigned long long *)env_spec(c, env), words);
 }
 
 // nbp_prep_kernel: pending bandwidth fits + KD builds of this product batch, one launch (grid: 3 * KS workgroups per fit,
@@ -1335,7 +1361,7 @@ static nbp_status launch_prep(nbp_ctx *c, nbp_launch_env &env, const nbp_fits_de
   if (f.depth) {
     blank_spec_areas(c, env, bw.n);
     hipLaunchKernelGGL(f.depth == 3 ? nbp_prep_kernel_spec<3> : nbp_prep_kernel_spec<2>, grid, dim3(f.threads), f.lds, env.stream, bw.slots, bw.manis,
-                       bw.n, dev, n, kdF, c->arena, env.ws, c->N, c->Npad, c->S, c->T, c->counters, c->spec);
+                       bw.n, dev, n, kdF, c->arena, env.ws, c->N, c->Npad, c->S, c->T, c->counters, env_spec(c, env));
   } else
     hipLaunchKernelGGL(f.w5 ? nbp_prep_kernel_w5 : nbp_prep_kernel, grid, dim3(f.threads), f.lds, env.stream, bw.slots, bw.manis, bw.n, dev, n, kdF,
                        c->arena, env.ws, c->N, c->Npad, c->S, c->T, c->counters);
@@ -1367,7 +1393,9 @@ static nbp_status launch_products(nbp_ctx *c, const nbp_launch_env &env, const n
   const char *why = nullptr;
   if (product_plan_refusal(p, env, &why)) return fail(NBP_ERR_RANGE, why);
   nbp_status rc = NBP_OK;
-  if (p.big) {
+  if (p.big && env.lane == 2) {  // (beside lane 0's launches: its own area, sized at nbp_program_finalize)
+    if (p.gstats > c->gstats1_doubles) return fail(NBP_ERR_RANGE, "statistics area too small for lane 1 of a program (sized at nbp_program_finalize)");
+  } else if (p.big) {
     rc = ensure_gstats(c, p.gstats);
     if (rc) return rc;
   }
@@ -1375,8 +1403,8 @@ static nbp_status launch_products(nbp_ctx *c, const nbp_launch_env &env, const n
   if (rc) return rc;
   (void)hipGetLastError();
   const int flagsF = (maxFD / 4) | (p.nch << NBP_PROD_NCH_SHIFT) | (p.all_levels ? NBP_PROD_ALL_LEVELS : 0);
-  hipLaunchKernelGGL(p.fn, dim3(n, p.G), dim3(p.wpb * 64), p.lds, env.stream, dev, c->arena, env.ws, flagsF, p.big ? c->gstats : nullptr, c->N, c->S,
-                     c->side, c->T);
+  hipLaunchKernelGGL(p.fn, dim3(n, p.G), dim3(p.wpb * 64), p.lds, env.stream, dev, c->arena, env.ws, flagsF,
+                     p.big ? (env.lane == 2 ? c->gstats1 : c->gstats) : nullptr, c->N, c->S, c->side, c->T);
   HIPCHK(hipGetLastError());
   return toc(c, c->ev[2]);
 }
@@ -1405,7 +1433,7 @@ static nbp_status launch_bandwidth(nbp_ctx *c, const nbp_launch_env &env, const 
   if (f.depth) {
     blank_spec_areas(c, env, bw.n);
     hipLaunchKernelGGL(f.depth == 3 ? nbp_bandwidth_kernel_spec<3> : nbp_bandwidth_kernel_spec<2>, dim3(bw.n, 3, f.KS), dim3(f.threads), f.lds, env.stream,
-                       bw.slots, bw.manis, c->arena, c->N, c->Npad, c->S, c->counters, c->spec);
+                       bw.slots, bw.manis, c->arena, c->N, c->Npad, c->S, c->counters, env_spec(c, env));
   } else {
     auto *kern = f.w5 ? nbp_bandwidth_kernel_w5 : nbp_bandwidth_kernel;
     if (c->debug_occupancy) {  // what the runtime says a CU can hold of this launch
@@ -1442,11 +1470,12 @@ static int products_maxfd(const nbp_product_desc *d, int n) {
   return F * 4 + D;
 }
 // whole slots, or (points_only: NBP_STAGE_COPY_POINTS) the points and the count, the destination's bandwidth left alone
-static nbp_status launch_copies(nbp_ctx *c, const nbp_copy_desc *dev, int n, bool points_only = false) {
+static nbp_status launch_copies(nbp_ctx *c, const nbp_copy_desc *dev, int n, bool points_only = false, hipStream_t stream = nullptr) {
   if (n <= 0) return NBP_OK;
   (void)hipGetLastError();
-  if (points_only) hipLaunchKernelGGL(nbp_copy_points_kernel, dim3(n), dim3(256), 0, c->stream, dev, c->arena, c->S, c->N);
-  else hipLaunchKernelGGL(nbp_copy_kernel, dim3(n), dim3(256), 0, c->stream, dev, c->arena, c->S);
+  if (!stream) stream = c->stream;
+  if (points_only) hipLaunchKernelGGL(nbp_copy_points_kernel, dim3(n), dim3(256), 0, stream, dev, c->arena, c->S, c->N);
+  else hipLaunchKernelGGL(nbp_copy_kernel, dim3(n), dim3(256), 0, stream, dev, c->arena, c->S);
   HIPCHK(hipGetLastError());
   return NBP_OK;
 }
@@ -2920,6 +2949,17 @@ struct nbp_stage {
   // where plan_pipeline put the descriptor the caller gave as the i-th of the stage (empty: where it was).  The seed table is
   // laid out through it (layout_blob): nbp_program_set_seeds takes its seeds in the CALLER's order
   std::vector<int> moved_to;
+  // lanes (plan_lanes): the hint as nbp_program_set_lanes gave it (caller order); descriptors [lane_split, n) are lane 1
+  // (-1: the stage has none)
+  std::vector<int32_t> lane_hint;
+  int lane_split = -1;
+  // as a PART of a program with lanes (nbp_program::parts): the lane, the stage it is a share of, every fit still pending
+  // on either lane where its stage begins (`bound`, on the first part of a stage: what a range that ends there runs), the
+  // parts of the other lane it waits for and whether one of them waits for it (nbp_lanes.h)
+  int lane = 0, user = -1;
+  nbp_fits bound;
+  std::vector<int> waits;
+  bool signals = false;
 };
 struct nbp_program {
   nbp_ctx *ctx = nullptr;
@@ -2941,6 +2981,11 @@ struct nbp_program {
   size_t seed_val_off = 0;  // n_seeds values behind the table: where nbp_program_set_seeds puts the new seeds before it scatters them
   int n_seeds = 0;
   std::vector<int32_t> seed_rank;  // nbp_program_seed_order
+  // lanes: the parts in list order + a trailing pseudo part (empty: the program has no lane 1); first_part[s] = the first
+  // part of stage s (n_user_stages + 1 entries); what lane 1 needs of the KD workspace and of the statistics area
+  std::vector<nbp_stage> parts;
+  std::vector<int> first_part;
+  size_t lane_ws = 0, lane_gstats = 0;
 };
 
 nbp_status nbp_program_create(nbp_ctx *c, nbp_program **out) {
@@ -2996,6 +3041,21 @@ nbp_status nbp_program_add_stage(nbp_program *p, int32_t kind, const void *descs
   if (n) memcpy(p->blob.data() + off, descs, esz * (size_t)n);
   st.kind = kind; st.n = n; st.offset = off;
   p->stages.push_back(st);
+  return NBP_OK;
+}
+
+// A hint, not an order: descriptor i of the stage may run on lane lane_of_descriptor[i] (0: the library stream, 1: the second
+// stream), beside whatever the other lane runs meanwhile.  What a lane waits for is derived from the slots (plan_lanes).
+nbp_status nbp_program_set_lanes(nbp_program *p, int32_t stage, const int32_t *lane_of_descriptor, int32_t n) {
+  if (!p || (!lane_of_descriptor && n > 0)) return fail(NBP_ERR_ARG, "null argument");
+  PROG_ALIVE(p);
+  if (p->finalized) return fail(NBP_ERR_ARG, "program already finalized");
+  if (stage < 0 || stage >= (int)p->stages.size()) return fail(NBP_ERR_RANGE, "set_lanes: no such stage");
+  nbp_stage &st = p->stages[(size_t)stage];
+  if (n != st.n) return fail(NBP_ERR_ARG, "set_lanes: one lane per descriptor of the stage");
+  for (int i = 0; i < n; i++)
+    if (lane_of_descriptor[i] != 0 && lane_of_descriptor[i] != 1) return fail(NBP_ERR_RANGE, "set_lanes: a lane is 0 or 1");
+  st.lane_hint.assign(lane_of_descriptor, lane_of_descriptor + n);
   return NBP_OK;
 }
 
@@ -3233,9 +3293,43 @@ static nbp_status launch_update(nbp_ctx *c, const nbp_stage &st, const nbp_updat
 // products of the stage), balances the halves, and reorders the descriptors of both stages so that each half is a
 // contiguous range.  Every launch of a half uses the geometry of the whole batch (helper rows per fit, lanes per sample),
 // so no particle depends on the split: tests/test_gpu_pipelined_rounds.py compares every slot, bit for bit.
+// ---- lanes --------------------------------------------------------------------------------------------------------------
+// A tree pass batches round tt - start[c] of every running clique into stage tt, so a clique with a long schedule pays for
+// each of its rounds the time of whatever chip-filling stage it rides in, and runs its last rounds alone on an idle chip.
+// The host that compiled the stages knows which cliques those are and says so (nbp_program_set_lanes); here the stages keep
+// their place and their descriptors, and below them the program runs two lanes: lane 0 on the library stream, lane 1 on
+// the second stream with launches of its own size.  plan_lanes moves the lane-1 descriptors of a stage behind the others
+// (moved_to: the seed table stays in the caller's order); plan_parts cuts the stages into parts, schedules the pending
+// fits per lane and derives from the slots what a part waits for on the other lane; run_lanes launches the parts.
+static void plan_lanes(nbp_program *p) {
+  if (p->ctx->no_lanes) return;
+  for (int s = 0; s < p->n_user_stages; s++) {
+    nbp_stage &st = p->stages[(size_t)s];
+    if (st.lane_hint.empty()) continue;
+    const size_t esz = st.kind == NBP_STAGE_PROPOSALS ? sizeof(nbp_proposal_desc) : (st.kind == NBP_STAGE_PRODUCTS ? sizeof(nbp_product_desc) :
+                       (st.kind == NBP_STAGE_COPY_POINTS ? sizeof(nbp_copy_desc) : 0));
+    if (!esz) continue;  // whole-slot copies and deconvolutions stay on lane 0
+    int n1 = 0;
+    for (int32_t l : st.lane_hint) n1 += l;
+    if (!n1) continue;
+    std::vector<char> moved((size_t)st.n * esz);
+    st.moved_to.assign((size_t)st.n, 0);
+    int at = 0;
+    for (int l = 0; l < 2; l++)
+      for (int i = 0; i < st.n; i++)
+        if (st.lane_hint[(size_t)i] == l) {
+          st.moved_to[(size_t)i] = at;
+          memcpy(moved.data() + (size_t)at++ * esz, p->blob.data() + st.offset + (size_t)i * esz, esz);
+        }
+    memcpy(p->blob.data() + st.offset, moved.data(), moved.size());
+    st.lane_split = st.n - n1;
+  }
+}
+
 static void plan_pipeline(nbp_program *p, int s) {
   nbp_stage &ps = p->stages[s], &qs = p->stages[s + 1];
   if (ps.kind != NBP_STAGE_PROPOSALS || qs.kind != NBP_STAGE_PRODUCTS || qs.n < p->ctx->pipe_min || qs.n < 128) return;
+  if (ps.lane_split >= 0 || qs.lane_split >= 0) return;  // lanes win: a round with lane-1 descriptors is not cut in two as well
   nbp_proposal_desc *pd = (nbp_proposal_desc *)(p->blob.data() + ps.offset);
   nbp_product_desc *qd = (nbp_product_desc *)(p->blob.data() + qs.offset);
   std::unordered_map<int32_t, int> prop_of, prod_of, reader_of;
@@ -3400,6 +3494,158 @@ static void split_piped_entry_fits(nbp_program *p) {
   }
 }
 
+// The parts of a program with lanes, their fits and their waits.  The stages themselves keep the schedule schedule_fits gave
+// them: a run without lanes (timing, a range that cuts a lane-1 region) launches them whole, as it always has.
+//   * parts: per stage its lane-0 descriptors, then its lane-1 descriptors; a trailing pseudo part like the trailing stage.
+//   * fits: one pending list per lane, walked like schedule_fits walks the one list.  A part that needs the bandwidth of a
+//     slot whose fit is pending on the OTHER lane, or overwrites such a slot, takes the fit over: it runs on the lane of
+//     the part that first reads its result (a points-only read leaves it where it is: a fit does not touch the points).  A
+//     points-only overwrite voids a pending fit on either lane.  Whole-slot copies and the end of the program take over
+//     everything.
+//   * waits: nbp_lane_sweep over what every part reads and writes, its fits included -- the points and the bandwidth of a
+//     slot apart (2 * slot, 2 * slot + 1): a fit reads the points and writes the bandwidth; the side buffer (hypothesis
+//     indices, labels) counts as one slot, an empty copy stage is a barrier.
+// No lanes (parts stay empty) where a stage with lane-1 descriptors runs fused.
+#define NBP_LANE_SLOT_SIDE (-2)
+static void plan_parts(nbp_program *p, const nbp_liveness &live) {
+  bool any = false;
+  for (int s = 0; s < p->n_user_stages; s++) {
+    const nbp_stage &st = p->stages[(size_t)s];
+    if (st.lane_split < 0) continue;
+    if (st.fused || st.fused_second) return;
+    any = true;
+  }
+  if (!any) return;
+  std::vector<nbp_stage> &parts = p->parts;
+  std::vector<const char *> dead;  // per part: the liveness row of its descriptors
+  p->first_part.assign((size_t)p->n_user_stages + 1, 0);
+  for (int s = 0; s < p->n_user_stages; s++) {
+    const nbp_stage &st = p->stages[(size_t)s];
+    p->first_part[(size_t)s] = (int)parts.size();
+    const size_t esz = st.kind == NBP_STAGE_PRODUCTS ? sizeof(nbp_product_desc) : (st.kind == NBP_STAGE_COPIES || st.kind == NBP_STAGE_COPY_POINTS ?
+                       sizeof(nbp_copy_desc) : sizeof(nbp_proposal_desc));
+    const int cut = st.lane_split < 0 ? st.n : st.lane_split;
+    for (int l = 0; l < 2; l++) {
+      const int from = l ? cut : 0, n = l ? st.n - cut : cut;
+      if (n == 0 && (l || st.lane_split >= 0)) continue;  // (an empty stage stays, as one empty lane-0 part: the barrier)
+      nbp_stage pt;
+      pt.kind = st.kind; pt.n = n; pt.offset = st.offset + (size_t)from * esz; pt.lane = l; pt.user = s;
+      pt.maxfd = st.maxfd; pt.mani = st.mani;
+      if (st.kind == NBP_STAGE_PRODUCTS && st.lane_split >= 0) {
+        pt.maxfd = products_maxfd((const nbp_product_desc *)(p->blob.data() + pt.offset), n);
+        pt.mani = products_uniform_manifold((const nbp_product_desc *)(p->blob.data() + pt.offset), n);
+      }
+      if (st.kind == NBP_STAGE_PROPOSALS && st.lane_split >= 0) pt.mani = proposals_uniform_class((const nbp_proposal_desc *)(p->blob.data() + pt.offset), n);
+      const std::vector<char> &row = st.kind == NBP_STAGE_PRODUCTS ? live.dead_product[(size_t)s] : live.dead_proposal[(size_t)s];
+      dead.push_back(row.empty() ? nullptr : row.data() + from);
+      parts.push_back(std::move(pt));
+    }
+  }
+  p->first_part[(size_t)p->n_user_stages] = (int)parts.size();
+  {
+    nbp_stage pt;  // trailing pseudo part (kind 0)
+    pt.user = p->n_user_stages;
+    dead.push_back(nullptr);
+    parts.push_back(std::move(pt));
+  }
+  // ---- the pending fits, per lane
+  nbp_fits pend[2];
+  std::vector<nbp_fits> ran(parts.size());  // what each part runs of fits, for the sweep
+  for (int k = 0; k < (int)parts.size(); k++) {
+    nbp_stage &st = parts[(size_t)k];
+    const int l = st.lane, o = 1 - l;
+    const char *d = p->blob.data() + st.offset;
+    if (k == p->first_part[(size_t)st.user]) {
+      st.bound = pend[0];
+      for (const nbp_fits::fit &f : pend[1].v) st.bound.push(f.slot, f.mani);
+    }
+    if (st.kind == NBP_STAGE_DECONV || st.kind == NBP_STAGE_COPY_POINTS)  // points-only overwrite: the fit of the old points is void
+      stage_writes(p, st, [&](int, int32_t slot) { pend[0].drop(slot); pend[1].drop(slot); });
+    if (!pend[o].empty()) {  // fits pending on the other lane that this part needs, or whose slots it overwrites: taken over
+      auto claim = [&](int32_t slot) {
+        for (size_t i = 0; i < pend[o].v.size();)
+          if (pend[o].v[i].slot == slot) { pend[l].v.push_back(pend[o].v[i]); pend[o].v.erase(pend[o].v.begin() + (long)i); } else i++;
+      };
+      // (the one points-only read of a product is its old_slot, topped up in place from the slot's bandwidth: schedule_fits)
+      stage_reads(p, st, [&](int, int32_t slot, nbp_access a) { if (a != NBP_RD_POINTS || st.kind == NBP_STAGE_PRODUCTS) claim(slot); });
+      if (st.kind == NBP_STAGE_PROPOSALS || st.kind == NBP_STAGE_PRODUCTS) stage_writes(p, st, [&](int, int32_t slot) { claim(slot); });
+      if (st.kind == NBP_STAGE_COPIES || st.kind == 0) {
+        for (const nbp_fits::fit &f : pend[o].v) pend[l].v.push_back(f);
+        pend[o].clear();
+      }
+    }
+    st.ent = pend[l];
+    auto flush_if_read = [&](nbp_access what) {
+      stage_reads(p, st, [&](int, int32_t slot, nbp_access a) { st.flush_before |= a == what && pend[l].has(slot); });
+      if (st.flush_before) { for (const nbp_fits::fit &f : pend[l].v) ran[(size_t)k].push(f.slot, f.mani); pend[l].clear(); }
+    };
+    if (st.kind == NBP_STAGE_PROPOSALS) {
+      flush_if_read(NBP_RD_KDE);
+      queue_fits(pend[l], (const nbp_proposal_desc *)d, st.n, dead[(size_t)k]);
+    } else if (st.kind == NBP_STAGE_PRODUCTS) {
+      const nbp_product_desc *qd = (const nbp_product_desc *)d;
+      st.need_prep = false;
+      for (int i = 0; i < st.n; i++) st.need_prep |= qd[i].nfactors > 1;
+      flush_if_read(NBP_RD_POINTS);
+      if (st.need_prep) {
+        for (const nbp_fits::fit &f : pend[l].v) ran[(size_t)k].push(f.slot, f.mani);
+        pend[l].clear();
+      } else {
+        for (int i = 0; i < st.n; i++) pend[l].rename(qd[i].in_slot[0], qd[i].out_slot);
+        pend[l].dedup();
+      }
+      queue_fits(pend[l], qd, st.n, dead[(size_t)k]);
+    } else if (st.kind == NBP_STAGE_DECONV || st.kind == NBP_STAGE_COPY_POINTS) {
+      if (st.kind == NBP_STAGE_DECONV)
+        for (int i = 0; i < st.n; i++) pend[l].push(((const nbp_proposal_desc *)d)[i].out_slot, ((const nbp_proposal_desc *)d)[i].manifold);
+    } else {  // whole-slot copies and the trailing pseudo part: everything pending runs first
+      st.flush_before = true;
+      for (const nbp_fits::fit &f : pend[l].v) ran[(size_t)k].push(f.slot, f.mani);
+      pend[l].clear();
+    }
+  }
+  // ---- what a part waits for on the other lane
+  std::vector<nbp_lane_part> sw(parts.size());
+  for (int k = 0; k < (int)parts.size(); k++) {
+    const nbp_stage &st = parts[(size_t)k];
+    nbp_lane_part &a = sw[(size_t)k];
+    a.stage = st.user;
+    a.lane = st.lane;
+    a.barrier = st.kind == 0 || ((st.kind == NBP_STAGE_COPIES || st.kind == NBP_STAGE_COPY_POINTS) && st.n == 0);
+    stage_reads(p, st, [&](int, int32_t slot, nbp_access acc) {
+      a.reads.push_back(2 * slot);
+      if (acc != NBP_RD_POINTS || st.kind == NBP_STAGE_PRODUCTS) a.reads.push_back(2 * slot + 1);
+      if (acc == NBP_RD_POINTS && st.kind == NBP_STAGE_PRODUCTS) a.writes.push_back(2 * slot);  // (old_slot: topped up in place)
+    }, true);
+    stage_writes(p, st, [&](int, int32_t slot) {
+      a.writes.push_back(2 * slot);
+      if (st.kind != NBP_STAGE_COPY_POINTS) a.writes.push_back(2 * slot + 1);
+    });
+    for (const nbp_fits::fit &f : ran[(size_t)k].v) { a.reads.push_back(2 * f.slot); a.writes.push_back(2 * f.slot + 1); }
+    const char *d = p->blob.data() + st.offset;
+    for (int i = 0; i < st.n; i++)
+      if (st.kind == NBP_STAGE_PROPOSALS || st.kind == NBP_STAGE_DECONV) {
+        const nbp_proposal_desc &q = ((const nbp_proposal_desc *)d)[i];
+        if (q.mhidx_in >= 0) a.reads.push_back(NBP_LANE_SLOT_SIDE);
+        if (q.mhidx_out >= 0) a.writes.push_back(NBP_LANE_SLOT_SIDE);
+      } else if (st.kind == NBP_STAGE_PRODUCTS && ((const nbp_product_desc *)d)[i].labels_out >= 0) {
+        a.writes.push_back(NBP_LANE_SLOT_SIDE);
+      }
+  }
+  nbp_lane_sweep(sw);
+  for (int k = 0; k < (int)parts.size(); k++) {
+    parts[(size_t)k].waits = sw[(size_t)k].waits;
+    parts[(size_t)k].signals = sw[(size_t)k].signals;
+  }
+  // ---- what lane 1 needs of the workspaces (presize)
+  for (const nbp_stage &st : parts)
+    if (st.lane == 1 && st.kind == NBP_STAGE_PRODUCTS && st.n > 0) {
+      p->lane_ws = std::max(p->lane_ws, (size_t)st.n * (size_t)(st.maxfd / 4) * nbp_kd_ws_doubles(p->ctx->N));
+      nbp_launch_env env = ctx_env(p->ctx);
+      p->lane_gstats = std::max(p->lane_gstats, std::max(product_plan(p->ctx, env, st.n, st.maxfd, st.mani).gstats, product_plan(p->ctx, env, st.n, st.maxfd, -1).gstats));
+    }
+}
+
 // Behind the descriptors, each region 64-byte aligned: the entry fits of every stage, the split-out fits of the fused
 // pairs, their update descriptors, the seed table.  (This order and these sizes are what captured graphs and the plan
 // cache of nbp_host.cpp hold offsets into.)
@@ -3410,6 +3656,10 @@ static void layout_blob(nbp_program *p) {
   for (nbp_stage &st : p->stages) append_fits(p->blob, st.ent);
   for (nbp_stage &st : p->stages)
     if (st.fused_second) append_fits(p->blob, st.split_out, 4);
+  for (nbp_stage &st : p->parts) {  // (none in a program without lanes)
+    append_fits(p->blob, st.ent);
+    append_fits(p->blob, st.bound);
+  }
   for (nbp_stage &st : p->stages)
     if (st.fused) {
       st.upd_off = (p->blob.size() + 63) & ~(size_t)63;
@@ -3449,6 +3699,33 @@ static nbp_status presize(nbp_program *p) {
       nbp_status rc = presize_products(p->ctx, st.n, st.maxfd, st.mani);
       if (rc) return rc;
     }
+  if (p->parts.empty()) return NBP_OK;
+  // lanes: lane 1 builds its KD trees in the last lane_ws doubles of the workspace, beside whatever lane 0 builds in front of
+  // them (its largest part is no larger than the largest stage, sized above), and keeps its node statistics in an area of
+  // its own
+  nbp_ctx *c = p->ctx;
+  size_t main = 0;
+  for (const nbp_stage &st : p->parts)
+    if (st.lane == 0 && st.kind == NBP_STAGE_PRODUCTS) main = std::max(main, (size_t)st.n * (size_t)(st.maxfd / 4) * nbp_kd_ws_doubles(c->N));
+  if (main + p->lane_ws > c->ws_doubles) {
+    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream2));
+    if (c->ws) HIPCHK(hipFree(c->ws));
+    c->ws = nullptr;
+    c->ws_doubles = 0;
+    c->ws_gen++;
+    const size_t grown = main + p->lane_ws + (main + p->lane_ws) / 4;
+    HIPCHK(hipMalloc(&c->ws, grown * 8));
+    c->ws_doubles = grown;
+  }
+  if (p->lane_gstats > c->gstats1_doubles) {
+    HIPCHK(hipStreamSynchronize(c->stream2));
+    if (c->gstats1) HIPCHK(hipFree(c->gstats1));
+    c->gstats1 = nullptr;
+    c->ws_gen++;
+    c->gstats1_doubles = p->lane_gstats + p->lane_gstats / 4;
+    HIPCHK(hipMalloc(&c->gstats1, c->gstats1_doubles * 8));
+  }
   return NBP_OK;
 }
 
@@ -3496,9 +3773,12 @@ nbp_status nbp_program_finalize(nbp_program *p) {
   HIPCHK(hipSetDevice(p->ctx->device));
   p->n_user_stages = (int)p->stages.size();
   p->stages.emplace_back();  // trailing pseudo stage (kind 0): the fits pending at exit
-  for (int s = 0; s + 1 < p->n_user_stages; s++) plan_pipeline(p, s);  // reorders descriptors: before anything indexes them
-  schedule_fits(p, product_liveness(p));
+  plan_lanes(p);  // reorder descriptors: before anything indexes them
+  for (int s = 0; s + 1 < p->n_user_stages; s++) plan_pipeline(p, s);
+  const nbp_liveness live = product_liveness(p);
+  schedule_fits(p, live);
   split_piped_entry_fits(p);
+  plan_parts(p, live);
   layout_blob(p);
   nbp_status rc = presize(p);
   if (!rc) rc = acquire_device_blob(p);
@@ -3508,7 +3788,77 @@ nbp_status nbp_program_finalize(nbp_program *p) {
   return NBP_OK;
 }
 
+// A range runs on two lanes when it holds lane-1 descriptors and neither starts nor ends inside a run of stages that have
+// some (the fits pending at such a place are spread over both lanes); not under per-kernel timing, whose events are the
+// library stream's.  Otherwise: the stages whole, in order, on the library stream (run_range below).
+static bool lanes_apply(const nbp_program *p, int first, int last) {
+  if (p->parts.empty() || p->ctx->timing || first >= last) return false;
+  auto has1 = [&](int s) { return s >= 0 && s < p->n_user_stages && p->stages[(size_t)s].lane_split >= 0; };
+  if ((has1(first - 1) && has1(first)) || (has1(last - 1) && has1(last))) return false;
+  for (int s = first; s < last; s++)
+    if (has1(s)) return true;
+  return false;
+}
+static nbp_status run_lanes(nbp_program *p, int first, int last) {
+  nbp_ctx *c = p->ctx;
+  if (p->lane_ws > c->ws_doubles) return fail(NBP_ERR_RANGE, "KD workspace smaller than lane 1's share (sized at nbp_program_finalize)");
+  nbp_launch_env env[2] = {ctx_env(c), ctx_env(c)};
+  env[0].lane = 1;
+  env[0].ws_doubles = c->ws_doubles - p->lane_ws;
+  env[1].lane = 2;
+  env[1].stream = c->stream2;
+  env[1].ws = c->ws + env[0].ws_doubles;
+  env[1].ws_doubles = p->lane_ws;
+  const int k0 = p->first_part[(size_t)first], k1 = p->first_part[(size_t)last];
+  std::vector<hipEvent_t> ev((size_t)(k1 - k0), nullptr);
+  int nev[2] = {0, 0};
+#define LANECHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return fail(NBP_ERR_HIP, std::string("lanes: " #expr ": ") + hipGetErrorString(e_)); } while (0)
+  // fork: lane 1 starts behind whatever the library stream holds in front of the range
+  LANECHK(hipEventRecord(c->lane_fork, c->stream));
+  LANECHK(hipStreamWaitEvent(c->stream2, c->lane_fork, 0));
+  for (int k = k0; k < k1; k++) {
+    const nbp_stage &st = p->parts[(size_t)k];
+    nbp_launch_env &e = env[st.lane];
+    for (int w : st.waits)
+      if (w >= k0) {  // (a part in front of the range has finished: the fork)
+        LANECHK(hipStreamWaitEvent(e.stream, ev[(size_t)(w - k0)], 0));
+        c->lane_waits++;
+      }
+    int launches = 0;
+    nbp_status rc = NBP_OK;
+    if (st.flush_before && st.ent.size()) { rc = launch_bandwidth(c, e, fits_dev(st.ent, p->dev)); launches++; }
+    if (rc) return rc;
+    if (st.kind == NBP_STAGE_PROPOSALS) {
+      rc = launch_proposals(c, e, (const nbp_proposal_desc *)(p->dev + st.offset), st.n, st.mani);
+      launches += st.n > 0;
+    } else if (st.kind == NBP_STAGE_PRODUCTS) {
+      const nbp_product_desc *dd = (const nbp_product_desc *)(p->dev + st.offset);
+      if (st.need_prep) { rc = launch_prep(c, e, fits_dev(st.ent, p->dev), dd, st.n, st.maxfd, st.mani); launches++; }
+      if (!rc) rc = launch_products(c, e, dd, st.n, st.maxfd, st.mani);
+      launches += st.n > 0;
+      if (st.lane) c->lane_side_updates += st.n;
+    } else if (st.kind == NBP_STAGE_DECONV) {
+      rc = launch_deconv(c, (const nbp_proposal_desc *)(p->dev + st.offset), nullptr, st.n);
+    } else {
+      rc = launch_copies(c, (const nbp_copy_desc *)(p->dev + st.offset), st.n, st.kind == NBP_STAGE_COPY_POINTS, e.stream);
+      launches += st.n > 0;
+    }
+    if (rc) return rc;
+    if (st.lane) c->lane_side_launches += launches;
+    if (st.signals) {
+      ev[(size_t)(k - k0)] = c->lane_ev[st.lane][nev[st.lane]++ % 4];
+      LANECHK(hipEventRecord(ev[(size_t)(k - k0)], e.stream));
+    }
+  }
+  // join, then whatever either lane still has pending where the range ends
+  LANECHK(hipEventRecord(c->lane_join, c->stream2));
+  LANECHK(hipStreamWaitEvent(c->stream, c->lane_join, 0));
+#undef LANECHK
+  return launch_bandwidth(c, ctx_env(c), fits_dev(p->parts[(size_t)k1].bound, p->dev));
+}
+
 static nbp_status run_range(nbp_program *p, int first, int last) {
+  if (lanes_apply(p, first, last)) return run_lanes(p, first, last);
   nbp_ctx *c = p->ctx;
   nbp_launch_env env = ctx_env(c);
   for (int s = first; s < last; s++) {
@@ -3712,6 +4062,21 @@ nbp_status nbp_program_num_two_stream(nbp_program *p, int32_t *out) {
   int n = 0;
   for (const nbp_stage &st : p->stages) n += st.pipe ? 1 : 0;
   *out = n;
+  return NBP_OK;
+}
+
+nbp_status nbp_program_lane_plan(nbp_program *p, nbp_lane_part_rec *out, int32_t cap, int32_t *n_out) {
+  if (!p || !n_out || (!out && cap > 0)) return fail(NBP_ERR_ARG, "null argument");
+  if (!p->finalized) return fail(NBP_ERR_ARG, "program not finalized");
+  const int np = p->parts.empty() ? 0 : (int)p->parts.size() - 1;  // (without the trailing pseudo part)
+  *n_out = np;
+  for (int k = 0; k < np && k < cap; k++) {
+    const nbp_stage &st = p->parts[(size_t)k];
+    const nbp_stage &us = p->stages[(size_t)st.user];
+    const size_t esz = st.kind == NBP_STAGE_PRODUCTS ? sizeof(nbp_product_desc) : (st.kind == NBP_STAGE_COPIES || st.kind == NBP_STAGE_COPY_POINTS ?
+                       sizeof(nbp_copy_desc) : sizeof(nbp_proposal_desc));
+    out[k] = {st.user, st.lane, (int32_t)((st.offset - us.offset) / esz), st.n, st.waits.empty() ? -1 : st.waits[0], st.signals ? 1 : 0};
+  }
   return NBP_OK;
 }
 
@@ -4088,6 +4453,10 @@ nbp_status nbp_diag_read(nbp_ctx *c, nbp_diag *out, int32_t reset) {
   out->proposal_launches_wave = c->prop_launches[1];
   out->proposal_launches_split = c->prop_launches[2];
   if (reset) c->prop_launches[0] = c->prop_launches[1] = c->prop_launches[2] = 0;
+  out->lane_side_launches = c->lane_side_launches;
+  out->lane_waits = c->lane_waits;
+  out->lane_side_updates = c->lane_side_updates;
+  if (reset) c->lane_side_launches = c->lane_waits = c->lane_side_updates = 0;
   if (reset) HIPCHK(hipMemset(c->counters, 0, offsetof(nbp_counters, flags)));  // (the flags are the context's, not counters)
   return NBP_OK;
 }

@@ -86,7 +86,7 @@ struct Clique {
   }
 };
 
-struct Stage { int kind; std::vector<char> bytes; int n; };
+struct Stage { int kind; std::vector<char> bytes; int n; std::vector<int32_t> lane; };  // lane: empty, or the lane hint per descriptor (nbp_program_set_lanes)
 using MeasKey = std::array<int, 5>;  // names the stored measurement of one density (needFreshMeasurements)
 
 }  // namespace
@@ -847,8 +847,12 @@ nbp_status assemble_program(nbp_ctx *ctx, const std::vector<Stage> &stages, cons
   if (rc) return rc;
   for (const auto &o : options)
     if (!rc) rc = nbp_program_set_option(p, o[0], o[1]);
-  for (const Stage &s : stages)
+  int at = 0;
+  for (const Stage &s : stages) {
     if (!rc) rc = nbp_program_add_stage(p, s.kind, s.bytes.empty() ? nullptr : s.bytes.data(), s.n);
+    if (!rc && !s.lane.empty()) rc = nbp_program_set_lanes(p, at, s.lane.data(), s.n);
+    at++;
+  }
   if (!rc) rc = nbp_program_finalize(p);
   if (rc) { nbp_program_destroy(p); return rc; }
   *out = p;
@@ -1256,9 +1260,11 @@ nbp_status nbp_tree_schedule(nbp_tree *t, uint64_t seed) {
   std::vector<nbp_proposal_desc> props;
   std::vector<nbp_product_desc> prods;
   // stage pair tt of a pass: round tt - start[c] of every clique of this rank that is running then
-  auto batch = [&](bool down, int tt, const std::vector<int> &start, const std::vector<int> &finish) {
+  // (side: the stragglers of the pass, by clique id -- their descriptors carry the lane hint 1; empty: none)
+  auto batch = [&](bool down, int tt, const std::vector<int> &start, const std::vector<int> &finish, const std::vector<char> &side) {
     props.clear();
     prods.clear();
+    std::vector<int32_t> plane, qlane;
     for (const Clique &c : t->cl) {
       if (!(start[c.id] <= tt && tt < finish[c.id]) || !t->mine(c.id)) continue;
       const std::vector<int> &round = (down ? t->drounds : t->urounds)[c.id - 1][tt - start[c.id]];
@@ -1269,9 +1275,45 @@ nbp_status nbp_tree_schedule(nbp_tree *t, uint64_t seed) {
                                         prods, fresh, (int)lane))
           return rc;
       }
+      plane.resize(props.size(), !side.empty() && side[c.id]);
+      qlane.resize(prods.size(), !side.empty() && side[c.id]);
     }
-    if (!prods.empty()) add_update_stages(t->stages, props, prods);
+    if (!prods.empty()) {
+      add_update_stages(t->stages, props, prods);
+      if (!side.empty()) {
+        t->stages[t->stages.size() - 2].lane = plane;
+        t->stages[t->stages.size() - 1].lane = qlane;
+      }
+    }
     return (nbp_status)NBP_OK;
+  };
+  // The stragglers of a pass ("Lanes").  A time step is narrow when it holds at most NBP_LANE_NARROW_MAX
+  // updates (environment; default 32: below the smallest launch that still occupies a quarter of the CUs in the latency
+  // geometries).  A clique whose schedule covers a narrow step AND a wide one rides in chip-filling stages and then runs
+  // alone: all its rounds of the pass get lane 1.  Nothing is marked when the stragglers would hold more than 64 updates in
+  // one step (lane 1 is for launches that leave the chip to lane 0), nor in the share of one rank of several.
+  auto stragglers = [&](bool down, int T, const std::vector<int> &start, const std::vector<int> &finish) {
+    std::vector<char> side;
+    if (!t->owner.empty() || T <= 0) return side;
+    const int narrow_max = getenv("NBP_LANE_NARROW_MAX") ? atoi(getenv("NBP_LANE_NARROW_MAX")) : 32;
+    const auto &rounds = down ? t->drounds : t->urounds;
+    std::vector<int> count((size_t)T, 0), held((size_t)T, 0);
+    for (const Clique &c : t->cl)
+      for (int tt = start[c.id]; tt < finish[c.id]; tt++) count[(size_t)tt] += (int)rounds[c.id - 1][(size_t)(tt - start[c.id])].size();
+    side.assign(t->cl.size() + 1, 0);
+    bool any = false;
+    for (const Clique &c : t->cl) {
+      bool narrow = false, wide = false;
+      for (int tt = start[c.id]; tt < finish[c.id]; tt++) {
+        if (count[(size_t)tt] <= narrow_max) narrow = true; else wide = true;
+      }
+      if (!(narrow && wide)) continue;
+      side[c.id] = 1;
+      any = true;
+      for (int tt = start[c.id]; tt < finish[c.id]; tt++) held[(size_t)tt] += (int)rounds[c.id - 1][(size_t)(tt - start[c.id])].size();
+    }
+    if (!any || *std::max_element(held.begin(), held.end()) > 64) side.clear();
+    return side;
   };
   // ---- up pass: a clique starts its schedule in the stage after its last child finished (the rendezvous of the
   // CliqueStateMachine, :221-234); stage t batches step t - start[c] of every running clique (solver.TreeProgram)
@@ -1287,6 +1329,7 @@ nbp_status nbp_tree_schedule(nbp_tree *t, uint64_t seed) {
       finish[cid] = st + (int)t->urounds[cid - 1].size();
       T = std::max(T, finish[cid]);
     }
+    const std::vector<char> side = stragglers(false, T, start, finish);
     for (int tt = 0; tt < T; tt++) {
       if (t->joint) {
         props.clear();  // the differential factors of the cliques that have just finished
@@ -1306,7 +1349,7 @@ nbp_status nbp_tree_schedule(nbp_tree *t, uint64_t seed) {
         up_edges(t, crossing, edges);
         rank_exchange(t, edges);
       }
-      if (nbp_status rc = batch(false, tt, start, finish)) return rc;
+      if (nbp_status rc = batch(false, tt, start, finish, side)) return rc;
     }
   }
   auto frontals_out = [&](const Clique &c, std::vector<nbp_copy_desc> &to) {  // this rank's solved frontals -> their main slots
@@ -1337,6 +1380,7 @@ nbp_status nbp_tree_schedule(nbp_tree *t, uint64_t seed) {
         finish[cid] = start[cid] + (int)t->drounds[cid - 1].size();
         T = std::max(T, finish[cid]);
       }
+      const std::vector<char> side = stragglers(true, T, start, finish);
       for (int tt = 0; tt <= T; tt++) {
         // one copy stage, or one more per link of a chain of cliques without updates of their own, which hand
         // the values on within the same time step
@@ -1360,14 +1404,19 @@ nbp_status nbp_tree_schedule(nbp_tree *t, uint64_t seed) {
           }
           rank_exchange(t, edges);
           cps.clear();
+          std::vector<int32_t> clane;  // (the copies that feed a straggler travel on its lane)
           for (const Clique &c : t->cl) {
             auto it = rnd.find(c.id);
             if (it == rnd.end() || it->second != r || !t->mine(c.id) || !t->mine(c.parent)) continue;
             for (int s : c.seps) cps.push_back({t->B[c.parent - 1].at(s), t->B[c.id - 1].at(s)});
+            clane.resize(cps.size(), !side.empty() && side[c.id]);
           }
-          if (!cps.empty()) add_stage(t->stages, NBP_STAGE_COPY_POINTS, cps.data(), sizeof(nbp_copy_desc), (int)cps.size());  // read as points only
+          if (!cps.empty()) {
+            add_stage(t->stages, NBP_STAGE_COPY_POINTS, cps.data(), sizeof(nbp_copy_desc), (int)cps.size());  // read as points only
+            if (!side.empty()) t->stages.back().lane = clane;
+          }
         }
-        if (nbp_status rc = batch(true, tt, start, finish)) return rc;
+        if (nbp_status rc = batch(true, tt, start, finish, side)) return rc;
       }
     }
     // transferUpdateSubGraph!, once for the whole pass (see solver.TreeProgram)
@@ -2606,6 +2655,13 @@ int32_t nbp_tree_num_stages(const nbp_tree *t) { return t ? (int32_t)t->stages.s
 nbp_status nbp_tree_stage(const nbp_tree *t, int32_t s, int32_t *kind, int32_t *n, void *out, int64_t cap) {
   if (!t || s < 0 || s >= (int)t->stages.size()) return hfail(NBP_ERR_RANGE, "stage index");
   return stage_out(t->stages[s], kind, n, out, cap);
+}
+nbp_status nbp_tree_stage_lanes(const nbp_tree *t, int32_t s, int32_t *lanes_out, int32_t cap) {
+  if (!t || s < 0 || s >= (int)t->stages.size()) return hfail(NBP_ERR_RANGE, "stage index");
+  if (!lanes_out && cap > 0) return hfail(NBP_ERR_ARG, "null argument");
+  const Stage &st = t->stages[s];
+  for (int i = 0; i < st.n && i < cap; i++) lanes_out[i] = st.lane.empty() ? 0 : st.lane[(size_t)i];
+  return NBP_OK;
 }
 
 }  // extern "C"
