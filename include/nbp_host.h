@@ -342,6 +342,10 @@ nbp_status nbp_tree_stage(const nbp_tree *t, int32_t s, int32_t *kind, int32_t *
  * nbp_tree_schedule gives lane 1 to every round of a clique whose schedule covers a time step of at most
  * NBP_LANE_NARROW_MAX updates (environment, default 32) and a wider one, and to the points-only copies that feed it */
 nbp_status nbp_tree_stage_lanes(const nbp_tree *t, int32_t s, int32_t *lanes_out, int32_t cap);
+/* chain promotion, kept apart from the stragglers' mark above (which is what it was): 1 for the descriptors of the promoted
+ * ancestors of a down-pass straggler (up to the first one without a round in a wide step) and of the copies that feed them;
+ * all 0 with NBP_LANE_NO_PROMOTE=1 in the environment.  The compiled program runs both marks on lane 1. */
+nbp_status nbp_tree_stage_promoted(const nbp_tree *t, int32_t s, int32_t *promoted_out, int32_t cap);
 
 #ifdef __cplusplus
 }

@@ -153,7 +153,7 @@ struct nbp_ctx {
   // statistics area and a share of the KD workspace of its own; the events of the cross-lane waits, per recording lane, plus
   // the fork and the join of a range.  NBP_NO_LANES=1: hints are ignored (the launch sequence of a program without them)
   bool no_lanes = false;
-  hipEvent_t lane_ev[2][4] = {{nullptr, nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr, nullptr}};
+  std::vector<hipEvent_t> lane_ev;  // one per signalling part of the largest program with lanes (presize)
   hipEvent_t lane_fork = nullptr, lane_join = nullptr;
   double *gstats1 = nullptr;
   size_t gstats1_doubles = 0;
@@ -404,7 +404,6 @@ nbp_status nbp_ctx_create(int32_t device, int32_t N, int32_t n_slots, void *aren
   HIPCHK(hipMalloc(&c->spec, sizeof(nbp_spec_area) * 3 * NBP_SPEC_MAXJOBS * 2));  // (the second half: lane 1 of a program)
   HIPCHK(hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking));
   for (int i = 0; i < 2; i++) HIPCHK(hipEventCreateWithFlags(&c->pipe_ev[i], hipEventDisableTiming));
-  for (int i = 0; i < 8; i++) HIPCHK(hipEventCreateWithFlags(&c->lane_ev[i / 4][i % 4], hipEventDisableTiming));
   HIPCHK(hipEventCreateWithFlags(&c->lane_fork, hipEventDisableTiming));
   HIPCHK(hipEventCreateWithFlags(&c->lane_join, hipEventDisableTiming));
   nbp_status rc = build_levels(c);
@@ -479,7 +478,7 @@ nbp_status nbp_ctx_destroy(nbp_ctx *c) {
   if (c->spec) hipFree(c->spec);
   if (c->stream2) hipStreamDestroy(c->stream2);
   for (int i = 0; i < 2; i++) if (c->pipe_ev[i]) hipEventDestroy(c->pipe_ev[i]);
-  for (int i = 0; i < 8; i++) if (c->lane_ev[i / 4][i % 4]) hipEventDestroy(c->lane_ev[i / 4][i % 4]);
+  for (hipEvent_t e : c->lane_ev) hipEventDestroy(e);
   if (c->lane_fork) hipEventDestroy(c->lane_fork);
   if (c->lane_join) hipEventDestroy(c->lane_join);
   if (c->gstats1) hipFree(c->gstats1);
@@ -3704,6 +3703,15 @@ static nbp_status presize(nbp_program *p) {
   // them (its largest part is no larger than the largest stage, sized above), and keeps its node statistics in an area of
   // its own
   nbp_ctx *c = p->ctx;
+  // one event per part that the other lane waits for: lane 1 is issued ahead of lane 0 (run_lanes), so a recorded event must
+  // keep its meaning until the last wait for it is issued
+  size_t nsig = 0;
+  for (const nbp_stage &st : p->parts) nsig += st.signals ? 1 : 0;
+  while (c->lane_ev.size() < nsig) {
+    hipEvent_t e = nullptr;
+    HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    c->lane_ev.push_back(e);
+  }
   size_t main = 0;
   for (const nbp_stage &st : p->parts)
     if (st.lane == 0 && st.kind == NBP_STAGE_PRODUCTS) main = std::max(main, (size_t)st.n * (size_t)(st.maxfd / 4) * nbp_kd_ws_doubles(c->N));
@@ -3811,12 +3819,32 @@ static nbp_status run_lanes(nbp_program *p, int first, int last) {
   env[1].ws_doubles = p->lane_ws;
   const int k0 = p->first_part[(size_t)first], k1 = p->first_part[(size_t)last];
   std::vector<hipEvent_t> ev((size_t)(k1 - k0), nullptr);
-  int nev[2] = {0, 0};
+  size_t nev = 0;
+  std::vector<char> issued((size_t)(k1 - k0), 0);
 #define LANECHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return fail(NBP_ERR_HIP, std::string("lanes: " #expr ": ") + hipGetErrorString(e_)); } while (0)
   // fork: lane 1 starts behind whatever the library stream holds in front of the range
   LANECHK(hipEventRecord(c->lane_fork, c->stream));
   LANECHK(hipStreamWaitEvent(c->stream2, c->lane_fork, 0));
-  for (int k = k0; k < k1; k++) {
+  // Issue order: each lane's parts in list order, and lane 1 ahead of lane 0 as far as its waits allow (a wait points
+  // backwards in list order, so when lane 1's next part waits for a part not yet issued, lane 0's next part waits for none).
+  // The order of issue orders nothing on the device; it decides the order of the edges of a captured graph.  The runtime
+  // keeps the first successor of a node on the node's own queue and deals the others out in turn over its few queues: were
+  // the lane-0 part that waits for a lane-1 part captured before that part's own successor, a chain of lane-1 parts would
+  // move to the next queue at every such part and, every fourth time, land behind lane 0 on the library stream's.
+  int nx[2] = {k0, k0};
+  auto seek = [&](int l) { while (nx[l] < k1 && p->parts[(size_t)nx[l]].lane != l) nx[l]++; };
+  auto ready = [&](int k) {
+    for (int w : p->parts[(size_t)k].waits)
+      if (w >= k0 && !issued[(size_t)(w - k0)]) return false;
+    return true;
+  };
+  for (;;) {
+    seek(0);
+    seek(1);
+    if (nx[0] >= k1 && nx[1] >= k1) break;
+    const int l = nx[1] < k1 && (ready(nx[1]) || nx[0] >= k1) ? 1 : 0;
+    const int k = nx[l]++;
+    issued[(size_t)(k - k0)] = 1;
     const nbp_stage &st = p->parts[(size_t)k];
     nbp_launch_env &e = env[st.lane];
     for (int w : st.waits)
@@ -3846,7 +3874,8 @@ static nbp_status run_lanes(nbp_program *p, int first, int last) {
     if (rc) return rc;
     if (st.lane) c->lane_side_launches += launches;
     if (st.signals) {
-      ev[(size_t)(k - k0)] = c->lane_ev[st.lane][nev[st.lane]++ % 4];
+      if (nev >= c->lane_ev.size()) return fail(NBP_ERR_RANGE, "lanes: fewer events than signalling parts (sized at nbp_program_finalize)");
+      ev[(size_t)(k - k0)] = c->lane_ev[nev++];
       LANECHK(hipEventRecord(ev[(size_t)(k - k0)], e.stream));
     }
   }

@@ -86,7 +86,7 @@ struct Clique {
   }
 };
 
-struct Stage { int kind; std::vector<char> bytes; int n; std::vector<int32_t> lane; };  // lane: empty, or the lane hint per descriptor (nbp_program_set_lanes)
+struct Stage { int kind; std::vector<char> bytes; int n; std::vector<int32_t> lane; };  // lane: empty, or the mark per descriptor: 1 a straggler's, 2 a promoted ancestor's (both: lane 1 of nbp_program_set_lanes)
 using MeasKey = std::array<int, 5>;  // names the stored measurement of one density (needFreshMeasurements)
 
 }  // namespace
@@ -850,7 +850,11 @@ nbp_status assemble_program(nbp_ctx *ctx, const std::vector<Stage> &stages, cons
   int at = 0;
   for (const Stage &s : stages) {
     if (!rc) rc = nbp_program_add_stage(p, s.kind, s.bytes.empty() ? nullptr : s.bytes.data(), s.n);
-    if (!rc && !s.lane.empty()) rc = nbp_program_set_lanes(p, at, s.lane.data(), s.n);
+    if (!rc && !s.lane.empty()) {
+      std::vector<int32_t> side(s.lane);  // stragglers and promoted ancestors alike: lane 1
+      for (int32_t &l : side) l = l != 0;
+      rc = nbp_program_set_lanes(p, at, side.data(), s.n);
+    }
     at++;
   }
   if (!rc) rc = nbp_program_finalize(p);
@@ -1260,7 +1264,7 @@ nbp_status nbp_tree_schedule(nbp_tree *t, uint64_t seed) {
   std::vector<nbp_proposal_desc> props;
   std::vector<nbp_product_desc> prods;
   // stage pair tt of a pass: round tt - start[c] of every clique of this rank that is running then
-  // (side: the stragglers of the pass, by clique id -- their descriptors carry the lane hint 1; empty: none)
+  // (side: by clique id, 1 the stragglers of the pass, 2 their promoted ancestors -- the mark their descriptors carry; empty: none)
   auto batch = [&](bool down, int tt, const std::vector<int> &start, const std::vector<int> &finish, const std::vector<char> &side) {
     props.clear();
     prods.clear();
@@ -1275,8 +1279,8 @@ nbp_status nbp_tree_schedule(nbp_tree *t, uint64_t seed) {
                                         prods, fresh, (int)lane))
           return rc;
       }
-      plane.resize(props.size(), !side.empty() && side[c.id]);
-      qlane.resize(prods.size(), !side.empty() && side[c.id]);
+      plane.resize(props.size(), side.empty() ? 0 : side[c.id]);
+      qlane.resize(prods.size(), side.empty() ? 0 : side[c.id]);
     }
     if (!prods.empty()) {
       add_update_stages(t->stages, props, prods);
@@ -1292,10 +1296,22 @@ nbp_status nbp_tree_schedule(nbp_tree *t, uint64_t seed) {
   // geometries).  A clique whose schedule covers a narrow step AND a wide one rides in chip-filling stages and then runs
   // alone: all its rounds of the pass get lane 1.  Nothing is marked when the stragglers would hold more than 64 updates in
   // one step (lane 1 is for launches that leave the chip to lane 0), nor in the share of one rank of several.
+  // Chain promotion, down pass only: a straggler starts when its parent has finished, and a parent that rides in a wide
+  // stage finishes when that stage's last launch drains.  So the ancestors of a straggler go to lane 1 with it, from the
+  // straggler towards the root, as long as they have a round in a wide step; the first ancestor whose rounds are all in
+  // narrow steps (or that has none) ends the walk: the top of the tree runs alone anyway.  The chain then depends on lane 0
+  // once, where it starts.  Only the chain of a straggler that needs it is promoted: a round beside a wide stage takes about
+  // as long as 200 updates take inside one (0.2 - 0.3 ms against 1.3 - 1.5 us per update), so a straggler whose rounds, at
+  // that rate, are no more than the updates of the wide steps from its start on finishes beside them as it is, and lane-1
+  // launches beside more wide stages would only stretch those.  The cap counts the promoted cliques too: above 64 in one
+  // step the promotion is dropped and the stragglers alone stay marked.  NBP_LANE_NO_PROMOTE=1 (environment): the stragglers
+  // alone, always.
+  const long round_updates = 200;
   auto stragglers = [&](bool down, int T, const std::vector<int> &start, const std::vector<int> &finish) {
     std::vector<char> side;
     if (!t->owner.empty() || T <= 0) return side;
     const int narrow_max = getenv("NBP_LANE_NARROW_MAX") ? atoi(getenv("NBP_LANE_NARROW_MAX")) : 32;
+    const bool promote = down && !(getenv("NBP_LANE_NO_PROMOTE") && atoi(getenv("NBP_LANE_NO_PROMOTE")) != 0);
     const auto &rounds = down ? t->drounds : t->urounds;
     std::vector<int> count((size_t)T, 0), held((size_t)T, 0);
     for (const Clique &c : t->cl)
@@ -1313,7 +1329,23 @@ nbp_status nbp_tree_schedule(nbp_tree *t, uint64_t seed) {
       for (int tt = start[c.id]; tt < finish[c.id]; tt++) held[(size_t)tt] += (int)rounds[c.id - 1][(size_t)(tt - start[c.id])].size();
     }
     if (!any || *std::max_element(held.begin(), held.end()) > 64) side.clear();
-    return side;
+    if (side.empty() || !promote) return side;
+    std::vector<char> chain(side);
+    for (const Clique &c : t->cl) {
+      if (!side[c.id]) continue;
+      long ahead = 0;  // the updates of the wide steps from the straggler's start on: what lane 0 still has to do beside it
+      for (int tt = start[c.id]; tt < T; tt++)
+        if (count[(size_t)tt] > narrow_max) ahead += count[(size_t)tt];
+      if ((long)(finish[c.id] - start[c.id]) * round_updates <= ahead) continue;  // its rounds hide beside them as it is
+      for (int a = c.parent; a != 0 && !chain[a]; a = t->cl[a - 1].parent) {
+        bool wide = false;
+        for (int tt = start[a]; tt < finish[a]; tt++) wide |= count[(size_t)tt] > narrow_max;
+        if (!wide) break;
+        chain[a] = 2;
+        for (int tt = start[a]; tt < finish[a]; tt++) held[(size_t)tt] += (int)rounds[a - 1][(size_t)(tt - start[a])].size();
+      }
+    }
+    return *std::max_element(held.begin(), held.end()) > 64 ? side : chain;
   };
   // ---- up pass: a clique starts its schedule in the stage after its last child finished (the rendezvous of the
   // CliqueStateMachine, :221-234); stage t batches step t - start[c] of every running clique (solver.TreeProgram)
@@ -1409,7 +1441,7 @@ nbp_status nbp_tree_schedule(nbp_tree *t, uint64_t seed) {
             auto it = rnd.find(c.id);
             if (it == rnd.end() || it->second != r || !t->mine(c.id) || !t->mine(c.parent)) continue;
             for (int s : c.seps) cps.push_back({t->B[c.parent - 1].at(s), t->B[c.id - 1].at(s)});
-            clane.resize(cps.size(), !side.empty() && side[c.id]);
+            clane.resize(cps.size(), side.empty() ? 0 : side[c.id]);
           }
           if (!cps.empty()) {
             add_stage(t->stages, NBP_STAGE_COPY_POINTS, cps.data(), sizeof(nbp_copy_desc), (int)cps.size());  // read as points only
@@ -2660,7 +2692,14 @@ nbp_status nbp_tree_stage_lanes(const nbp_tree *t, int32_t s, int32_t *lanes_out
   if (!t || s < 0 || s >= (int)t->stages.size()) return hfail(NBP_ERR_RANGE, "stage index");
   if (!lanes_out && cap > 0) return hfail(NBP_ERR_ARG, "null argument");
   const Stage &st = t->stages[s];
-  for (int i = 0; i < st.n && i < cap; i++) lanes_out[i] = st.lane.empty() ? 0 : st.lane[(size_t)i];
+  for (int i = 0; i < st.n && i < cap; i++) lanes_out[i] = !st.lane.empty() && st.lane[(size_t)i] == 1;
+  return NBP_OK;
+}
+nbp_status nbp_tree_stage_promoted(const nbp_tree *t, int32_t s, int32_t *promoted_out, int32_t cap) {
+  if (!t || s < 0 || s >= (int)t->stages.size()) return hfail(NBP_ERR_RANGE, "stage index");
+  if (!promoted_out && cap > 0) return hfail(NBP_ERR_ARG, "null argument");
+  const Stage &st = t->stages[s];
+  for (int i = 0; i < st.n && i < cap; i++) promoted_out[i] = !st.lane.empty() && st.lane[(size_t)i] == 2;
   return NBP_OK;
 }
 

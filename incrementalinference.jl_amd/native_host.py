@@ -62,7 +62,7 @@ HOST_EXPORTS = ["nbp_graph_create", "nbp_graph_destroy", "nbp_graph_add_variable
                 "nbp_graph_order_nested_dissection", "nbp_graph_init_plan", "nbp_graph_init_num_variables", "nbp_graph_init_variables",
                 "nbp_graph_init_num_stages", "nbp_graph_init_stage", "nbp_graph_init_compile", "nbp_tree_build", "nbp_tree_destroy", "nbp_tree_num_cliques",
                 "nbp_tree_clique", "nbp_tree_clique_idlists", "nbp_tree_max_schedule", "nbp_tree_plan_slots", "nbp_tree_main_slots", "nbp_tree_compile", "nbp_tree_schedule",
-                "nbp_tree_get_stats", "nbp_tree_num_stages", "nbp_tree_stage", "nbp_tree_stage_lanes", "nbp_clique_slots", "nbp_clique_upsolve", "nbp_clique_upsolve_joint", "nbp_clique_downsolve", "nbp_clique_solve_batch", "nbp_clique_seam_times",
+                "nbp_tree_get_stats", "nbp_tree_num_stages", "nbp_tree_stage", "nbp_tree_stage_lanes", "nbp_tree_stage_promoted", "nbp_clique_slots", "nbp_clique_upsolve", "nbp_clique_upsolve_joint", "nbp_clique_downsolve", "nbp_clique_solve_batch", "nbp_clique_seam_times",
                 "nbp_clique_submit_batch", "nbp_clique_wait", "nbp_resident_write", "nbp_resident_read", "nbp_resident_copy",
                 "nbp_tree_partition", "nbp_tree_set_owner", "nbp_tree_num_segments", "nbp_tree_segment",
                 "nbp_tree_run_sharded", "nbp_tree_run_sharded_cb",
@@ -109,6 +109,7 @@ def _lib():
         lib.nbp_tree_num_stages.argtypes = [vp]
         lib.nbp_tree_stage.argtypes = [vp, i32, ip, ip, vp, i64]
         lib.nbp_tree_stage_lanes.argtypes = [vp, i32, ip, i32]
+        lib.nbp_tree_stage_promoted.argtypes = [vp, i32, ip, i32]
         lib.nbp_tree_partition.argtypes = [vp, i32, ip]
         lib.nbp_tree_set_owner.argtypes = [vp, ip, i32]
         lib.nbp_tree_num_segments.argtypes = [vp]
@@ -576,6 +577,18 @@ class NativeTree:
             _check(self.lib.nbp_tree_stage(self._t, s, C.byref(kind), C.byref(n), None, 0))
             arr = (i32 * max(n.value, 1))()
             _check(self.lib.nbp_tree_stage_lanes(self._t, s, arr, n.value))
+            out.append(list(arr[:n.value]))
+        return out
+
+    def stage_promoted(self):
+        """chain promotion, per stage of the last compile: [[1 for a descriptor of a promoted ancestor of a down-pass straggler]]
+        (nbp_tree_stage_promoted; the compiled program runs these on lane 1 like the descriptors stage_lanes marks)"""
+        out = []
+        for s in range(self.lib.nbp_tree_num_stages(self._t)):
+            kind, n = C.c_int32(0), C.c_int32(0)
+            _check(self.lib.nbp_tree_stage(self._t, s, C.byref(kind), C.byref(n), None, 0))
+            arr = (i32 * max(n.value, 1))()
+            _check(self.lib.nbp_tree_stage_promoted(self._t, s, arr, n.value))
             out.append(list(arr[:n.value]))
         return out
 
