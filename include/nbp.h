@@ -702,6 +702,86 @@ nbp_status nbp_run_factor_likelihood(nbp_ctx *ctx, const nbp_likelihood_desc *de
  * are not read; b_NxP is not read for a unary item */
 nbp_status nbp_factor_likelihood(nbp_ctx *ctx, const nbp_likelihood_desc *desc, const double *a_NxP, int32_t na, const double *b_NxP,
                                  int32_t nb, double *loglik_out, double *comp_loglik_out /* NBP_MAXC, nullable */);
+/* ---- local products on a grid ("Local products on a grid"; DEFINED by this library, unpinned: DESIGN.md 8) ------------
+ * The product of the messages a variable's factors send it, WITHOUT particles for the variable itself: its clouds are replaced by a
+ * regular grid over its coordinates, every factor's message is the closed-form measurement density at the cell summed over the
+ * neighbour's cloud, the logs are added and normalised by quadrature.  It is what one Gibbs update of the variable would return
+ * with infinitely many particles and no kernel smoothing, given the same neighbour clouds.  No bandwidth enters a value.
+ * GRID.  The variable lies on `manifold` with D = 1, 2 or 3 coordinates; the grid has one axis per coordinate, in coordinate order;
+ * cell (k0, k1, k2) is the point x = (lo[a] + (double)k_a step[a])_a; n[a] for a >= D must be 1.  The output is row-major, coordinate
+ * 0 slowest.  flags & NBP_PGRID_AUTO_EXTENT: lo and step are not read; per axis the rule of nbp_grid_desc from the resident belief
+ * in `slot` (Euclidean: min_j x - margin bw .. max_j x + margin bw, step = (hi - lo) / (n - 1), n >= 2; circular: lo = -pi, step =
+ * 2 pi / n) -- the same code, so for D <= 2 the axes are nbp_run_marginal_grid's bit for bit.  Without the flag `slot` is not read.
+ * ITEM.  A measurement model (`lik`, read exactly as nbp_run_factor_likelihood reads it; its slot_a / slot_b are NOT read), the role
+ * the grid's variable fills and the slot `other` of the other variable's resident belief u_0 .. u_{n-1} (n: the count of the slot):
+ *   role 0   x stands for a_i and u_j for b_j;   role 1   u_j stands for a_i and x for b_j;   a unary item: role 0, other = -1, n = 1
+ *   e_jc(x)  the e_ijc of nbp_run_factor_likelihood for that pair: zhat, log p_c, the wrap rules, the partial masks, the families
+ *            and one rounding per written operation are those defined there; (sin, cos) of an SE(2) heading by the same sincos
+ *   M        max_{j,c} e_jc(x);   S_c = sum_j exp(e_jc(x) - M), j ascending from 0.0, a term with e_jc - M < -700 counts as zero;
+ *            S = sum_c S_c, c ascending from 0.0; both passes in the lane that owns the cell
+ *   log m(x) (M + log S) - log((double)n);   M = -inf: -inf
+ * GROUP.  Every item carries `group`, non-decreasing along the item range of every grid, and `log_prior`.  Consecutive items of one group are the
+ * hypotheses of one multihypo factor whose certain variable is the grid's; t_k = log_prior_k + log m_k(x).  A group of ONE item:
+ * l_g = t_0 (log_prior = 0: log m(x) untouched).  More: a running max-shift in item order, (mx, s) = (-inf, 0);
+ *   t_k > mx:  s = (mx > -inf ? s exp(mx - t_k) : 0) + 1, mx = t_k;    else t_k > -inf:  s = s + exp(t_k - mx)
+ * (the exponentials as in S, below -700 zero); l_g = mx + log s, or -inf where mx = -inf.
+ * RESULT.  L(x) = sum_g l_g(x), the groups added in list order starting from 0.0: a grid without items is 0.0 everywhere.  A value
+ * depends on its point and its item list alone -- not on the grid, the chunk of 256 cells or the launch around it.  A second kernel,
+ * one workgroup of 256 lanes per grid, lane t owning the cells t, t + 256, .. in ascending order:
+ *   logmax = max L (exact);  argmax = the lowest cell index among equals;  Z' = sum exp(L - logmax) (below -700: zero), the lanes
+ *   added by the library's fixed-order block sum;  logZ = (logmax + log Z') + (sum_{a < D, n[a] > 1} log step[a]), a ascending from
+ *   0.0 -- an axis with n = 1 is a slice and adds nothing.  Every cell -inf: logZ = logmax = -inf, argmax = -1.
+ * BATCH.  Descriptor i fills logp_out[first[i] .. first[i+1] - 1] and names the items first_item .. first_item + n_items - 1 of
+ * `items`; several descriptors may name the same range.  One upload, one launch sequence (extents, cells, normalisation), one copy
+ * back of the records and extents beside the grids' own; synchronises.  extent_out: lo0, step0, lo1, step1, lo2, step2 as used
+ * (axes >= D: 0, 0).  n_desc = 0 returns NBP_OK.
+ * Refused before anything is launched, naming the descriptor or the item: everything nbp_run_factor_likelihood refuses (the same
+ * check, with `other` in place of the slots); NBP_ERR_ARG: a role outside 0 / 1, role 1 or other != -1 on a unary item, groups that
+ * decrease within a grid's range, a log_prior that is NaN or +inf, an item whose manifold is not the grid's, an unknown manifold or flag; NBP_ERR_RANGE: n
+ * outside 1 .. NBP_GRID_MAX (or != 1 beyond D), more than 2^22 cells in a grid, n < 2 on a Euclidean axis with the automatic extent,
+ * a slot out of range (automatic extent), a non-finite lo, a step that is not finite and positive (explicit extent), a non-finite
+ * margin (automatic extent), an item range outside the list, offsets that do not match.
+ * Out of this version: factors where the grid's variable is a FRACTIONAL variable of a multihypo (their message has a flat part
+ * without a normaliser), and nullhypo, which is ignored. */
+#define NBP_PGRID_AUTO_EXTENT 1
+#define NBP_PGRID_MAX_CELLS (1 << 22)
+#define NBP_PGRID_CHUNK 256 /* cells per workgroup, one per lane; also the lanes of the normalisation */
+typedef struct nbp_product_item {
+  nbp_likelihood_desc lik; /* the measurement model; slot_a / slot_b are not read                 */
+  int32_t role;            /* 0: the grid's variable fills role a, 1: role b                      */
+  int32_t other;           /* the slot of the other variable; -1: unary                           */
+  int32_t group;           /* non-decreasing along the list                                       */
+  int32_t pad;
+  double log_prior;        /* log of the hypothesis' prior; 0 for a plain factor                  */
+} nbp_product_item;
+typedef struct nbp_product_grid_desc {
+  int32_t manifold;
+  int32_t slot; /* the variable's own resident belief: read for the automatic extent only       */
+  int32_t n[3];
+  int32_t flags;
+  int32_t first_item;
+  int32_t n_items;
+  double lo[3];
+  double step[3];
+  double margin;
+} nbp_product_grid_desc;
+typedef struct nbp_product_grid_rec {
+  double logZ;
+  double logmax;
+  int32_t argmax;
+  int32_t pad;
+} nbp_product_grid_rec;
+nbp_status nbp_run_product_grid(nbp_ctx *ctx, const nbp_product_grid_desc *descs, int32_t n_desc, const nbp_product_item *items,
+                                int32_t n_items, const int32_t *first /* n_desc + 1 */, double *logp_out /* first[n_desc] */,
+                                nbp_product_grid_rec *recs_out /* n_desc, nullable */, double *extent_out /* n_desc x 6, nullable */);
+/* host-buffer form for one grid, like nbp_factor_likelihood: the variable's own points own_NxP (n_own of them) and bandwidth own_bw_D
+ * go through slot 0 -- read for the automatic extent only, and all three may be NULL / 0 without it -- and the cloud others[k] (counts[k]
+ * points, NULL for a unary item) of item k through slot 1 + k: slots 0 .. n_items are clobbered and the context needs 1 + n_items
+ * slots.  desc->slot, first_item and n_items and every item's `other` are not read.  Every refusal comes before a slot is touched. */
+nbp_status nbp_product_grid(nbp_ctx *ctx, const nbp_product_grid_desc *desc, const nbp_product_item *items, int32_t n_items,
+                            const double *const *others /* n_items */, const int32_t *counts /* n_items */, const double *own_NxP,
+                            int32_t n_own, const double *own_bw_D, double *logp_out, nbp_product_grid_rec *rec_out /* nullable */,
+                            double *extent_out_6 /* nullable */);
 /* ---- factor likelihoods, mode by mode ("Joint hypotheses"; DEFINED by this library, unpinned: DESIGN.md 8) ----------
  * Which mode of one variable belongs with which mode of another: the likelihood of a factor's measurement model given "a is in its
  * group k and b is in its group l", for every pair of groups at once.  One ITEM is (measurement model, slot A, slot B, label row of

@@ -4,7 +4,7 @@ clique Gibbs schedule).  Compute lives in csrc/libnbp.so (hand-written HIP, gfx9
 C ABI of include/nbp.h; this package is the host-side mirror of the reference's API for that
 path.  There is no CPU fallback: the compute entry points raise when libnbp.so or a GPU is
 missing."""
-from . import abi, bayestree, beliefquery, beliefstats, canonical, credible, heatmap, jointmodes, likelihood, marginal, mixture, modes, overlap, ppe, scene, seeds  # noqa: F401
+from . import abi, bayestree, beliefquery, beliefstats, canonical, credible, heatmap, jointmodes, likelihood, marginal, mixture, modes, overlap, ppe, productgrid, scene, seeds  # noqa: F401
 from .backend import HipBackend, NbpError  # noqa: F401
 from .beliefquery import (Belief, density_numpy, getBelief, isapproxBeliefs, mmd, mmd_numpy, mmdVariables,  # noqa: F401
                           ppe_coords)
@@ -19,6 +19,7 @@ from .jointmodes import (FactorModeLikelihood, FactorModeLikelihoods, JointModes
 from .overlap import (Overlap, Overlaps, beliefOverlap, findBeliefsNear, findOverlaps, findVariablesNear,  # noqa: F401
                       overlap_numpy, overlap_search_numpy, overlapVariables)
 from .scene import Scene, scene_extent_numpy, scene_grid_numpy, sceneGrid  # noqa: F401
+from .productgrid import ProductGrid, localProductGrid, localProductGridAll, product_grid_numpy  # noqa: F401
 from .credible import (Credibility, CredibleRegion, coverage, credibility, credible_numpy, credibleRegion,  # noqa: F401
                        credibleRegionAll)
 from .mixture import BeliefMixture, fitBeliefMixture, fitBeliefMixtureAll, mixture_numpy  # noqa: F401

@@ -119,6 +119,28 @@ class LikelihoodDesc(C.Structure):
                 ("partial_mask", C.c_int32), ("comp", (C.c_double * COMP_STRIDE) * MAXC)]
 
 
+class ProductItem(C.Structure):
+    """nbp_product_item: one message of nbp_run_product_grid -- a measurement model (its own slots are not read), the role the grid's
+    variable fills (0: a, 1: b), the slot of the other variable (-1: unary), the group (a multihypo factor) and the log prior"""
+    _fields_ = [("lik", LikelihoodDesc), ("role", C.c_int32), ("other", C.c_int32), ("group", C.c_int32), ("pad", C.c_int32),
+                ("log_prior", C.c_double)]
+
+
+class ProductGridDesc(C.Structure):
+    """nbp_product_grid_desc: one grid over all coordinates of a variable (flags & PGRID_AUTO_EXTENT: lo and step are not read, the
+    belief in `slot` is) and the range of items it multiplies"""
+    _fields_ = [("manifold", C.c_int32), ("slot", C.c_int32), ("n", C.c_int32 * 3), ("flags", C.c_int32), ("first_item", C.c_int32),
+                ("n_items", C.c_int32), ("lo", C.c_double * 3), ("step", C.c_double * 3), ("margin", C.c_double)]
+
+
+class ProductGridRec(C.Structure):
+    """nbp_product_grid_rec"""
+    _fields_ = [("logZ", C.c_double), ("logmax", C.c_double), ("argmax", C.c_int32), ("pad", C.c_int32)]
+
+
+PGRID_AUTO_EXTENT, PGRID_MAX_CELLS, PGRID_CHUNK, PGRID_MARGIN = 1, 1 << 22, 256, 4.0
+
+
 MAXK = 8  # NBP_MAXK: groups (modes) per belief in nbp_run_factor_mode_likelihood
 
 
@@ -275,7 +297,7 @@ EXPORTS = [
     "nbp_ctx_reserve_resident", "nbp_ctx_resident", "nbp_belief_write_batch_async", "nbp_belief_read_batch_begin", "nbp_belief_read_batch_end",
     "nbp_run_copies_async", "nbp_program_retire",
     "nbp_slot_write", "nbp_slot_read", "nbp_belief_write", "nbp_belief_read", "nbp_belief_write_batch", "nbp_belief_read_batch", "nbp_run_resample", "nbp_side_write", "nbp_side_read",
-    "nbp_run_proposals", "nbp_run_bandwidth", "nbp_run_ppe", "nbp_kde_ppe", "nbp_run_evaluate", "nbp_kde_evaluate", "nbp_run_marginal_grid", "nbp_kde_marginal_grid", "nbp_run_evaluate_marginal", "nbp_run_mmd", "nbp_kde_mmd", "nbp_run_meancov", "nbp_kde_meancov", "nbp_run_kld", "nbp_kde_kld", "nbp_run_overlap", "nbp_kde_overlap", "nbp_run_overlap_search", "nbp_run_scene_grid", "nbp_run_credible", "nbp_kde_credible", "nbp_run_modes", "nbp_kde_modes", "nbp_run_mixture", "nbp_kde_mixture", "nbp_run_factor_likelihood", "nbp_factor_likelihood", "nbp_run_factor_mode_likelihood", "nbp_factor_mode_likelihood", "nbp_heatmap_create", "nbp_heatmap_build", "nbp_heatmap_draw", "nbp_heatmap_info", "nbp_heatmap_destroy", "nbp_heatmap_scan_eval", "nbp_heatmap_search_eval", "nbp_run_products", "nbp_run_copies", "nbp_run_deconv", "nbp_kde_bandwidth", "nbp_conv", "nbp_manifold_product",
+    "nbp_run_proposals", "nbp_run_bandwidth", "nbp_run_ppe", "nbp_kde_ppe", "nbp_run_evaluate", "nbp_kde_evaluate", "nbp_run_marginal_grid", "nbp_kde_marginal_grid", "nbp_run_evaluate_marginal", "nbp_run_mmd", "nbp_kde_mmd", "nbp_run_meancov", "nbp_kde_meancov", "nbp_run_kld", "nbp_kde_kld", "nbp_run_overlap", "nbp_kde_overlap", "nbp_run_overlap_search", "nbp_run_scene_grid", "nbp_run_credible", "nbp_kde_credible", "nbp_run_modes", "nbp_kde_modes", "nbp_run_mixture", "nbp_kde_mixture", "nbp_run_factor_likelihood", "nbp_factor_likelihood", "nbp_run_factor_mode_likelihood", "nbp_factor_mode_likelihood", "nbp_run_product_grid", "nbp_product_grid", "nbp_heatmap_create", "nbp_heatmap_build", "nbp_heatmap_draw", "nbp_heatmap_info", "nbp_heatmap_destroy", "nbp_heatmap_scan_eval", "nbp_heatmap_search_eval", "nbp_run_products", "nbp_run_copies", "nbp_run_deconv", "nbp_kde_bandwidth", "nbp_conv", "nbp_manifold_product",
     "nbp_program_create", "nbp_program_add_stage", "nbp_program_set_option", "nbp_program_finalize", "nbp_program_run",
     "nbp_program_reseed", "nbp_program_num_seeds", "nbp_program_set_seeds", "nbp_program_seed_order", "nbp_ctx_attach", "nbp_ctx_attached", "nbp_program_num_stages", "nbp_program_num_fused", "nbp_program_num_two_stream", "nbp_program_set_lanes", "nbp_program_lane_plan", "nbp_program_destroy",
     "nbp_timing_enable", "nbp_timing_read", "nbp_timing_read_n", "nbp_diag_read",
@@ -365,6 +387,9 @@ def load_library(path=None):
     lib.nbp_factor_likelihood.argtypes = [vp, C.POINTER(LikelihoodDesc), dp, i32, dp, i32, dp, dp]
     lib.nbp_run_factor_mode_likelihood.argtypes = [vp, C.POINTER(LikelihoodDesc), ip, ip, i32, ip, i32, dp, ip]
     lib.nbp_factor_mode_likelihood.argtypes = [vp, C.POINTER(LikelihoodDesc), dp, i32, ip, dp, i32, ip, dp, ip]
+    lib.nbp_run_product_grid.argtypes = [vp, C.POINTER(ProductGridDesc), i32, C.POINTER(ProductItem), i32, ip, dp, C.POINTER(ProductGridRec), dp]
+    lib.nbp_product_grid.argtypes = [vp, C.POINTER(ProductGridDesc), C.POINTER(ProductItem), i32, C.POINTER(dp), ip, dp, i32, dp, dp,
+                                     C.POINTER(ProductGridRec), dp]
     lib.nbp_heatmap_create.argtypes = [vp, dp, i32, i32, dp, dp, C.c_double, C.POINTER(vp)]
     lib.nbp_heatmap_build.argtypes = [vp, i32, C.c_uint64, ip, dp, dp, dp]
     lib.nbp_heatmap_draw.argtypes = [vp, i32, C.c_uint64, i32, i32, ip, dp, dp]

@@ -432,6 +432,48 @@ class HipBackend:
         self._check(self.lib.nbp_factor_likelihood(self._ctx, C.byref(desc), ap, na, bp, nb, C.byref(ll), _ptr(cl)))
         return ll.value, cl
 
+    # ---- local products on a grid (nbp_run_product_grid; productgrid.py) ---------------------------------------------------------
+    PGRID_REC = np.dtype([("logZ", np.float64), ("logmax", np.float64), ("argmax", np.int32), ("pad", np.int32)])
+
+    @staticmethod
+    def _pgrid_shape(g):
+        return tuple(max(int(g.n[a]), 0) for a in range(abi.MANIFOLD_DIM.get(int(g.manifold), abi.MAXD)))
+
+    def run_product_grid(self, grids, items):
+        """the products of factor messages on grids (nbp_run_product_grid: every grid in one launch sequence); grids: a sequence of
+        abi.ProductGridDesc, items: a sequence (or ctypes array) of abi.ProductItem the grids' item ranges index ->
+        (one array per grid of shape n[:D], coordinate 0 slowest; records[n] of PGRID_REC; extents[n, 6] as used)"""
+        grids = list(grids)
+        nd = len(grids)
+        garr = (abi.ProductGridDesc * max(nd, 1))(*grids)
+        iarr, ni = _as_array(items, abi.ProductItem) if len(items) else (None, 0)
+        shapes = [self._pgrid_shape(g) for g in grids]
+        first = np.zeros(nd + 1, dtype=np.int64)
+        for i, g in enumerate(grids):
+            first[i + 1] = first[i] + max(int(g.n[0]), 0) * max(int(g.n[1]), 0) * max(int(g.n[2]), 0)
+        if first[-1] >= 1 << 31:
+            raise ValueError("run_product_grid: more than 2^31 cells in one call")
+        first = first.astype(np.int32)
+        out, rec, ext = np.zeros(int(first[-1])), np.zeros(nd, dtype=self.PGRID_REC), np.zeros((nd, 6))
+        self._check(self.lib.nbp_run_product_grid(self._ctx, garr, nd, iarr, ni, _ptr(first), _ptr(out), _ptr(rec, abi.ProductGridRec), _ptr(ext)))
+        return [out[first[i]:first[i + 1]].reshape(sh) for i, sh in enumerate(shapes)], rec, ext
+
+    def product_grid(self, grid, items, others, own=None, own_bw=None):
+        """one grid from beliefs held on the host (nbp_product_grid; clobbers slots 0 .. len(items)): others[k] the host points
+        (n x P) of item k's other variable, None for a unary item; own, own_bw the variable's own points and bandwidth, read for the
+        automatic extent only -> (grid of shape n[:D], record, extent[6])"""
+        iarr, ni = _as_array(items, abi.ProductItem) if len(items) else (None, 0)
+        m = int(grid.manifold)
+        held = [None if o is None else _host_belief(m, o) for o in others]
+        ptrs = (_DP * max(ni, 1))(*[None if h is None else h[0] for h in held])
+        cnt, cp = _i32([0 if h is None else h[1] for h in held])
+        op, on, obp = (None, 0, None) if own is None else _host_belief(m, own, own_bw)
+        sh = self._pgrid_shape(grid)
+        out, rec, ext = np.zeros(max(int(np.prod(sh)), 0)), np.zeros(1, dtype=self.PGRID_REC), np.zeros(6)
+        self._check(self.lib.nbp_product_grid(self._ctx, C.byref(grid), iarr, ni, ptrs, cp, op, on, obp, _ptr(out),
+                                              _ptr(rec, abi.ProductGridRec), _ptr(ext)))
+        return out.reshape(sh), rec[0], ext
+
     def run_factor_mode_likelihood(self, descs, row_a, row_b, labels):
         """the likelihood of factors under resident beliefs, mode by mode (nbp_run_factor_mode_likelihood: every item in one launch);
         descs: a sequence (or ctypes array) of abi.LikelihoodDesc; row_a, row_b: per item the row of `labels` (n_rows x N, int32,

@@ -31,6 +31,7 @@
 #include "nbp_credible.h"
 #include "nbp_mixture.h"
 #include "nbp_scene.h"
+#include "nbp_productgrid.h"
 #include "../../include/nbp_lanes.h"
 
 static thread_local std::string g_err;
@@ -2522,17 +2523,21 @@ static refusal likelihood_refusal(const nbp_likelihood_desc &p) {
   return {NBP_OK, nullptr};
 }
 
-// item by item, in nbp_run_ppe's order: the slots, the manifold, then the rest of the descriptor
+// one item, in nbp_run_ppe's order: the slots, the manifold, then the rest of the descriptor (the product grids check their items
+// through it as well)
+static refusal likelihood_item_refusal(const nbp_ctx *c, const nbp_likelihood_desc &p) {
+  refusal r{NBP_OK, nullptr};
+  if (p.slot_a < 0 || p.slot_a >= c->n_slots) r = {NBP_ERR_RANGE, "slot_a out of range"};
+  else if (p.slot_b != -1 && (p.slot_b < 0 || p.slot_b >= c->n_slots)) r = {NBP_ERR_RANGE, "slot_b out of range"};
+  else if (!manifold_ok(p.manifold)) r = {NBP_ERR_ARG, "unknown manifold"};
+  else r = likelihood_refusal(p);
+  if (!r.what && p.kind != NBP_F_PRIOR && p.slot_b == -1) r = {NBP_ERR_RANGE, "slot_b out of range (a relative factor has two roles)"};
+  return r;
+}
 static nbp_status likelihood_check(nbp_ctx *c, const nbp_likelihood_desc *descs, int n) {
   HIPCHK(hipSetDevice(c->device));
   for (int i = 0; i < n; i++) {
-    const nbp_likelihood_desc &p = descs[i];
-    refusal r{NBP_OK, nullptr};
-    if (p.slot_a < 0 || p.slot_a >= c->n_slots) r = {NBP_ERR_RANGE, "slot_a out of range"};
-    else if (p.slot_b != -1 && (p.slot_b < 0 || p.slot_b >= c->n_slots)) r = {NBP_ERR_RANGE, "slot_b out of range"};
-    else if (!manifold_ok(p.manifold)) r = {NBP_ERR_ARG, "unknown manifold"};
-    else r = likelihood_refusal(p);
-    if (!r.what && p.kind != NBP_F_PRIOR && p.slot_b == -1) r = {NBP_ERR_RANGE, "slot_b out of range (a relative factor has two roles)"};
+    const refusal r = likelihood_item_refusal(c, descs[i]);
     if (r.what) return fail(r.code, "factor_likelihood: item " + std::to_string(i) + ": " + r.what);
   }
   return NBP_OK;
@@ -2649,6 +2654,122 @@ nbp_status nbp_factor_mode_likelihood(nbp_ctx *c, const nbp_likelihood_desc *des
   }
   NBPCHK(kde_write(c, p.manifold, {{a, na, nullptr}, {unary ? nullptr : b, nb, nullptr}}));
   return nbp_run_factor_mode_likelihood(c, &p, &ra, &rb, 1, rows.data(), n_rows, table_out, counts_out);
+}
+
+// ---- local products on a grid (nbp_productgrid.h) ------------------------------------------------------------------------------
+// what nbp_run_product_grid refuses: the items first (the measurement model through the factor likelihood's own check, with `other`
+// in place of its slots), then descriptor by descriptor; nothing has been launched or written
+static nbp_status product_grid_check(nbp_ctx *c, const nbp_product_grid_desc *descs, int n_desc, const nbp_product_item *items, int n_items,
+                                     const int32_t *first) {
+  HIPCHK(hipSetDevice(c->device));
+  for (int i = 0; i < n_items; i++) {
+    const nbp_product_item &it = items[i];
+    nbp_likelihood_desc p = it.lik;
+    const bool unary = p.kind == NBP_F_PRIOR;
+    refusal r{NBP_OK, nullptr};
+    if (it.role != 0 && it.role != 1) r = {NBP_ERR_ARG, "role outside 0 / 1"};
+    else if (unary && it.role == 1) r = {NBP_ERR_ARG, "role 1 on a unary item"};
+    else if (unary && it.other != -1) r = {NBP_ERR_ARG, "a unary item has no other slot: other must be -1"};
+    else if (!unary && (it.other < 0 || it.other >= c->n_slots)) r = {NBP_ERR_RANGE, "other slot out of range"};
+    if (!r.what) {
+      p.slot_a = unary ? 0 : it.other;
+      p.slot_b = unary ? -1 : it.other;
+      r = likelihood_item_refusal(c, p);
+    }
+    if (!r.what && (std::isnan(it.log_prior) || it.log_prior == INFINITY)) r = {NBP_ERR_ARG, "log_prior is NaN or +inf"};
+    if (r.what) return fail(r.code, "product grid: item " + std::to_string(i) + ": " + r.what);
+  }
+  if (first[0] != 0) return fail(NBP_ERR_RANGE, "product grid: descriptor 0: first[0] must be 0");
+  for (int i = 0; i < n_desc; i++) {
+    const nbp_product_grid_desc &g = descs[i];
+    const std::string who = "product grid: descriptor " + std::to_string(i) + ": ";
+    if (!manifold_ok(g.manifold)) return fail(NBP_ERR_ARG, who + "unknown manifold");
+    if (g.flags & ~NBP_PGRID_AUTO_EXTENT) return fail(NBP_ERR_ARG, who + "unknown flag");
+    const bool autoext = g.flags & NBP_PGRID_AUTO_EXTENT;
+    const int D = manifold_dim_h(g.manifold);
+    if (autoext && (g.slot < 0 || g.slot >= c->n_slots)) return fail(NBP_ERR_RANGE, who + "slot out of range");
+    if (autoext && !std::isfinite(g.margin)) return fail(NBP_ERR_RANGE, who + "margin not finite");
+    int64_t cells = 1;
+    for (int a = 0; a < 3; a++) {
+      if (g.n[a] < 1 || g.n[a] > NBP_GRID_MAX) return fail(NBP_ERR_RANGE, who + "n outside 1 .. " + std::to_string(NBP_GRID_MAX));
+      if (a >= D && g.n[a] != 1) return fail(NBP_ERR_RANGE, who + "n must be 1 on an axis the manifold does not have");
+      if (a < D && autoext && !manifold_circ_h(g.manifold, a) && g.n[a] < 2)
+        return fail(NBP_ERR_RANGE, who + "automatic extent of a Euclidean axis needs n >= 2");
+      if (a < D && !autoext && !std::isfinite(g.lo[a])) return fail(NBP_ERR_RANGE, who + "lo not finite");
+      if (a < D && !autoext && !(g.step[a] > 0.0 && std::isfinite(g.step[a]))) return fail(NBP_ERR_RANGE, who + "step must be finite and positive");
+      cells *= g.n[a];
+    }
+    if (cells > (int64_t)NBP_PGRID_MAX_CELLS) return fail(NBP_ERR_RANGE, who + "more than 2^22 cells");
+    if (g.first_item < 0 || g.n_items < 0 || (int64_t)g.first_item + g.n_items > n_items) return fail(NBP_ERR_RANGE, who + "item range outside the list");
+    for (int k = g.first_item; k < g.first_item + g.n_items; k++) {
+      if (items[k].lik.manifold != g.manifold) return fail(NBP_ERR_ARG, who + "item " + std::to_string(k) + " lies on another manifold than the grid");
+      if (k > g.first_item && items[k].group < items[k - 1].group)
+        return fail(NBP_ERR_ARG, who + "item " + std::to_string(k) + ": groups must not decrease along the grid's items");
+    }
+    if ((int64_t)first[i + 1] - (int64_t)first[i] != cells) return fail(NBP_ERR_RANGE, who + "offsets do not match the grid size");
+  }
+  return NBP_OK;
+}
+
+// L(x) of any number of grids: the descriptors, the items, the offsets and the chunk table go up in one staging copy; the extents, one
+// workgroup per chunk of 256 cells, the normalisation; the grids are copied straight into the caller's buffer, the records and the
+// extents in one more copy (scratch_layout::fetch_split)
+nbp_status nbp_run_product_grid(nbp_ctx *c, const nbp_product_grid_desc *descs, int32_t n_desc, const nbp_product_item *items, int32_t n_items,
+                                const int32_t *first, double *logp_out, nbp_product_grid_rec *recs_out, double *extent_out) {
+  if (!c || n_desc < 0 || n_items < 0 || ((!descs || !first) && n_desc > 0) || (!items && n_items > 0)) return fail(NBP_ERR_ARG, "product grid: null argument or a negative count");
+  if (n_desc == 0) return NBP_OK;
+  NBPCHK(product_grid_check(c, descs, n_desc, items, n_items, first));
+  if (!logp_out) return fail(NBP_ERR_ARG, "product grid: null argument");
+  std::vector<int32_t> chunks;
+  for (int i = 0; i < n_desc; i++)
+    for (int32_t k = 0; k < first[i + 1] - first[i]; k += NBP_PGRID_CHUNK) {
+      chunks.push_back(i);
+      chunks.push_back(k);
+    }
+  static_assert(sizeof(nbp_product_item) % 8 == 0 && sizeof(nbp_product_grid_desc) % 8 == 0, "the product-grid structs keep their doubles aligned in an array");
+  static_assert(sizeof(nbp_product_grid_rec) == 24, "nbp_product_grid_rec fills three doubles of the query scratch");
+  const size_t n = (size_t)n_desc, total = (size_t)first[n_desc];
+  const scratch_layout q{{sizeof(nbp_product_grid_rec), n, recs_out}, {sizeof(double), 6 * n, extent_out}, {sizeof(double), total, logp_out}};
+  const int32_t *d[4];
+  NBPCHK(stage_columns(c, {{descs, sizeof(nbp_product_grid_desc) * n}, {items, sizeof(nbp_product_item) * (size_t)n_items}, {first, 4 * (n + 1)},
+                           {chunks.data(), 4 * chunks.size()}}, d, q.total()));
+  const nbp_product_grid_desc *dd = (const nbp_product_grid_desc *)d[0];
+  NBPCHK(launch_checked(c, nbp_product_extent_kernel, n, 64, 0, dd, (const double *)c->arena, c->N, c->S, q.at(c, 1)));
+  NBPCHK(launch_checked(c, nbp_product_fill_kernel, chunks.size() / 2, NBP_PGRID_CHUNK, nbp_product_fill_lds_bytes(c->N), dd,
+                        (const nbp_product_item *)d[1], d[2], d[3], (const double *)q.at(c, 1), (const double *)c->arena, c->N, c->S, q.at(c, 2)));
+  NBPCHK(launch_checked(c, nbp_product_norm_kernel, n, NBP_PGRID_CHUNK, 0, dd, d[2], (const double *)q.at(c, 1), (const double *)q.at(c, 2),
+                        (nbp_product_grid_rec *)q.at(c, 0)));
+  return q.fetch_split(c, 2);  // (the grids straight into the caller's buffer)
+}
+
+// host-buffer form for one grid: the variable's own belief through slot 0 (automatic extent only), the cloud of item k through slot
+// 1 + k -- slots 0 .. n_items are clobbered; every refusal comes before the first write
+nbp_status nbp_product_grid(nbp_ctx *c, const nbp_product_grid_desc *desc, const nbp_product_item *items, int32_t n_items,
+                            const double *const *others, const int32_t *counts, const double *own, int32_t n_own, const double *own_bw,
+                            double *logp_out, nbp_product_grid_rec *rec_out, double *extent_out) {
+  if (!c || !desc || !logp_out || n_items < 0 || (n_items > 0 && (!items || !others || !counts))) return fail(NBP_ERR_ARG, "product grid: null argument or a negative count");
+  nbp_product_grid_desc g = *desc;
+  g.slot = 0;
+  g.first_item = 0;
+  g.n_items = n_items;
+  const bool autoext = g.flags & NBP_PGRID_AUTO_EXTENT;
+  if (autoext && (!own || !own_bw || n_own < 1)) return fail(NBP_ERR_ARG, "product grid: the automatic extent needs the variable's own points and bandwidth");
+  if (c->n_slots < 1 + n_items) return fail(NBP_ERR_RANGE, "product grid: the context needs 1 + n_items slots");
+  std::vector<nbp_product_item> its(items, items + n_items);
+  for (int k = 0; k < n_items; k++) {
+    const bool unary = its[k].lik.kind == NBP_F_PRIOR;
+    its[k].other = unary ? -1 : 1 + k;
+    if (!unary && (!others[k] || counts[k] < 1)) return fail(NBP_ERR_ARG, "product grid: item " + std::to_string(k) + ": a belief holds at least one point");
+  }
+  int64_t cells = 1;
+  for (int a = 0; a < 3; a++) cells *= std::max(g.n[a], 0);
+  const int32_t first[2] = {0, (int32_t)std::min<int64_t>(cells, INT32_MAX)};
+  NBPCHK(product_grid_check(c, &g, 1, its.data(), n_items, first));  // (before a slot is touched)
+  const double ones[NBP_MAXD] = {1.0, 1.0, 1.0};
+  if (autoext) NBPCHK(nbp_belief_write(c, 0, g.manifold, own, n_own, own_bw, nullptr));
+  for (int k = 0; k < n_items; k++)
+    if (its[k].other >= 0) NBPCHK(nbp_belief_write(c, its[k].other, g.manifold, others[k], counts[k], ones, nullptr));
+  return nbp_run_product_grid(c, &g, 1, its.data(), n_items, first, logp_out, rec_out, extent_out);
 }
 
 // ---- heatmap densities (nbp_heatmap.h) -------------------------------------------------------------------------------------------

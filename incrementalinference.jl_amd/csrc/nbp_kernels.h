@@ -34,7 +34,8 @@
 #define NBP_TU_PROPSPLIT 524288  // proposal kernels, two waves per proposal (launches between the workgroup and the one-wave geometry)
 #define NBP_TU_MIXTURE 1048576   // the mixture-summary kernel (nbp_mixture.h)
 #define NBP_TU_SCENE 2097152     // the scene-density kernels (nbp_scene.h)
-#define NBP_TU_ALL (2 * NBP_TU_SCENE - 1)  // every bit up to the last of the list
+#define NBP_TU_PRODUCTGRID 4194304 // the local-product-on-a-grid kernels (nbp_productgrid.h)
+#define NBP_TU_ALL (2 * NBP_TU_PRODUCTGRID - 1)  // every bit up to the last of the list
 #ifndef NBP_TU
 #define NBP_TU NBP_TU_ALL
 #endif

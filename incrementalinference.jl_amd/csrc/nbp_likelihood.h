@@ -30,7 +30,8 @@ struct nbp_likelihood_rec {
 #define NBP_MODE_LIKELIHOOD_ARGS                                                                                                 \
   const nbp_likelihood_desc *descs, const int32_t *row_a, const int32_t *row_b, const int32_t *labels, const double *arena, int N, \
       int64_t S, double *table, int32_t *counts
-#if NBP_TU & NBP_TU_LIKELIHOOD
+#if NBP_TU & (NBP_TU_LIKELIHOOD | NBP_TU_PRODUCTGRID)
+// ---- shared with the local products on a grid (nbp_productgrid.h): the pair term and the component, the same bits there ----
 // what a lane and a component bring to the pair loop: the lane's point (and the sine and cosine of its heading, formed once), the
 // coordinates the mask keeps and whether each is circular (block-uniform), the component's parameters (block-uniform)
 struct lik_lane {
@@ -101,6 +102,8 @@ __device__ __forceinline__ double lik_term(const lik_lane &l, const lik_comp &k,
   return k.logw + lp;
 }
 
+#endif
+#if NBP_TU & NBP_TU_LIKELIHOOD
 // one pass of lane i over j = 0 .. cb - 1 for one component: PASS 0 the maximum of e, PASS 1 the sum of exp(e - M).  B in LDS, every
 // lane of a wave reads the same address (broadcast).  A unary item has cb = 1 and reads no B.
 template <int KIND, int ZD, int FAM, int PASS>
@@ -150,6 +153,8 @@ __device__ __forceinline__ double lik_scan_kind(int kind, int zd, int fam, const
   }
 }
 
+#endif
+#if NBP_TU & (NBP_TU_LIKELIHOOD | NBP_TU_PRODUCTGRID)
 // component c of the descriptor as the pair loops read it (block-uniform: every lane forms the same values)
 __device__ __forceinline__ lik_comp lik_component(const nbp_likelihood_desc *d, int c, int zd, int fam, double wsum) {
   const double *p = d->comp[c];
@@ -175,6 +180,8 @@ __device__ __forceinline__ lik_comp lik_component(const nbp_likelihood_desc *d, 
   return k;
 }
 
+#endif
+#if NBP_TU & NBP_TU_LIKELIHOOD
 // One workgroup per item, 64 ceil(N / 64) lanes (at most 512).  LDS: exp table | B[3][N] | red | S_c[NBP_MAXC].  Lane i owns a_i;
 // per component two passes over j, the maximum over the whole item between them (block_max), the lanes' sums added by block_sum;
 // lane 0 writes the record.  A value depends on the item alone.  No atomics.  The host has checked the descriptor.

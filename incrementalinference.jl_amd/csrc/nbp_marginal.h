@@ -45,7 +45,8 @@ __device__ __forceinline__ double grid_axis_term(double g, double x, bool circ, 
   return exp_nonpos(-0.5 * (d * d), tab);
 }
 #endif
-#if NBP_TU & NBP_TU_MARGINAL
+#if NBP_TU & (NBP_TU_MARGINAL | NBP_TU_PRODUCTGRID)
+// (the product grids of nbp_productgrid.h take their automatic axes from it too: the same bits)
 // the automatic extent of one axis from the exact minimum and maximum of its coordinate
 __device__ __forceinline__ void grid_auto_axis(bool circ, double mn, double mx, double h, double margin, int n, double *lo,
                                                double *step) {
@@ -58,6 +59,8 @@ __device__ __forceinline__ void grid_auto_axis(bool circ, double mn, double mx, 
     *step = (u - l) / (double)(n - 1);
   }
 }
+#endif
+#if NBP_TU & NBP_TU_MARGINAL
 
 // One workgroup (one wave) per tile.  LDS: exp table | X[2][CHUNK] | E[2][CHUNK][TILE].  2-D: over chunks of particles in
 // ascending order the wave stages the two coordinate rows, fills E_0[j][k0] and E_1[j][k1] -- one exponential per (axis point,

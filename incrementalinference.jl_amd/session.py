@@ -287,6 +287,20 @@ class SolveSession:
                                            lambda p, **kw: likelihood.factorLikelihood(self.fg, p.label, **kw))
         return likelihood.FactorLikelihoods(res.items(), skipped=skipped)
 
+    def localProductGrids(self, labels=None, n=64, extent=None, margin=abi.PGRID_MARGIN):
+        """The product of the messages every variable's factors send it, on a grid per variable (productgrid.py) ->
+        {label: ProductGrid} in natural order.  labels: default every variable the last solve worked on; n, extent and margin as in
+        `productgrid.localProductGridAll`.  Served by ONE `run_product_grid` for every grid where libnbp holds the beliefs
+        (`_query_resident_factors`: a variable and its neighbours are one plan): no belief travels and `stats` does not move; on the
+        host copy, `productgrid.localProductGrid`."""
+        from . import productgrid
+        if labels is None:
+            labels = list(self._labels) if self._labels else self.fg.ls()
+        plans = [productgrid.variable_items(self.fg, v) for v in sorted(labels, key=productgrid._natural)]
+        return self._query_resident_factors(plans, "run_product_grid",
+                                            lambda be, here, place: productgrid.run_plans(be, here, place, n, extent, margin),
+                                            lambda p, **kw: productgrid.localProductGrid(self.fg, p.label, n, extent, margin, **kw))
+
     def jointModes(self, labels=None, maxModes=abi.MAXK, bwScale=abi.MODES_BW_SCALE, tol=abi.MODES_TOL, maxIter=abi.MODES_MAX_ITER,
                    merge=abi.MODES_MERGE):
         """The joint hypothesis of the graph under the variables' current beliefs (jointmodes.py): which mode of one variable
