@@ -108,6 +108,8 @@ struct NbpDiag
   lane_side_launches::Int64
   lane_waits::Int64
   lane_side_updates::Int64
+  sunk_updates::Int64
+  sink_launches::Int64
 end
 
 # nbp_solver_params (include/nbp_host.h): the SolverParams fields the path reads (entities/SolverParams.jl:12-75)

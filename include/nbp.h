@@ -199,6 +199,10 @@ typedef struct nbp_diag {
   int64_t lane_side_launches;
   int64_t lane_waits;
   int64_t lane_side_updates;
+  /* sinks (NBP_OPT_UP_PASS_SINKS): variable updates (product descriptors) that ran in a later stage than their own, and the
+     launches of the parts they ran in */
+  int64_t sunk_updates;
+  int64_t sink_launches;
 } nbp_diag;
 
 typedef struct nbp_ctx nbp_ctx;
@@ -939,7 +943,16 @@ nbp_status nbp_program_add_stage(nbp_program *prog, int32_t kind, const void *de
 enum nbp_program_option { NBP_OPT_LAZY_BANDWIDTH = 1, NBP_OPT_GRAPH_REPLAY = 2, NBP_OPT_FUSED_UPDATES = 3,
                           NBP_OPT_ASYNC_UPLOAD = 4 /* (default 0) nbp_program_finalize sends the descriptors stream-ordered from a
                                                       pinned buffer and does not wait: for short-lived programs queued behind
-                                                      running ones (the asynchronous clique seam, nbp_host.h) */ };
+                                                      running ones (the asynchronous clique seam, nbp_host.h) */,
+                          NBP_OPT_UP_PASS_SINKS = 5 /* (default 0) the products of the up pass that nothing in that pass reads run
+                                                       in one or two later "sink" stages of the pass instead of the stage of
+                                                       their round, as one launch that fills the chip (include/nbp_sinks.h has
+                                                       the rules; the up pass = the first run of stages between whole-slot copy
+                                                       stages that holds products).  The stage list, the seed order and every
+                                                       result stay what they are: the compiler works on gathered copies of the
+                                                       descriptors.  For whole-tree programs of one rank (nbp_tree_compile sets
+                                                       it).  Environment NBP_NO_SINKS=1 or NBP_NO_LANES=1 (read at
+                                                       nbp_ctx_create): ignored */ };
 /* options are set before nbp_program_finalize; NBP_OPT_GRAPH_REPLAY alone may also be switched afterwards (it is a property of the
  * runs: graphs already captured stay with the program) */
 nbp_status nbp_program_set_option(nbp_program *prog, int32_t option, int32_t value);
@@ -978,6 +991,10 @@ typedef struct nbp_lane_part_rec {
   int32_t stage, lane, first_desc, n, wait, signals;
 } nbp_lane_part_rec;
 nbp_status nbp_program_lane_plan(nbp_program *prog, nbp_lane_part_rec *out, int32_t cap, int32_t *n_out);
+/* Beside it, per part in the same order: the descriptors the part gained from earlier stages (NBP_OPT_UP_PASS_SINKS; such a
+ * part runs a gathered copy of its stage's remaining lane-0 descriptors and the gained ones: first_desc = 0, n = all of them).
+ * A stage that lost descriptors shows in nbp_program_lane_plan as a lane-0 part shorter than the stage. */
+nbp_status nbp_program_sink_plan(nbp_program *prog, int32_t *gained, int32_t cap, int32_t *n_out);
 nbp_status nbp_program_destroy(nbp_program *prog);
 /* destroy without waiting: the program is dropped once everything queued on the library stream so far has run */
 nbp_status nbp_program_retire(nbp_program *prog);

@@ -17,6 +17,8 @@ STAGE_PROPOSALS, STAGE_PRODUCTS, STAGE_COPIES, STAGE_DECONV, STAGE_COPY_POINTS =
 OPT_LAZY_BANDWIDTH = 1
 OPT_GRAPH_REPLAY = 2
 OPT_FUSED_UPDATES = 3
+OPT_ASYNC_UPLOAD = 4
+OPT_UP_PASS_SINKS = 5  # set by nbp_tree_compile for whole-tree programs of one rank; the Python host does not set it
 
 MANIFOLD_DIM = {EUCLID1: 1, EUCLID2: 2, EUCLID3: 3, CIRCULAR: 1, SE2: 3}
 MANIFOLD_P = {EUCLID1: 1, EUCLID2: 2, EUCLID3: 3, CIRCULAR: 1, SE2: 6}
@@ -210,6 +212,8 @@ class Diag(C.Structure):
         ("lane_side_launches", C.c_int64),
         ("lane_waits", C.c_int64),
         ("lane_side_updates", C.c_int64),
+        ("sunk_updates", C.c_int64),
+        ("sink_launches", C.c_int64),
     ]
 
 
@@ -299,7 +303,7 @@ EXPORTS = [
     "nbp_slot_write", "nbp_slot_read", "nbp_belief_write", "nbp_belief_read", "nbp_belief_write_batch", "nbp_belief_read_batch", "nbp_run_resample", "nbp_side_write", "nbp_side_read",
     "nbp_run_proposals", "nbp_run_bandwidth", "nbp_run_ppe", "nbp_kde_ppe", "nbp_run_evaluate", "nbp_kde_evaluate", "nbp_run_marginal_grid", "nbp_kde_marginal_grid", "nbp_run_evaluate_marginal", "nbp_run_mmd", "nbp_kde_mmd", "nbp_run_meancov", "nbp_kde_meancov", "nbp_run_kld", "nbp_kde_kld", "nbp_run_overlap", "nbp_kde_overlap", "nbp_run_overlap_search", "nbp_run_scene_grid", "nbp_run_credible", "nbp_kde_credible", "nbp_run_modes", "nbp_kde_modes", "nbp_run_mixture", "nbp_kde_mixture", "nbp_run_factor_likelihood", "nbp_factor_likelihood", "nbp_run_factor_mode_likelihood", "nbp_factor_mode_likelihood", "nbp_run_product_grid", "nbp_product_grid", "nbp_heatmap_create", "nbp_heatmap_build", "nbp_heatmap_draw", "nbp_heatmap_info", "nbp_heatmap_destroy", "nbp_heatmap_scan_eval", "nbp_heatmap_search_eval", "nbp_run_products", "nbp_run_copies", "nbp_run_deconv", "nbp_kde_bandwidth", "nbp_conv", "nbp_manifold_product",
     "nbp_program_create", "nbp_program_add_stage", "nbp_program_set_option", "nbp_program_finalize", "nbp_program_run",
-    "nbp_program_reseed", "nbp_program_num_seeds", "nbp_program_set_seeds", "nbp_program_seed_order", "nbp_ctx_attach", "nbp_ctx_attached", "nbp_program_num_stages", "nbp_program_num_fused", "nbp_program_num_two_stream", "nbp_program_set_lanes", "nbp_program_lane_plan", "nbp_program_destroy",
+    "nbp_program_reseed", "nbp_program_num_seeds", "nbp_program_set_seeds", "nbp_program_seed_order", "nbp_ctx_attach", "nbp_ctx_attached", "nbp_program_num_stages", "nbp_program_num_fused", "nbp_program_num_two_stream", "nbp_program_set_lanes", "nbp_program_lane_plan", "nbp_program_sink_plan", "nbp_program_destroy",
     "nbp_timing_enable", "nbp_timing_read", "nbp_timing_read_n", "nbp_diag_read",
     "nbp_plan_products", "nbp_plan_fits", "nbp_plan_proposals", "nbp_last_plans",
     "nbp_comm_unique_id", "nbp_comm_create", "nbp_comm_destroy", "nbp_comm_info", "nbp_exchange", "nbp_math_eval",
@@ -428,6 +432,7 @@ def load_library(path=None):
     lib.nbp_program_num_two_stream.argtypes = [vp, C.POINTER(i32)]
     lib.nbp_program_set_lanes.argtypes = [vp, i32, ip, i32]
     lib.nbp_program_lane_plan.argtypes = [vp, C.POINTER(LanePartRec), i32, C.POINTER(i32)]
+    lib.nbp_program_sink_plan.argtypes = [vp, C.POINTER(i32), i32, C.POINTER(i32)]
     lib.nbp_diag_read.argtypes = [vp, C.POINTER(Diag), i32]
     lib.nbp_plan_products.argtypes = [C.POINTER(ProductPlanReq), C.POINTER(ProductPlanRec), i64]
     lib.nbp_plan_fits.argtypes = [C.POINTER(FitPlanReq), C.POINTER(FitPlanRec), i64]

@@ -859,6 +859,14 @@ class HipProgram:
         self.backend._check(self.backend.lib.nbp_program_lane_plan(self._p, recs, n.value, C.byref(n)))
         return [{k: getattr(r, k) for k, _ in abi.LanePartRec._fields_} for r in recs[:n.value]]
 
+    def sink_plan(self):
+        """beside lane_plan(), per part: the descriptors it gained from earlier stages (nbp_program_sink_plan; all 0: no sinks)"""
+        n = C.c_int32(0)
+        self.backend._check(self.backend.lib.nbp_program_sink_plan(self._p, None, 0, C.byref(n)))
+        arr = (C.c_int32 * max(n.value, 1))()
+        self.backend._check(self.backend.lib.nbp_program_sink_plan(self._p, arr, n.value, C.byref(n)))
+        return list(arr[:n.value])
+
     def num_fused(self):
         """rounds (PROPOSALS + PRODUCTS stage pairs) that run as one launch of the fused update kernel"""
         n = C.c_int32(0)

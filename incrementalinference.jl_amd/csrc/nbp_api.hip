@@ -33,6 +33,7 @@
 #include "nbp_scene.h"
 #include "nbp_productgrid.h"
 #include "../../include/nbp_lanes.h"
+#include "../../include/nbp_sinks.h"
 
 static thread_local std::string g_err;
 static nbp_status fail(nbp_status code, const std::string &msg) {
@@ -161,6 +162,12 @@ struct nbp_ctx {
   // since the last reset of nbp_diag_read, counted where the launch is issued: launches on lane 1, cross-lane waits, updates
   // (product descriptors) that ran on lane 1
   int64_t lane_side_launches = 0, lane_waits = 0, lane_side_updates = 0;
+  // sinks (plan_sinks: NBP_OPT_UP_PASS_SINKS).  NBP_NO_SINKS=1: the option is ignored (A/B runs); NBP_SINK_PLACEMENT=1: one sink
+  // per pass, its last step (nbp_sinks.h).  Counted like the lanes': updates that ran in a later stage than their own, and
+  // the launches of the parts they ran in
+  bool no_sinks = false;
+  int sink_placement = 0;
+  int64_t sunk_updates = 0, sink_launches = 0;
   // fit launches (fit_plan): NBP_LCV_P2_MIN / NBP_LCV_P1_MIN = workgroups of a launch above which a fit runs on two / one helper
   // rows; NBP_NO_W5_FITS: never the five-wave instances; NBP_DEBUG_OCCUPANCY: print what the runtime says a CU holds of a
   // plain bandwidth launch
@@ -352,6 +359,8 @@ static void ctx_plan_fields(nbp_ctx *c, int N) {
   if (getenv("NBP_PROPOSAL_SPLIT_MIN")) c->prop_split_min = atoi(getenv("NBP_PROPOSAL_SPLIT_MIN"));
   if (getenv("NBP_PIPELINE_MIN")) c->pipe_min = atoi(getenv("NBP_PIPELINE_MIN"));
   c->no_lanes = getenv("NBP_NO_LANES") && atoi(getenv("NBP_NO_LANES")) != 0;
+  c->no_sinks = getenv("NBP_NO_SINKS") && atoi(getenv("NBP_NO_SINKS")) != 0;
+  if (getenv("NBP_SINK_PLACEMENT")) c->sink_placement = atoi(getenv("NBP_SINK_PLACEMENT"));
   if (getenv("NBP_FUSED_P1_MIN")) c->fused_p1_min = atoi(getenv("NBP_FUSED_P1_MIN"));
   if (getenv("NBP_PRODUCT_HL2_MIN")) c->prod_hl2_min = atoi(getenv("NBP_PRODUCT_HL2_MIN"));
   if (getenv("NBP_PRODUCT_NCH")) c->prod_nch = atoi(getenv("NBP_PRODUCT_NCH"));
@@ -3042,10 +3051,12 @@ nbp_status nbp_run_resample(nbp_ctx *c, const int32_t *slots, const int32_t *man
 // nbp_bandwidth_kernel launch) when a later stage reads the bandwidth of that slot: a MsgPrior
 // proposal sampling from it, or a copy stage moving whole slots.  Per update the critical path is
 // proposal -> prep (LCV || KD) -> product.
-// nbp_program_finalize compiles the stages in named steps: plan_pipeline (reorders the descriptors of a round into its two
-// halves), product_liveness, schedule_fits (the walk over the pending fits; schedule_fused_pair where a round runs as one
-// launch), split_piped_entry_fits, layout_blob, presize, acquire_device_blob, upload_blob.  What a stage of any kind reads
-// and writes they all learn from one walk, stage_reads / stage_writes.
+// nbp_program_finalize compiles the stages in named steps: plan_sinks (which update of the up pass runs in a later stage),
+// plan_lanes (lane 1's descriptors and the leaving ones behind the others), gather_sinks (the gathered copies a sink stage
+// runs), plan_pipeline (reorders the descriptors of a round into its two halves), product_liveness, schedule_fits (the walk
+// over the pending fits; schedule_fused_pair where a round runs as one launch), split_piped_entry_fits, plan_parts,
+// layout_blob, presize, acquire_device_blob, upload_blob.  What a stage of any kind reads and writes they all learn from
+// one walk, stage_reads / stage_writes.
 struct nbp_stage {
   int kind = 0, n = 0, maxfd = 0, mani = 0;  // mani: products_uniform_manifold / proposals_uniform_class
   size_t offset = 0;            // byte offset of the descriptors in the program blob
@@ -3073,6 +3084,18 @@ struct nbp_stage {
   // (-1: the stage has none)
   std::vector<int32_t> lane_hint;
   int lane_split = -1;
+  // sinks (plan_sinks / gather_sinks).  sink_to: per descriptor in the caller's order the stage it runs in (empty: every one
+  // in its own); plan_lanes puts the lane-0 descriptors that leave behind those that stay: [0, sink_stay) stay (-1: none
+  // leaves).  A stage that gains descriptors has a gathered copy of its remaining lane-0 descriptors and the gained ones in
+  // the blob: gather_n of them at gather_off, copied from (stage, place in that stage) gather_src; `gained` of them came
+  // from other stages.  The descriptors of the stage itself stay whole where they are, for the runs that execute stages
+  // whole.  On a part: the part runs such a copy.
+  std::vector<int> sink_to;
+  int sink_stay = -1;
+  size_t gather_off = 0;
+  int gather_n = 0, gained = 0;
+  std::vector<std::pair<int, int>> gather_src;
+  bool sink_touched = false, gathered = false;
   // as a PART of a program with lanes (nbp_program::parts): the lane, the stage it is a share of, every fit still pending
   // on either lane where its stage begins (`bound`, on the first part of a stage: what a range that ends there runs), the
   // parts of the other lane it waits for and whether one of them waits for it (nbp_lanes.h)
@@ -3106,6 +3129,14 @@ struct nbp_program {
   std::vector<nbp_stage> parts;
   std::vector<int> first_part;
   size_t lane_ws = 0, lane_gstats = 0;
+  // sinks: the option; whether the parts are built from the moved list; per sink the stages [first, last] its updates span
+  // (a range that starts or ends inside runs the stages whole); behind the seed table the seed fields of the gathered
+  // copies, n_dup of them, and behind the values the entry of the table each one follows (layout_blob)
+  bool sinks = false;  // NBP_OPT_UP_PASS_SINKS
+  bool sunk = false;
+  std::vector<std::pair<int, int>> sink_regions;
+  size_t dup_src_off = 0;
+  int n_dup = 0;
 };
 
 nbp_status nbp_program_create(nbp_ctx *c, nbp_program **out) {
@@ -3191,6 +3222,7 @@ nbp_status nbp_program_set_option(nbp_program *p, int32_t option, int32_t value)
   if (option == NBP_OPT_GRAPH_REPLAY) { p->use_graph = value != 0; return NBP_OK; }
   if (option == NBP_OPT_FUSED_UPDATES) { p->use_fused = value != 0; return NBP_OK; }
   if (option == NBP_OPT_ASYNC_UPLOAD) { p->async_upload = value != 0; return NBP_OK; }
+  if (option == NBP_OPT_UP_PASS_SINKS) { p->sinks = value != 0; return NBP_OK; }
   return fail(NBP_ERR_ARG, "unknown program option");
 }
 
@@ -3233,6 +3265,31 @@ static void stage_writes(const nbp_program *p, const nbp_stage &st, F &&f) {
     if (st.kind == NBP_STAGE_PROPOSALS || st.kind == NBP_STAGE_DECONV) f(i, ((const nbp_proposal_desc *)d)[i].out_slot);
     else if (st.kind == NBP_STAGE_PRODUCTS) f(i, ((const nbp_product_desc *)d)[i].out_slot);
     else if (st.kind == NBP_STAGE_COPIES || st.kind == NBP_STAGE_COPY_POINTS) f(i, ((const nbp_copy_desc *)d)[i].dst_slot);
+}
+// The same for the planners that order launches (plan_sinks, the lane sweep of plan_parts): rd(descriptor, x), wr(descriptor, x)
+// with the points and the bandwidth of a slot apart (x = 2 * slot, 2 * slot + 1), an old_slot counted also where no kernel
+// reads it, and the side buffer (hypothesis indices, labels) as one slot.
+#define NBP_LANE_SLOT_SIDE (-2)
+template <class R, class W>
+static void stage_touches(const nbp_program *p, const nbp_stage &st, R &&rd, W &&wr) {
+  stage_reads(p, st, [&](int i, int32_t slot, nbp_access acc) {
+    rd(i, 2 * slot);
+    if (acc != NBP_RD_POINTS || st.kind == NBP_STAGE_PRODUCTS) rd(i, 2 * slot + 1);
+    if (acc == NBP_RD_POINTS && st.kind == NBP_STAGE_PRODUCTS) wr(i, 2 * slot);  // (old_slot: topped up in place)
+  }, true);
+  stage_writes(p, st, [&](int i, int32_t slot) {
+    wr(i, 2 * slot);
+    if (st.kind != NBP_STAGE_COPY_POINTS) wr(i, 2 * slot + 1);
+  });
+  const char *d = p->blob.data() + st.offset;
+  for (int i = 0; i < st.n; i++)
+    if (st.kind == NBP_STAGE_PROPOSALS || st.kind == NBP_STAGE_DECONV) {
+      const nbp_proposal_desc &q = ((const nbp_proposal_desc *)d)[i];
+      if (q.mhidx_in >= 0) rd(i, NBP_LANE_SLOT_SIDE);
+      if (q.mhidx_out >= 0) wr(i, NBP_LANE_SLOT_SIDE);
+    } else if (st.kind == NBP_STAGE_PRODUCTS && ((const nbp_product_desc *)d)[i].labels_out >= 0) {
+      wr(i, NBP_LANE_SLOT_SIDE);
+    }
 }
 }  // extern "C++"
 
@@ -3421,28 +3478,118 @@ static nbp_status launch_update(nbp_ctx *c, const nbp_stage &st, const nbp_updat
 // the second stream with launches of its own size.  plan_lanes moves the lane-1 descriptors of a stage behind the others
 // (moved_to: the seed table stays in the caller's order); plan_parts cuts the stages into parts, schedules the pending
 // fits per lane and derives from the slots what a part waits for on the other lane; run_lanes launches the parts.
+// ---- sinks --------------------------------------------------------------------------------------------------------------
+// The up pass of a tree batches a clique's round into the stage of that round, also the products nothing reads before the
+// down pass: above the leaves the frontal of every clique, beside the pass-throughs of its separators, which alone carry
+// the chain up the tree.  With NBP_OPT_UP_PASS_SINKS those products and their proposals run in one or two later stages of
+// the pass, as launches that fill the chip, and the chain's stages shrink to the pass-throughs (the rules: nbp_sinks.h).
+// plan_sinks says which descriptor runs where (in the caller's order, before anything moves); plan_lanes puts the ones that
+// leave behind the ones that stay; gather_sinks copies, for every stage that gains descriptors, its remaining lane-0
+// descriptors and the gained ones into an array of their own behind the stages' descriptors.  The stages themselves stay
+// whole: per-kernel timing, NBP_NO_LANES / NBP_NO_SINKS and ranges that cut a region run them as they always have.
+static size_t lane_desc_bytes(int kind) {  // descriptors that may leave lane 0's part of their stage; 0: the kind stays whole
+  return kind == NBP_STAGE_PROPOSALS ? sizeof(nbp_proposal_desc) : (kind == NBP_STAGE_PRODUCTS ? sizeof(nbp_product_desc) :
+         (kind == NBP_STAGE_COPY_POINTS ? sizeof(nbp_copy_desc) : 0));
+}
+static void plan_sinks(nbp_program *p) {
+  if (!p->sinks || p->ctx->no_lanes || p->ctx->no_sinks) return;
+  const int ns = p->n_user_stages;
+  std::vector<nbp_sink_stage> sk((size_t)ns);
+  // the up pass: the first run of stages between whole-slot copy stages (or empty copy stages: barriers) that holds products
+  int first = -1, last = -1;
+  for (int s = 0, from = 0; s <= ns && first < 0; s++) {
+    const bool edge = s == ns || p->stages[(size_t)s].kind == NBP_STAGE_COPIES || (p->stages[(size_t)s].kind == NBP_STAGE_COPY_POINTS && p->stages[(size_t)s].n == 0);
+    if (!edge) continue;
+    for (int t = from; t < s; t++)
+      if (p->stages[(size_t)t].kind == NBP_STAGE_PRODUCTS) { first = from; last = s - 1; break; }
+    from = s + 1;
+  }
+  if (first < 0) return;
+  for (int s = 0; s < ns; s++) {
+    const nbp_stage &st = p->stages[(size_t)s];
+    nbp_sink_stage &g = sk[(size_t)s];
+    g.kind = st.kind == NBP_STAGE_PROPOSALS ? NBP_SINK_PROPOSALS : (st.kind == NBP_STAGE_PRODUCTS ? NBP_SINK_PRODUCTS : NBP_SINK_OTHER);
+    g.pass = s >= first && s <= last ? 0 : -1;
+    g.d.resize((size_t)st.n);
+    for (int i = 0; i < st.n; i++) {
+      g.d[(size_t)i].lane = !st.lane_hint.empty() && lane_desc_bytes(st.kind) ? st.lane_hint[(size_t)i] : 0;
+      if (st.kind == NBP_STAGE_PRODUCTS) g.d[(size_t)i].nfactors = ((const nbp_product_desc *)(p->blob.data() + st.offset))[i].nfactors;
+    }
+    stage_touches(p, st, [&](int i, int32_t x) { g.d[(size_t)i].reads.push_back(x); }, [&](int i, int32_t x) { g.d[(size_t)i].writes.push_back(x); });
+  }
+  nbp_sink_plan(sk, p->ctx->sink_placement == 1 ? NBP_SINK_LAST : NBP_SINK_TWO);
+  for (int s = 0; s < ns; s++) {
+    nbp_stage &st = p->stages[(size_t)s];
+    bool leaves = false;
+    for (const nbp_sink_desc &d : sk[(size_t)s].d) leaves = leaves || d.to != s;
+    if (!leaves) continue;
+    st.sink_to.resize((size_t)st.n);
+    for (int i = 0; i < st.n; i++) st.sink_to[(size_t)i] = sk[(size_t)s].d[(size_t)i].to;
+    st.sink_touched = true;
+    p->sunk = true;
+  }
+}
+
 static void plan_lanes(nbp_program *p) {
   if (p->ctx->no_lanes) return;
   for (int s = 0; s < p->n_user_stages; s++) {
     nbp_stage &st = p->stages[(size_t)s];
-    if (st.lane_hint.empty()) continue;
-    const size_t esz = st.kind == NBP_STAGE_PROPOSALS ? sizeof(nbp_proposal_desc) : (st.kind == NBP_STAGE_PRODUCTS ? sizeof(nbp_product_desc) :
-                       (st.kind == NBP_STAGE_COPY_POINTS ? sizeof(nbp_copy_desc) : 0));
+    if (st.lane_hint.empty() && st.sink_to.empty()) continue;
+    const size_t esz = lane_desc_bytes(st.kind);
     if (!esz) continue;  // whole-slot copies and deconvolutions stay on lane 0
-    int n1 = 0;
-    for (int32_t l : st.lane_hint) n1 += l;
-    if (!n1) continue;
+    // lane 0's descriptors that stay, lane 0's that leave for a sink (they are lane 0's: nbp_sinks.h), lane 1's
+    auto place = [&](int i) { return !st.lane_hint.empty() && st.lane_hint[(size_t)i] ? 2 : (!st.sink_to.empty() && st.sink_to[(size_t)i] != s ? 1 : 0); };
+    int cnt[3] = {0, 0, 0};
+    for (int i = 0; i < st.n; i++) cnt[place(i)]++;
+    if (!cnt[1] && !cnt[2]) continue;
     std::vector<char> moved((size_t)st.n * esz);
     st.moved_to.assign((size_t)st.n, 0);
     int at = 0;
-    for (int l = 0; l < 2; l++)
+    for (int l = 0; l < 3; l++)
       for (int i = 0; i < st.n; i++)
-        if (st.lane_hint[(size_t)i] == l) {
+        if (place(i) == l) {
           st.moved_to[(size_t)i] = at;
           memcpy(moved.data() + (size_t)at++ * esz, p->blob.data() + st.offset + (size_t)i * esz, esz);
         }
     memcpy(p->blob.data() + st.offset, moved.data(), moved.size());
-    st.lane_split = st.n - n1;
+    if (cnt[2]) st.lane_split = st.n - cnt[2];
+    if (cnt[1]) st.sink_stay = cnt[0];
+  }
+}
+
+// the gathered copies (behind the descriptors of the stages, in front of everything layout_blob appends), and per sink the
+// stages its updates span
+static void gather_sinks(nbp_program *p) {
+  if (!p->sunk) return;
+  const int ns = p->n_user_stages;
+  std::vector<std::vector<std::pair<int, int>>> came((size_t)ns);  // per stage: (stage, place there now) of what it gains, in list order
+  std::vector<int> from((size_t)ns, -1);
+  for (int s = 0; s < ns; s++) {
+    const nbp_stage &st = p->stages[(size_t)s];
+    for (int i = 0; i < (int)st.sink_to.size(); i++) {
+      const int to = st.sink_to[(size_t)i];
+      if (to == s) continue;
+      came[(size_t)to].push_back({s, st.moved_to[(size_t)i]});
+      if (from[(size_t)to] < 0) from[(size_t)to] = s;
+    }
+  }
+  for (int s = 0; s < ns; s++) {
+    if (came[(size_t)s].empty()) continue;
+    nbp_stage &st = p->stages[(size_t)s];
+    const size_t esz = lane_desc_bytes(st.kind);
+    const int own = st.sink_stay >= 0 ? st.sink_stay : (st.lane_split >= 0 ? st.lane_split : st.n);
+    for (int i = 0; i < own; i++) st.gather_src.push_back({s, i});
+    for (auto &c : came[(size_t)s]) st.gather_src.push_back(c);
+    st.gained = (int)came[(size_t)s].size();
+    st.gather_n = (int)st.gather_src.size();
+    st.gather_off = (p->blob.size() + 63) & ~(size_t)63;
+    st.sink_touched = true;
+    p->blob.resize(st.gather_off + (size_t)st.gather_n * esz);
+    for (int j = 0; j < st.gather_n; j++)
+      memcpy(p->blob.data() + st.gather_off + (size_t)j * esz,
+             p->blob.data() + p->stages[(size_t)st.gather_src[(size_t)j].first].offset + (size_t)st.gather_src[(size_t)j].second * esz, esz);
+    // (from the proposal stage in front of the first product that left to the sink's product stage)
+    if (st.kind == NBP_STAGE_PRODUCTS) p->sink_regions.push_back({from[(size_t)s] - 1, s});
   }
 }
 
@@ -3450,6 +3597,7 @@ static void plan_pipeline(nbp_program *p, int s) {
   nbp_stage &ps = p->stages[s], &qs = p->stages[s + 1];
   if (ps.kind != NBP_STAGE_PROPOSALS || qs.kind != NBP_STAGE_PRODUCTS || qs.n < p->ctx->pipe_min || qs.n < 128) return;
   if (ps.lane_split >= 0 || qs.lane_split >= 0) return;  // lanes win: a round with lane-1 descriptors is not cut in two as well
+  if (ps.sink_touched || qs.sink_touched) return;        // nor one that updates leave or come to (the gathered copies are made)
   nbp_proposal_desc *pd = (nbp_proposal_desc *)(p->blob.data() + ps.offset);
   nbp_product_desc *qd = (nbp_product_desc *)(p->blob.data() + qs.offset);
   std::unordered_map<int32_t, int> prop_of, prod_of, reader_of;
@@ -3626,7 +3774,9 @@ static void split_piped_entry_fits(nbp_program *p) {
 //     slot apart (2 * slot, 2 * slot + 1): a fit reads the points and writes the bandwidth; the side buffer (hypothesis
 //     indices, labels) counts as one slot, an empty copy stage is a barrier.
 // No lanes (parts stay empty) where a stage with lane-1 descriptors runs fused.
-#define NBP_LANE_SLOT_SIDE (-2)
+// Sinks (plan_sinks, gather_sinks): the lane-0 part of a stage that updates left is the descriptors that stay; the lane-0 part
+// of a sink stage is the gathered copy.  Everything below walks the parts as they will run, so the fits, the liveness rows,
+// the workspaces and the waits follow the moved list by themselves.  No sinks where a stage they touch runs fused.
 static void plan_parts(nbp_program *p, const nbp_liveness &live) {
   bool any = false;
   for (int s = 0; s < p->n_user_stages; s++) {
@@ -3635,9 +3785,15 @@ static void plan_parts(nbp_program *p, const nbp_liveness &live) {
     if (st.fused || st.fused_second) return;
     any = true;
   }
-  if (!any) return;
+  for (int s = 0; s < p->n_user_stages && p->sunk; s++)
+    if (p->stages[(size_t)s].sink_touched && (p->stages[(size_t)s].fused || p->stages[(size_t)s].fused_second)) p->sunk = false;
+  if (!any && !p->sunk) return;
   std::vector<nbp_stage> &parts = p->parts;
   std::vector<const char *> dead;  // per part: the liveness row of its descriptors
+  std::vector<std::vector<char>> dead_gathered((size_t)p->n_user_stages);  // (of a gathered part: gathered like its descriptors)
+  auto dead_row = [&](int s) -> const std::vector<char> & {
+    return p->stages[(size_t)s].kind == NBP_STAGE_PRODUCTS ? live.dead_product[(size_t)s] : live.dead_proposal[(size_t)s];
+  };
   p->first_part.assign((size_t)p->n_user_stages + 1, 0);
   for (int s = 0; s < p->n_user_stages; s++) {
     const nbp_stage &st = p->stages[(size_t)s];
@@ -3646,18 +3802,27 @@ static void plan_parts(nbp_program *p, const nbp_liveness &live) {
                        sizeof(nbp_copy_desc) : sizeof(nbp_proposal_desc));
     const int cut = st.lane_split < 0 ? st.n : st.lane_split;
     for (int l = 0; l < 2; l++) {
-      const int from = l ? cut : 0, n = l ? st.n - cut : cut;
-      if (n == 0 && (l || st.lane_split >= 0)) continue;  // (an empty stage stays, as one empty lane-0 part: the barrier)
+      const bool gathered = !l && p->sunk && st.gather_n > 0;
+      const int from = l ? cut : 0, n = l ? st.n - cut : (gathered ? st.gather_n : (p->sunk && st.sink_stay >= 0 ? st.sink_stay : cut));
+      if (n == 0 && (l || st.lane_split >= 0 || st.n > 0)) continue;  // (an empty stage stays, as one empty lane-0 part: the barrier)
       nbp_stage pt;
-      pt.kind = st.kind; pt.n = n; pt.offset = st.offset + (size_t)from * esz; pt.lane = l; pt.user = s;
+      pt.kind = st.kind; pt.n = n; pt.offset = gathered ? st.gather_off : st.offset + (size_t)from * esz; pt.lane = l; pt.user = s;
       pt.maxfd = st.maxfd; pt.mani = st.mani;
-      if (st.kind == NBP_STAGE_PRODUCTS && st.lane_split >= 0) {
+      pt.gathered = gathered;
+      pt.gained = gathered ? st.gained : 0;
+      if (st.kind == NBP_STAGE_PRODUCTS && (n != st.n || gathered)) {
         pt.maxfd = products_maxfd((const nbp_product_desc *)(p->blob.data() + pt.offset), n);
         pt.mani = products_uniform_manifold((const nbp_product_desc *)(p->blob.data() + pt.offset), n);
       }
-      if (st.kind == NBP_STAGE_PROPOSALS && st.lane_split >= 0) pt.mani = proposals_uniform_class((const nbp_proposal_desc *)(p->blob.data() + pt.offset), n);
-      const std::vector<char> &row = st.kind == NBP_STAGE_PRODUCTS ? live.dead_product[(size_t)s] : live.dead_proposal[(size_t)s];
-      dead.push_back(row.empty() ? nullptr : row.data() + from);
+      if (st.kind == NBP_STAGE_PROPOSALS && (n != st.n || gathered)) pt.mani = proposals_uniform_class((const nbp_proposal_desc *)(p->blob.data() + pt.offset), n);
+      const std::vector<char> &row = dead_row(s);
+      if (gathered && (st.kind == NBP_STAGE_PRODUCTS || st.kind == NBP_STAGE_PROPOSALS)) {
+        std::vector<char> &g = dead_gathered[(size_t)s];
+        for (const auto &src : st.gather_src) g.push_back(dead_row(src.first)[(size_t)src.second]);
+        dead.push_back(g.data());
+      } else {
+        dead.push_back(row.empty() ? nullptr : row.data() + from);
+      }
       parts.push_back(std::move(pt));
     }
   }
@@ -3732,25 +3897,8 @@ static void plan_parts(nbp_program *p, const nbp_liveness &live) {
     a.stage = st.user;
     a.lane = st.lane;
     a.barrier = st.kind == 0 || ((st.kind == NBP_STAGE_COPIES || st.kind == NBP_STAGE_COPY_POINTS) && st.n == 0);
-    stage_reads(p, st, [&](int, int32_t slot, nbp_access acc) {
-      a.reads.push_back(2 * slot);
-      if (acc != NBP_RD_POINTS || st.kind == NBP_STAGE_PRODUCTS) a.reads.push_back(2 * slot + 1);
-      if (acc == NBP_RD_POINTS && st.kind == NBP_STAGE_PRODUCTS) a.writes.push_back(2 * slot);  // (old_slot: topped up in place)
-    }, true);
-    stage_writes(p, st, [&](int, int32_t slot) {
-      a.writes.push_back(2 * slot);
-      if (st.kind != NBP_STAGE_COPY_POINTS) a.writes.push_back(2 * slot + 1);
-    });
+    stage_touches(p, st, [&](int, int32_t x) { a.reads.push_back(x); }, [&](int, int32_t x) { a.writes.push_back(x); });
     for (const nbp_fits::fit &f : ran[(size_t)k].v) { a.reads.push_back(2 * f.slot); a.writes.push_back(2 * f.slot + 1); }
-    const char *d = p->blob.data() + st.offset;
-    for (int i = 0; i < st.n; i++)
-      if (st.kind == NBP_STAGE_PROPOSALS || st.kind == NBP_STAGE_DECONV) {
-        const nbp_proposal_desc &q = ((const nbp_proposal_desc *)d)[i];
-        if (q.mhidx_in >= 0) a.reads.push_back(NBP_LANE_SLOT_SIDE);
-        if (q.mhidx_out >= 0) a.writes.push_back(NBP_LANE_SLOT_SIDE);
-      } else if (st.kind == NBP_STAGE_PRODUCTS && ((const nbp_product_desc *)d)[i].labels_out >= 0) {
-        a.writes.push_back(NBP_LANE_SLOT_SIDE);
-      }
   }
   nbp_lane_sweep(sw);
   for (int k = 0; k < (int)parts.size(); k++) {
@@ -3766,8 +3914,9 @@ static void plan_parts(nbp_program *p, const nbp_liveness &live) {
     }
 }
 
-// Behind the descriptors, each region 64-byte aligned: the entry fits of every stage, the split-out fits of the fused
-// pairs, their update descriptors, the seed table.  (This order and these sizes are what captured graphs and the plan
+// Behind the descriptors (and the gathered copies of the sinks, which gather_sinks has put right behind them), each region
+// 64-byte aligned: the entry fits of every stage, the split-out fits of the fused pairs, the fits of the parts, the update
+// descriptors, the seed table with the copies' entries, the seed values, the entries the copies follow.  (This order and these sizes are what captured graphs and the plan
 // cache of nbp_host.cpp hold offsets into.)
 // The seed table is in the CALLER's order -- the stages as nbp_program_add_stage took them -- whatever plan_pipeline did to
 // the descriptors of a two-stream round since (nbp_stage::moved_to): entry i is the field seeds[i] of nbp_program_set_seeds
@@ -3805,11 +3954,41 @@ static void layout_blob(nbp_program *p) {
   std::sort(sorted.begin(), sorted.end());
   p->seed_rank.resize(so.size());
   for (size_t i = 0; i < so.size(); i++) p->seed_rank[i] = (int32_t)(std::lower_bound(sorted.begin(), sorted.end(), so[i]) - sorted.begin());
+  // The gathered copies of a sink (gather_sinks) carry seed fields of their own: each follows the entry of the table its
+  // original has, so that nbp_program_reseed re-keys both alike and nbp_program_set_seeds writes both.  Their offsets stand
+  // behind the table's n_seeds entries, the entries they follow behind the values.
+  std::vector<int64_t> dup;
+  std::vector<int32_t> dup_src;
+  if (p->sunk || !p->sink_regions.empty()) {
+    std::unordered_map<int64_t, int32_t> entry;
+    for (size_t i = 0; i < so.size(); i++) entry[so[i]] = (int32_t)i;
+    for (int s = 0; s < p->n_user_stages; s++) {
+      const nbp_stage &st = p->stages[(size_t)s];
+      const size_t esz = st.kind == NBP_STAGE_PRODUCTS ? sizeof(nbp_product_desc) : sizeof(nbp_proposal_desc);
+      for (int j = 0; j < st.gather_n; j++) {
+        const int64_t from = (int64_t)(p->stages[(size_t)st.gather_src[(size_t)j].first].offset + (size_t)st.gather_src[(size_t)j].second * esz);
+        const int64_t to = (int64_t)(st.gather_off + (size_t)j * esz);
+        for (size_t field : {st.kind == NBP_STAGE_PRODUCTS ? offsetof(nbp_product_desc, seed) : offsetof(nbp_proposal_desc, seed),
+                             st.kind == NBP_STAGE_PRODUCTS ? (size_t)0 : offsetof(nbp_proposal_desc, meas_seed)}) {
+          auto it = field ? entry.find(from + (int64_t)field) : entry.end();
+          if (it == entry.end()) continue;
+          dup.push_back(to + (int64_t)field);
+          dup_src.push_back(it->second);
+        }
+      }
+    }
+  }
   p->seed_off = (p->blob.size() + 63) & ~(size_t)63;
   p->n_seeds = (int)so.size();
-  p->seed_val_off = p->seed_off + so.size() * 8;
-  p->blob.resize(p->seed_val_off + so.size() * 8);
+  p->n_dup = (int)dup.size();
+  p->seed_val_off = p->seed_off + (so.size() + dup.size()) * 8;
+  p->dup_src_off = p->seed_val_off + so.size() * 8;
+  p->blob.resize(p->dup_src_off + dup.size() * 4);
   if (!so.empty()) memcpy(p->blob.data() + p->seed_off, so.data(), so.size() * 8);
+  if (!dup.empty()) {
+    memcpy(p->blob.data() + p->seed_off + so.size() * 8, dup.data(), dup.size() * 8);
+    memcpy(p->blob.data() + p->dup_src_off, dup_src.data(), dup.size() * 4);
+  }
 }
 
 // size the workspaces now: nothing may allocate once a launch sequence is being captured
@@ -3820,6 +3999,11 @@ static nbp_status presize(nbp_program *p) {
       if (rc) return rc;
     }
   if (p->parts.empty()) return NBP_OK;
+  for (const nbp_stage &st : p->parts)  // (a sink's part may hold more products than any stage)
+    if (st.gathered && st.kind == NBP_STAGE_PRODUCTS) {
+      nbp_status rc = presize_products(p->ctx, st.n, st.maxfd, st.mani);
+      if (rc) return rc;
+    }
   // lanes: lane 1 builds its KD trees in the last lane_ws doubles of the workspace, beside whatever lane 0 builds in front of
   // them (its largest part is no larger than the largest stage, sized above), and keeps its node statistics in an area of
   // its own
@@ -3902,7 +4086,16 @@ nbp_status nbp_program_finalize(nbp_program *p) {
   HIPCHK(hipSetDevice(p->ctx->device));
   p->n_user_stages = (int)p->stages.size();
   p->stages.emplace_back();  // trailing pseudo stage (kind 0): the fits pending at exit
+  plan_sinks(p);  // (NBP_OPT_UP_PASS_SINKS) which update runs where: over the stages as the caller gave them
   plan_lanes(p);  // reorder descriptors: before anything indexes them
+  gather_sinks(p);
+  for (int s = 0; s < p->n_user_stages; s++) {  // a gathered copy is held to what nbp_program_add_stage asks of a stage
+    const nbp_stage &st = p->stages[(size_t)s];
+    if (!st.gather_n) continue;
+    const nbp_status rc = st.kind == NBP_STAGE_PRODUCTS ? check_products(p->ctx, (const nbp_product_desc *)(p->blob.data() + st.gather_off), st.gather_n)
+                                                        : check_proposals(p->ctx, (const nbp_proposal_desc *)(p->blob.data() + st.gather_off), st.gather_n);
+    if (rc) return rc;
+  }
   for (int s = 0; s + 1 < p->n_user_stages; s++) plan_pipeline(p, s);
   const nbp_liveness live = product_liveness(p);
   schedule_fits(p, live);
@@ -3924,6 +4117,16 @@ static bool lanes_apply(const nbp_program *p, int first, int last) {
   if (p->parts.empty() || p->ctx->timing || first >= last) return false;
   auto has1 = [&](int s) { return s >= 0 && s < p->n_user_stages && p->stages[(size_t)s].lane_split >= 0; };
   if ((has1(first - 1) && has1(first)) || (has1(last - 1) && has1(last))) return false;
+  // sinks: a range that starts or ends between the first stage an update left and the stage it runs in would run it twice
+  // or never; one that holds the region whole runs the parts
+  bool sink = false;
+  if (p->sunk)
+    for (const auto &r : p->sink_regions) {
+      auto inside = [&](int cut) { return r.first < cut && cut <= r.second; };
+      if (inside(first) || inside(last)) return false;
+      sink = sink || (first <= r.first && r.second < last);
+    }
+  if (sink) return true;
   for (int s = first; s < last; s++)
     if (has1(s)) return true;
   return false;
@@ -3994,6 +4197,10 @@ static nbp_status run_lanes(nbp_program *p, int first, int last) {
     }
     if (rc) return rc;
     if (st.lane) c->lane_side_launches += launches;
+    if (st.gained) {
+      c->sink_launches += launches;
+      if (st.kind == NBP_STAGE_PRODUCTS) c->sunk_updates += st.gained;
+    }
     if (st.signals) {
       if (nev >= c->lane_ev.size()) return fail(NBP_ERR_RANGE, "lanes: fewer events than signalling parts (sized at nbp_program_finalize)");
       ev[(size_t)(k - k0)] = c->lane_ev[nev++];
@@ -4140,9 +4347,10 @@ nbp_status nbp_program_reseed(nbp_program *p, uint64_t salt) {
   nbp_ctx *c = p->ctx;
   HIPCHK(hipSetDevice(c->device));
   (void)hipGetLastError();
+  // (the seed fields of a sink's gathered copies stand behind the table's own entries and are re-keyed like their originals)
   if (p->n_seeds > 0)
-    hipLaunchKernelGGL(nbp_reseed_kernel, dim3((p->n_seeds + 255) / 256), dim3(256), 0, c->stream, p->dev,
-                       (const int64_t *)(p->dev + p->seed_off), p->n_seeds, salt);
+    hipLaunchKernelGGL(nbp_reseed_kernel, dim3((p->n_seeds + p->n_dup + 255) / 256), dim3(256), 0, c->stream, p->dev,
+                       (const int64_t *)(p->dev + p->seed_off), p->n_seeds + p->n_dup, salt);
   HIPCHK(hipGetLastError());
   return NBP_OK;
 }
@@ -4153,9 +4361,10 @@ nbp_status nbp_program_reseed(nbp_program *p, uint64_t salt) {
 // product descriptor its seed -- the order in which the caller added the stages and their descriptors, which is the order of the
 // program's seed table (layout_blob), also where a two-stream round has reordered its descriptors.  Stream-ordered: behind what
 // the program has queued so far, in front of its next run.
-__global__ void nbp_setseed_kernel(char *blob, const int64_t *seed_off, const uint64_t *vals, int n) {
+// Entries [n, n + ndup) of the table are the seed fields of a sink's gathered copies: each takes the value of the entry it follows.
+__global__ void nbp_setseed_kernel(char *blob, const int64_t *seed_off, const uint64_t *vals, int n, const int32_t *dup_src, int ndup) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) *(uint64_t *)(blob + seed_off[i]) = vals[i];
+  if (i < n + ndup) *(uint64_t *)(blob + seed_off[i]) = vals[i < n ? i : dup_src[i - n]];
 }
 nbp_status nbp_program_num_seeds(nbp_program *p, int32_t *out) {
   if (!p || !out) return fail(NBP_ERR_ARG, "null argument");
@@ -4178,8 +4387,8 @@ nbp_status nbp_program_set_seeds(nbp_program *p, const uint64_t *seeds, int32_t 
   pin_release_behind_stream(c, b);
   if (e != hipSuccess) return fail(NBP_ERR_HIP, std::string("hipMemcpyAsync (seeds): ") + hipGetErrorString(e));
   (void)hipGetLastError();
-  hipLaunchKernelGGL(nbp_setseed_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, p->dev, (const int64_t *)(p->dev + p->seed_off),
-                     (const uint64_t *)(p->dev + p->seed_val_off), n);
+  hipLaunchKernelGGL(nbp_setseed_kernel, dim3((n + p->n_dup + 255) / 256), dim3(256), 0, c->stream, p->dev, (const int64_t *)(p->dev + p->seed_off),
+                     (const uint64_t *)(p->dev + p->seed_val_off), n, (const int32_t *)(p->dev + p->dup_src_off), p->n_dup);
   HIPCHK(hipGetLastError());
   return NBP_OK;
 }
@@ -4225,8 +4434,17 @@ nbp_status nbp_program_lane_plan(nbp_program *p, nbp_lane_part_rec *out, int32_t
     const nbp_stage &us = p->stages[(size_t)st.user];
     const size_t esz = st.kind == NBP_STAGE_PRODUCTS ? sizeof(nbp_product_desc) : (st.kind == NBP_STAGE_COPIES || st.kind == NBP_STAGE_COPY_POINTS ?
                        sizeof(nbp_copy_desc) : sizeof(nbp_proposal_desc));
-    out[k] = {st.user, st.lane, (int32_t)((st.offset - us.offset) / esz), st.n, st.waits.empty() ? -1 : st.waits[0], st.signals ? 1 : 0};
+    out[k] = {st.user, st.lane, st.gathered ? 0 : (int32_t)((st.offset - us.offset) / esz), st.n, st.waits.empty() ? -1 : st.waits[0], st.signals ? 1 : 0};
   }
+  return NBP_OK;
+}
+
+nbp_status nbp_program_sink_plan(nbp_program *p, int32_t *gained, int32_t cap, int32_t *n_out) {
+  if (!p || !n_out || (!gained && cap > 0)) return fail(NBP_ERR_ARG, "null argument");
+  if (!p->finalized) return fail(NBP_ERR_ARG, "program not finalized");
+  const int np = p->parts.empty() ? 0 : (int)p->parts.size() - 1;
+  *n_out = np;
+  for (int k = 0; k < np && k < cap; k++) gained[k] = p->parts[(size_t)k].gained;
   return NBP_OK;
 }
 
@@ -4607,6 +4825,9 @@ nbp_status nbp_diag_read(nbp_ctx *c, nbp_diag *out, int32_t reset) {
   out->lane_waits = c->lane_waits;
   out->lane_side_updates = c->lane_side_updates;
   if (reset) c->lane_side_launches = c->lane_waits = c->lane_side_updates = 0;
+  out->sunk_updates = c->sunk_updates;
+  out->sink_launches = c->sink_launches;
+  if (reset) c->sunk_updates = c->sink_launches = 0;
   if (reset) HIPCHK(hipMemset(c->counters, 0, offsetof(nbp_counters, flags)));  // (the flags are the context's, not counters)
   return NBP_OK;
 }

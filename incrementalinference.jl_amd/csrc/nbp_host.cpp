@@ -1537,7 +1537,11 @@ nbp_status nbp_tree_compile(nbp_tree *t, nbp_ctx *ctx, uint64_t seed, nbp_progra
   nbp_status rc = nbp_tree_schedule(t, seed);
   if (rc) return rc;
   // a whole solve: the bandwidth of a belief that the same program overwrites before reading is dead
-  return assemble_program(ctx, t->stages, {{NBP_OPT_LAZY_BANDWIDTH, 1}}, out);
+  std::vector<std::array<int32_t, 2>> opts{{NBP_OPT_LAZY_BANDWIDTH, 1}};
+  // the whole tree on one rank: the products of the up pass that only the down pass reads leave the chain up the tree
+  // (a rank of several cuts its up pass at every exchange: left as it is)
+  if (t->owner.empty()) opts.push_back({NBP_OPT_UP_PASS_SINKS, 1});
+  return assemble_program(ctx, t->stages, opts, out);
 }
 
 // ---- multi-rank compile ---------------------------------------------------------------------------------------------
