@@ -2,7 +2,10 @@
 kinds x manifolds x the variable solved for x nullhypo x mixtures x multihypo (door sightings) x partial masks x inflation cycles
 and spread x measurement noise from 1e-3 to 3 x beliefs centred at 0 / 100 / -1e4 with spreads from 1e-3 to 3 (on the circle: all
 the way round, the lifted and the walked geodesic means), one input belief in seven with fewer points than the slot -- in MIXED launches (the generic kernel), in uniform ones of 1 / 40 /
-1200 proposals (the single-manifold workgroup kernels, the one-wave-per-proposal kernels), at N = 64 / 200 / 257 / 300; every
+1200 proposals (the single-manifold workgroup kernels; of the 1200 plain proposals only Euclid(2) at N = 64 leaves them, for the
+two-waves-per-proposal kernel: the one-wave kernels start at 3500 proposals on Euclid(2), at 1500 on Euclid(3) with N > 256 and
+never below -- run_launch(env={"NBP_PROPOSAL_WAVE_MIN": "1"}, expect_geometry=(0, 1, 0), riders=True) runs them, with message
+priors and pass-through densities mixed in), at N = 64 / 200 / 257 / 300; every
 output's points (raw rows), bandwidths and hypothesis indices compared with np.array_equal.
 usage (GPU box): fuzz_proposals.py [seeds=6] [first seed=0]"""
 import os, sys
@@ -66,8 +69,28 @@ def make_case(rng, name, kind, man, slots, out_slot, side_off, N, simple):
     return relative_factor_desc(kind, man, 2, int(rng.integers(0, 2)), slots[:2], out_slot, int(rng.integers(1, 2**31)), mean, sig, **kw), 2
 
 
-def run_launch(seed, N, B, which, simple):
+def make_rider(rrng, man, ins, out_slot, seed, N):
+    """a descriptor that rides along in a simple uniform launch: a message prior, or a pass-through density under keep_count 0 / 1 /
+    2 -- target ins[0], message or density ins[1], every second one with fewer points than N (of these every fourth with exactly
+    64 where N > 64: a count that ends on a chunk of the wave kernels).  Drawn from `rrng` alone.  -> (descriptor, name, the
+    count of the belief in ins[1])"""
+    kind = abi.F_MSGPRIOR if rrng.random() < 0.4 else abi.F_PASSTHROUGH
+    d = relative_factor_desc(kind, man, 1, 0, ins[:2], out_slot, seed, [0], [0])
+    count = N
+    if rrng.random() < 0.5:
+        count = 64 if (N > 64 and rrng.random() < 0.25) else int(rrng.integers(2, N))
+    if kind == abi.F_PASSTHROUGH:
+        d.keep_count = int(rrng.integers(0, 3))
+    return d, ("msgprior" if kind == abi.F_MSGPRIOR else f"passthrough(keep_count={d.keep_count})"), count
+
+
+def run_launch(seed, N, B, which, simple, env=None, expect_geometry=None, riders=False):
+    """env: the switches the HIP context is created under (launch_plan_cases.options); expect_geometry: what nbp_diag must say the
+    launch ran, (workgroup, wave, split) launches; riders: one descriptor in five of a simple uniform launch becomes a message
+    prior or a pass-through density (make_rider), drawn from a generator of its own -- with the defaults the stream of `seed` is
+    what it always was."""
     rng = np.random.default_rng(seed)
+    rrng = np.random.default_rng([seed, 0x51DE]) if riders else None
     nslots = 5 * B + 4
     descs, writes, outs = [], [], []
     s = 0
@@ -75,27 +98,50 @@ def run_launch(seed, N, B, which, simple):
         name, kind, man = KINDS[int(rng.integers(0, len(KINDS)))] if which is None else which
         ins = list(range(s, s + 4))
         d, used = make_case(rng, name, kind, man, ins, s + 4, j * N, N, simple)
+        beliefs = [belief(rng, man, N) for k in range(used)]
+        if riders and simple and used == 2 and rrng.random() < 0.2:
+            d, name, count = make_rider(rrng, man, ins, s + 4, int(d.seed), N)
+            beliefs[1] = beliefs[1][:count] if count < beliefs[1].shape[0] else beliefs[1]
         for k in range(used):
-            writes.append((ins[k], man, belief(rng, man, N)))
+            writes.append((ins[k], man, beliefs[k]))
         descs.append(d); outs.append((s + 4, man, name, d))
         s += 5
-    res = []
-    for make in (lambda: OracleBackend(N, nslots, B * N, threads=32), lambda: iif.HipBackend(N, nslots, side_ints=B * N)):
+    res, counts = [], []
+
+    def hip():
+        if env is None:
+            return iif.HipBackend(N, nslots, side_ints=B * N)
+        from launch_plan_cases import options
+        with options(env):
+            return iif.HipBackend(N, nslots, side_ints=B * N)
+
+    for make in (lambda: OracleBackend(N, nslots, B * N, threads=32), hip):
         be = make()
         try:
             for sl, man, pts in writes:
-                if pts.shape[0] == N:
+                if pts.shape[0] == N and not riders:
                     be.slot_write(sl, man, pts)
-                else:
+                else:  # (with riders every belief has a bandwidth: a message prior draws with it, a pass-through hands it on)
                     be.belief_write(sl, man, pts, np.full(abi.MANIFOLD_DIM[man], 0.1))
+            if riders:
+                be.side_write(0, np.full(B * N, -7, dtype=np.int32))  # (a rider names no hypothesis indices: its stretch stays as it is)
+            if expect_geometry is not None:
+                be.diag(reset=True)
             be.run_proposals(descs)
+            dg = be.diag() if expect_geometry is not None else {}
+            if "proposal_launches_wave" in dg:  # (the HIP leg: the oracle has no geometries)
+                ran = (dg["proposal_launches_workgroup"], dg["proposal_launches_wave"], dg["proposal_launches_split"])
+                assert ran == tuple(expect_geometry), f"the launch ran {ran} (workgroup, wave, split), not {tuple(expect_geometry)}"
             res.append(([be.slot_read(o, abi.EUCLID3) for o, _, _, _ in outs], be.side_read(0, B * N)))
+            counts.append([be.belief_read(o, abi.EUCLID3)[0].shape[0] for o, _, _, _ in outs] if riders else None)
         finally:
             be.close()
     bad = []
     (po, so), (ph, sh) = res
     for j, (o, man, name, d) in enumerate(outs):
         same = np.array_equal(po[j][0], ph[j][0]) and np.array_equal(np.asarray(po[j][1]), np.asarray(ph[j][1])) and np.array_equal(so[j * N:(j + 1) * N], sh[j * N:(j + 1) * N])
+        if riders and counts[0][j] != counts[1][j]:
+            same = False
         if not same:
             dp = np.abs(po[j][0] - ph[j][0])
             bad.append(f"    op {j} {name} nvars {d.nvars} sfidx {d.sfidx} nullhypo {d.nullhypo} ncomp {d.ncomp} partial {d.partial_mask} multihypo {d.has_multihypo} cycles {d.inflate_cycles} "
@@ -156,7 +202,7 @@ def main():
         plans = [("mixed launch of 60 (every kind, every option)", 60, None, False)]
         for w in (KINDS[1], KINDS[2], KINDS[3], KINDS[4]):
             plans.append((f"uniform {w[0]}, 40, every option", 40, w, False))
-        plans.append((f"uniform {KINDS[1 + seed % 2][0]}, 1200 plain proposals (one wave per proposal)", 1200, KINDS[1 + seed % 2], True))
+        plans.append((f"uniform {KINDS[1 + seed % 2][0]}, 1200 plain proposals ({'two waves per proposal' if seed % 2 == 0 and N <= 256 else 'the workgroup kernel'})", 1200, KINDS[1 + seed % 2], True))
         plans.append((f"uniform se2, 400 plain proposals", 400, KINDS[4], True))
         plans.append(("a lone proposal", 1, None, False))
         for what, B, which, simple in plans:

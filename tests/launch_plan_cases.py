@@ -15,7 +15,8 @@ MAX_CASES = 200
 
 # every switch the planners read: a context (or a query) under an option set has exactly that set
 PLAN_VARS = ("NBP_PRODUCT_HL2_MIN", "NBP_PRODUCT_NCH", "NBP_PRODUCT_ALL_LEVELS_HL", "NBP_NO_XS_PRODUCTS", "NBP_NO_UNIFORM_LATENCY_PRODUCTS",
-             "NBP_NO_SPECULATIVE_FITS", "NBP_SPEC_DEPTH3", "NBP_LCV_P2_MIN", "NBP_LCV_P1_MIN", "NBP_NO_W5_FITS")
+             "NBP_NO_SPECULATIVE_FITS", "NBP_SPEC_DEPTH3", "NBP_LCV_P2_MIN", "NBP_LCV_P1_MIN", "NBP_NO_W5_FITS",
+             "NBP_PROPOSAL_WAVE_MIN", "NBP_PROPOSAL_SPLIT_MIN")
 OPTION_SETS = {
     "defaults": {},
     "hl2min1": {"NBP_PRODUCT_HL2_MIN": "1"},

@@ -4,7 +4,10 @@ Random descriptors over everything a descriptor can say -- factor kinds x manifo
 mixtures x door-sighting multihypo x partial masks x inflation cycles and spread x measurement noise 1e-3 .. 3 x beliefs at
 0 / 100 / -1e4 with spreads 1e-3 .. 3 (on the circle: all the way round); products of 1 .. 7 (now and then 20 / 60) densities,
 Niter 1 .. 3, partial inputs with old points, labels -- in mixed launches and in uniform ones of every geometry (a lone op,
-dozens, hundreds: the latency kernels, the single-manifold ones, one wave per proposal, throughput rows), N = 64 / 200 / 257 / 300.
+dozens, hundreds: the latency kernels, the single-manifold ones, throughput rows), N = 64 / 200 / 257 / 300.  The 1200 plain
+proposals of test_random_proposal_launches_are_the_oracles run the two-waves-per-proposal kernel at seed 0 (Euclid(2), N = 64) and
+the workgroup kernels at the others (the one-wave kernels start at 3500 / 1500 proposals now); one wave per proposal is
+test_random_plain_launches_with_riders_on_the_wave_kernels_are_the_oracles, which asserts the geometry that ran.
 The builder's run of 36 000 ops (profiles/r06_fuzz_ops.txt) found what four rounds of parity tests on well-scaled inputs had
 not: a search that STALLS with an objective of ~1e8 (a pose 1e4 from its start) compares EQUAL vertex values, and Optim orders
 those by their slot (nm_cswap in csrc/nbp_device.h).  That launch is the first case here."""
@@ -40,6 +43,17 @@ def test_random_proposal_launches_are_the_oracles(seed):
     for B, which, simple in ((60, None, False), (40, fz.KINDS[1 + seed % 4], False), (1200, fz.KINDS[1 + seed % 2], True), (1, None, False)):
         n, bad = fz.run_launch(500000 + 1000 * seed + B, N, B, which, simple)
         assert n == B and not bad, (B, which, bad[:3])
+
+
+@pytest.mark.parametrize("which,N", [(1, 64), (1, 200), (2, 200), (2, 300)], ids=["lin2_N64", "lin2_N200", "lin3_N200", "lin3n5_N300"])
+def test_random_plain_launches_with_riders_on_the_wave_kernels_are_the_oracles(which, N):
+    """1200 plain proposals with message priors and pass-through densities (keep_count 0 / 1 / 2, short densities) mixed in, one
+    wave per proposal (NBP_PROPOSAL_WAVE_MIN=1 at context creation): nbp_proposal_wave_kernel_lin2 / _lin3 / _lin3n5, and the
+    launch counters say so"""
+    fz = load("fuzz_proposals")
+    n, bad = fz.run_launch(600000 + 1000 * which + N, N, 1200, fz.KINDS[which], True, env={"NBP_PROPOSAL_WAVE_MIN": "1"},
+                           expect_geometry=(0, 1, 0), riders=True)
+    assert n == 1200 and not bad, bad[:3]
 
 
 @pytest.mark.parametrize("seed", [0, 1, 2, 3])

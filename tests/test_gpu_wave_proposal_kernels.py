@@ -1,7 +1,7 @@
 """Chip-filling launches of "simple" Euclidean proposals (LinearRelative between two variables, no multihypo, no nullhypo;
 priors, message priors and pass-through densities ride along) run one WAVE per proposal (nbp_proposal_wave_kernel_lin2 /
-_lin3 / _lin3n5, launch_proposals in nbp_api.hip; selected from NBP_PROPOSAL_WAVE_MIN proposals per launch on, 3000 by
-default).  Lane l of the wave owns the particles l, l + 64, ...; the spread statistics add the chunks of 64 in the order
+_lin3 / _lin3n5, launch_proposals in nbp_api.hip; selected from NBP_PROPOSAL_WAVE_MIN proposals per launch on; by
+default 3500 on Euclid(2), 1500 on Euclid(3) with N > 256).  Lane l of the wave owns the particles l, l + 64, ...; the spread statistics add the chunks of 64 in the order
 the workgroup kernels add their wave partials, every particle's search is the same sequence of operations.  The particles
 must not depend on the geometry: compared with the workgroup instance of the same class, BIT FOR BIT -- as many
 residual evaluations in every search, the same particles and bandwidths to the last bit.  (Since round 5 libnbp is built with
@@ -60,6 +60,9 @@ def test_wave_geometry_equals_workgroup_geometry(man, dim, N):
         out[mode] = ([be.slot_read(s, man) for s in outs], np.array(be.side_read(0, N)), dg)
         be.close()
     (wg, mh_wg, dg_wg), (wv, mh_wv, dg_wv) = out["workgroup"], out["wave"]
+    # the switch took effect: each leg's one launch ran the geometry it is named for
+    assert (dg_wv["proposal_launches_workgroup"], dg_wv["proposal_launches_wave"], dg_wv["proposal_launches_split"]) == (0, 1, 0), dg_wv
+    assert (dg_wg["proposal_launches_workgroup"], dg_wg["proposal_launches_wave"], dg_wg["proposal_launches_split"]) == (1, 0, 0), dg_wg
     assert np.array_equal(mh_wg, mh_wv) and (mh_wv == 1).all()
     # the same searches were run: as many solves and residual evaluations
     assert dg_wg["solves"] == dg_wv["solves"] and dg_wg["residual_evals"] == dg_wv["residual_evals"], (dg_wg, dg_wv)
